@@ -15,11 +15,18 @@ embarrassingly (one process per GPU, no data-path collective); the only collecti
 the per-pair pose records at the end of the run (80 B/pair), inside the timed region.  Weak scaling.
 
   python bench.py --gpus 1 --steps 10 --warmup 3
+  python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
+  python bench.py --full                         # + roofline (live kernel timers), CPU baseline, parity vs the oracle, secondary configs
   python bench.py --gpus 8                       # starts 8 ranks itself (torch.distributed.run, 127.0.0.1)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W  # the driver's form: ranks already exist
 `n_gpus` in the JSON line is the world size RCCL actually formed; --gpus N on a box with fewer GPUs, or a
 mismatch between --gpus and WORLD_SIZE, is an error (exit code 2), never a silent 1-GPU run.
+
+A plain run sets up, warms up, times --steps steps and prints the headline line (metric, value, unit, dtype, ms_per_step, config).
+Everything else the line can carry -- roofline figures (HIP-event kernel timers inside the timed region, extra eager steps after a
+graph-replayed region), the synthetic-pose error, the CPU baseline, the parity leg and the secondary configurations -- is measured
+only with --full.
 """
 import argparse
 import json
@@ -67,6 +74,10 @@ def parse(argv=None):
     ap.add_argument("--cpu-out", default="", help=argparse.SUPPRESS)
     ap.add_argument("--no-kernel-timer", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: roofline (live kernel timers), synthetic-pose "
+                    "error, CPU baseline, parity vs the oracle and, for the default configuration, the secondary configurations")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the outputs of the last timed step as "
+                    "DIR/<name>.npy (float32 / float64, at most 64 MB in all; rank 0)")
     ap.add_argument("--no-secondary", action="store_true", help="default run (sg_pnp, 1 GPU): do not append the loftr_emat and rpr_train "
                     "bench lines under \"secondary\"")
     ap.add_argument("--secondary-budget", type=float, default=110.0, help="seconds each secondary config may take (child process)")
@@ -81,6 +92,8 @@ def parse(argv=None):
                     "encoder pass, BatchNorm statistics per view = the arithmetic of the reference's two encoder calls), graph (TRAINING.GRAPH_STEP: "
                     "forward + loss + backward replayed from one HIP graph), channels_last, fp32; 'none' = two encoder calls, eager launches")
     a = ap.parse_args(argv)
+    if not a.full:                                # the side measurements below are part of --full only
+        a.no_kernel_timer, a.no_cpu_baseline, a.no_secondary = True, True, True
     if a.batch <= 0:
         a.batch = {"sg_pnp": 32, "loftr_emat": 16, "rpr_train": 10}[a.config]
     if a.cpu_pairs <= 0:
@@ -631,8 +644,13 @@ def rpr_train_bench(args, rank, world, dev, use_dist):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what the caller of train_step receives (the three losses of the last step) + a fixed sample of the weights it updated
+        flat = torch.cat([p.detach().reshape(-1).float() for p in tr.model.parameters()])
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(flat.numel(), min(flat.numel(), 1 << 20), replace=False))).to(flat.device)
+        dump_outputs(args.dump_outputs, {"R_loss": losses[0], "t_loss": losses[1], "loss": losses[2], "params_sample": flat[idx]})
     timed_steps = args.steps
-    if tr.graph_step and tr._gstep is not None:
+    if args.full and tr.graph_step and tr._gstep is not None:
         timed_steps = 3                                   # the launches below are the ones the timers (and the flop counter) see
         # HIP events cannot be recorded inside a replay: time the correlation-volume kernels over eager steps right after the region
         saved = (tr._gstep, tr._gkeys)
@@ -688,8 +706,9 @@ def rpr_train_bench(args, rank, world, dev, use_dist):
                    "precision": cfg.TRAINING.PRECISION, "siamese_batch": bool(cfg.TRAINING.SIAMESE_BATCH), "channels_last": bool(cfg.TRAINING.CHANNELS_LAST), "graph_step": bool(tr.graph_step),
                    "volume_positions": N, "feature_channels": D, "parameters": n_param, "optimizer": "Adam (fused), eps 1e-6",
                    "last_losses": [round(float(x.float().sum()), 5) for x in losses]},
-        "roofline": rpr_roofline(tr, batches[0], B, 1e3 * elapsed / args.steps, own, own_fwd_step),
     }
+    if args.full:
+        line["roofline"] = rpr_roofline(tr, batches[0], B, 1e3 * elapsed / args.steps, own, own_fwd_step)
     if world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_subprocess("rpr_train", args.cpu_pairs, args.cpu_threads, "")
     print(json.dumps(line))
@@ -701,7 +720,7 @@ def secondary_line(config, extra, budget_s):
     t0 = time.perf_counter()
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--config", config, "--no-secondary", "--no-all-cores"] + extra,
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--config", config, "--full", "--no-secondary", "--no-all-cores"] + extra,
                            capture_output=True, text=True, timeout=budget_s, env=env)
         for ln in reversed(r.stdout.strip().splitlines()):
             if ln.startswith("{"):
@@ -747,6 +766,24 @@ def _pose_error(o, gtb):
         return {"error": str(e)[:200]}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy, floating point kept as float32 / float64, integer and boolean outputs as float64
+    (exact).  An array larger than its share of the 64 MB budget is replaced by a fixed sample of its flattened elements (seeded, sorted
+    indices), so that two builds compare the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in sorted(arrays.items())}
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = a.astype(np.float32 if a.dtype in (np.float16, np.float32) else np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -778,7 +815,8 @@ def main():
             _fail(f"--gpus {args.gpus} requested but only {n_dev} HIP device(s) are visible; refusing to report a smaller run as {args.gpus} GPUs")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
                "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        import subprocess
+        sys.exit(subprocess.call(cmd))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -866,7 +904,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    if use_graph:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: v for k, v in results[-1][1].items() if isinstance(v, torch.Tensor)})
+    if args.full and use_graph:
         # HIP events cannot be recorded inside a graph replay: the dominant kernels are timed over eager steps of the same
         # workload right after the timed region (same process, same clocks, same inputs); not part of `value`
         wl.pipe.graph = False
@@ -895,18 +935,22 @@ def main():
                           "eager kernel launches; the RANSAC stage of step i on a second HIP stream under the matcher of step i + 1 (one join before the gather)" if overlap
                           else "eager kernel launches, one stream"),
                "pairs_solved_last_step": int((o["status"] == 0).sum()), "mean_matches_last_step": float(o["n_corr"].float().mean()),
-               "gathered_records": int(rec.shape[0]), "synthetic_pose_error": _pose_error(o, batches[(args.steps - 1) & 1])}
+               "gathered_records": int(rec.shape[0])}
+        if args.full:
+            cfg["synthetic_pose_error"] = _pose_error(o, batches[(args.steps - 1) & 1])
         cfg.update(wl.config(o))
         line = {
             "metric": wl.metric, "value": round(value, 3), "unit": "image-pairs/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": wl.dtype,
             "data": "synthetic (3-band planar scenes, seeded random weights; no dataset/checkpoints offline)",
-            "config": cfg, "roofline": wl.roofline(o),
+            "config": cfg,
             # scaling diagnostics: every rank's own pairs/s over its K steps (before the collective) and what the one gather cost it
             "per_rank": {"pairs_per_s": [round(B * args.steps / max(p[0], 1e-9), 2) for p in per_rank],
                          "gather_ms": [round(1e3 * p[1], 3) for p in per_rank], "record_bytes_per_pair": 80},
         }
+        if args.full:
+            line["roofline"] = wl.roofline(o)
         if world == 1 and not args.no_cpu_baseline:
             with tempfile.TemporaryDirectory() as td:
                 npz = os.path.join(td, "oracle_pairs.npz")

@@ -32,16 +32,17 @@ def test_config_rejects_unknown_keys_and_decodes_none(tmp_path):
         cfg.merge_from_file(str(bad))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/config"), reason="reference checkout not present")
-def test_every_reference_matching_config_merges():
-    """the reference's own yaml files must load unchanged (drop-in config surface)"""
+def test_every_reference_matching_config_merges(golden_dir):
+    """the reference's own yaml files must load unchanged (drop-in config surface); copies of its config/{mapfree,scannet,sevenscenes}.yaml
+    and config/matching/ are kept under tests/golden/ref_config/"""
     import glob
-    files = glob.glob("/root/reference/config/matching/**/*.yaml", recursive=True)
+    conf = os.path.join(golden_dir, "ref_config")
+    files = glob.glob(os.path.join(conf, "matching", "**", "*.yaml"), recursive=True)
     assert len(files) >= 50
     for ds in ("mapfree", "scannet", "sevenscenes"):
         for f in [x for x in files if f"/{ds}/" in x]:
             cfg = get_cfg_defaults()
-            cfg.merge_from_file(f"/root/reference/config/{ds}.yaml")
+            cfg.merge_from_file(os.path.join(conf, f"{ds}.yaml"))
             cfg.merge_from_file(f)
             assert cfg.MODEL == "FeatureMatching" and cfg.POSE_SOLVER in ("EssentialMatrix", "EssentialMatrixMetric", "PNP", "Procrustes")
 
@@ -522,6 +523,26 @@ def test_bench_module_contract_pieces_importable():
         assert isinstance(dt, str) and "f16" in dt and isinstance(wl.metric, str) and isinstance(wl.workload, str)
     c = b.census_summary()
     assert c["hard2"]["sg_pnp"]["pose_within_bar"] == c["hard2"]["sg_pnp"]["pairs"] and c["hard1"]["sg_pnp"]["inlier_index_sets_identical"] == 64
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """a plain bench.py run measures only the headline (no kernel timers, CPU baseline or secondary lines: those are --full), and
+    --dump-outputs writes float32 / float64 .npy files, sampling an array that exceeds its share of the 64 MB budget"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    a = b.parse(["--steps", "7", "--dump-outputs", str(tmp_path)])
+    assert a.steps == 7 and not a.full and a.no_kernel_timer and a.no_cpu_baseline and a.no_secondary and a.dump_outputs == str(tmp_path)
+    f = b.parse(["--full"])
+    assert f.full and not f.no_kernel_timer and not f.no_cpu_baseline and not f.no_secondary
+    big = torch.arange(9 << 20, dtype=torch.float32)
+    b.dump_outputs(str(tmp_path), {"R": torch.eye(3, dtype=torch.float64)[None], "status": torch.tensor([0, 7], dtype=torch.int32), "big": big})
+    R, st, s = (np.load(tmp_path / f"{n}.npy") for n in ("R", "status", "big"))
+    assert R.dtype == np.float64 and R.shape == (1, 3, 3) and st.dtype == np.float64 and st.tolist() == [0.0, 7.0]
+    assert s.dtype == np.float32 and s.nbytes <= b.DUMP_LIMIT_BYTES // 3 and np.all(np.diff(s) > 0)
+    b.dump_outputs(str(tmp_path / "again"), {"R": torch.eye(3, dtype=torch.float64)[None], "status": torch.zeros(2), "big": big})
+    assert np.array_equal(np.load(tmp_path / "again" / "big.npy"), s)                 # the same sample every time
 
 
 def test_round5_entry_points_reject_bad_arguments_before_touching_a_device():

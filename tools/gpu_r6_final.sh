@@ -5,7 +5,7 @@ O=gpurun_out/final6
 mkdir -p $O
 timeout 1800 python -m pytest tests -m gpu -q -x > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log; tail -4 $O/pytest.log
 timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')" > $O/smoke.log 2>&1; tail -2 $O/smoke.log
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err; cut -c1-200 $O/bench.json
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err; cut -c1-200 $O/bench.json
 bash tools/gpu_r6_profiles.sh sg_pnp loftr_emat rpr_train > $O/profiles.log 2>&1; grep -E "^\{\"metric|kernel_ms_per_step" $O/profiles.log | cut -c1-200
 for w in conv1ab dconv_l1out2 dconv_l1 dconv_conv2a gemm; do
   case $w in conv1ab) k=wino_split_c1;; dconv*) k=conv_direct;; gemm) k=gemm_split_d;; esac
