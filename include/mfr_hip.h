@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define MFR_ABI_VERSION 6   /* 6 (round 6): mfr_conv3x3_direct_f16x2*, mfr_conv3x3s2_direct_f16x2, mfr_mlp_ln_*; 5 (round 6): mfr_f16x2_guard_bind (the f16x2 range guard); 2: intrinsics as (const void *K, int k_dtype) instead of const float *; 3: mfr_emat_solve_batch takes the
+#define MFR_ABI_VERSION 6   /* 6 (round 6): mfr_conv3x3_direct_f16x2*, later (additive) the SIFT detector mfr_sift_*, mfr_conv3x3s2_direct_f16x2, mfr_mlp_ln_*; 5 (round 6): mfr_f16x2_guard_bind (the f16x2 range guard); 2: intrinsics as (const void *K, int k_dtype) instead of const float *; 3: mfr_emat_solve_batch takes the
                              * model-quality method (MAGSAC++ / count) and its table; 4 (round 5): the f16x2 entry points (mfr_gemm_f16x2*,
                              * mfr_wino_f16x2_*, mfr_conv3x3_wino_f16x2, mfr_conv_igemm_f16x2), mfr_sg_attention_variant renumbered (0 f16x2,
                              * 1 exact fp32, 2 bf16x3), the measurement-only entry points (mfr_conv3x3_wino_bf16x3_variant,
@@ -472,6 +472,34 @@ int mfr_desc_ratio_match(const float *des0, const float *des1, const float *norm
                          const int32_t *n0, const int32_t *n1, double ratio,
                          int32_t *nn_idx, float *nn_d2, float *pts0, float *pts1, int maxN, int32_t *n_corr,
                          void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * SIFT keypoint detection + description (csrc/sift.hip): OpenCV 4.8 SIFT_create(nfeatures) with default parameters
+ * (3 layers, contrast 0.04, edge 10, sigma 1.6, doubled input), restated step by step in sift_ops.py's docstring.
+ * Reference call sites: SIFT_create(cfg.SIFT.NUM_FEATURES).detectAndCompute (lib/models/matching/feature_matching.py:58,82-83)
+ * and SIFT_create(2048) (etc/feature_matching_baselines/matchers.py:146-147).  Added to ABI v6 without a version bump
+ * (purely additive).
+ *   mfr_sift_workspace_bytes  workspace of mfr_sift_detect for B images of H x W (H, W >= 8) and a candidate capacity
+ *                             (<= 0: the default, 16384 refined extrema per image); 0 for unsupported arguments
+ *   mfr_sift_level_offset     byte offset of Gaussian level `level` (0..5) of octave `octave` inside that workspace (the
+ *                             level is [B, Ho, Wo] f32, sizes written to *_host); -1 when the level does not exist
+ *   mfr_sift_blur_taps        host: the f32 taps c[0..16] (c[0] centre, c[i] at distance i) and radius of the blur that
+ *                             produces level `level` (level 0: the blur of the doubled base image)
+ *   mfr_sift_detect           gray [B,H,W] u8 -> per image the keypoints OpenCV's detectAndCompute keeps, in ascending
+ *                             (x, y, size desc, angle, response desc, octave desc) order: kpts [B,Nmax,2] (x, y) in
+ *                             input pixels, desc [B,Nmax,128] (whole numbers 0..255 as f32), size/angle/response
+ *                             [B,Nmax] f32, octave [B,Nmax] i32 (OpenCV's packed word), n [B] rows written (rows >= n
+ *                             are not touched), status [B] bit set (0 = complete):
+ */
+#define MFR_SIFT_ST_CAND_OVERFLOW 1   /* more refined extrema than the candidate capacity: the excess was dropped */
+#define MFR_SIFT_ST_KPT_OVERFLOW  2   /* more oriented keypoints than 16384 before selection: the excess was dropped */
+#define MFR_SIFT_ST_OUT_OVERFLOW  4   /* the selected set (ties included) has more than Nmax rows: n = Nmax */
+size_t mfr_sift_workspace_bytes(int B, int H, int W, int cand_cap);
+long long mfr_sift_level_offset(int B, int H, int W, int octave, int level, int *Ho_host, int *Wo_host);
+int mfr_sift_blur_taps(int level, float *taps_host, int *radius_host);
+int mfr_sift_detect(const uint8_t *gray, int B, int H, int W, int nfeatures, int Nmax, int cand_cap, void *workspace,
+                    size_t workspace_bytes, float *kpts, float *desc, float *size, float *angle, float *response,
+                    int32_t *octave, int32_t *n, int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * 3x3 / stride 1 / pad 1 convolutions of the SuperPoint encoder (conv1b..conv4b, convPa, convDa; same

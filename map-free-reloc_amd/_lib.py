@@ -108,6 +108,10 @@ SIGNATURES = {
     "mfr_kabsch_bwd": (_i, [_vp, _vp, _i, _vp, _vp]),
     "mfr_rootsift": (_i, [_vp, _i, _vp, _vp, _vp]),
     "mfr_desc_ratio_match": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _d, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "mfr_sift_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "mfr_sift_level_offset": (C.c_longlong, [_i, _i, _i, _i, _i, _vp, _vp]),
+    "mfr_sift_blur_taps": (_i, [_i, _vp, _vp]),
+    "mfr_sift_detect": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mfr_scale_workspace_bytes": (_sz, [_i, _i]),
     "mfr_scale_from_depth_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp,
                                         _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),

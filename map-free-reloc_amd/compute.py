@@ -5,6 +5,7 @@ quirk Q4) and write `correspondences_{matcher}.npz` (key `correspondences`, NaN-
 [Npairs, maxN, 4] float64) into the scene directory.
 
     python -m mapfree_reloc_amd.compute -ds Mapfree -m SG [--outdoor] [--data_root data/mapfree]
+    python -m mapfree_reloc_amd.compute -ds Mapfree -m SIFT --sift-detector hip      (SIFT on the GPU, no OpenCV)
 """
 import argparse
 from pathlib import Path
@@ -20,9 +21,13 @@ def main(argv=None):
     ap.add_argument('--scenes', '-sc', type=str, nargs='*', default=None)
     ap.add_argument('--outdoor', action='store_true')
     ap.add_argument('--data_root', type=Path, default=Path('data/mapfree/'))
+    ap.add_argument('--sift-detector', type=str, default='opencv', choices=['opencv', 'hip'])     # new: -m SIFT's keypoint detector
     args = ap.parse_args(argv)
     resize = 540, 720                                                       # compute.py:42
-    matcher = MATCHERS[args.matcher](resize, args.outdoor)
+    if args.matcher == 'SIFT':
+        matcher = MATCHERS['SIFT'](resize, args.outdoor, detector='hip' if args.sift_detector == 'hip' else None)
+    else:
+        matcher = MATCHERS[args.matcher](resize, args.outdoor)
     scenes = [f for split in ('test', 'val') if (args.data_root / split).is_dir()
               for f in sorted((args.data_root / split).iterdir()) if f.is_dir()]
     if args.scenes:

@@ -51,6 +51,7 @@ def get_cfg_defaults():
     c.FEATURE_MATCHING = None      # 'SIFT' | 'Precomputed' | 'SuperGlue' | 'LoFTR' (new: online, on the GPU)
     c.POSE_SOLVER = None           # 'EssentialMatrix' | 'EssentialMatrixMetric' | 'Procrustes' | 'PNP'
     c.SIFT = CN(); c.SIFT.NUM_FEATURES = None; c.SIFT.RATIO_THRESHOLD = None
+    c.SIFT.DETECTOR = 'opencv'      # new: 'opencv' (cv.SIFT_create, the reference's) | 'hip' (sift_ops.SiftDetector, on the GPU)
     c.MATCHES_FILE_PATH = None
     c.EMAT_RANSAC = CN(); c.EMAT_RANSAC.PIX_THRESHOLD = None; c.EMAT_RANSAC.SCALE_THRESHOLD = None
     c.EMAT_RANSAC.CONFIDENCE = None

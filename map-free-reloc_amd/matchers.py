@@ -94,6 +94,9 @@ class SIFT_matcher:
         from .descriptor_ops import DescriptorRatioMatcher
         from .matching.feature_matching import _cv_sift_detector
         self.resize = resize
+        if detector == "hip":                                                             # csrc/sift.hip (sift_ops.py)
+            from .sift_ops import SiftDetector
+            detector = SiftDetector(2048).per_image
         self.detector = detector if detector is not None else _cv_sift_detector(2048)     # :146-147
         self.matcher = DescriptorRatioMatcher(0.8)                                          # :145
 

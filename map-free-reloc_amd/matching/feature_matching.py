@@ -7,8 +7,8 @@ pixel frame, N may be 0 (np.array([])).  Mirrors lib/models/matching/feature_mat
   SuperGlueMatching    NEW: online SuperPoint+SuperGlue on the GPU (the reference only has it
                        offline, etc/feature_matching_baselines/matchers.py:62-120)
   LoFTRMatching        NEW: online LoFTR on the GPU (reference: offline only, matchers.py:12-59)
-  SIFTMatching         feature_matching.py:53-118: detectAndCompute from OpenCV (or a caller-supplied
-                       detector; raises ImportError when neither exists), rootSIFT + exact 2-NN + ratio
+  SIFTMatching         feature_matching.py:53-118: detectAndCompute from OpenCV, the HIP detector (SIFT.DETECTOR 'hip',
+                       sift_ops.py) or a caller-supplied detector (raises ImportError when none exists), rootSIFT + exact 2-NN + ratio
                        test on the GPU (csrc/descriptor_match.hip) instead of FLANN
 """
 import numpy as np
@@ -217,7 +217,13 @@ class SIFTMatching:
     def __init__(self, cfg, detector=None):
         from ..descriptor_ops import DescriptorRatioMatcher
         self.ratio_threshold = cfg.SIFT.RATIO_THRESHOLD
-        self.detector = detector if detector is not None else _cv_sift_detector(cfg.SIFT.NUM_FEATURES)
+        if detector is None:
+            if cfg.SIFT.get("DETECTOR", "opencv") == "hip":                 # keypoints + descriptors on the GPU (csrc/sift.hip)
+                from ..sift_ops import SiftDetector
+                detector = SiftDetector(cfg.SIFT.NUM_FEATURES).per_image
+            else:
+                detector = _cv_sift_detector(cfg.SIFT.NUM_FEATURES)
+        self.detector = detector
         self.matcher = DescriptorRatioMatcher(self.ratio_threshold)
         self.debug = cfg.DEBUG
 

@@ -318,7 +318,7 @@ class _RefCachedSuperGlue:
 
 class FusedPosePipeline:
     """The batched twin of FeatureMatchingModel (lib/models/matching/model.py:7-40): the same two config keys pick the
-    stages -- FEATURE_MATCHING in {'Precomputed', 'SuperGlue', 'LoFTR'} x POSE_SOLVER in {'PNP', 'EssentialMatrix',
+    stages -- FEATURE_MATCHING in {'Precomputed', 'SuperGlue', 'LoFTR', 'SIFT' (SIFT.DETECTOR 'hip')} x POSE_SOLVER in {'PNP', 'EssentialMatrix',
     'EssentialMatrixMetric', 'Procrustes'} -- but every stage consumes / produces a device-resident batch of pairs.
     __call__(batch) with the dict PairBatchLoader yields -> dict(R [b,3,3] f64, t [b,3] f64, n_inliers, status, n_corr)."""
 
@@ -370,8 +370,11 @@ class FusedPosePipeline:
             from .nets.loftr import LoFTRHIP
             lp.loftr, lp.pad_to, lp.device = LoFTRHIP(sd, self.device), 8, self.device
             self.match = lambda b: lp.match(b["images"])
+        elif fm == "SIFT" and cfg.SIFT.get("DETECTOR", "opencv") == "hip":
+            from .sift_ops import SiftDetector, sift_ratio_stage
+            self.match = sift_ratio_stage(SiftDetector(cfg.SIFT.NUM_FEATURES, self.device), cfg.SIFT.RATIO_THRESHOLD)
         else:
-            raise NotImplementedError(f"FEATURE_MATCHING={fm!r} has no batched stage (SIFT detection is OpenCV / per pair)")
+            raise NotImplementedError(f"FEATURE_MATCHING={fm!r} has no batched stage (SIFT with DETECTOR 'opencv' is OpenCV / per pair)")
         ps = cfg.POSE_SOLVER
         if ps == "PNP":
             pnp = ops.PnPBatchSolver(cfg.PNP.RANSAC_ITER, cfg.PNP.REPROJECTION_INLIER_THRESHOLD, cfg.PNP.CONFIDENCE, seed)
