@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define MFR_ABI_VERSION 6   /* 6 (round 6): mfr_conv3x3_direct_f16x2*, later (additive) the SIFT detector mfr_sift_*, mfr_conv3x3s2_direct_f16x2, mfr_mlp_ln_*; 5 (round 6): mfr_f16x2_guard_bind (the f16x2 range guard); 2: intrinsics as (const void *K, int k_dtype) instead of const float *; 3: mfr_emat_solve_batch takes the
+#define MFR_ABI_VERSION 6   /* 6 (round 6): mfr_conv3x3_direct_f16x2*, later (additive) the SIFT detector mfr_sift_*, the JPEG decoder mfr_jpeg_*, mfr_conv3x3s2_direct_f16x2, mfr_mlp_ln_*; 5 (round 6): mfr_f16x2_guard_bind (the f16x2 range guard); 2: intrinsics as (const void *K, int k_dtype) instead of const float *; 3: mfr_emat_solve_batch takes the
                              * model-quality method (MAGSAC++ / count) and its table; 4 (round 5): the f16x2 entry points (mfr_gemm_f16x2*,
                              * mfr_wino_f16x2_*, mfr_conv3x3_wino_f16x2, mfr_conv_igemm_f16x2), mfr_sg_attention_variant renumbered (0 f16x2,
                              * 1 exact fp32, 2 bf16x3), the measurement-only entry points (mfr_conv3x3_wino_bf16x3_variant,
@@ -500,6 +500,25 @@ int mfr_sift_blur_taps(int level, float *taps_host, int *radius_host);
 int mfr_sift_detect(const uint8_t *gray, int B, int H, int W, int nfeatures, int Nmax, int cand_cap, void *workspace,
                     size_t workspace_bytes, float *kpts, float *desc, float *size, float *angle, float *response,
                     int32_t *octave, int32_t *n, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Baseline JPEG decode (csrc/jpeg.hip): sequential, Huffman-coded, 8-bit files -> the loaders' gray plane, bit for bit
+ * datasets.read_gray_plane(path, None) (PIL's RGB decode: libjpeg-turbo JDCT_ISLOW + fancy upsampling, then luma_u8, / 255f).
+ * Call site: the batched loaders of predict_fused with HIP.JPEG_DECODE 'device' (datasets.PairBatchLoader / DevicePrefetcher,
+ * jpeg_ops.JpegDecoder).  The host half is csrc/host_decode.c mfr_host_jpeg_parse (libmfr_host.so), which writes one
+ * mfr_jpeg_header and one record per file (include/mfr_jpeg.h).  Added to ABI v6 without a version bump (purely additive).
+ *   mfr_jpeg_workspace_bytes  workspace of mfr_jpeg_decode for n images of H x W whose records are at most max_record_bytes,
+ *                             at subsequence length subseq_bits (0 = the default); 0 for unsupported arguments
+ *   mfr_jpeg_decode           headers [n] (device), records (device, offsets [n+1] i64 bytes, each a multiple of 16) ->
+ *                             gray [n,1,H,W] f32, rgb [n,H,W,3] u8 (may be NULL), status [n] (0 ok; a parse code of the
+ *                             header passed through, its image untouched; MFR_JPEG_E_* bits from the device: that image's
+ *                             planes are undefined), rounds [n] (may be NULL: the entropy stage's fixed-point rounds, a debug
+ *                             counter).  subseq_bits: test-only subsequence length in bits (0 = default, >= 16 otherwise).
+ */
+size_t mfr_jpeg_workspace_bytes(int n, int H, int W, long long max_record_bytes, int subseq_bits);
+int mfr_jpeg_decode(const void *headers, const uint8_t *records, const long long *offsets, int n, int H, int W,
+                    long long max_record_bytes, float *gray, uint8_t *rgb, int32_t *status, int32_t *rounds, void *workspace,
+                    size_t workspace_bytes, int subseq_bits, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * 3x3 / stride 1 / pad 1 convolutions of the SuperPoint encoder (conv1b..conv4b, convPa, convDa; same

@@ -112,6 +112,8 @@ SIGNATURES = {
     "mfr_sift_level_offset": (C.c_longlong, [_i, _i, _i, _i, _i, _vp, _vp]),
     "mfr_sift_blur_taps": (_i, [_i, _vp, _vp]),
     "mfr_sift_detect": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mfr_jpeg_workspace_bytes": (_sz, [_i, _i, _i, C.c_longlong, _i]),
+    "mfr_jpeg_decode": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
     "mfr_scale_workspace_bytes": (_sz, [_i, _i]),
     "mfr_scale_from_depth_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp,
                                         _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),

@@ -17,6 +17,10 @@ keys this implementation adds (declared here because unknown keys are rejected o
                      LOADER_DECODE: 'process' | 'thread' -- who decodes the JPEG / PNG files of predict_fused's batches: forked worker
                      processes writing into pinned shared-memory batch slots (default; 820 vs 437 pairs/s on the 16-CPU GPU box,
                      profiles/r04_fused_split_1gpu_sg_pnp_{process,thread}.json) or a thread pool under one interpreter lock (datasets.py);
+                     JPEG_DECODE: 'host' | 'device' -- orthogonal to LOADER_DECODE: 'host' (default) decodes the JPEGs with PIL on those workers;
+                     'device' has them only parse baseline JPEGs into packed slots that DevicePrefetcher decodes on the GPU (jpeg_ops.py,
+                     csrc/jpeg.hip; same planes bit for bit); other files, depth PNGs and resized / synthetic scenes stay on the host route;
+                     validated by datasets.check_jpeg_decode;
                      CONV / CONV_KERNEL / FUSED_CONV_RELU / RPR_CONV / RPR_CONV_BWD / RPR_CONV_ORDER / RPR_WGRAD_SPLITS: which of two
                      implementations of a layer runs (A/B measurement, parity tests) -- options.py lists values and defaults
   LOFTR.WEIGHTS      checkpoint of the online LoFTR matcher ('LoFTR' feature matching)
@@ -77,7 +81,7 @@ def get_cfg_defaults():
     # ---- additions of this implementation ----
     c.RANSAC = CN(); c.RANSAC.SEED = 0
     c.HIP = CN(); c.HIP.BATCH_PAIRS = 16; c.HIP.MAX_KEYPOINTS = 1024; c.HIP.MAX_CORRESPONDENCES = 8192; c.HIP.GRAPH_BATCH1 = True; c.HIP.GRAPH_FUSED = False
-    c.HIP.EMAT_SCORE = 'magsac'; c.HIP.MAGSAC_MAX_THR_RATIO = 1.0; c.HIP.REF_FEATURE_CACHE = True; c.HIP.LOADER_DECODE = 'process'; c.HIP.LOADER_WORKERS = 0
+    c.HIP.EMAT_SCORE = 'magsac'; c.HIP.MAGSAC_MAX_THR_RATIO = 1.0; c.HIP.REF_FEATURE_CACHE = True; c.HIP.LOADER_DECODE = 'process'; c.HIP.JPEG_DECODE = 'host'; c.HIP.LOADER_WORKERS = 0
     from .. import options as _opt                     # kernel-selection options (options.py): declared with their defaults, applied by apply_cfg
     for _k in _opt.names():
         c.HIP[_k] = _opt.default(_k)

@@ -178,7 +178,8 @@ _HOST_LIB = False           # False = not looked for yet, None = absent (numpy e
 
 
 def _host_lib():
-    """csrc/libmfr_host.so (host_decode.c: the loaders' two per-pixel loops in C), or None -- then the numpy expressions run"""
+    """csrc/libmfr_host.so (host_decode.c: the loaders' two per-pixel loops in C, ABI 3: and the JPEG parse of jpeg_ops), or None -- then the
+    numpy expressions run"""
     global _HOST_LIB
     if _HOST_LIB is False:
         import ctypes
@@ -188,7 +189,10 @@ def _host_lib():
             vp, sz = ctypes.c_void_p, ctypes.c_size_t
             lib.mfr_host_gray_from_rgb.argtypes = [vp, sz, vp, vp]; lib.mfr_host_gray_from_rgb.restype = None
             lib.mfr_host_depth_from_u16.argtypes = [vp, sz, vp, vp]; lib.mfr_host_depth_from_u16.restype = None
-            _HOST_LIB = lib if lib.mfr_host_abi_version() == 2 else None
+            lib.mfr_host_jpeg_parse.argtypes = [vp, sz, vp, vp, sz, vp]; lib.mfr_host_jpeg_parse.restype = ctypes.c_int
+            lib.mfr_host_jpeg_record_bound.argtypes = [sz, ctypes.c_int]; lib.mfr_host_jpeg_record_bound.restype = sz
+            lib.mfr_host_jpeg_header_bytes.argtypes = []; lib.mfr_host_jpeg_header_bytes.restype = sz
+            _HOST_LIB = lib if lib.mfr_host_abi_version() == 3 else None
         except (OSError, AttributeError):
             _HOST_LIB = None
     return _HOST_LIB
@@ -352,12 +356,14 @@ class MapFreeScene:
                     _FRAME_CACHE.popitem(last=False)
         return img, d
 
-    def _gray_frame(self, rel, keep=False, out_g=None, out_d=None):
+    def _gray_frame(self, rel, keep=False, out_g=None, out_d=None, reader=None):
         """(gray plane [h,w] f32, depth [h,w] f32 or None) of one frame as numpy arrays -- to_gray(image) / depth of _frame(rel), bit for bit at
         the file's own size (gray_pair, the only caller, refuses other sizes), without the float RGB image, decoded straight into out_g / out_d when given; keep=True: the same small least-recently-used cache as
         _frame under its own keys (the cached arrays are copied into out_g / out_d)"""
         path = os.path.join(self.scene_root, rel)
         dpath = path.replace(".jpg", f".{self.estimated_depth}.png") if self.estimated_depth is not None else None
+        if reader is not None:                                  # the device JPEG route: the reader prepares the file for the device
+            return (reader(path, out_g) if out_g is not None else None), (read_depth_plane(dpath, out_d) if dpath else None)
         if not keep:
             return read_gray_plane(path, self.resize, out_g), (read_depth_plane(dpath, out_d) if dpath else None)
         try:
@@ -393,19 +399,21 @@ class MapFreeScene:
         route, so the batched loaders, the reference-view cache and the per-pair plugin see ONE plane."""
         return self.resize is None or all(sz == (int(self.resize[0]), int(self.resize[1])) for sz in self._file_sizes)
 
-    def gray_pair(self, index, want_ref=True, out=None):
+    def gray_pair(self, index, want_ref=True, out=None, readers=None):
         """what the batched loaders need of sample `index`: (gray0 or None, depth0, gray1, depth1, K0, K1, pair_id, (name0, name1)), numpy arrays
         with the values of to_gray(self[index]['image0' / 'image1']) and its depth maps -- bit for bit AT THE FILES' OWN SIZE, the only case this
         route serves (resize_is_native(); otherwise None).  out = (g0, d0, g1, d1) destination arrays (entries
         may be None): the planes are then decoded / copied straight into them.  Returns None when this scene's images are not plain RGB reads
-        (black_white training transform): the caller takes the generic sample then."""
+        (black_white training transform): the caller takes the generic sample then.  readers = (reader0, reader1): callables (path, out_g)
+        that take the place of read_gray_plane for the two frames (the device JPEG route, _jpeg_reader); depth is read as usual."""
         if self.black_white or not self.resize_is_native():
             return None
         sa, ia, sb, ib = self.pairs[index]
         p1, p2 = f"seq{sa}/frame_{ia:05}.jpg", f"seq{sb}/frame_{ib:05}.jpg"
         og0, od0, og1, od1 = out if out is not None else (None, None, None, None)
-        g0, d0 = self._gray_frame(p1, keep=True, out_g=og0 if want_ref else None, out_d=od0)
-        g1, d1 = self._gray_frame(p2, out_g=og1, out_d=od1)
+        r0, r1 = readers if readers is not None else (None, None)
+        g0, d0 = self._gray_frame(p1, keep=True, out_g=og0 if want_ref else None, out_d=od0, reader=r0)
+        g1, d1 = self._gray_frame(p2, out_g=og1, out_d=od1, reader=r1)
         return (g0 if want_ref else None, d0, g1, d1, self.K[p1].copy(), self.K[p2].copy(), index * self.sample_factor, (p1, p2))
 
     def __getitem__(self, index):
@@ -581,6 +589,34 @@ def to_gray(img):
 # as pinned host memory, so the H2D copy of a slot is an asynchronous DMA exactly as from a pinned buffer.
 _PW = {}
 
+JPEG_DECODE_MODES = ("host", "device")
+JPEG_RECORD_CAP = 256 << 10    # bytes of a frame's slot on the device JPEG route (header parse output); a larger file takes the host route
+
+
+def check_jpeg_decode(mode):
+    """HIP.JPEG_DECODE: 'host' (PIL on the decode workers, the default) | 'device' (workers parse the JPEG, jpeg_ops decodes it on the GPU)"""
+    if mode not in JPEG_DECODE_MODES:
+        raise ValueError(f"HIP.JPEG_DECODE must be one of {JPEG_DECODE_MODES}, got {mode!r}")
+    return mode
+
+
+def _jpeg_reader(hdr, rec, row, info):
+    """gray_pair reader of the device JPEG route for batch row `row`: the file's header + record go to hdr[row] / rec[row] and
+    info[row] = (0, record bytes, path); a file the device does not take (unsupported, invalid, above the slot's cap) is decoded here as on the
+    host route, into the row's plane, and info[row] = (parse status, 0, path)"""
+    def read(path, out_g):
+        from . import jpeg_ops as J
+        with open(path, "rb") as f:
+            data = f.read()
+        st, nb = J.parse_into(data, hdr[row], rec[row])
+        if st == J.OK:
+            info[row] = (0, nb, path)
+        else:
+            read_gray_plane(path, None, out_g)
+            info[row] = (st, 0, path)
+        return out_g
+    return read
+
 
 def _slot_views(flat, n_slots, B, Hh, Ww, has_depth):
     """carve the ring's batch slots out of ONE shared tensor (one shared-memory segment = one descriptor per worker)"""
@@ -595,7 +631,15 @@ def _slot_views(flat, n_slots, B, Hh, Ww, has_depth):
     return out
 
 
-def _pw_init(scenes, flat, layout):
+def _jpeg_views(jflat, n_slots, B, cap):
+    """per slot: (headers u8 [2B, HEADER_BYTES], records u8 [2B, cap]) of the device JPEG route, out of one shared byte tensor"""
+    from .jpeg_ops import HEADER_BYTES
+    per = 2 * B * (HEADER_BYTES + cap)
+    return [(jflat[k * per:k * per + 2 * B * HEADER_BYTES].view(2 * B, HEADER_BYTES), jflat[k * per + 2 * B * HEADER_BYTES:(k + 1) * per].view(2 * B, cap))
+            for k in range(n_slots)]
+
+
+def _pw_init(scenes, flat, layout, jflat=None, jcap=0):
     # Everything inherited from the parent becomes permanent in this process: a garbage-collection pass of the child must never finalise the
     # PARENT's objects -- a dead multiprocessing.Pool of an earlier loader among them, whose __del__ writes to a queue under a lock that a
     # thread of the parent may have held at fork time (the child then waits for it for ever: round 5's first full CPU test run hung exactly
@@ -604,6 +648,7 @@ def _pw_init(scenes, flat, layout):
     gc.freeze()
     torch.set_num_threads(1)
     _PW["scenes"], _PW["slots"] = scenes, _slot_views(flat, *layout)
+    _PW["jslots"] = _jpeg_views(jflat, layout[0], layout[1], jcap) if jflat is not None else None
 
 
 def _pw_fill(task):
@@ -616,11 +661,15 @@ def _pw_fill(task):
     im = sl["images"].numpy()
     if getattr(sc, "has_gray_pair", False):                 # gray planes / depth straight from the files' bytes into the slot (MapFreeScene)
         has_d = sl["depth0"] is not None
+        info, readers = {}, None
+        if _PW["jslots"] is not None:                        # device JPEG route: headers + records into the slot's packed buffers
+            hdr, rec = (t.numpy() for t in _PW["jslots"][k])
+            readers = (_jpeg_reader(hdr, rec, 2 * p, info), _jpeg_reader(hdr, rec, 2 * p + 1, info))
         fast = sc.gray_pair(i, want_ref, out=(im[2 * p, 0], sl["depth0"].numpy()[p] if has_d else None, im[2 * p + 1, 0],
-                                              sl["depth1"].numpy()[p] if has_d else None))
+                                              sl["depth1"].numpy()[p] if has_d else None), readers=readers)
         if fast is not None:
             _, _, _, _, K0, K1, pid, (n0, n1) = fast
-            return (np.asarray(K0), np.asarray(K1), int(pid), n1, n0, _t.perf_counter() - t0)
+            return (np.asarray(K0), np.asarray(K1), int(pid), n1, n0, _t.perf_counter() - t0, info)
     smp = sc[i]
     npv = lambda t: t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
     if want_ref:
@@ -629,7 +678,7 @@ def _pw_fill(task):
     if sl["depth0"] is not None and smp["depth0"].numel() > 0:
         sl["depth0"].numpy()[p] = npv(smp["depth0"]); sl["depth1"].numpy()[p] = npv(smp["depth1"])
     return (np.asarray(smp["K_color0"]), np.asarray(smp["K_color1"]), int(smp["pair_id"]), smp["pair_names"][1], smp["pair_names"][0],
-            _t.perf_counter() - t0)
+            _t.perf_counter() - t0, {})
 
 
 def _pw_ping(i):
@@ -640,16 +689,23 @@ class _ProcessDecoder:
     """pool of decode processes + ring of shared-memory batch slots (see above).  A slot is reused only after the H2D copies issued from it
     have completed (DevicePrefetcher stores its event in `events[k]`)."""
 
-    def __init__(self, scenes, B, Hh, Ww, has_depth, workers, n_slots, pin):
+    def __init__(self, scenes, B, Hh, Ww, has_depth, workers, n_slots, pin, jpeg_cap=0):
         import torch.multiprocessing as mp
         layout = (n_slots, B, Hh, Ww, has_depth)
         per = 2 * B * Hh * Ww + (2 * B * Hh * Ww if has_depth else 0)
         self.flat = torch.empty(n_slots * per, dtype=torch.float32).share_memory_()
         self.slots = _slot_views(self.flat, *layout)
+        self.jflat, self.jslots = None, None
+        if jpeg_cap:                                           # the device JPEG route's packed headers + records, one more shared segment
+            from .jpeg_ops import HEADER_BYTES
+            self.jflat = torch.empty(n_slots * 2 * B * (HEADER_BYTES + jpeg_cap), dtype=torch.uint8).share_memory_()
+            self.jslots = _jpeg_views(self.jflat, n_slots, B, jpeg_cap)
         self.events = [None] * n_slots
-        self.pinned = False
+        self.pinned = self.jpinned = False
         if pin and torch.cuda.is_available():
             self.pinned = int(torch.cuda.cudart().cudaHostRegister(self.flat.data_ptr(), self.flat.numel() * 4, 0)) == 0
+            if self.jflat is not None:
+                self.jpinned = int(torch.cuda.cudart().cudaHostRegister(self.jflat.data_ptr(), self.jflat.numel(), 0)) == 0
         # the look-up tables and the C helper are set up BEFORE the fork (inherited, not rebuilt per worker), and cyclic garbage of earlier
         # loaders (their pools) is finalised here, in the parent, not in a child (see _pw_init)
         import gc
@@ -658,7 +714,7 @@ class _ProcessDecoder:
         # FORK, like torch's DataLoader workers: the children inherit the scene objects and the shared segment without re-importing anything
         # (spawned workers each re-imported torch: 36 s to start 32 of them under a 16-CPU container quota, tools/bench_fused_split.py) and
         # never touch the HIP runtime -- they run PIL / zlib / numpy only
-        self.pool = mp.get_context("fork").Pool(workers, initializer=_pw_init, initargs=(scenes, self.flat, layout))
+        self.pool = mp.get_context("fork").Pool(workers, initializer=_pw_init, initargs=(scenes, self.flat, layout, self.jflat, jpeg_cap))
         self.next = 0
 
     def acquire(self):
@@ -678,6 +734,9 @@ class _ProcessDecoder:
         if self.pinned:
             torch.cuda.cudart().cudaHostUnregister(self.flat.data_ptr())
             self.pinned = False
+        if self.jpinned:
+            torch.cuda.cudart().cudaHostUnregister(self.jflat.data_ptr())
+            self.jpinned = False
 
 
 class PairBatchLoader:
@@ -692,15 +751,21 @@ class PairBatchLoader:
     global_ids [b] i64, names [b], scene_ids [b] / scene_roots [b] (per pair), scenes_done (ids of the scenes whose LAST pair is in
     this batch), scene_id / scene_root / last_of_scene (of the batch's last pair, kept for single-scene consumers))."""
 
-    def __init__(self, scenes, batch_pairs=32, prefetch=2, pin=None, global_offsets=None, workers=8, span_scenes=True, decode="thread"):
+    def __init__(self, scenes, batch_pairs=32, prefetch=2, pin=None, global_offsets=None, workers=8, span_scenes=True, decode="thread",
+                 jpeg_decode="host", jpeg_cap=JPEG_RECORD_CAP):
         """workers: decode threads per batch (PIL / zlib / numpy release the GIL): a pair is two JPEGs + one or two 16-bit PNGs,
-        ~12 ms of decode on one core, so one thread feeds ~80 pairs/s where the fused pipeline consumes ~700"""
+        ~12 ms of decode on one core, so one thread feeds ~80 pairs/s where the fused pipeline consumes ~700.
+        jpeg_decode 'device' (HIP.JPEG_DECODE): on the fast route (gray_pair: MapFreeScene files at their own size) the workers only parse
+        the JPEGs into packed header / record slots of `jpeg_cap` bytes per frame and the batch carries them under "jpeg"; DevicePrefetcher
+        decodes them on the GPU (jpeg_ops).  Frames the device does not take are decoded on the host as before; other routes are unchanged."""
         self.scenes, self.B, self.prefetch = list(scenes), int(batch_pairs), int(prefetch)
         self.workers = max(1, int(workers))
         self._pool = None
         if decode not in ("thread", "process"):
             raise ValueError(f"PairBatchLoader: decode must be 'thread' or 'process', got {decode!r}")
         self.decode, self._proc = decode, None
+        self.jpeg_decode = check_jpeg_decode(jpeg_decode)
+        self.jpeg_cap = (int(jpeg_cap) + 15) // 16 * 16
         self.stats = {}                                        # process decoder: pool start, time in pool.map, summed worker task time, ...
         self.pin = torch.cuda.is_available() if pin is None else pin
         self.offsets = global_offsets
@@ -762,13 +827,21 @@ class PairBatchLoader:
         d0_np, d1_np = (depth0.numpy(), depth1.numpy()) if has_depth else (None, None)
         gray_of = {}                                           # id(map-frame tensor) -> (the tensor, its gray plane): one conversion per scene
                                                                # keyframe; the tensor is held so that its id cannot be reused inside the batch
+        jp = self._jpeg_batch(items, mk) if self.jpeg_decode == "device" else None
 
         def fill(p, smp=None):
             sc_ = self.scenes[items[p][0]]
             if smp is None and getattr(sc_, "has_gray_pair", False):      # gray planes / depth straight from the files' bytes into the batch buffers
-                fast = sc_.gray_pair(items[p][1], True, out=(im_np[2 * p, 0], d0_np[p] if has_depth else None, im_np[2 * p + 1, 0],
-                                                             d1_np[p] if has_depth else None))
+                want, readers = True, None
+                if jp is not None:
+                    want = jp["want"][p]
+                    h_np, r_np = jp["headers"].numpy(), jp["records"].numpy()
+                    readers = (_jpeg_reader(h_np, r_np, 2 * p, jp["rows"]), _jpeg_reader(h_np, r_np, 2 * p + 1, jp["rows"]))
+                fast = sc_.gray_pair(items[p][1], want, out=(im_np[2 * p, 0], d0_np[p] if has_depth else None, im_np[2 * p + 1, 0],
+                                                             d1_np[p] if has_depth else None), readers=readers)
                 if fast is not None:
+                    if not want:
+                        jp["rows"][2 * p] = ("dup", 2 * jp["first_of"][jp["key"][p]])
                     _, _, _, _, K0_, K1_, pid, (n0, n1) = fast
                     return (torch.as_tensor(K0_), torch.as_tensor(K1_), int(pid), n1, n0)
             smp = get(items[p]) if smp is None else smp
@@ -797,7 +870,8 @@ class PairBatchLoader:
             K0[p] = m[0]; K1[p] = m[1]
         sc = self.scenes[items[-1][0]]
         done = [self.scenes[si].scene_id for si, i in items if i == len(self.scenes[si]) - 1]
-        return dict(images=images, depth0=depth0, depth1=depth1, K0=K0, K1=K1,
+        extra = {} if jp is None else dict(jpeg=dict(headers=jp["headers"], records=jp["records"], rows=jp["rows"]))
+        return dict(images=images, depth0=depth0, depth1=depth1, K0=K0, K1=K1, **extra,
                     seed_ids=torch.tensor([m[2] for m in meta], dtype=torch.int64),
                     global_ids=torch.tensor([self.offsets[si] + i for si, i in items], dtype=torch.int64),
                     names=[m[3] for m in meta], scene_ids=[self.scenes[si].scene_id for si, _ in items],
@@ -808,6 +882,24 @@ class PairBatchLoader:
                     ref_keys=[self._ref_key(si, m[4]) if getattr(self.scenes[si], "shared_reference", False) else None
                               for (si, _), m in zip(items, meta)],
                     scene_id=sc.scene_id, scene_root=sc.scene_root, scene_index=items[-1][0], last_of_scene=bool(done and done[-1] == sc.scene_id))
+
+    def _jpeg_batch(self, items, mk=None, slot=None):
+        """device JPEG route of one batch: packed buffers (fresh pinned ones, or a process slot's), the row table (None = host plane in
+        `images`; (status, record bytes, path) from _jpeg_reader; ("dup", row) = device copy of that row) and the reference views to decode:
+        one per distinct (scene, shared reference), as the process decoder's want_ref"""
+        from .jpeg_ops import HEADER_BYTES
+        b = len(items)
+        if slot is None:
+            headers, records = mk(2 * b, HEADER_BYTES, dtype=torch.uint8), mk(2 * b, self.jpeg_cap, dtype=torch.uint8)
+        else:
+            headers, records = slot
+        first_of, want, key = {}, [], []
+        for p, (si, i) in enumerate(items):
+            k = si if getattr(self.scenes[si], "shared_reference", False) else ("pair", p)
+            key.append(k)
+            want.append(k not in first_of)
+            first_of.setdefault(k, p)
+        return dict(headers=headers, records=records, rows=[None] * (2 * b), want=want, key=key, first_of=first_of)
 
     POOL_ANSWER_S = 600.0            # a batch is < 1 s of decode; a pool that stays silent this long is dead (never wait for it for ever)
 
@@ -829,7 +921,8 @@ class PairBatchLoader:
             t0 = _t.perf_counter()
             first = self.scenes[items[0][0]][items[0][1]]
             Hh, Ww = first["image0"].shape[-2:]
-            self._proc = _ProcessDecoder(self.scenes, self.B, Hh, Ww, first["depth0"].numel() > 0, self.workers, max(self.prefetch, 0) + 4, self.pin)
+            self._proc = _ProcessDecoder(self.scenes, self.B, Hh, Ww, first["depth0"].numel() > 0, self.workers, max(self.prefetch, 0) + 4, self.pin,
+                                         jpeg_cap=self.jpeg_cap if self.jpeg_decode == "device" else 0)
             self._pool_map(_pw_ping, range(self.workers * 2))                          # every worker has started and imported its modules
             st["process_pool_start_s"] = _t.perf_counter() - t0
         pr = self._proc
@@ -845,13 +938,21 @@ class PairBatchLoader:
             want.append(key not in first_of)
             first_of.setdefault(key, p)
         meta = self._pool_map(_pw_fill, [(k, p, si, i, want[p]) for p, (si, i) in enumerate(items)])
+        jp = None
+        if pr.jslots is not None:
+            jp = self._jpeg_batch(items, slot=pr.jslots[k])
+            for p, m in enumerate(meta):
+                for r, v in m[6].items():
+                    jp["rows"][r] = v
+                if not want[p] and jp["rows"][2 * p + 1] is not None:     # a device-route pair whose reference is decoded in another row
+                    jp["rows"][2 * p] = ("dup", 2 * first_of[items[p][0]])
         st["decode_map_s"] = st.get("decode_map_s", 0.0) + _t.perf_counter() - t0
         st["worker_task_s"] = st.get("worker_task_s", 0.0) + sum(m[5] for m in meta)
         st["batches"] = st.get("batches", 0) + 1
         t0 = _t.perf_counter()
         im = sl["images"].numpy()
         for p, (si, i) in enumerate(items):
-            if not want[p]:
+            if not want[p] and (jp is None or jp["rows"][2 * p] is None):
                 q = first_of[si]
                 np.copyto(im[2 * p, 0], im[2 * q, 0])
         st["ref_copy_s"] = st.get("ref_copy_s", 0.0) + _t.perf_counter() - t0
@@ -859,8 +960,9 @@ class PairBatchLoader:
         sc = self.scenes[items[-1][0]]
         done = [self.scenes[si].scene_id for si, i in items if i == len(self.scenes[si]) - 1]
         has_depth = sl["depth0"] is not None
+        extra = {} if jp is None else dict(jpeg=dict(headers=jp["headers"], records=jp["records"], rows=jp["rows"]))
         return dict(images=sl["images"][:2 * b], depth0=sl["depth0"][:b] if has_depth else None, depth1=sl["depth1"][:b] if has_depth else None,
-                    K0=K0, K1=K1, seed_ids=torch.tensor([m[2] for m in meta], dtype=torch.int64),
+                    K0=K0, K1=K1, **extra, seed_ids=torch.tensor([m[2] for m in meta], dtype=torch.int64),
                     global_ids=torch.tensor([self.offsets[si] + i for si, i in items], dtype=torch.int64),
                     names=[m[3] for m in meta], scene_ids=[self.scenes[si].scene_id for si, _ in items],
                     scene_roots=[self.scenes[si].scene_root for si, _ in items], scenes_done=done,
@@ -918,16 +1020,61 @@ class DevicePrefetcher:
         self.loader, self.device = loader, torch.device(device)
         self.stream = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
 
+    _jdec = None
+
     def _put(self, hb):
         if self.stream is None:
-            return dict(hb), None
+            if "jpeg" in hb:
+                from ._lib import MfrLibraryError
+                raise MfrLibraryError("the device JPEG route needs a HIP device (there is no CPU fallback)")
+            return dict(hb), None, None
         with torch.cuda.stream(self.stream):
-            db = {k: (v.to(self.device, non_blocking=True) if isinstance(v, torch.Tensor) else v) for k, v in hb.items() if k != "_slot"}
+            skip = ("_slot", "jpeg", "images") if "jpeg" in hb else ("_slot",)
+            db = {k: (v.to(self.device, non_blocking=True) if isinstance(v, torch.Tensor) else v) for k, v in hb.items() if k not in skip}
+            check = self._put_jpeg(hb, db) if "jpeg" in hb else None
             ev = torch.cuda.Event(); ev.record(self.stream)
             if "_slot" in hb:                                  # shared-memory slot of the process decoder: reusable once these copies are done
                 pr, k = hb["_slot"]
                 pr.events[k] = ev
-        return db, ev
+        return db, ev, check
+
+    def _put_jpeg(self, hb, db):
+        """device JPEG route (on the side stream): host planes of the rows the host decoded, then the packed headers / records of the others
+        and the decode kernels straight into the batch's device images, then the duplicated reference rows.  The per-image status goes to a
+        pinned word array that _ready checks when the batch is handed out."""
+        from . import jpeg_ops as J
+        jp, images = hb["jpeg"], hb["images"]
+        n2, (H, W) = images.shape[0], images.shape[-2:]
+        rows = jp["rows"]
+        d_img = torch.empty((n2, 1, H, W), dtype=torch.float32, device=self.device)
+        dev_rows = [r for r in range(n2) if rows[r] is not None and rows[r][0] == 0]
+        for r in range(n2):
+            if rows[r] is None or (rows[r][0] not in ("dup", 0)):
+                d_img[r].copy_(images[r], non_blocking=True)
+        h_status = None
+        if dev_rows:
+            if self._jdec is None:
+                self._jdec = J.JpegDecoder(self.device)
+            hdr, rec = jp["headers"][:n2], jp["records"][:n2]
+            st_field = hdr.numpy()[:, :4].view(np.int32)            # rows the device must not touch are marked unsupported
+            for r in range(n2):
+                if r not in dev_rows:
+                    st_field[r, 0] = J.UNSUPPORTED
+            cap = rec.shape[1]
+            d_hdr = hdr.to(self.device, non_blocking=True)
+            d_rec = torch.empty(n2 * cap + 16, dtype=torch.uint8, device=self.device)
+            for r in dev_rows:
+                d_rec[r * cap:r * cap + rows[r][1]].copy_(rec[r, :rows[r][1]], non_blocking=True)
+            d_off = torch.arange(n2 + 1, dtype=torch.int64, device=self.device) * cap
+            d_st = torch.zeros(n2, dtype=torch.int32, device=self.device)
+            self._jdec.decode_device(d_hdr, d_rec, d_off, n2, H, W, cap, d_img, d_st)
+            h_status = torch.empty(n2, dtype=torch.int32, pin_memory=True)
+            h_status.copy_(d_st, non_blocking=True)
+        for r in range(n2):
+            if rows[r] is not None and rows[r][0] == "dup":
+                d_img[r].copy_(d_img[rows[r][1]], non_blocking=True)
+        db["images"] = d_img
+        return (h_status, [(r, rows[r][2]) for r in dev_rows]) if dev_rows else None
 
     def __iter__(self):
         nxt = None
@@ -939,7 +1086,13 @@ class DevicePrefetcher:
             yield self._ready(nxt)
 
     def _ready(self, item):
-        db, ev = item
+        db, ev, check = item
+        if check is not None:                                  # device JPEG statuses of this batch (its side-stream work is done first)
+            ev.synchronize()
+            st = check[0].numpy()
+            bad = [(path, int(st[r])) for r, path in check[1] if st[r] != 0]
+            if bad:
+                raise OSError(f"device JPEG decode failed for {bad[0][0]} (status {bad[0][1]:#x}; {len(bad)} frame(s) of the batch)")
         if ev is not None:
             torch.cuda.current_stream(self.device).wait_event(ev)
             for v in db.values():

@@ -1,0 +1,157 @@
+"""Baseline JPEG decode on the GPU (csrc/jpeg.hip, include/mfr_hip.h mfr_jpeg_*), with the header parse on the host (csrc/host_decode.c,
+libmfr_host.so mfr_host_jpeg_parse; layout in include/mfr_jpeg.h).  The result is the loaders' gray plane of the file,
+datasets.read_gray_plane(path, None), bit for bit: PIL's RGB decode (libjpeg-turbo, libjpeg 6.2 API: JDCT_ISLOW, fancy upsampling,
+no DCT scaling), then datasets.luma_u8, then / 255 in float32.  Torch only provides memory and the stream.
+
+| stage | what | where |
+|---|---|---|
+| parse | SOI / APPn / DQT / SOF0-1 (8-bit) / DHT / DRI / SOS / EOI; quantisation tables in natural order; canonical Huffman tables (T.81 C.2) as a 9-bit look-up plus maxcode per length; entropy data unstuffed, RSTn removed, one {byte offset, MCU count} per restart segment | host, plain C |
+| entropy | per restart segment, subsequences of S bits decoded speculatively from a guessed state (bit offset, zig-zag index, block in MCU) and re-decoded from their predecessor's exit state until nothing changes (Weissenberger & Schmidt 2018); exclusive scan of the blocks each subsequence completes; a final pass writes int16 coefficients, DC as differences | one workgroup per image |
+| DC | per-component prefix sum of the DC differences, reset at every restart segment | same workgroup |
+| IDCT | dequantise, libjpeg's JDCT_ISLOW integer inverse DCT (13-bit constants, 2 fractional bits between the passes), range-limit to u8 planes padded to whole MCUs | 8 lanes per block |
+| colour | libjpeg's fancy (triangle) upsampling for h2v1 / h2v2 (edges replicate the last real row / column), fixed-point YCbCr -> RGB (16-bit tables, ONE_HALF rounding), luma (19595 R + 38470 G + 7471 B + 2^15) >> 16, / 255f | one lane per pixel |
+
+Files the parse calls unsupported (progressive, arithmetic, 12-bit, multi-scan, CMYK / RGB colour, other sampling) are the caller's to decode on
+the host; `decode` reports them per image in `status` (1) and leaves their planes untouched.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+
+OK, UNSUPPORTED, INVALID, CAPACITY = 0, 1, 2, 3
+E_HUFF, E_TRUNC, E_SIZE = 0x10, 0x20, 0x40
+
+
+class Huff(C.Structure):
+    _fields_ = [("maxcode", C.c_int32 * 20), ("valoff", C.c_int32 * 20), ("fast", C.c_uint16 * 512), ("bits", C.c_uint8 * 16),
+                ("val", C.c_uint8 * 256)]
+
+
+class Header(C.Structure):
+    """include/mfr_jpeg.h mfr_jpeg_header"""
+    _fields_ = [(f, C.c_int32) for f in ("status", "width", "height", "ncomp", "hmax", "vmax", "mcus_x", "mcus_y", "blocks_per_mcu",
+                                         "restart_interval", "nseg", "total_mcus", "seg_table_bytes", "data_bytes", "record_bytes",
+                                         "adobe_transform")] + \
+               [(f, C.c_int32 * 4) for f in ("comp_id", "comp_h", "comp_v", "comp_tq", "comp_td", "comp_ta", "comp_bw", "comp_bh",
+                                             "comp_off", "plane_w", "plane_h", "plane_off", "down_w", "down_h")] + \
+               [("mcu_comp", C.c_int32 * 12), ("qt", (C.c_uint16 * 64) * 4), ("dc", Huff * 2), ("ac", Huff * 2)]
+
+
+HEADER_BYTES = C.sizeof(Header)
+
+
+def _host():
+    from . import datasets
+    lib = datasets._host_lib()
+    if lib is None:
+        raise _lib.MfrLibraryError("csrc/libmfr_host.so (ABI 3) not found: build it with __graft_entry__.build()")
+    assert lib.mfr_host_jpeg_header_bytes() == HEADER_BYTES, "jpeg_ops.Header does not mirror include/mfr_jpeg.h"
+    return lib
+
+
+def record_bound(nbytes, nseg=1):
+    """bytes a file of `nbytes` needs as a record when it has at most `nseg` restart segments (always enough: nseg <= nbytes)"""
+    return int(_host().mfr_host_jpeg_record_bound(int(nbytes), int(nseg)))
+
+
+def parse(data, cap=None):
+    """one file's bytes -> (status, Header, record u8 array or None).  cap: record buffer size (default: always enough)"""
+    lib = _host()
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    cap = record_bound(buf.size, buf.size // 3 + 1) if cap is None else int(cap)        # a segment takes >= 1 byte + its RSTn
+    rec = np.zeros(max(cap, 16), dtype=np.uint8)
+    h = Header()
+    nb = C.c_size_t(0)
+    st = lib.mfr_host_jpeg_parse(buf.ctypes.data, buf.size, C.byref(h), rec.ctypes.data, cap, C.byref(nb))
+    return st, h, (rec[:nb.value] if st == OK else None)
+
+
+def parse_into(data, header_row, slot):
+    """parse straight into a batch: header_row = u8 [HEADER_BYTES] view, slot = u8 view (16-aligned) -> (status, record bytes)"""
+    lib = _host()
+    buf = np.frombuffer(data, dtype=np.uint8)
+    nb = C.c_size_t(0)
+    st = lib.mfr_host_jpeg_parse(buf.ctypes.data, buf.size, header_row.ctypes.data, slot.ctypes.data, slot.size, C.byref(nb))
+    return st, nb.value
+
+
+class PackedBatch:
+    """a batch for the device: headers u8 [n, HEADER_BYTES], records u8 [sum] (each 16-aligned), offsets i64 [n + 1], parse status i32 [n]"""
+
+    def __init__(self, headers, records, offsets, status, H, W):
+        self.headers, self.records, self.offsets, self.status, self.H, self.W = headers, records, offsets, status, H, W
+
+    @property
+    def n(self):
+        return len(self.status)
+
+
+def pack(files, H=None, W=None):
+    """list of file bytes -> PackedBatch.  H, W: the batch's size (default: the first parsed file's; 0 x 0 when none parses)"""
+    heads, recs, status = [], [], []
+    for f in files:
+        st, h, rec = parse(f)
+        if st == OK and H is None:
+            H, W = h.height, h.width
+        heads.append(np.frombuffer(bytes(h), dtype=np.uint8))
+        recs.append(rec if rec is not None else np.zeros(0, np.uint8))
+        status.append(st)
+    offsets = np.zeros(len(files) + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum([r.size for r in recs])
+    return PackedBatch(np.stack(heads) if heads else np.zeros((0, HEADER_BYTES), np.uint8),
+                       np.concatenate(recs + [np.zeros(16, np.uint8)]), offsets, np.asarray(status, np.int32), H or 0, W or 0)
+
+
+class JpegDecoder:
+    """JpegDecoder(device).decode(files: list[bytes] | PackedBatch, out=None, rgb=False) -> (gray [n,1,H,W] f32, status [n] i32) on the
+    device (plus rgb [n,H,W,3] u8 with rgb=True).  status: 0 ok, 1 unsupported (host's to decode: its plane is left as it was), 2 / 3
+    invalid / capacity at the parse, E_HUFF / E_TRUNC / E_SIZE bits from the device.  subseq_bits: test-only subsequence length (0 =
+    default).  No CPU fallback: without libmfr_hip.so or a GPU it raises MfrLibraryError."""
+
+    def __init__(self, device="cuda", subseq_bits=0):
+        self.device = torch.device(device)
+        self.subseq_bits = int(subseq_bits)
+        self._ws = None
+        self.rounds = None
+
+    def workspace(self, n, H, W, max_record):
+        lib = _lib.load(require_gpu=True)
+        nb = lib.mfr_jpeg_workspace_bytes(n, H, W, int(max_record), self.subseq_bits)
+        if nb == 0:
+            raise ValueError(f"JPEG: unsupported batch {n}x{H}x{W}, record {max_record} B, S {self.subseq_bits}")
+        if self._ws is None or self._ws.numel() < nb:
+            self._ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def decode_device(self, headers, records, offsets, n, H, W, max_record, out, status, rgb=None):
+        """the device half on tensors already on the device (headers u8 [n, HEADER_BYTES], records u8, offsets i64 [n + 1]), launched on
+        torch's current stream; the workspace and the round counters are marked as used by that stream (the caching allocator then does
+        not hand them to other work before these launches are done, whichever stream allocated them)"""
+        lib = _lib.load(require_gpu=True)
+        ws = self.workspace(n, H, W, max_record)
+        self.rounds = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        cur = torch.cuda.current_stream(self.device)
+        _lib.check(lib.mfr_jpeg_decode(_lib.ptr(headers), _lib.ptr(records), _lib.ptr(offsets), n, H, W, int(max_record), _lib.ptr(out), _lib.ptr(rgb),
+                                       _lib.ptr(status), _lib.ptr(self.rounds), _lib.ptr(ws), ws.numel(), self.subseq_bits,
+                                       cur.cuda_stream), "mfr_jpeg_decode")
+        ws.record_stream(cur)
+        self.rounds.record_stream(cur)
+
+    def decode(self, files, out=None, rgb=False):
+        _lib.load(require_gpu=True)
+        pb = files if isinstance(files, PackedBatch) else pack(files)
+        n, H, W = pb.n, pb.H, pb.W
+        dev = self.device
+        if out is None:
+            out = torch.zeros(n, 1, H, W, dtype=torch.float32, device=dev)
+        assert out.shape == (n, 1, H, W) and out.dtype == torch.float32 and out.is_contiguous()
+        rgb_t = torch.zeros(n, H, W, 3, dtype=torch.uint8, device=dev) if rgb else None
+        status = torch.from_numpy(pb.status.copy()).to(dev)
+        if n and bool((pb.status == OK).any()):                # nothing the device takes (e.g. only progressive files): statuses only
+            max_rec = max(16, int(np.max(np.diff(pb.offsets))))
+            self.decode_device(torch.from_numpy(pb.headers).to(dev), torch.from_numpy(pb.records).to(dev),
+                               torch.from_numpy(pb.offsets).to(dev), n, H, W, max_rec, out, status, rgb_t)
+        return (out, status, rgb_t) if rgb else (out, status)
