@@ -757,6 +757,9 @@ __global__ void __launch_bounds__(EM_SEL_THREADS) emat_select_kernel(
     int cntf = 0;
     if (st == MFR_ST_OK) {
         orthonormalize(R);
+        if (!is_rotation(R)) st = MFR_ST_NO_MODEL;          // too far from the essential manifold: no rotation came out
+    }
+    if (st == MFR_ST_OK) {
         __threadfence();
         __syncthreads();                                    // rm: written by other wavefronts
         int cw = 0;

@@ -249,6 +249,28 @@ MFR_DEV void kinv(const void *K, int k_dtype, int b, double Ki[4])
         Ki[1] = -(k[2] * Ki[0]); Ki[3] = -(k[5] * Ki[2]);
     }
 }
+// status OK needs a rotation (oracle: mfr_ref_is_rotation): every entry finite, |R^T R - I| <= 1e-12 entrywise, det R > 0
+MFR_DEV bool is_rotation(const double R[9])
+{
+    bool ok = true;
+    for (int i = 0; i < 9; ++i) ok = ok && isfinite(R[i]);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double d = ((R[i] * R[j] + R[3 + i] * R[3 + j]) + R[6 + i] * R[6 + j]) - ((i == j) ? 1.0 : 0.0);
+            ok = ok && (d <= 1e-12 && d >= -1e-12);
+        }
+    const double det = (R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6])) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+    return ok && det > 0.0;
+}
+// np.int32(x) truncation of a keypoint coordinate as a pixel index in [0, size) (oracle: mfr_ref_pix_trunc).  The range test
+// comes before the conversion: v_cvt_i32_f32 turns NaN into 0, which would lift a NaN keypoint as pixel 0; here a NaN / +-inf
+// coordinate makes the correspondence invalid, and every other value gives the truncation's result.
+MFR_DEV bool pix_trunc(float x, int size, int &out)
+{
+    if (!(x > -1.0f && x < (float)size)) return false;
+    out = (int)x;
+    return true;
+}
 // pose_solver.py:6-17: ray = inv(K) @ [u, v, 1] as the float64 matrix product evaluates it, xyz = depth * ray
 MFR_DEV void backproject(int u, int v, float depth, const double Ki[4], double *xyz)
 {

@@ -92,8 +92,7 @@ __global__ void __launch_bounds__(256) pnp_lift_kernel(
         int u = 0, v = 0;
         float d = 0.f;
         if (i < n) {
-            u = (int)p0[2 * i]; v = (int)p0[2 * i + 1];                  // np.int32 truncation (:186, Q1)
-            if (u >= 0 && u < W && v >= 0 && v < H) {
+            if (pix_trunc(p0[2 * i], W, u) && pix_trunc(p0[2 * i + 1], H, v)) {   // np.int32 truncation (:186, Q1)
                 d = dm[v * W + u];                                        // :193
                 valid = d > dmin;                                         // :196 (Q6)
             }
@@ -430,15 +429,16 @@ __global__ void __launch_bounds__(64) pnp_select_kernel(
         }
     }
     if (st == MFR_ST_OK) {
-        bool bad = false;
-        for (int k = 0; k < 9; ++k) bad |= !(R[k] == R[k]);
-        for (int k = 0; k < 3; ++k) bad |= !(t[k] == t[k]);
+        bool bad = !is_rotation(R);                                             // OK needs a finite rotation ...
+        for (int k = 0; k < 3; ++k) bad |= !isfinite(t[k]);                    // ... and a finite translation
         if (bad) st = MFR_ST_NO_MODEL;
     }
     if (st == MFR_ST_OK) {
         const double tn = sqrt(dot3(t, t));
         if (tn > 1000.0) st = MFR_ST_DEGENERATE;                                 // pose_solver.py:223-225
     }
+    if (st != MFR_ST_OK && mask_valid)                       // a failed pair has no inliers (each lane clears what it wrote above)
+        for (int i = lane; i < n; i += 64) mask_valid[(size_t)b * maxN + i] = 0;
     if (lane == 0) {
         for (int k = 0; k < 9; ++k) Rout[9 * b + k] = (st == MFR_ST_OK) ? R[k] : qnan;
         for (int k = 0; k < 3; ++k) tout[3 * b + k] = (st == MFR_ST_OK) ? t[k] : qnan;

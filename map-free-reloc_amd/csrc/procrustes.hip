@@ -120,8 +120,8 @@ __global__ void __launch_bounds__(256) proc_lift_kernel(
         int u0 = 0, v0 = 0, u1 = 0, v1 = 0;
         float d0 = 0.f, d1 = 0.f;
         if (i < n) {
-            u0 = (int)p0[2 * i]; v0 = (int)p0[2 * i + 1]; u1 = (int)p1[2 * i]; v1 = (int)p1[2 * i + 1];
-            if (u0 >= 0 && u0 < W && v0 >= 0 && v0 < H && u1 >= 0 && u1 < W && v1 >= 0 && v1 < H) {
+            if (pix_trunc(p0[2 * i], W, u0) && pix_trunc(p0[2 * i + 1], H, v0) && pix_trunc(p1[2 * i], W, u1) &&
+                pix_trunc(p1[2 * i + 1], H, v1)) {
                 d0 = d0m[v0 * W + u0]; d1 = d1m[v1 * W + u1];
                 valid = (d0 > m0) && (d1 > m1);
             }

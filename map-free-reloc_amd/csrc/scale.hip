@@ -54,9 +54,9 @@ __global__ void __launch_bounds__(256) scale_lift_kernel(
         bool valid = false;
         double sc = 0.0;
         if (i < n && (!mk || mk[i] == 1)) {
-            const int u0 = (int)p0[2 * i], v0 = (int)p0[2 * i + 1];
-            const int u1 = (int)p1[2 * i], v1 = (int)p1[2 * i + 1];
-            if (u0 >= 0 && u0 < W && v0 >= 0 && v0 < H && u1 >= 0 && u1 < W && v1 >= 0 && v1 < H) {
+            int u0, v0, u1, v1;
+            if (pix_trunc(p0[2 * i], W, u0) && pix_trunc(p0[2 * i + 1], H, v0) && pix_trunc(p1[2 * i], W, u1) &&
+                pix_trunc(p1[2 * i + 1], H, v1)) {
                 const float d0 = d0m[v0 * W + u0], d1 = d1m[v1 * W + u1];
                 if (d0 > 0.f && d1 > 0.f) {
                     valid = true;

@@ -228,15 +228,16 @@ int mfr_ref_backproject(const int32_t *uv, const float *depth, int n, const void
     return 0;
 }
 
+/* depth_0.min() over the pixels that hold a number: a NaN pixel is invalid (it fails d > min) and takes no part in the minimum,
+ * wherever it lies (documented deviation: numpy's min would propagate it and reject every point; the dataset's uint16 PNG maps
+ * hold no NaN).  An all-NaN map gives +inf, which rejects every point too. */
 float mfr_ref_depth_min(const float *depth, int hw)
 {
-    float m = depth[0];
-    for (int i = 1; i < hw; ++i) if (depth[i] < m) m = depth[i];
+    float m = INFINITY;
+    for (int i = 0; i < hw; ++i) if (depth[i] < m) m = depth[i];
     return m;
 }
 
-/* np.int32(x) on float32: C truncation toward zero */
-static inline int32_t trunc_i32(float x) { return (int32_t)x; }
 
 /* pose_solver.py:186-206.  Out-of-image pixels (numpy would raise IndexError,
  * or wrap for negatives) are treated as invalid -- documented deviation. */
@@ -248,8 +249,8 @@ int mfr_ref_pnp_lift(const float *pts0, const float *pts1, int n, const float *d
     if (mfr_ref_load_intr(K0, k_dtype, &ki)) return -1;
     int m = 0;
     for (int i = 0; i < n; ++i) {
-        int32_t u = trunc_i32(pts0[2 * i]), v = trunc_i32(pts0[2 * i + 1]);
-        if (u < 0 || u >= W || v < 0 || v >= H) continue;
+        int32_t u, v;
+        if (!mfr_ref_pix_trunc(pts0[2 * i], W, &u) || !mfr_ref_pix_trunc(pts0[2 * i + 1], H, &v)) continue;
         float d = depth0[v * W + u];
         if (!(d > dmin)) continue;
         backproject_intr(&ki, u, v, d, xyz + 3 * m);
@@ -621,15 +622,15 @@ int mfr_ref_pnp_ransac(const double *xyz, const double *obs, int n, const void *
     }
     free(idx);
     if (st == MFR_ST_OK) {
-        for (int i = 0; i < 9; ++i) if (!(bR[i] == bR[i])) st = MFR_ST_NO_MODEL;
-        for (int i = 0; i < 3; ++i) if (!(bt[i] == bt[i])) st = MFR_ST_NO_MODEL;
+        if (!mfr_ref_is_rotation(bR)) st = MFR_ST_NO_MODEL;               /* OK needs a finite rotation ... */
+        for (int i = 0; i < 3; ++i) if (!isfinite(bt[i])) st = MFR_ST_NO_MODEL;   /* ... and a finite translation */
     }
     if (st == MFR_ST_OK) {
         double tn = sqrt(dot3(bt, bt));
         if (tn > 1000.0) st = MFR_ST_DEGENERATE;     /* pose_solver.py:223-225 */
     }
     if (st == MFR_ST_OK) { memcpy(R, bR, 72); memcpy(t, bt, 24); }
-    else { *n_inl = 0; }
+    else { *n_inl = 0; if (mask) memset(mask, 0, (size_t)n); }           /* a failed pair has no inliers */
     return st;
 }
 
@@ -666,9 +667,9 @@ int mfr_ref_scale_lift(const float *pts0, const float *pts1, const uint8_t *mask
     if (mfr_ref_load_intr(K0, k_dtype, &ki0) || mfr_ref_load_intr(K1, k_dtype, &ki1)) return -1;
     for (int i = 0; i < n; ++i) {
         if (mask && mask[i] != 1) continue;                                 /* :137 mask == 1 */
-        int32_t u0 = trunc_i32(pts0[2 * i]), v0 = trunc_i32(pts0[2 * i + 1]);   /* :138 */
-        int32_t u1 = trunc_i32(pts1[2 * i]), v1 = trunc_i32(pts1[2 * i + 1]);   /* :139 */
-        if (u0 < 0 || u0 >= W || v0 < 0 || v0 >= H || u1 < 0 || u1 >= W || v1 < 0 || v1 >= H) continue;
+        int32_t u0, v0, u1, v1;                                                 /* :138-139 */
+        if (!mfr_ref_pix_trunc(pts0[2 * i], W, &u0) || !mfr_ref_pix_trunc(pts0[2 * i + 1], H, &v0) ||
+            !mfr_ref_pix_trunc(pts1[2 * i], W, &u1) || !mfr_ref_pix_trunc(pts1[2 * i + 1], H, &v1)) continue;
         float d0 = depth0[v0 * W + u0], d1 = depth1[v1 * W + u1];           /* :140-141 */
         if (!(d0 > 0.f) || !(d1 > 0.f)) continue;                           /* :144 */
         double p0[3], p1[3], rp0[3];

@@ -23,6 +23,7 @@
  */
 #ifndef MFR_ORACLE_H
 #define MFR_ORACLE_H
+#include <math.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -66,6 +67,30 @@ int mfr_ref_poly_real_roots(const double *c, int deg, double *roots);
 int mfr_ref_backproject(const int32_t *uv, const float *depth, int n, const void *K, int k_dtype, double *xyz);
 
 float mfr_ref_depth_min(const float *depth, int hw);
+
+/* a pose may come back with status OK only if R is a rotation: every entry finite, |R^T R - I| <= 1e-12 entrywise, det R > 0
+ * (degenerate data -- collinear points, a planar-degenerate E -- can drive P3P / the E decomposition to a non-rotation) */
+static inline int mfr_ref_is_rotation(const double R[9])
+{
+    for (int i = 0; i < 9; ++i) if (!isfinite(R[i])) return 0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double d = ((R[i] * R[j] + R[3 + i] * R[3 + j]) + R[6 + i] * R[6 + j]) - ((i == j) ? 1.0 : 0.0);
+            if (!(d <= 1e-12 && d >= -1e-12)) return 0;
+        }
+    const double det = (R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6])) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+    return det > 0.0;
+}
+
+/* np.int32(x) on float32 (C truncation toward zero) as a pixel index in [0, size): the range test comes BEFORE the cast, so a
+ * NaN / +-inf / out-of-int32 coordinate makes the correspondence invalid instead of reaching an undefined conversion (x86 gives
+ * INT_MIN for NaN, the GPU's v_cvt_i32_f32 gives 0).  For every other value the result is the truncation's. */
+static inline int mfr_ref_pix_trunc(float x, int size, int32_t *out)
+{
+    if (!(x > -1.0f && x < (float)size)) return 0;
+    *out = (int32_t)x;
+    return 1;
+}
 
 /* pose_solver.py:186-206 (PnP input prep): int-truncate pts0, gather depth0,
  * valid = d > depth_min, compact, back-project with K0.  obs = pts1 (f64). */

@@ -745,6 +745,9 @@ int mfr_ref_emat_solve(const float *pts0, const float *pts1, int n, const void *
     }
     if (st == MFR_ST_OK) {
         mfr_ref_orthonormalize(Rb);                                           /* Horn's R inherits E's distance from the essential manifold */
+        if (!mfr_ref_is_rotation(Rb)) st = MFR_ST_NO_MODEL;                  /* too far from it: no rotation came out */
+    }
+    if (st == MFR_ST_OK) {
         int cnt = 0;
         for (int i = 0; i < n; ++i) {
             int in = rm[i] && cheirality(Rb, tb, x0[2 * i], x0[2 * i + 1], x1[2 * i], x1[2 * i + 1]);

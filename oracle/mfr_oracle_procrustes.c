@@ -142,8 +142,9 @@ int mfr_ref_procrustes_lift(const float *pts0, const float *pts1, int n, const f
     float m0 = mfr_ref_depth_min(depth0, H * W), m1 = mfr_ref_depth_min(depth1, H * W);
     int m = 0;
     for (int i = 0; i < n; ++i) {
-        int32_t u0 = (int32_t)pts0[2 * i], v0 = (int32_t)pts0[2 * i + 1], u1 = (int32_t)pts1[2 * i], v1 = (int32_t)pts1[2 * i + 1];
-        if (u0 < 0 || u0 >= W || v0 < 0 || v0 >= H || u1 < 0 || u1 >= W || v1 < 0 || v1 >= H) continue;
+        int32_t u0, v0, u1, v1;
+        if (!mfr_ref_pix_trunc(pts0[2 * i], W, &u0) || !mfr_ref_pix_trunc(pts0[2 * i + 1], H, &v0) ||
+            !mfr_ref_pix_trunc(pts1[2 * i], W, &u1) || !mfr_ref_pix_trunc(pts1[2 * i + 1], H, &v1)) continue;
         float d0 = depth0[v0 * W + u0], d1 = depth1[v1 * W + u1];
         if (!(d0 > m0) || !(d1 > m1)) continue;                              /* :261 */
         int32_t a[2] = { u0, v0 }, b[2] = { u1, v1 };

@@ -1,5 +1,7 @@
 """The C oracle under AddressSanitizer + UndefinedBehaviorSanitizer (`make -C oracle asan`): every solver entry point is driven through the
-instrumented library in a child process (libasan preloaded); any report aborts the child."""
+instrumented library in a child process (libasan preloaded); any report aborts the child.
+The hard scenes of tests/solver_scenes.py go through it too: non-finite keypoints and depths, border coordinates, degenerate geometry;
+float-cast-overflow is on, so a NaN keypoint reaching a float -> int conversion would abort the run."""
 import os
 import subprocess
 import sys
@@ -23,6 +25,21 @@ for seed, n, outl in ((1, 300, 0.3), (2, 64, 0.6), (3, 5, 0.0), (4, 4, 0.0), (5,
             O.scale_ransac(sc, 0.1); n_ok += 1
     O.pnp_solve(p["pts0"], p["pts1"], p["depth0"], p["K0"], p["K1"], 300, 3.0, 0.9999, 0, seed)
     O.procrustes_solve(p["pts0"], p["pts1"], p["depth0"], p["depth1"], p["K0"], p["K1"], 0.05, 0.999, 512, 0, seed)
+from tests import solver_scenes as S
+for c in S.catalogue() + S.catalogue(k64=True):
+    pid = c["pair_id"]
+    xyz, obs, _ = O.pnp_lift(c["pts0"], c["pts1"], c["depth0"], c["K0"])
+    O.pnp_ransac(xyz, obs, c["K1"], 300, 3.0, 0.9999, 0, pid, want_counts=True)
+    O.pnp_solve(c["pts0"], c["pts1"], c["depth0"], c["K0"], c["K1"], 300, 3.0, 0.9999, 0, pid)
+    for score in (O.EMAT_MAGSAC, O.EMAT_COUNT):
+        e = O.emat_solve(c["pts0"], c["pts1"], c["K0"], c["K1"], 2.0, 0.9999, 300, 0, pid, want_counts=True, score=score)
+        if e["status"] == 0:
+            O.scale_ransac(O.scale_lift(c["pts0"], c["pts1"], e["mask"], c["depth0"], c["depth1"], c["K0"], c["K1"], e["R"], e["t"]), 0.1)
+    st, R, t, _ = O.procrustes_solve(c["pts0"], c["pts1"], c["depth0"], c["depth1"], c["K0"], c["K1"], 0.05, 0.999, 512, 0, pid)
+    if st == 0 and c["name"] in ("wall_0", "nonfinite_pts1", "bad_depth", "nan_depth_at_origin"):
+        O.procrustes_icp(c["depth0"], c["depth1"], c["K0"], c["K1"], R, t.reshape(3), 0.05, max_iter=5)
+X, obs, K1, _, _ = S.degenerate_translation()
+assert O.pnp_ransac(X, obs, K1, 300, 3.0, 0.9999, 0, 7050)["status"] == O.ST_DEGENERATE
 rng = np.random.default_rng(0)
 d0 = rng.integers(0, 120, (200, 128)).astype(np.float32); d1 = rng.integers(0, 120, (180, 128)).astype(np.float32)
 O.sift_ratio_match(d0, d1, rng.random((200, 2)).astype(np.float32) * 500, rng.random((180, 2)).astype(np.float32) * 500, 0.8)
