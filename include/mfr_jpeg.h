@@ -13,7 +13,8 @@
 
 #define MFR_JPEG_OK 0
 #define MFR_JPEG_UNSUPPORTED 1      /* valid JPEG the device decoder does not take: progressive, arithmetic, lossless, 12-bit, multi-scan,
-                                       > 3 components, RGB / CMYK / YCCK colour, sampling other than 4:4:4, 4:2:2, 4:2:0 or gray */
+                                       > 3 components, RGB / CMYK / YCCK colour, sampling other than 4:4:4, 4:2:2, 4:2:0 or gray,
+                                       Huffman table ids 2 / 3 */
 #define MFR_JPEG_INVALID 2          /* truncated or malformed input */
 #define MFR_JPEG_CAPACITY 3         /* the record buffer is too small */
 /* device status bits (mfr_jpeg_decode's per-image status; host parse codes above are passed through unchanged) */

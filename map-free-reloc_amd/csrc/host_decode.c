@@ -30,7 +30,7 @@ int mfr_host_abi_version(void) { return 3; }   /* 3: mfr_host_jpeg_parse */
 /* ---- baseline JPEG: header parse + entropy-segment preparation for the device decoder (csrc/jpeg.hip) ----
  * ITU-T T.81: markers B.1, frame / scan headers B.2, tables B.2.4, restart intervals B.2.4.4 and F.1.2.3, canonical Huffman codes C.
  * Colour interpretation as the JFIF / Adobe APP14 conventions: three components are YCbCr unless an Adobe marker says transform 0, or,
- * with neither a JFIF nor an Adobe marker, the component ids spell 'R', 'G', 'B'.  Every read is bounded by n.  Layout: include/mfr_jpeg.h. */
+ * with neither a JFIF (APP0 "JFIF\0" of >= 14 bytes) nor an Adobe marker, the component ids spell 'R', 'G', 'B'.  Every read is bounded by n.  Layout: include/mfr_jpeg.h. */
 #include <string.h>
 #include "mfr_jpeg.h"
 
@@ -38,8 +38,10 @@ static const uint8_t zz_natural[64] = {
     0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-/* canonical code tables (T.81 C.2 / F.2.2.3) from BITS / HUFFVAL; 0 = ok, -1 = BITS over-subscribe the code space */
-static int huff_build(mfr_jpeg_huff *t)
+/* canonical code tables (T.81 C.2 / F.2.2.3) from BITS / HUFFVAL; 0 = ok, -1 = a table libjpeg refuses to decode with ("bogus Huffman
+ * table"): BITS over-subscribe the code space, the last code of a length is all ones (T.81 C reserves it), or a DC table holds a
+ * category above 15 */
+static int huff_build(mfr_jpeg_huff *t, int is_dc)
 {
     int code = 0, k = 0;
     memset(t->fast, 0, sizeof(t->fast));
@@ -57,9 +59,13 @@ static int huff_build(mfr_jpeg_huff *t)
                 }
             }
             t->maxcode[l] = code - 1;
+            if (code >= (1 << l)) return -1;
         }
         code <<= 1;
     }
+    if (is_dc)
+        for (int i = 0; i < k; ++i)
+            if (t->val[i] > 15) return -1;
     return 0;
 }
 
@@ -119,8 +125,8 @@ int mfr_host_jpeg_parse(const uint8_t *buf, size_t n, mfr_jpeg_header *h, uint8_
                 for (int l = 0; l < 16; ++l) cnt += (t->bits[l] = s[p + 1 + l]);
                 if (cnt > 256 || p + 17 + (size_t)cnt > sl) FAIL(MFR_JPEG_INVALID);
                 memcpy(t->val, s + p + 17, (size_t)cnt);
-                if (huff_build(t)) FAIL(MFR_JPEG_INVALID);
-                if (tc) have_ac[th] = 1; else have_dc[th] = 1;
+                /* as libjpeg, a bogus table only makes the file invalid when the scan uses it (checked below): until then it is undefined */
+                if (tc) have_ac[th] = !huff_build(t, 0); else have_dc[th] = !huff_build(t, 1);
                 p += 17 + (size_t)cnt;
             }
         } else if (m == 0xDB) {                                          /* DQT */
@@ -137,7 +143,7 @@ int mfr_host_jpeg_parse(const uint8_t *buf, size_t n, mfr_jpeg_header *h, uint8_
             if (sl != 2) FAIL(MFR_JPEG_INVALID);
             h->restart_interval = (s[0] << 8) | s[1];
         } else if (m == 0xE0) {                                          /* APP0 */
-            if (sl >= 5 && !memcmp(s, "JFIF\0", 5)) jfif = 1;
+            if (sl >= 14 && !memcmp(s, "JFIF\0", 5)) jfif = 1;             /* libjpeg: a shorter payload is not a JFIF header */
         } else if (m == 0xEE) {                                          /* APP14 */
             if (sl >= 12 && !memcmp(s, "Adobe", 5)) h->adobe_transform = s[11];
         } else if (m == 0xDA) {                                          /* SOS */

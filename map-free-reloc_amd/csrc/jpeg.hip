@@ -12,7 +12,7 @@
 //             and the result does not depend on how fast the code resynchronises.  An exclusive scan of the blocks each
 //             subsequence completes places it; a final pass writes the int16 coefficients (DC as differences), stopping at the
 //             segment's MCU count.  Then the per-component DC prediction: a segmented prefix sum, reset at restart segments.
-//   idct      dequantise + libjpeg's JDCT_ISLOW (CONST_BITS 13, PASS1_BITS 2) + the post-IDCT range limit, 8 lanes per block
+//   idct      dequantise + libjpeg's JDCT_ISLOW (CONST_BITS 13, PASS1_BITS 2) + the clamp of its output to [-128, 127], 8 lanes per block
 //             (pass 1 one column per lane, pass 2 one row per lane), into u8 component planes padded to whole MCUs
 //   colour    one lane per pixel: fancy (triangle) upsampling of the chroma (h2v1, h2v2), fixed-point YCbCr -> RGB, luma
 //             (19595 R + 38470 G + 7471 B + 2^15) >> 16, / 255f into the [n,1,H,W] f32 batch (and optionally RGB u8)
@@ -432,8 +432,8 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const mfr_jpeg_header *h
         islow_1d(x, o, 13 + 2 + 3);
         uint32_t w0 = 0, w1 = 0;
         for (int i = 0; i < 8; ++i) {
-            int s = ((o[i] + 512) & 1023) - 512 + 128;        // libjpeg's post-IDCT range-limit table
-            s = s < 0 ? 0 : (s > 255 ? 255 : s);
+            // libjpeg-turbo's SIMD ISLOW packs the descaled output with signed saturation: a clamp to [-128, 127], then + 128
+            const int s = min(max(o[i], -128), 127) + 128;
             if (i < 4) w0 |= (uint32_t)s << (8 * i); else w1 |= (uint32_t)s << (8 * (i - 4));
         }
         uint8_t *pl = base + L.planes + h->plane_off[c];

@@ -8,11 +8,22 @@ no DCT scaling), then datasets.luma_u8, then / 255 in float32.  Torch only provi
 | parse | SOI / APPn / DQT / SOF0-1 (8-bit) / DHT / DRI / SOS / EOI; quantisation tables in natural order; canonical Huffman tables (T.81 C.2) as a 9-bit look-up plus maxcode per length; entropy data unstuffed, RSTn removed, one {byte offset, MCU count} per restart segment | host, plain C |
 | entropy | per restart segment, subsequences of S bits decoded speculatively from a guessed state (bit offset, zig-zag index, block in MCU) and re-decoded from their predecessor's exit state until nothing changes (Weissenberger & Schmidt 2018); exclusive scan of the blocks each subsequence completes; a final pass writes int16 coefficients, DC as differences | one workgroup per image |
 | DC | per-component prefix sum of the DC differences, reset at every restart segment | same workgroup |
-| IDCT | dequantise, libjpeg's JDCT_ISLOW integer inverse DCT (13-bit constants, 2 fractional bits between the passes), range-limit to u8 planes padded to whole MCUs | 8 lanes per block |
+| IDCT | dequantise, libjpeg's JDCT_ISLOW integer inverse DCT (13-bit constants, 2 fractional bits between the passes), its output clamped to [-128, 127] then + 128 (the signed-saturating pack of libjpeg-turbo's SIMD routine, which PIL runs; not the modulo-1024 range-limit table of libjpeg's C code) into u8 planes padded to whole MCUs | 8 lanes per block |
 | colour | libjpeg's fancy (triangle) upsampling for h2v1 / h2v2 (edges replicate the last real row / column), fixed-point YCbCr -> RGB (16-bit tables, ONE_HALF rounding), luma (19595 R + 38470 G + 7471 B + 2^15) >> 16, / 255f | one lane per pixel |
 
-Files the parse calls unsupported (progressive, arithmetic, 12-bit, multi-scan, CMYK / RGB colour, other sampling) are the caller's to decode on
-the host; `decode` reports them per image in `status` (1) and leaves their planes untouched.
+Files the parse calls unsupported (progressive, arithmetic, 12-bit, multi-scan, CMYK / RGB colour, other sampling, Huffman table ids 2 / 3,
+which only an extended-sequential SOF1 file may use) are the caller's to decode on the host; `decode` reports them per image in `status` (1)
+and leaves their planes untouched.  The parse takes: SOF0 / SOF1 at 8 bits, one interleaved scan (or one component), gray or YCbCr at
+4:4:4 / 4:2:2 / 4:2:0, quantisation table ids 0-3 with 8- or 16-bit entries, Huffman table ids 0 / 1, any component ids.  Three components
+are YCbCr unless an Adobe APP14 marker says transform 0, or, with neither an Adobe marker nor a JFIF APP0 (payload >= 14 bytes, as libjpeg
+asks), the ids spell 'R', 'G', 'B'.  A Huffman table libjpeg refuses ("bogus Huffman table": the all-ones code of a length assigned, the
+code space over-subscribed, a DC category above 15) makes the file invalid when the scan uses it.
+
+Bit-exactness with PIL is promised for files in which every block has sum_k |coef_k q_k| <= 4096 (quantised coefficient times its table
+entry), which every encoder working from 8-bit pixels satisfies: the first IDCT pass scales a term by at most ~1.39 * 4, so its outputs
+stay below 2^15 and the 16-bit intermediates of libjpeg-turbo's SIMD IDCT cannot saturate.  Beyond that bound PIL's result depends on
+that saturation, which is not restated here.  tests/jpeg_craft.py writes files up to the bound; tests/test_jpeg_crafted_host.py and
+tests/test_gpu_jpeg_crafted.py compare them with PIL.
 """
 import ctypes as C
 

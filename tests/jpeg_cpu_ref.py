@@ -49,6 +49,7 @@ def coefficients(h, rec):
                     r, sz = rs >> 4, rs & 15
                     if sz:
                         k += r
+                        assert p + sz <= bits.size, "bad AC code"
                         v = int("".join(map(str, bits[p:p + sz])), 2)
                         if v < (1 << (sz - 1)):
                             v -= (1 << sz) - 1
@@ -92,8 +93,9 @@ def idct_islow(coef, q):
     d = coef.astype(np.int64).reshape(-1, 8, 8) * q.astype(np.int64).reshape(1, 8, 8)
     ws = np.stack(one_d(*[d[:, r, :] for r in range(8)], True), axis=1)          # columns: [N, row, col]
     out = np.stack(one_d(*[ws[:, :, c] for c in range(8)], False), axis=2)       # rows
-    w = ((out + 512) & 1023) - 512                                               # libjpeg's post-IDCT range-limit table
-    return np.clip(w + 128, 0, 255).astype(np.uint8)
+    # libjpeg-turbo's SIMD ISLOW packs the descaled output with signed saturation: a clamp to [-128, 127], then + 128.  (libjpeg's C code
+    # looks the output up modulo 1024 in its range-limit table; PIL's decoder runs the SIMD routine.)
+    return (np.clip(out, -128, 127) + 128).astype(np.uint8)
 
 
 def planes(h, coef):

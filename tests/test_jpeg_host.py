@@ -15,6 +15,7 @@ from mapfree_reloc_amd import jpeg_ops as J
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import jpeg_cpu_ref as R  # noqa: E402
+import jpeg_craft as JC  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -156,6 +157,58 @@ for name in sorted(os.listdir(sys.argv[2])):
         assert st == want or (cap == 48 and st == 3), (name, st, want)
         n += 1
 print("SANITIZED_OK", n)
+
+# the crafted corpus (tests/jpeg_craft.py), every file whole, cut at each of its markers, and with each single byte of its SOF / SOS /
+# DHT / DQT / DRI segments set to 0x00 and to 0xFF: the sanitised parse returns what the plain build (argv[4]) returns
+plain = ctypes.CDLL(sys.argv[4])
+plain.mfr_host_jpeg_parse.argtypes = lib.mfr_host_jpeg_parse.argtypes
+
+def status(l, d, cap):
+    h = ctypes.create_string_buffer(hb)
+    rec = ctypes.create_string_buffer(cap)
+    nb = sz(0)
+    return l.mfr_host_jpeg_parse(d, len(d), h, rec, cap, ctypes.byref(nb))
+
+def markers(d):
+    # (marker, offset of the FF right before it, end of its segment) for every marker of a single-scan file
+    out, i = [], 2
+    while i + 1 < len(d):
+        while d[i + 1] == 0xFF:
+            i += 1
+        m = d[i + 1]
+        if m == 0xD9 or 0xD0 <= m <= 0xD7:
+            out.append((m, i, i + 2))
+            if m == 0xD9:
+                break
+            i += 2
+        else:
+            end = i + 2 + int.from_bytes(d[i + 2:i + 4], "big")
+            out.append((m, i, end))
+            i = end
+        if m == 0xDA or 0xD0 <= m <= 0xD7:                      # entropy-coded data up to the next marker
+            while not (d[i] == 0xFF and d[i + 1] != 0x00):
+                i += 1
+    return out
+
+m = 0
+for name in sorted(os.listdir(sys.argv[3])):
+    d = open(os.path.join(sys.argv[3], name), "rb").read()
+    cap = len(d) * 2 + 4096
+    variants = [d]
+    for mk, a, e in markers(d):
+        variants.append(d[:a])
+        variants.append(d[:a + 1])
+        if mk in (0xC0, 0xC1, 0xDA, 0xC4, 0xDB, 0xDD):
+            for i in range(a + 2, e):
+                for v in (0x00, 0xFF):
+                    if d[i] != v:
+                        variants.append(d[:i] + bytes([v]) + d[i + 1:])
+    for v in variants:
+        st = status(lib, v, cap)
+        assert st == status(plain, v, cap), (name, st)
+        m += 1
+    assert status(lib, d, 48) in (status(plain, d, cap), 3), name
+print("CRAFTED_OK", m)
 '''
 
 
@@ -177,9 +230,21 @@ def test_parse_under_asan_ubsan(tmp_path):
         (inputs / f"0_good{k}").write_bytes(d)
     for k, (name, d, want) in enumerate(bad_inputs()):
         (inputs / f"{want}_{k}_{name}").write_bytes(d)
+    crafted = tmp_path / "crafted"
+    crafted.mkdir()
+    n_crafted = 0
+    for hw in ((48, 64), (37, 29), (1, 1), (17, 33)):
+        for c in JC.corpus(*hw):
+            (crafted / c.name).write_bytes(c.data)
+            n_crafted += 1
+    for name, d in JC.malformed():
+        (crafted / f"malformed_{name}").write_bytes(d)
+    from mapfree_reloc_amd import datasets
+    plain = datasets._host_lib()._name
     env = dict(os.environ, LD_PRELOAD=libasan, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    p = subprocess.run([sys.executable, "-c", DRIVER, so, str(inputs)], capture_output=True, text=True, env=env, timeout=600)
+    p = subprocess.run([sys.executable, "-c", DRIVER, so, str(inputs), str(crafted), plain], capture_output=True, text=True, env=env, timeout=1500)
     assert p.returncode == 0 and "SANITIZED_OK" in p.stdout, (p.stdout[-500:], p.stderr[-3000:])
+    assert "CRAFTED_OK" in p.stdout and int(p.stdout.split("CRAFTED_OK")[1]) > 100 * n_crafted, p.stdout[-500:]
 
 
 @pytest.mark.parametrize("sub", [0, 1, 2])
