@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define MFR_ABI_VERSION 6   /* 6 (round 6): mfr_conv3x3_direct_f16x2*, later (additive) the SIFT detector mfr_sift_*, the JPEG decoder mfr_jpeg_*, mfr_conv3x3s2_direct_f16x2, mfr_mlp_ln_*; 5 (round 6): mfr_f16x2_guard_bind (the f16x2 range guard); 2: intrinsics as (const void *K, int k_dtype) instead of const float *; 3: mfr_emat_solve_batch takes the
+#define MFR_ABI_VERSION 6   /* 6 (round 6): mfr_conv3x3_direct_f16x2*, later (additive) the SIFT detector mfr_sift_*, the JPEG decoder mfr_jpeg_*, mfr_conv3x3s2_direct_f16x2, mfr_mlp_ln_*, mfr_loftr_ot_match (LoFTR's optimal-transport coarse matching); 5 (round 6): mfr_f16x2_guard_bind (the f16x2 range guard); 2: intrinsics as (const void *K, int k_dtype) instead of const float *; 3: mfr_emat_solve_batch takes the
                              * model-quality method (MAGSAC++ / count) and its table; 4 (round 5): the f16x2 entry points (mfr_gemm_f16x2*,
                              * mfr_wino_f16x2_*, mfr_conv3x3_wino_f16x2, mfr_conv_igemm_f16x2), mfr_sg_attention_variant renumbered (0 f16x2,
                              * 1 exact fp32, 2 bf16x3), the measurement-only entry points (mfr_conv3x3_wino_bf16x3_variant,
@@ -333,6 +333,10 @@ int mfr_sg_sinkhorn_match_variant(const float *S, int B, int ldS, const int32_t 
  *                                (f0/sqrt C)(f1/sqrt C)^T; conf = softmax_i(S/T) * softmax_j(S/T);
  *                                conf > thr, border removal, mutual max -> i_ids, j_ids [B,L0] i32
  *                                (ascending i), mconf [B,L0], n_match [B]
+ *   mfr_loftr_ot_match           CoarseMatching(sinkhorn) + get_coarse_match, the matcher the `*_ot.ckpt` weights of matchers.py:16-18
+ *                                were trained with (upstream src/loftr/utils/coarse_matching.py, MATCH_TYPE 'sinkhorn', SKH_ITERS 3):
+ *                                log-domain Sinkhorn on [[S, a], [a, a]] (a = coarse_matching.bin_score), conf = exp(Z)[:m, :n];
+ *                                same outputs as mfr_loftr_coarse_match
  *   mfr_loftr_gather_windows     FinePreprocess unfold(win, stride, pad win/2) restricted to the
  *                                matched cells: feat [Bimg,Hf,Wf,C] NHWC -> out [M, win*win, C]
  *   mfr_loftr_fine_match         FineMatching: centre-feature correlation, softmax, spatial expectation,
@@ -353,6 +357,17 @@ int mfr_loftr_coarse_match(const float *S, int B, int h0, int w0, int h1, int w1
 int mfr_loftr_coarse_match_variant(const float *S, int B, int h0, int w0, int h1, int w1, float temperature, float thr, int border,
                                    void *workspace, size_t workspace_bytes, int32_t *i_ids, int32_t *j_ids, float *mconf,
                                    int32_t *n_match, int variant, void *stream);
+/* Optimal-transport coarse matching.  S [B, h0*w0, h1*w1] as for mfr_loftr_coarse_match (no temperature), read-only; the dustbin row / column
+ * (the constant bin_score) are never materialised.  iters >= 1 Sinkhorn iterations (upstream 3).  variant 0: iters + 1 sweeps over S (per
+ * iteration one sweep forms u_i from a complete row and adds S_ij + u_i to per-column partial logsumexps, folded in a fixed order; rows of up to
+ * 8192 columns, longer rows run variant 1's kernels); variant 1: a row and a column kernel per iteration (2 iters + 1 sweeps; A/B, cross-check).
+ * Both are bit-reproducible (no float atomics).  u_out [B, h0*w0 + 1] / v_out [B, h1*w1 + 1]: the final potentials incl. the dustbin entry
+ * (log assignment = S_ij + u_i + v_j + log(m + n)), each may be NULL.  i_ids / j_ids / mconf [B, h0*w0], n_match [B]: ascending i, lowest j on a
+ * tie, entries at index >= n_match unspecified. */
+size_t mfr_loftr_ot_match_workspace_bytes(int B, int L0, int L1);
+int mfr_loftr_ot_match(const float *S, int B, int h0, int w0, int h1, int w1, float bin_score, int iters, float thr, int border,
+                       void *workspace, size_t workspace_bytes, int32_t *i_ids, int32_t *j_ids, float *mconf, int32_t *n_match,
+                       float *u_out, float *v_out, int variant, void *stream);
 int mfr_loftr_gather_windows(const float *feat, int Bimg, int Hf, int Wf, int C, const int32_t *img_ids,
                              const int32_t *cell_ids, int M, int wc, int stride, int win, float *out, void *stream);
 /* FineMatching (the last step of LoFTR_matcher.match, matchers.py:50-55 -> mkpts1_f): per matched window, similarity of view 0's centre

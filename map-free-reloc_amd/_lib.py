@@ -69,6 +69,8 @@ SIGNATURES = {
     "mfr_loftr_linear_attention": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i, _vp]),
     "mfr_loftr_coarse_match_workspace_bytes": (_sz, [_i, _i, _i]),
     "mfr_loftr_coarse_match": (_i, [_vp, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "mfr_loftr_ot_match_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mfr_loftr_ot_match": (_i, [_vp, _i, _i, _i, _i, _i, C.c_float, _i, C.c_float, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "mfr_loftr_coarse_match_variant": (_i, [_vp, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _vp, _sz, _vp, _vp, _vp, _vp, _i, _vp]),
     "mfr_loftr_fine_attention": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "mfr_loftr_gather_windows": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),

@@ -6,12 +6,19 @@ quirk Q4) and write `correspondences_{matcher}.npz` (key `correspondences`, NaN-
 
     python -m mapfree_reloc_amd.compute -ds Mapfree -m SG [--outdoor] [--data_root data/mapfree]
     python -m mapfree_reloc_amd.compute -ds Mapfree -m SIFT --sift-detector hip      (SIFT on the GPU, no OpenCV)
+    python -m mapfree_reloc_amd.compute -ds Mapfree -m LoFTR --loftr-match-type sinkhorn
+        (the optimal-transport matcher of the *_ot.ckpt weights; writes correspondences_LoFTR_OT.npz, never the dual-softmax file's name)
 """
 import argparse
 from pathlib import Path
 
 from . import wire
 from .matchers import MATCHERS
+
+
+def output_tag(matcher, loftr_match_type='dual_softmax'):
+    """file-name tag of a matcher's correspondences: the reference's names, and LoFTR_OT for the optimal-transport LoFTR stage"""
+    return 'LoFTR_OT' if matcher == 'LoFTR' and loftr_match_type == 'sinkhorn' else matcher
 
 
 def main(argv=None):
@@ -22,10 +29,13 @@ def main(argv=None):
     ap.add_argument('--outdoor', action='store_true')
     ap.add_argument('--data_root', type=Path, default=Path('data/mapfree/'))
     ap.add_argument('--sift-detector', type=str, default='opencv', choices=['opencv', 'hip'])     # new: -m SIFT's keypoint detector
+    ap.add_argument('--loftr-match-type', type=str, default='dual_softmax', choices=['dual_softmax', 'sinkhorn'])     # new: -m LoFTR's coarse matching
     args = ap.parse_args(argv)
     resize = 540, 720                                                       # compute.py:42
     if args.matcher == 'SIFT':
         matcher = MATCHERS['SIFT'](resize, args.outdoor, detector='hip' if args.sift_detector == 'hip' else None)
+    elif args.matcher == 'LoFTR':
+        matcher = MATCHERS['LoFTR'](resize, args.outdoor, match_type=args.loftr_match_type)
     else:
         matcher = MATCHERS[args.matcher](resize, args.outdoor)
     scenes = [f for split in ('test', 'val') if (args.data_root / split).is_dir()
@@ -35,7 +45,7 @@ def main(argv=None):
     for scene_dir in scenes:
         qs = wire.parse_mapfree_query_frames(scene_dir / 'poses.txt')
         pts = [matcher.match((str(scene_dir / 'seq0' / 'frame_00000.jpg'), str(scene_dir / q))) for q in qs]
-        wire.save_correspondences(scene_dir / f'correspondences_{args.matcher}.npz', pts)
+        wire.save_correspondences(scene_dir / f'correspondences_{output_tag(args.matcher, args.loftr_match_type)}.npz', pts)
         print(f'Finished {scene_dir.name}: {len(pts)} pairs')
 
 

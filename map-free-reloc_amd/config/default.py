@@ -24,6 +24,9 @@ keys this implementation adds (declared here because unknown keys are rejected o
                      CONV / CONV_KERNEL / FUSED_CONV_RELU / RPR_CONV / RPR_CONV_BWD / RPR_CONV_ORDER / RPR_WGRAD_SPLITS: which of two
                      implementations of a layer runs (A/B measurement, parity tests) -- options.py lists values and defaults
   LOFTR.WEIGHTS      checkpoint of the online LoFTR matcher ('LoFTR' feature matching)
+  LOFTR.MATCH_TYPE   'dual_softmax' (default: what the reference runs, also with the `*_ot.ckpt` files) | 'sinkhorn' (upstream
+                     MATCH_COARSE.MATCH_TYPE: optimal transport with the checkpoint's coarse_matching.bin_score, csrc/loftr_ot.hip)
+  LOFTR.SKH_ITERS    Sinkhorn iterations of MATCH_TYPE 'sinkhorn' (upstream SKH_ITERS 3)
   ALLOW_SYNTHETIC_WEIGHTS  hand out seeded synthetic network weights when no checkpoint is configured (tests / benches)
   TRAINING.PRECISION 'bf16' (autocast; the aggregator kernel and the pose algebra stay fp32) | 'fp32'
   TRAINING.SIAMESE_BATCH  encode both images of a pair in one encoder pass; BatchNorm keeps per-view statistics (= the two-call arithmetic)
@@ -89,7 +92,7 @@ def get_cfg_defaults():
     for k, v in dict(NMS_RADIUS=4, KEYPOINT_THRESHOLD=0.005, MAX_KEYPOINTS=1024, SINKHORN_ITERATIONS=20,
                      MATCH_THRESHOLD=0.2, SUPERPOINT_WEIGHTS=None, SUPERGLUE_WEIGHTS=None, SYNTHETIC_SEED=1234).items():
         c.SUPERGLUE[k] = v
-    c.LOFTR = CN(); c.LOFTR.WEIGHTS = None
+    c.LOFTR = CN(); c.LOFTR.WEIGHTS = None; c.LOFTR.MATCH_TYPE = 'dual_softmax'; c.LOFTR.SKH_ITERS = 3
     c.ALLOW_SYNTHETIC_WEIGHTS = False
     return c
 

@@ -66,12 +66,14 @@ class SuperGlue_matcher:
 
 
 class LoFTR_matcher:
-    def __init__(self, resize, outdoor=False, weights_dir="LoFTR/weights"):
+    def __init__(self, resize, outdoor=False, weights_dir="LoFTR/weights", match_type="dual_softmax"):
+        """match_type 'dual_softmax': the reference's behaviour (matchers.py:16-18 loads the OT checkpoint strict=False into the dual-softmax
+        model, dropping coarse_matching.bin_score); 'sinkhorn': the optimal-transport matcher those weights were trained with"""
         from .pipeline import LoFTREmatPipeline
         self.resize = resize
         sd = _weights(os.path.join(weights_dir, "outdoor_ot.ckpt" if outdoor else "indoor_ot.ckpt"), WT.loftr_state_dict, "LoFTR")
         sd = {k[len("matcher."):] if k.startswith("matcher.") else k: v for k, v in sd.items()}
-        self._pipe = LoFTREmatPipeline("cuda", loftr_state=sd)
+        self._pipe = LoFTREmatPipeline("cuda", loftr_state=sd, match_type=match_type)
 
     def match_tensors(self, im0, im1):
         ims = torch.from_numpy(np.stack([im0, im1]))[:, None].to(self._pipe.device)

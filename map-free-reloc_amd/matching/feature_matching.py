@@ -141,7 +141,8 @@ class LoFTRMatching:
         lw = cfg.LOFTR.WEIGHTS
         sd = WT.strip_prefix(WT.load_checkpoint(lw), "matcher.") if lw else WT.synthetic_or_raise("LoFTR", cfg, WT.loftr_state_dict)
         self.device = torch.device("cuda")
-        self.net = LoFTRHIP(sd, self.device)
+        # LOFTR.MATCH_TYPE 'sinkhorn': the optimal-transport matcher with the checkpoint's bin_score (default: dual softmax, as the reference)
+        self.net = LoFTRHIP(sd, self.device, match_type=cfg.LOFTR.get("MATCH_TYPE", "dual_softmax"), skh_iters=cfg.LOFTR.get("SKH_ITERS", 3))
         self._gray = _GrayPairStage()
         self.use_graph = bool(cfg.HIP.GRAPH_BATCH1)
         self._graphs = {}

@@ -1,6 +1,9 @@
 """LoFTR on MI355X: ResNet-FPN backbone, linear layers and LayerNorm through PyTorch-ROCm (dense
 library work), the coarse transformer's linear attention, the dual-softmax coarse matching and the
-fine-window gather through csrc/loftr.hip.
+fine-window gather through csrc/loftr.hip; the optimal-transport coarse matching (match_type
+"sinkhorn": upstream MATCH_COARSE.MATCH_TYPE, the matcher the `*_ot.ckpt` weights were trained with,
+bin_score = the checkpoint's `coarse_matching.bin_score`) through csrc/loftr_ot.hip.  The default stays
+"dual_softmax": that is what the reference runs the OT checkpoints with (strict=False drops bin_score).
 
 Reference call site: LoFTR_matcher (etc/feature_matching_baselines/matchers.py:12-59): LoFTR
 (default_cfg) + `*_ot.ckpt` loaded strict=False; network = un-vendored zju3dv/LoFTR submodule,
@@ -35,9 +38,19 @@ def position_encoding_sine(d_model, H, W, device):
     return pe.to(device)
 
 
+MATCH_TYPES = ("dual_softmax", "sinkhorn")
+
+
 class LoFTRHIP:
-    def __init__(self, state_dict, device="cuda", thr=0.2, border_rm=2, temperature=0.1, window=5):
+    def __init__(self, state_dict, device="cuda", thr=0.2, border_rm=2, temperature=0.1, window=5, match_type="dual_softmax", skh_iters=3):
+        if match_type not in MATCH_TYPES:
+            raise ValueError(f"LoFTRHIP: match_type {match_type!r} is not one of {MATCH_TYPES}")
+        if int(skh_iters) < 1:
+            raise ValueError(f"LoFTRHIP: skh_iters must be >= 1, got {skh_iters!r}")
         _lib.load(require_gpu=True)
+        self.match_type, self.skh_iters = match_type, int(skh_iters)
+        # upstream CoarseMatching's learnable dustbin score (SKH_INIT_BIN_SCORE 1.0: what a checkpoint without the key implies)
+        self.bin_score = float(state_dict["coarse_matching.bin_score"]) if "coarse_matching.bin_score" in state_dict else 1.0
         self.device = torch.device(device)
         self.thr, self.border, self.temp, self.W = float(thr), int(border_rm), float(temperature), int(window)
         sd = {k: v.float() for k, v in state_dict.items()}
@@ -91,7 +104,7 @@ class LoFTRHIP:
         self.fine = encoder("loftr_fine", 2)
         self.down_proj = (dev(sd["fine_preprocess.down_proj.weight"]), dev(sd["fine_preprocess.down_proj.bias"]))
         self.merge_feat = (dev(sd["fine_preprocess.merge_feat.weight"]), dev(sd["fine_preprocess.merge_feat.bias"]))
-        self._ws_la = self._ws_cm = None
+        self._ws_la = self._ws_cm = self._ws_ot = None
         self._fine_lin = None
         # the coarse similarity matrix feat_c0 feat_c1^T / C as one batched f16x2 launch (csrc/gemm_split.hip); the bf16x3 arithmetic keeps the library's GEMM
         if options.get("SPLIT") == "f16x2":
@@ -202,6 +215,26 @@ class LoFTRHIP:
                    "mfr_loftr_coarse_match")
         return i_ids, j_ids, mconf, n
 
+    def ot_match(self, S, hw0, hw1, variant=0, return_potentials=False):
+        """optimal-transport coarse matching (csrc/loftr_ot.hip): skh_iters Sinkhorn iterations on S with the dustbin score, then the same
+        threshold / border / mutual-maximum selection.  variant 0: iters + 1 sweeps over S (default); 1: a row and a column kernel per
+        iteration (A/B, cross-check).  return_potentials: additionally the final u [B, L0 + 1], v [B, L1 + 1] (dustbin entry last)"""
+        lib = _lib.load()
+        B, L0, L1 = S.shape
+        need = lib.mfr_loftr_ot_match_workspace_bytes(B, L0, L1)
+        if self._ws_ot is None or self._ws_ot.numel() < need:
+            self._ws_ot = torch.empty(need, dtype=torch.uint8, device=S.device)
+        i_ids = torch.empty(B, L0, dtype=torch.int32, device=S.device); j_ids = torch.empty_like(i_ids)
+        mconf = torch.empty(B, L0, dtype=torch.float32, device=S.device)
+        n = torch.empty(B, dtype=torch.int32, device=S.device)
+        u = torch.empty(B, L0 + 1, dtype=torch.float32, device=S.device) if return_potentials else None
+        v = torch.empty(B, L1 + 1, dtype=torch.float32, device=S.device) if return_potentials else None
+        _lib.check(lib.mfr_loftr_ot_match(_lib.ptr(S.contiguous()), B, hw0[0], hw0[1], hw1[0], hw1[1], self.bin_score, self.skh_iters, self.thr,
+                                          self.border, _lib.ptr(self._ws_ot), self._ws_ot.numel(), _lib.ptr(i_ids), _lib.ptr(j_ids),
+                                          _lib.ptr(mconf), _lib.ptr(n), _lib.ptr(u) if u is not None else None,
+                                          _lib.ptr(v) if v is not None else None, variant, _lib.stream_ptr()), "mfr_loftr_ot_match")
+        return (i_ids, j_ids, mconf, n, u, v) if return_potentials else (i_ids, j_ids, mconf, n)
+
     def upsample2x_add(self, lo, y):
         """y += F.interpolate(lo, scale_factor=2, bilinear, align_corners=True), one pass (csrc/loftr_fused.hip)"""
         lib = _lib.load()
@@ -223,7 +256,8 @@ class LoFTRHIP:
         return out
 
     def coarse_match_features(self, f0, f1, hw):
-        """coarse features [B,L,256] x2 -> dual-softmax mutual-NN matches (upstream CoarseMatching, dual_softmax)"""
+        """coarse features [B,L,256] x2 -> mutual-NN matches (upstream CoarseMatching: dual_softmax, or sinkhorn on the same S without the
+        temperature)"""
         C = f0.shape[-1]
         # (f0 / sqrt C) . (f1 / sqrt C): for C a power of two (256) scaling the 6 MB operand is EXACT and commutes with the
         # contraction bit for bit, so the 150 MB/pair similarity matrix is written once and never rescaled in place
@@ -234,6 +268,8 @@ class LoFTRHIP:
         else:
             S = torch.bmm(f0, f1.transpose(1, 2))
             S.mul_(1.0 / C)
+        if self.match_type == "sinkhorn":
+            return self.ot_match(S, hw, hw)
         return self.coarse_match(S, hw, hw)
 
     def fine_match(self, xf, M, lin_idx, k1, pts1, out_scale, expec=None):

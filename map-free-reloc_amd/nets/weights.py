@@ -70,12 +70,14 @@ def superglue_state_dict(seed=4321, gnn_gain=0.1, kenc_gain=0.1, proj_gain=12.0,
     return sd
 
 
-def loftr_state_dict(seed=2468, feat_gain=20.0, msg_gain=0.1):
+def loftr_state_dict(seed=2468, feat_gain=20.0, msg_gain=0.1, bin_score=None):
     """LoFTR (default_cfg architecture) with upstream parameter names (`backbone.*`,
     `loftr_coarse.layers.N.*`, `fine_preprocess.*`, `loftr_fine.layers.N.*`).  Structured random like
     the SuperGlue recipe: zero-sum conv filters, identity-like BatchNorm, coarse features scaled so
     that the dual-softmax is peaky (conf > 0.2 needs a ~9 nat margin over 6120 candidates), and
-    transformer messages scaled down through norm2 so the GNN stays a perturbation."""
+    transformer messages scaled down through norm2 so the GNN stays a perturbation.  bin_score: add the
+    optimal-transport matcher's `coarse_matching.bin_score` (what an `*_ot.ckpt` carries); left out by default,
+    as in a dual-softmax model's state dict."""
     g = torch.Generator().manual_seed(seed)
     sd = {}
 
@@ -121,6 +123,8 @@ def loftr_state_dict(seed=2468, feat_gain=20.0, msg_gain=0.1):
     lin("fine_preprocess.down_proj", 256, 128, gain=0.05, bias=True)
     lin("fine_preprocess.merge_feat", 256, 128, bias=True)
     encoder("loftr_fine", 128, 2)
+    if bin_score is not None:
+        sd["coarse_matching.bin_score"] = torch.tensor(float(bin_score))
     return sd
 
 

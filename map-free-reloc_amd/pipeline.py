@@ -199,16 +199,18 @@ class LoFTREmatPipeline:
     CONFIDENCE 0.9999), one device-resident pass over a batch of pairs.  Replaces
     LoFTR_matcher.match (matchers.py:24-59) + EssentialMatrixMetricSolver (pose_solver.py:115-172)."""
 
-    def __init__(self, device="cuda", loftr_state=None, pix_thr=2.0, scale_thr=0.1, conf=0.9999, seed=0, pad_to=8, emat_score="magsac", overlap_solver=False):
+    def __init__(self, device="cuda", loftr_state=None, pix_thr=2.0, scale_thr=0.1, conf=0.9999, seed=0, pad_to=8, emat_score="magsac", overlap_solver=False,
+                 match_type="dual_softmax", skh_iters=3):
         from .nets.loftr import LoFTRHIP
         from .solver_ops import EssentialBatchSolver, ScaleFromDepthBatch
         _lib.load(require_gpu=True)
         self.device = torch.device(device)
-        self.loftr = LoFTRHIP(loftr_state or WT.loftr_state_dict(), self.device)
+        self.loftr = LoFTRHIP(loftr_state or WT.loftr_state_dict(), self.device, match_type=match_type, skh_iters=skh_iters)
         self.emat = EssentialBatchSolver(pix_thr, conf, seed, score=emat_score)
         self.scale = ScaleFromDepthBatch(scale_thr)
         self.pad_to = pad_to
-        self.guard = RangeGuard(self.device, lambda: LoFTREmatPipeline(device, loftr_state, pix_thr, scale_thr, conf, seed, pad_to, emat_score))
+        self.guard = RangeGuard(self.device, lambda: LoFTREmatPipeline(device, loftr_state, pix_thr, scale_thr, conf, seed, pad_to, emat_score,
+                                                                        match_type=match_type, skh_iters=skh_iters))
         self._ov = SolverOverlap(self.device) if overlap_solver else None      # E-mat + scale stage under the next call's matcher; join() before reading
 
     def join(self):
@@ -368,7 +370,8 @@ class FusedPosePipeline:
             sd = WT.strip_prefix(WT.load_checkpoint(lw), "matcher.") if lw else WT.synthetic_or_raise("LoFTR", cfg, WT.loftr_state_dict)
             lp = LoFTREmatPipeline.__new__(LoFTREmatPipeline)
             from .nets.loftr import LoFTRHIP
-            lp.loftr, lp.pad_to, lp.device = LoFTRHIP(sd, self.device), 8, self.device
+            lp.loftr = LoFTRHIP(sd, self.device, match_type=cfg.LOFTR.get("MATCH_TYPE", "dual_softmax"), skh_iters=cfg.LOFTR.get("SKH_ITERS", 3))
+            lp.pad_to, lp.device = 8, self.device
             self.match = lambda b: lp.match(b["images"])
         elif fm == "SIFT" and cfg.SIFT.get("DETECTOR", "opencv") == "hip":
             from .sift_ops import SiftDetector, sift_ratio_stage
