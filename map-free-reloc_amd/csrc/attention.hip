@@ -25,10 +25,9 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
+#include "wave_dev.h"
 #include "split_f16.h"
 #include "guard.h"
-
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -186,17 +185,6 @@ typedef short bf16x4 __attribute__((ext_vector_type(4)));
 #define AB_KS 72            // K tile row stride (bf16): 144 B
 #define AB_VS 40            // V^T tile row stride (bf16): 80 B
 
-__device__ __forceinline__ void split3(float x, unsigned &h, unsigned &m, unsigned &l)
-{
-    // upper 16 bits of each term = its bf16 pattern; h + m + l == x exactly
-    h = __float_as_uint(x);
-    const float r = x - __uint_as_float(h & 0xffff0000u);
-    m = __float_as_uint(r);
-    l = __float_as_uint(r - __uint_as_float(m & 0xffff0000u));
-}
-// pack the bf16 (upper) halves of two fp32 bit patterns: lo -> bits 15:0, hi -> bits 31:16
-__device__ __forceinline__ unsigned pack_hi16(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
-
 // two values at a time: the subtractions are packed fp32 instructions (v_pk_add_f32 with a negated operand, one issue slot for two lanes of data)
 typedef float at_f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void split_pair(at_f2 x, unsigned &ph, unsigned &pm, unsigned &pl)
@@ -207,7 +195,7 @@ __device__ __forceinline__ void split_pair(at_f2 x, unsigned &ph, unsigned &pm, 
     const unsigned r0 = __float_as_uint(r.x), r1 = __float_as_uint(r.y);
     at_f2 m; m.x = __uint_as_float(r0 & 0xffff0000u); m.y = __uint_as_float(r1 & 0xffff0000u);
     const at_f2 l = r - m;
-    ph = pack_hi16(x0, x1); pm = pack_hi16(r0, r1); pl = pack_hi16(__float_as_uint(l.x), __float_as_uint(l.y));
+    ph = bf_pack_hi16(x0, x1); pm = bf_pack_hi16(r0, r1); pl = bf_pack_hi16(__float_as_uint(l.x), __float_as_uint(l.y));
 }
 template <int N8>
 __device__ __forceinline__ void split_pack(const float (&x)[N8], unsigned (&ph)[N8 / 2], unsigned (&pm)[N8 / 2], unsigned (&pl)[N8 / 2])
@@ -281,8 +269,8 @@ __global__ void __launch_bounds__(512, 1) sg_attention_bf16x3_p_kernel(
     const int sr = tid >> 4, sc4 = (tid & 15) * 4;
     const unsigned rowb = (unsigned)ld * 4u;
     const unsigned span = nk > 0 ? (unsigned)(nk - 1) * rowb + AT_D * 4u : 0u;
-    const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void *)(Kp + (size_t)bk * N * ld + h * AT_D), 0, (int)span, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void *)(Vp + (size_t)bk * N * ld + h * AT_D), 0, (int)span, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void *)(Kp + (size_t)bk * N * ld + h * AT_D), 0, (int)span, MFR_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void *)(Vp + (size_t)bk * N * ld + h * AT_D), 0, (int)span, MFR_RSRC_FLAGS);
     const unsigned koff = (unsigned)sr * rowb + 4u * (unsigned)sc4, voff = 4u * (unsigned)lane;
     const int ntiles = (nk + AT_KT - 1) / AT_KT;
     float4 kr;
@@ -522,8 +510,8 @@ __global__ void __launch_bounds__(512, 1) sg_attention_f16x2_p_kernel(
     const int sr = tid >> 4, sc4 = (tid & 15) * 4;
     const unsigned rowb = (unsigned)ld * 4u;
     const unsigned span = nk > 0 ? (unsigned)(nk - 1) * rowb + AT_D * 4u : 0u;
-    const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void *)(Kp + (size_t)bk * N * ld + h * AT_D), 0, (int)span, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void *)(Vp + (size_t)bk * N * ld + h * AT_D), 0, (int)span, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void *)(Kp + (size_t)bk * N * ld + h * AT_D), 0, (int)span, MFR_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void *)(Vp + (size_t)bk * N * ld + h * AT_D), 0, (int)span, MFR_RSRC_FLAGS);
     const unsigned koff = (unsigned)sr * rowb + 4u * (unsigned)sc4, voff = 4u * (unsigned)lane;
     const int ntiles = (nk + AT_KT - 1) / AT_KT;
     float4 kr;

@@ -39,13 +39,13 @@
 #include <type_traits>
 
 #include "../../include/mfr_hip.h"
+#include "wave_dev.h"
 #include "split_f16.h"
 #include "guard.h"
 
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
+using namespace mfr;
 
 typedef float dc_f32x16 __attribute__((ext_vector_type(16)));
-#define DC_RSRC_FLAGS 0x00020000
 #define DC_OOB 0x80000000u
 #define DC_PC 34                     // patch columns: 32 + halo
 #define DC_FRAGS_PER_TAP 6           // 2 channel blocks x 3 terms
@@ -94,8 +94,7 @@ __global__ void __launch_bounds__(64) dc_scale_kernel(const float *__restrict__ 
     float mx = 0.f;
     if (co < Cout)
         for (int t = lane; t < Cin * 9; t += 64) mx = fmaxf(mx, fabsf(w[(size_t)co * Cin * 9 + t]));
-#pragma unroll
-    for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    mx = wave_max(mx);
     if (lane == 0 && co < cpad) oscale[co] = 1.0f / sf_feature_scale(mx);
 }
 __global__ void __launch_bounds__(256) dc_pack_kernel(const float *__restrict__ w, int Cin, int Cout, int nks, long long total, const float *__restrict__ oscale, uint4 *__restrict__ out)
@@ -149,7 +148,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_direct_f16x2_kernel(
     const bool tail = !POOL && NW == 4 && MG == 2 && cgi == ncgw - 1 && (Cout - cgi * 128 + 31) / 32 == 3;
 
     // ---- staging plan (K-loop invariant): round r, item i = NT r + tid -> channel half hh = i / PPAD (wave-uniform: PPAD % 64 == 0), patch pixel p
-    const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void *)(x + (size_t)b * Cin * HW), 0, Cin * HW * 4, DC_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void *)(x + (size_t)b * Cin * HW), 0, Cin * HW * 4, MFR_RSRC_FLAGS);
     unsigned voff[G::R];
     int wdst[G::R], hh[G::R];
 #pragma unroll
@@ -181,7 +180,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_direct_f16x2_kernel(
     };
 
     // ---- weight fragments: [m][term] of the current tap; fragment index wave-uniform (scalar offset), vector address = lane * 16
-    const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void *)wp, 0, (int)wp_bytes, DC_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void *)wp, 0, (int)wp_bytes, MFR_RSRC_FLAGS);
     const unsigned lane16 = (unsigned)lane * 16u;
     auto body = [&](auto mbc, auto nbc) {
     constexpr int MB = decltype(mbc)::value, NB = decltype(nbc)::value;
@@ -321,13 +320,13 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_direct_f16x2_kernel(
     const int cpad1 = (Cout + 63) / 64 * 64 - 1;
     auto activate = [&](float v) { return act == 1 ? fmaxf(v, 0.f) : act == 2 ? (v > 0.f ? v : 0.01f * v) : v; };
     // invalid channel part 0x40000000, invalid pixel part 0x80000000: any sum of the two lies beyond a buffer of < 2^30 bytes (host check), none wraps
-    const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void *)(y + (size_t)b * Cout * cstride), 0, (int)(Cout * cstride * 4), DC_RSRC_FLAGS);
-    const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc((void *)(residual ? residual + (size_t)b * Cout * HW : nullptr), 0, residual ? Cout * HW * 4 : 0, DC_RSRC_FLAGS);   // (one image)
+    const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void *)(y + (size_t)b * Cout * cstride), 0, (int)(Cout * cstride * 4), MFR_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc((void *)(residual ? residual + (size_t)b * Cout * HW : nullptr), 0, residual ? Cout * HW * 4 : 0, MFR_RSRC_FLAGS);   // (one image)
     if (ldrows > 0) {
         // ROWS output (round 6): y [B H W, ldrows] token-major, channel c of pixel p at y[p * ldrows + c] -- what the linear layer behind the convolution
         // reads (SuperPoint's descriptor head, LoFTR's fine map): the accumulators already hold four consecutive channels of a pixel per register
         // group, so each group leaves as one 16-byte store and the NCHW -> rows transposition pass (mfr_nchw_to_rows) disappears.
-        const __amdgpu_buffer_rsrc_t rsQ = __builtin_amdgcn_make_buffer_rsrc((void *)(y + (size_t)b * HW * ldrows), 0, HW * ldrows * 4, DC_RSRC_FLAGS);
+        const __amdgpu_buffer_rsrc_t rsQ = __builtin_amdgcn_make_buffer_rsrc((void *)(y + (size_t)b * HW * ldrows), 0, HW * ldrows * 4, MFR_RSRC_FLAGS);
         unsigned pixrow[NB];
 #pragma unroll
         for (int n = 0; n < NB; ++n) {

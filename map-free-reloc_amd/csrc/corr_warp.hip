@@ -29,8 +29,7 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
-
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
+#include "wave_dev.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

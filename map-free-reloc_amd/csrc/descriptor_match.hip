@@ -23,8 +23,9 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
+#include "wave_dev.h"
 
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
+using namespace mfr;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -173,12 +174,10 @@ __global__ void __launch_bounds__(256) desc_ratio_kernel(
     const float *__restrict__ nn_d2, double ratio, const float *__restrict__ kp0, const float *__restrict__ kp1,
     float *__restrict__ pts0, float *__restrict__ pts1, int maxN, int *__restrict__ n_corr)
 {
-    __shared__ int wave_cnt[4];
-    __shared__ int base_s;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    __shared__ Compact256 cs;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int m = n0v[b], n = n1v[b];
-    if (tid == 0) base_s = 0;
-    __syncthreads();
+    int total = 0;
     for (int start = 0; start < m; start += 256) {
         const int i = start + tid;
         bool valid = false;
@@ -189,14 +188,8 @@ __global__ void __launch_bounds__(256) desc_ratio_kernel(
             const float d2 = sqrt_rn_f32(nn_d2[((size_t)b * N0 + i) * 2 + 1]);
             valid = (double)d1 < ratio * (double)d2;
         }
-        const unsigned long long bal = __ballot(valid);
-        const int wpre = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_cnt[wid] = __popcll(bal);
-        __syncthreads();
-        int off = base_s;
-        for (int w = 0; w < wid; ++w) off += wave_cnt[w];
+        const int o = compact256_slot(cs, valid, total);
         if (valid) {
-            const int o = off + wpre;
             if (o < maxN) {
                 pts0[((size_t)b * maxN + o) * 2] = kp0[((size_t)b * N0 + i) * 2];
                 pts0[((size_t)b * maxN + o) * 2 + 1] = kp0[((size_t)b * N0 + i) * 2 + 1];
@@ -204,11 +197,8 @@ __global__ void __launch_bounds__(256) desc_ratio_kernel(
                 pts1[((size_t)b * maxN + o) * 2 + 1] = kp1[((size_t)b * N1 + j) * 2 + 1];
             }
         }
-        __syncthreads();
-        if (tid == 0) base_s = off + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-        __syncthreads();
     }
-    if (tid == 0) n_corr[b] = min(base_s, maxN);
+    if (tid == 0) n_corr[b] = min(total, maxN);
 }
 
 extern "C" {

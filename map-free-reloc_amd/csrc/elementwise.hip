@@ -13,8 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
-
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
+#include "wave_dev.h"
 
 __global__ void __launch_bounds__(256) bias_relu_kernel(float *__restrict__ x, const float *__restrict__ bias, int C, int HW)
 {

@@ -29,7 +29,6 @@ using namespace mfr;
 // was 256 workgroups = ONE wavefront per SIMD of latency-bound fp64 work; a hypothesis' result does not depend on the grouping
 #define EM_HYP_PER_WG 16
 #define EM_TILE 1024
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
 
 __global__ void __launch_bounds__(256) emat_prep_kernel(
     const float *__restrict__ pts0, const float *__restrict__ pts1, const int32_t *__restrict__ n_corr, int maxN,
@@ -209,55 +208,6 @@ __global__ void __launch_bounds__(256) emat_score_kernel(
 }
 
 // ------------------------------------------------------------------------------------------
-static __device__ __forceinline__ void quat_right_update(const double *R, const double *dw, double *Rn)
-{
-    const double hx = 0.5 * dw[0], hy = 0.5 * dw[1], hz = 0.5 * dw[2];
-    const double nn = sqrt(((hx * hx + hy * hy) + hz * hz) + 1.0);
-    const double w = 1.0 / nn, x = hx / nn, y = hy / nn, z = hz / nn;
-    double Q[9];
-    Q[0] = 1.0 - 2.0 * (y * y + z * z); Q[1] = 2.0 * (x * y - w * z);       Q[2] = 2.0 * (x * z + w * y);
-    Q[3] = 2.0 * (x * y + w * z);       Q[4] = 1.0 - 2.0 * (x * x + z * z); Q[5] = 2.0 * (y * z - w * x);
-    Q[6] = 2.0 * (x * z - w * y);       Q[7] = 2.0 * (y * z + w * x);       Q[8] = 1.0 - 2.0 * (x * x + y * y);
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j)
-            Rn[3 * i + j] = (R[3 * i] * Q[j] + R[3 * i + 1] * Q[3 + j]) + R[3 * i + 2] * Q[6 + j];
-}
-
-static __device__ __forceinline__ int chol_solve6(const double *A, const double *bvec, double *x)
-{
-    double L[36];
-#pragma unroll
-    for (int i = 0; i < 36; ++i) L[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-            double s = A[6 * i + j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) s = s - L[6 * i + k] * L[6 * j + k];
-            if (i == j) {
-                if (!(s > 0.0)) return -1;
-                L[6 * i + i] = sqrt(s);
-            } else L[6 * i + j] = s / L[6 * j + j];
-        }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double s = bvec[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) s = s - L[6 * i + k] * y[k];
-        y[i] = s / L[6 * i + i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) s = s - L[6 * k + i] * x[k];
-        x[i] = s / L[6 * i + i];
-    }
-    return 0;
-}
-
 // emat_select_kernel runs one workgroup of EM_SEL_WAVES wavefronts per pair (round 5; rounds 1-4: ONE wavefront per pair -- 16 wavefronts on the
 // whole GPU for LoFTR's 16 pairs, 1.85 ms of pure latency).  Sums over points: point i belongs to thread i mod (64 EM_SEL_WAVES), a wavefront's
 // 64 partials merge in the xor butterfly (wave_sum), the wavefront totals are added in sequence -- the order oracle/mfr_oracle_emat.c's
@@ -789,7 +739,6 @@ __global__ void __launch_bounds__(EM_SEL_THREADS) emat_select_kernel(
     }
 }
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 struct EmWs { size_t x0, x1, thr2, Es, nsol, counts, bestm, losses, idx, rm, total; };
 static EmWs em_ws_layout(int B, int maxN, int iters)
 {

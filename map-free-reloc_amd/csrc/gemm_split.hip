@@ -31,10 +31,11 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
+#include "wave_dev.h"
 #include "split_f16.h"
 #include "guard.h"
 
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
+using namespace mfr;
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -48,15 +49,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define GB_W_TILE_UNITS(F16) (GB_WT(F16) * 512)   // packed W tile: terms x 4 k groups x 128 features, 16 bytes each
 
 union GbFrag { bf16x8 v; unsigned u[4]; uint4 q; };
-
-__device__ __forceinline__ void gb_split3(float x, unsigned &h, unsigned &m, unsigned &l)
-{
-    h = __float_as_uint(x);
-    const float r = x - __uint_as_float(h & 0xffff0000u);
-    m = __float_as_uint(r);
-    l = __float_as_uint(r - __uint_as_float(m & 0xffff0000u));
-}
-__device__ __forceinline__ unsigned gb_pack(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
 
 // f16x2: wq = rne_f16(wh * 2^-11), eight weights at a time (4 x v_pk_mul_f16; a power of two: exact unless the product is subnormal)
 typedef _Float16 gb_h8 __attribute__((ext_vector_type(8)));
@@ -81,10 +73,10 @@ __device__ __forceinline__ void gb_xsplit_store(uint4 *lds, const float4 &p, con
         const float x[8] = { p.x, p.y, p.z, p.w, q.x, q.y, q.z, q.w };
         unsigned h[8], m[8], l[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) gb_split3(x[e], h[e], m[e], l[e]);
-        lds[0 * GB_TERM_UNITS + dst] = make_uint4(gb_pack(h[0], h[1]), gb_pack(h[2], h[3]), gb_pack(h[4], h[5]), gb_pack(h[6], h[7]));
-        lds[1 * GB_TERM_UNITS + dst] = make_uint4(gb_pack(m[0], m[1]), gb_pack(m[2], m[3]), gb_pack(m[4], m[5]), gb_pack(m[6], m[7]));
-        lds[2 * GB_TERM_UNITS + dst] = make_uint4(gb_pack(l[0], l[1]), gb_pack(l[2], l[3]), gb_pack(l[4], l[5]), gb_pack(l[6], l[7]));
+        for (int e = 0; e < 8; ++e) bf_split3(x[e], h[e], m[e], l[e]);
+        lds[0 * GB_TERM_UNITS + dst] = make_uint4(bf_pack_hi16(h[0], h[1]), bf_pack_hi16(h[2], h[3]), bf_pack_hi16(h[4], h[5]), bf_pack_hi16(h[6], h[7]));
+        lds[1 * GB_TERM_UNITS + dst] = make_uint4(bf_pack_hi16(m[0], m[1]), bf_pack_hi16(m[2], m[3]), bf_pack_hi16(m[4], m[5]), bf_pack_hi16(m[6], m[7]));
+        lds[2 * GB_TERM_UNITS + dst] = make_uint4(bf_pack_hi16(l[0], l[1]), bf_pack_hi16(l[2], l[3]), bf_pack_hi16(l[4], l[5]), bf_pack_hi16(l[6], l[7]));
     }
 }
 
@@ -118,8 +110,7 @@ __global__ void __launch_bounds__(64) gb_scale_kernel(const float *__restrict__ 
     float mx = 0.f;
     if (n < N)
         for (int k = lane; k < K; k += 64) mx = fmaxf(mx, fabsf(w[(size_t)n * ldw + k]));
-#pragma unroll
-    for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    mx = wave_max(mx);
     if (lane == 0 && n < npad) oscale[n] = out_mul / sf_feature_scale(mx);           // powers of two: the reciprocal is exact (out_mul: a power of two the caller wants folded into the product)
 }
 template <bool F16>
@@ -145,14 +136,14 @@ __global__ void __launch_bounds__(256) gb_pack_kernel(const float *__restrict__ 
             unsigned short wh, wl, wq;
             sf_split_w(x * s, wh, wl, wq);
             (void)wq;
-            word[e] = (unsigned)(term == 0 ? wh : wl) << 16;                         // (upper half, as the bf16 terms: gb_pack takes the upper halves)
+            word[e] = (unsigned)(term == 0 ? wh : wl) << 16;                         // (upper half, as the bf16 terms: bf_pack_hi16 takes the upper halves)
         } else {
             unsigned h, m, l;
-            gb_split3(x, h, m, l);
+            bf_split3(x, h, m, l);
             word[e] = term == 0 ? h : term == 1 ? m : l;
         }
     }
-    out[t] = make_uint4(gb_pack(word[0], word[1]), gb_pack(word[2], word[3]), gb_pack(word[4], word[5]), gb_pack(word[6], word[7]));
+    out[t] = make_uint4(bf_pack_hi16(word[0], word[1]), bf_pack_hi16(word[2], word[3]), bf_pack_hi16(word[4], word[5]), bf_pack_hi16(word[6], word[7]));
 }
 
 // ---- baseline: one tile per workgroup (round 3) --------------------------------------------------------------------------------------
@@ -280,7 +271,6 @@ __global__ void __launch_bounds__(256, 2) gemm_split_kernel(const float *__restr
 // in flight during the current tile's last multiply and -- for the accumulating epilogue -- Y is fetched during the last K step.
 // Same arithmetic per output element as the kernel above, bit for bit.  Grid = 2 workgroups per CU (512: the SuperGlue shapes are
 // 1024 / 2048 / 3072 tiles); tiles are dealt per XCD so that the workgroups sharing an X row block share an L2 (row block mb lives on XCD mb % 8).
-#define GB_RSRC_FLAGS 0x00020000
 template <int FLAGS, bool F16>
 __global__ void __launch_bounds__(256, 2) gemm_split_pk_kernel(const float *__restrict__ X, int ldx, const uint4 *__restrict__ Wp, const float *__restrict__ oscale,
                                                                const float *__restrict__ bias, float *__restrict__ Y, int ldy, int M, int N, int K, int nnb, int nmb,
@@ -317,8 +307,8 @@ __global__ void __launch_bounds__(256, 2) gemm_split_pk_kernel(const float *__re
     const int arow = (lane >> 5) * GB_KG_STRIDE + 64 * wm + (lane & 31);
     const int brow = (lane >> 5) * GB_KG_STRIDE + 64 * wn + (lane & 31);
     const unsigned rowb = (unsigned)ldy * 4u;              // bytes per row of Y
-    const __amdgpu_buffer_rsrc_t rbias = __builtin_amdgcn_make_buffer_rsrc((void *)bias, 0, bias ? N * 4 : 0, GB_RSRC_FLAGS);   // no bias: every read returns 0
-    const __amdgpu_buffer_rsrc_t rscale = __builtin_amdgcn_make_buffer_rsrc((void *)oscale, 0, F16 ? nnb * GB_BN * 4 : 0, GB_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rbias = __builtin_amdgcn_make_buffer_rsrc((void *)bias, 0, bias ? N * 4 : 0, MFR_RSRC_FLAGS);   // no bias: every read returns 0
+    const __amdgpu_buffer_rsrc_t rscale = __builtin_amdgcn_make_buffer_rsrc((void *)oscale, 0, F16 ? nnb * GB_BN * 4 : 0, MFR_RSRC_FLAGS);
 
     // the LOAD stream runs one K step ahead of the multiply, across tile boundaries
     const float *lx0, *lx1;
@@ -351,7 +341,7 @@ __global__ void __launch_bounds__(256, 2) gemm_split_pk_kernel(const float *__re
         GB_TILE(j, mb, nb);
         const int m0 = mb * GB_BM;
         // this tile's rows of Y as one buffer (rows beyond M fall outside it: reads return 0, stores are dropped)
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void *)(Y + (size_t)m0 * ldy), 0, (int)((unsigned)min(GB_BM, M - m0) * rowb), GB_RSRC_FLAGS);
+        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void *)(Y + (size_t)m0 * ldy), 0, (int)((unsigned)min(GB_BM, M - m0) * rowb), MFR_RSRC_FLAGS);
         const int n0 = nb * GB_BN + 64 * wn + (lane & 31);
         const unsigned yoff = (unsigned)(64 * wm + 4 * (lane >> 5)) * rowb + 4u * (unsigned)n0;
         const float bv0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rbias, 4u * (unsigned)n0, 0, 0));
@@ -491,8 +481,8 @@ __global__ void __launch_bounds__(256, 2) gemm_split_d_kernel(const float *__res
     const int arow = (lane >> 5) * GB_KG_STRIDE + 64 * wm + (lane & 31);
     const int brow = XT * GB_TERM_UNITS + (lane >> 5) * 128 + 64 * wn + (lane & 31);
     const unsigned rowb = (unsigned)ldy * 4u;
-    const __amdgpu_buffer_rsrc_t rbias = __builtin_amdgcn_make_buffer_rsrc((void *)bias, 0, bias ? N * 4 : 0, GB_RSRC_FLAGS);
-    const __amdgpu_buffer_rsrc_t rscale = __builtin_amdgcn_make_buffer_rsrc((void *)oscale, 0, F16 ? nnb * GB_BN * 4 : 0, GB_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rbias = __builtin_amdgcn_make_buffer_rsrc((void *)bias, 0, bias ? N * 4 : 0, MFR_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rscale = __builtin_amdgcn_make_buffer_rsrc((void *)oscale, 0, F16 ? nnb * GB_BN * 4 : 0, MFR_RSRC_FLAGS);
 
     // W stream (LDS-DMA, one step ahead): descriptor over the whole packed weight, scalar offset = tile image + this wavefront's chunks
     typedef unsigned gd_u32x4 __attribute__((ext_vector_type(4)));
@@ -500,7 +490,7 @@ __global__ void __launch_bounds__(256, 2) gemm_split_d_kernel(const float *__res
     wdesc.x = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)Wp);
     wdesc.y = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)Wp >> 32) & 0xffffu);
     wdesc.z = wp_bytes;
-    wdesc.w = GB_RSRC_FLAGS;
+    wdesc.w = MFR_RSRC_FLAGS;
     const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) uint4 *)lds;
     const unsigned lane16 = 16u * (unsigned)lane;
     int wj = j, wk = 0;                                    // item / K step the W stream is at
@@ -586,7 +576,7 @@ __global__ void __launch_bounds__(256, 2) gemm_split_d_kernel(const float *__res
     for (;;) {
         GD_TILE(j, mb, nb);
         const int m0 = mb * GB_BM;
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void *)(Y + (size_t)m0 * ldy), 0, (int)((unsigned)min(GB_BM, M - m0) * rowb), GB_RSRC_FLAGS);
+        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void *)(Y + (size_t)m0 * ldy), 0, (int)((unsigned)min(GB_BM, M - m0) * rowb), MFR_RSRC_FLAGS);
         const int n0 = nb * GB_BN + 64 * wn + (lane & 31);
         const unsigned yoff = (unsigned)(64 * wm + 4 * (lane >> 5)) * rowb + 4u * (unsigned)n0;
         const float bv0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rbias, 4u * (unsigned)n0, 0, 0));
@@ -772,10 +762,10 @@ __global__ void __launch_bounds__(256, 2) mlp_ln_kernel(const float *__restrict_
     gd_u32x4 wdesc1, wdesc2;
     wdesc1.x = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)W1p);
     wdesc1.y = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)W1p >> 32) & 0xffffu);
-    wdesc1.z = w1_bytes; wdesc1.w = GB_RSRC_FLAGS;
+    wdesc1.z = w1_bytes; wdesc1.w = MFR_RSRC_FLAGS;
     wdesc2.x = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)W2p);
     wdesc2.y = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)W2p >> 32) & 0xffffu);
-    wdesc2.z = w2_bytes; wdesc2.w = GB_RSRC_FLAGS;
+    wdesc2.z = w2_bytes; wdesc2.w = MFR_RSRC_FLAGS;
     const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) uint4 *)lds;
     const unsigned lane16 = 16u * (unsigned)lane;
     int wstep = 0;
@@ -833,7 +823,7 @@ __global__ void __launch_bounds__(256, 2) mlp_ln_kernel(const float *__restrict_
     const float be0 = ln_beta[64 * wn + (lane & 31)], be1 = ln_beta[64 * wn + 32 + (lane & 31)];
     for (;;) {
         const int mb = j * 8 + xcd, m0 = mb * GB_BM;
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void *)(Y + (size_t)m0 * ldy), 0, (int)((unsigned)min(GB_BM, M - m0) * rowb), GB_RSRC_FLAGS);
+        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void *)(Y + (size_t)m0 * ldy), 0, (int)((unsigned)min(GB_BM, M - m0) * rowb), MFR_RSRC_FLAGS);
         const int n0 = 64 * wn + (lane & 31);
         const unsigned yoff = (unsigned)(64 * wm + 4 * (lane >> 5)) * rowb + 4u * (unsigned)n0;
 #pragma unroll
@@ -1031,7 +1021,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_f16x2_kernel(const float *_
     const int nb = blockIdx.x % nnb;
     const int pt = (blockIdx.x / nnb) % npt, b = blockIdx.x / (nnb * npt);
     const int HW = H * W, HoWo = Ho * Wo;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void *)(X + (size_t)b * Cin * HW), 0, Cin * HW * 4, GB_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void *)(X + (size_t)b * Cin * HW), 0, Cin * HW * 4, MFR_RSRC_FLAGS);
 
     // X staging: unit u = tid + 256 i -> pixel u & 127 of the tile, k group u >> 7 (wave-uniform)
     int xdst[2], kg[2];
@@ -1157,8 +1147,8 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_f16x2_kernel(const float *_
     // predicated stores] -- cost more than the whole K loop of a 1x1 / 7x7 layer.  Now: scale / bias of all 32 registers are fetched before the
     // first store, the up-sampling taps two iterations ahead of their use, and every store is an unconditional buffer store whose offset lies
     // beyond the buffer where nothing must be written (invalid channel part 0x40000000, invalid pixel part 0x80000000: host check Cout Ho Wo 4 < 2^30).
-    const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void *)(Y + (size_t)b * Cout * HoWo), 0, Cout * HoWo * 4, GB_RSRC_FLAGS);
-    const __amdgpu_buffer_rsrc_t rsL = __builtin_amdgcn_make_buffer_rsrc((void *)(UP ? lo + (size_t)b * Cout * ((size_t)Hl * Wl) : nullptr), 0, UP ? Cout * Hl * Wl * 4 : 0, GB_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void *)(Y + (size_t)b * Cout * HoWo), 0, Cout * HoWo * 4, MFR_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rsL = __builtin_amdgcn_make_buffer_rsrc((void *)(UP ? lo + (size_t)b * Cout * ((size_t)Hl * Wl) : nullptr), 0, UP ? Cout * Hl * Wl * 4 : 0, MFR_RSRC_FLAGS);
     float osv[2][16], bvv[2][16];
     unsigned cho[2][16];
 #pragma unroll

@@ -9,8 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define MFR_DEV static __device__ __forceinline__
-#define MFR_DEV_NOINLINE static __device__ __noinline__
+#include "wave_dev.h"          // MFR_DEV, wave_sum, lane_id
 
 namespace mfr {
 
@@ -391,14 +390,67 @@ MFR_DEV int pnp_hypothesis(const double *xyz, const double *obs, const int *s, c
     return 1;
 }
 
-// ---------------------------------------------------------------- wave64 helpers
-MFR_DEV double wave_sum(double v)
+// ---------------------------------------------------------------- depth minimum
+// mfr_depth_min (pnp.hip) leaves MFR_NSEG per-segment minima per image ([B,16] in include/mfr_hip.h); the lift kernels fold them in
+// segment order with a strict <, as depth_min_kernel folds its lanes: depth.min() of the whole map (pose_solver.py:196, quirk Q6)
+#define MFR_NSEG 16
+MFR_DEV float depth_min_fold(const float *__restrict__ partial_min, int b)
 {
-    // xor butterfly 32,16,8,4,2,1: every lane ends with the same bits (a+b == b+a)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-    return v;
+    float m = partial_min[b * MFR_NSEG];
+    for (int s = 1; s < MFR_NSEG; ++s) { const float v = partial_min[b * MFR_NSEG + s]; if (v < m) m = v; }
+    return m;
 }
-MFR_DEV int lane_id() { return (int)(threadIdx.x & 63); }
+
+// ---------------------------------------------------------------- Levenberg-Marquardt pieces (pnp.hip, emat.hip)
+// R <- R * Q(dw): right-multiplication by the unit quaternion (1, dw / 2) / |..|
+MFR_DEV void quat_right_update(const double *R, const double *dw, double *Rn)
+{
+    const double hx = 0.5 * dw[0], hy = 0.5 * dw[1], hz = 0.5 * dw[2];
+    const double nn = sqrt(((hx * hx + hy * hy) + hz * hz) + 1.0);
+    const double w = 1.0 / nn, x = hx / nn, y = hy / nn, z = hz / nn;
+    double Q[9];
+    Q[0] = 1.0 - 2.0 * (y * y + z * z); Q[1] = 2.0 * (x * y - w * z);       Q[2] = 2.0 * (x * z + w * y);
+    Q[3] = 2.0 * (x * y + w * z);       Q[4] = 1.0 - 2.0 * (x * x + z * z); Q[5] = 2.0 * (y * z - w * x);
+    Q[6] = 2.0 * (x * z - w * y);       Q[7] = 2.0 * (y * z + w * x);       Q[8] = 1.0 - 2.0 * (x * x + y * y);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            Rn[3 * i + j] = (R[3 * i] * Q[j] + R[3 * i + 1] * Q[3 + j]) + R[3 * i + 2] * Q[6 + j];
+}
+
+// A x = b for a symmetric positive definite 6 x 6 A (lower triangle read) by Cholesky; -1 when a pivot is not positive
+MFR_DEV int chol_solve6(const double *A, const double *bvec, double *x)
+{
+    double L[36];
+#pragma unroll
+    for (int i = 0; i < 36; ++i) L[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            double s = A[6 * i + j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s = s - L[6 * i + k] * L[6 * j + k];
+            if (i == j) {
+                if (!(s > 0.0)) return -1;
+                L[6 * i + i] = sqrt(s);
+            } else L[6 * i + j] = s / L[6 * j + j];
+        }
+    double y[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double s = bvec[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s = s - L[6 * i + k] * y[k];
+        y[i] = s / L[6 * i + i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double s = y[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) s = s - L[6 * k + i] * x[k];
+        x[i] = s / L[6 * i + i];
+    }
+    return 0;
+}
 
 }  // namespace mfr

@@ -22,9 +22,8 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
+#include "wave_dev.h"
 #include "../../include/mfr_jpeg.h"
-
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
 
 #define JE_THREADS 1024             // entropy workgroup: one image
 #define JE_WAVES (JE_THREADS / 64)

@@ -17,8 +17,7 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
-
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
+#include "wave_dev.h"
 
 #define KB_FN static __device__
 #include "kabsch_math.h"

@@ -24,8 +24,10 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
+#include "wave_dev.h"
 
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
+using namespace mfr;
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static __device__ __forceinline__ float phi(float x) { return x > 0.f ? x + 1.f : expf(x); }   // elu(x) + 1
@@ -148,18 +150,6 @@ __global__ void __launch_bounds__(256) la_out_kernel(const float *__restrict__ Q
 }
 
 // ------------------------------------------------------------------------------------------ dual softmax
-struct Lse { float m, s; };
-static __device__ __forceinline__ void lse_add(Lse &a, float x)
-{
-    if (x > a.m) { a.s = a.s * expf(a.m - x) + 1.f; a.m = x; }
-    else a.s = a.s + expf(x - a.m);
-}
-static __device__ __forceinline__ void lse_merge(Lse &a, float m, float s)
-{
-    if (m == -INFINITY) return;
-    if (m > a.m) { a.s = a.s * expf(a.m - m) + s; a.m = m; }
-    else a.s = a.s + s * expf(m - a.m);
-}
 // conf_ij = softmax over rows-dim * softmax over cols-dim; ONE definition used by every kernel
 static __device__ __forceinline__ float conf_val(float s, float rmax, float rsum, float cmax, float csum)
 {
@@ -173,13 +163,9 @@ __global__ void __launch_bounds__(256) dsm_rowstat_kernel(const float *__restric
     const int b = blockIdx.y, lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= L0) return;
     const float *row = S + ((size_t)b * L0 + i) * L1;
-    Lse a = { -INFINITY, 0.f };
-    for (int j = lane; j < L1; j += 64) lse_add(a, row[j] / temp);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float om = __shfl_xor(a.m, off, 64), os = __shfl_xor(a.s, off, 64);
-        lse_merge(a, om, os);
-    }
+    LsePrecise a = { -INFINITY, 0.f };
+    for (int j = lane; j < L1; j += 64) lse_precise_add(a, row[j] / temp);
+    lse_precise_wave_merge(a);
     if (lane == 0) { rmax[(size_t)b * L0 + i] = a.m; rsum[(size_t)b * L0 + i] = a.s; }
 }
 
@@ -189,15 +175,15 @@ __global__ void __launch_bounds__(1024) dsm_colstat_kernel(const float *__restri
 {
     __shared__ float sm[16][64], ss[16][64];
     const int b = blockIdx.y, lane = threadIdx.x & 63, g = threadIdx.x >> 6, j = blockIdx.x * 64 + lane;
-    Lse a = { -INFINITY, 0.f };
+    LsePrecise a = { -INFINITY, 0.f };
     if (j < L1) {
         const float *colp = S + (size_t)b * L0 * L1 + j;
-        for (int i = g; i < L0; i += 16) lse_add(a, colp[(size_t)i * L1] / temp);
+        for (int i = g; i < L0; i += 16) lse_precise_add(a, colp[(size_t)i * L1] / temp);
     }
     sm[g][lane] = a.m; ss[g][lane] = a.s;
     __syncthreads();
     if (g == 0 && j < L1) {
-        for (int k = 1; k < 16; ++k) lse_merge(a, sm[k][lane], ss[k][lane]);
+        for (int k = 1; k < 16; ++k) lse_precise_merge(a, sm[k][lane], ss[k][lane]);
         cmax[(size_t)b * L1 + j] = a.m; csum[(size_t)b * L1 + j] = a.s;
     }
 }
@@ -216,11 +202,7 @@ __global__ void __launch_bounds__(256) dsm_rowbest_kernel(const float *__restric
         const float c = conf_val(row[j] / temp, rm, rs, cmax[(size_t)b * L1 + j], csum[(size_t)b * L1 + j]);
         if (c > best) { best = c; bj = j; }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ob = __shfl_xor(best, off, 64); const int oj = __shfl_xor(bj, off, 64);
-        if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }
-    }
+    wave_argmax(best, bj);
     if (lane == 0) { rbest[(size_t)b * L0 + i] = best; rarg[(size_t)b * L0 + i] = bj; }
 }
 
@@ -264,38 +246,6 @@ __global__ void __launch_bounds__(1024) dsm_colbest_kernel(const float *__restri
 // wavefront-wide maximum first and ONE v_exp_f32 per term; column partials over the four rows in flight at once (1.5 per term); the
 // confidences from two v_exp_f32 and the reciprocals of the sums (per column: registers, per row: LDS).  The four-sweep kernels (variant 1)
 // keep the round-1 arithmetic; the two agree to round-off (tests/test_gpu_loftr_parity.py).
-template <int CTRL> static __device__ __forceinline__ float dsm_dpp(float x)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
-}
-static __device__ __forceinline__ void dsm_swap16(float &a, float &b) { asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
-static __device__ __forceinline__ void dsm_swap32(float &a, float &b) { asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
-static __device__ __forceinline__ float dsm_wave_max(float x)
-{
-    x = fmaxf(x, dsm_dpp<0xB1>(x)); x = fmaxf(x, dsm_dpp<0x4E>(x)); x = fmaxf(x, dsm_dpp<0x141>(x)); x = fmaxf(x, dsm_dpp<0x140>(x));
-    float y = x; dsm_swap16(x, y); x = fmaxf(x, y);
-    y = x; dsm_swap32(x, y); x = fmaxf(x, y);
-    return x;
-}
-static __device__ __forceinline__ float dsm_wave_sum(float x)
-{
-    x += dsm_dpp<0xB1>(x); x += dsm_dpp<0x4E>(x); x += dsm_dpp<0x141>(x); x += dsm_dpp<0x140>(x);
-    float y = x; dsm_swap16(x, y); x += y;
-    y = x; dsm_swap32(x, y); x += y;
-    return x;
-}
-
-static __device__ __forceinline__ void dsm_load4(const float *__restrict__ row, int j0, int nval, bool vec, float x[4])
-{
-    if (nval == 4 && vec) {
-        const float4 t = *(const float4 *)(row + j0);
-        x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x[k] = k < nval ? row[j0 + k] : 0.f;
-    }
-}
-
 __global__ void __launch_bounds__(256) dsm_stats_tile_kernel(const float *__restrict__ S, int L0, int L1, float temp,
                                                              float *__restrict__ rpm, float *__restrict__ rps,
                                                              float *__restrict__ cpm, float *__restrict__ cps)
@@ -307,7 +257,7 @@ __global__ void __launch_bounds__(256) dsm_stats_tile_kernel(const float *__rest
     const int i0 = st * DSM_RS, nrows = min(DSM_RS, L0 - i0);
     const bool vec = (L1 & 3) == 0;
     const float *base = S + ((size_t)b * L0 + i0) * L1;
-    Lse c[4];
+    LsePrecise c[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) c[k] = { -INFINITY, 0.f };
     const float itemp = 1.0f / temp;
@@ -315,7 +265,7 @@ __global__ void __launch_bounds__(256) dsm_stats_tile_kernel(const float *__rest
         float x[DSM_RU][4];
 #pragma unroll
         for (int u = 0; u < DSM_RU; ++u)
-            if (r0 + u < nrows) dsm_load4(base + (size_t)(r0 + u) * L1, j0, nval, vec, x[u]);
+            if (r0 + u < nrows) load4(base + (size_t)(r0 + u) * L1, j0, nval, vec, 0.f, x[u]);
         float t[DSM_RU][4];
 #pragma unroll
         for (int u = 0; u < DSM_RU; ++u)
@@ -324,9 +274,9 @@ __global__ void __launch_bounds__(256) dsm_stats_tile_kernel(const float *__rest
         // rows: the wavefront's maximum first, one exponential per term (an all-absent lane / row contributes exp(-inf) = 0)
 #pragma unroll
         for (int u = 0; u < DSM_RU; ++u) {
-            const float mx = dsm_wave_max(fmaxf(fmaxf(t[u][0], t[u][1]), fmaxf(t[u][2], t[u][3])));
+            const float mx = wave_max_dpp(fmaxf(fmaxf(t[u][0], t[u][1]), fmaxf(t[u][2], t[u][3])));
             const float ms = (mx > -INFINITY) ? mx : 0.f;
-            const float sm = dsm_wave_sum(((__expf(t[u][0] - ms) + __expf(t[u][1] - ms)) + __expf(t[u][2] - ms)) + __expf(t[u][3] - ms));
+            const float sm = wave_sum_dpp(((__expf(t[u][0] - ms) + __expf(t[u][1] - ms)) + __expf(t[u][2] - ms)) + __expf(t[u][3] - ms));
             if (lane == 0 && r0 + u < nrows) { wm[r0 + u][wid] = mx; wsum[r0 + u][wid] = sm; }
         }
         // columns: the four rows at once (row r0 exists; absent rows are -inf)
@@ -342,9 +292,9 @@ __global__ void __launch_bounds__(256) dsm_stats_tile_kernel(const float *__rest
     }
     __syncthreads();
     if (tid < nrows) {
-        Lse a = { wm[tid][0], wsum[tid][0] };
+        LsePrecise a = { wm[tid][0], wsum[tid][0] };
 #pragma unroll
-        for (int w = 1; w < 4; ++w) lse_merge(a, wm[tid][w], wsum[tid][w]);
+        for (int w = 1; w < 4; ++w) lse_precise_merge(a, wm[tid][w], wsum[tid][w]);
         const size_t o = ((size_t)b * ncb + cb) * L0 + i0 + tid;
         rpm[o] = a.m; rps[o] = a.s;
     }
@@ -365,13 +315,13 @@ __global__ void __launch_bounds__(256) dsm_stats_fold_kernel(int L0, int L1, int
 {
     const int b = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
     if (t < L0) {
-        Lse a = { -INFINITY, 0.f };
-        for (int k = 0; k < ncb; ++k) lse_merge(a, rpm[((size_t)b * ncb + k) * L0 + t], rps[((size_t)b * ncb + k) * L0 + t]);
+        LsePrecise a = { -INFINITY, 0.f };
+        for (int k = 0; k < ncb; ++k) lse_precise_merge(a, rpm[((size_t)b * ncb + k) * L0 + t], rps[((size_t)b * ncb + k) * L0 + t]);
         rmax[(size_t)b * L0 + t] = a.m; rsum[(size_t)b * L0 + t] = a.s;
     }
     if (t < L1) {
-        Lse a = { -INFINITY, 0.f };
-        for (int k = 0; k < nst; ++k) lse_merge(a, cpm[((size_t)b * nst + k) * L1 + t], cps[((size_t)b * nst + k) * L1 + t]);
+        LsePrecise a = { -INFINITY, 0.f };
+        for (int k = 0; k < nst; ++k) lse_precise_merge(a, cpm[((size_t)b * nst + k) * L1 + t], cps[((size_t)b * nst + k) * L1 + t]);
         cmax[(size_t)b * L1 + t] = a.m; csum[(size_t)b * L1 + t] = a.s;
     }
 }
@@ -404,7 +354,7 @@ __global__ void __launch_bounds__(256) dsm_best_tile_kernel(const float *__restr
         float x[DSM_RU][4];
 #pragma unroll
         for (int u = 0; u < DSM_RU; ++u)
-            if (r0 + u < nrows) dsm_load4(base + (size_t)(r0 + u) * L1, j0, nval, vec, x[u]);
+            if (r0 + u < nrows) load4(base + (size_t)(r0 + u) * L1, j0, nval, vec, 0.f, x[u]);
         float best[DSM_RU]; int bj[DSM_RU];
 #pragma unroll
         for (int u = 0; u < DSM_RU; ++u) {
@@ -421,6 +371,7 @@ __global__ void __launch_bounds__(256) dsm_best_tile_kernel(const float *__restr
                     }
             }
         }
+        // (wave_argmax of the rows in flight, interleaved by hand: one row after the other costs dsm_best_tile_kernel a wavefront of occupancy)
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) {
 #pragma unroll
@@ -477,11 +428,9 @@ __global__ void __launch_bounds__(256) dsm_match_kernel(int L0, int L1, int h0, 
                                                         int *__restrict__ j_ids, float *__restrict__ mconf,
                                                         int *__restrict__ n_match)
 {
-    __shared__ int wave_cnt[4];
-    __shared__ int base_s;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    if (tid == 0) base_s = 0;
-    __syncthreads();
+    __shared__ Compact256 cs;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int total = 0;
     for (int start = 0; start < L0; start += 256) {
         const int i = start + tid;
         bool valid = false; int j = 0; float c = 0.f;
@@ -492,21 +441,12 @@ __global__ void __launch_bounds__(256) dsm_match_kernel(int L0, int L1, int h0, 
                              y1 >= border && y1 < h1 - border && x1 >= border && x1 < w1 - border;
             valid = (c > thr) && inb && (c == cbest[(size_t)b * L1 + j]);
         }
-        const unsigned long long bal = __ballot(valid);
-        const int wpre = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_cnt[wid] = __popcll(bal);
-        __syncthreads();
-        int off = base_s;
-        for (int w = 0; w < wid; ++w) off += wave_cnt[w];
+        const int o = compact256_slot(cs, valid, total);
         if (valid) {
-            const int o = off + wpre;
             i_ids[(size_t)b * L0 + o] = i; j_ids[(size_t)b * L0 + o] = j; mconf[(size_t)b * L0 + o] = c;
         }
-        __syncthreads();
-        if (tid == 0) base_s = off + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-        __syncthreads();
     }
-    if (tid == 0) n_match[b] = base_s;
+    if (tid == 0) n_match[b] = total;
 }
 
 // ------------------------------------------------------------------------------------------ fine windows
@@ -643,8 +583,6 @@ __global__ void __launch_bounds__(128) fine_attention_kernel(const float *__rest
     }
 }
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 
 // ---------------------------------------------------------------------------------------------------------------
 // fine matching (LoFTR FineMatching, reached from LoFTR_matcher.match, etc/feature_matching_baselines/matchers.py:50-55 -> mkpts1_f):
@@ -666,23 +604,17 @@ __global__ void __launch_bounds__(256) fine_match_kernel(const float *__restrict
         const float *q = g1 + ((size_t)m * WW + r) * ld;
         float sacc = 0.f;
         for (int c = lane; c < C; c += 64) sacc = sacc + pc[c] * q[c];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) sacc = sacc + __shfl_xor(sacc, off, 64);
+        sacc = wave_sum(sacc);
         if (lane == r) mine = sacc * inv_sqrt_c;
     }
-    float mx = mine;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    const float mx = wave_max(mine);
     const float e = (lane < WW) ? __expf(mine - mx) : 0.f;
-    float sum = e;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) sum = sum + __shfl_xor(sum, off, 64);
+    const float sum = wave_sum(e);
     const float heat = e / sum;
     const float step = (W > 1) ? 2.0f / (float)(W - 1) : 0.f;
     float cx = (lane < WW) ? heat * (-1.0f + step * (float)(lane % W)) : 0.f;
     float cy = (lane < WW) ? heat * (-1.0f + step * (float)(lane / W)) : 0.f;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { cx = cx + __shfl_xor(cx, off, 64); cy = cy + __shfl_xor(cy, off, 64); }
+    cx = wave_sum(cx); cy = wave_sum(cy);
     if (lane == 0) {
         if (expec) { expec[2 * (size_t)m] = cx; expec[2 * (size_t)m + 1] = cy; }
         if (pts1) {

@@ -17,15 +17,9 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
+#include "wave_dev.h"
 
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
+using namespace mfr;
 
 template <int VEC>          // C = 64 * VEC
 __global__ void __launch_bounds__(256) layernorm_kernel(const float *__restrict__ x, int ldx, const float *__restrict__ gamma,

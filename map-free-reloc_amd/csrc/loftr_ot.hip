@@ -27,58 +27,14 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
+#include "wave_dev.h"
 
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
+using namespace mfr;
+
 #define OT_CB 1024          // columns per register block (256 threads x 4)
 #define OT_NQMAX 8          // register blocks: variant 0 holds rows of up to 8192 columns
 #define OT_RU 2             // rows in flight
 #define OT_RSMAX 64         // rows per stripe: 64, 32 or 16 (ot_stripe_rows)
-
-struct OtLse { float m, s; };
-static __device__ __forceinline__ void ot_lse_add(OtLse &a, float x)
-{
-    if (x > a.m) { a.s = a.s * expf(a.m - x) + 1.f; a.m = x; }
-    else a.s = a.s + expf(x - a.m);
-}
-static __device__ __forceinline__ void ot_lse_merge(OtLse &a, float m, float s)
-{
-    if (m == -INFINITY) return;
-    if (m > a.m) { a.s = a.s * expf(a.m - m) + s; a.m = m; }
-    else a.s = a.s + s * expf(m - a.m);
-}
-
-// wavefront reductions (the DPP / permlane forms of csrc/loftr.hip's dual-softmax tiles)
-template <int CTRL> static __device__ __forceinline__ float ot_dpp(float x)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
-}
-static __device__ __forceinline__ void ot_swap16(float &a, float &b) { asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
-static __device__ __forceinline__ void ot_swap32(float &a, float &b) { asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
-static __device__ __forceinline__ float ot_wave_max(float x)
-{
-    x = fmaxf(x, ot_dpp<0xB1>(x)); x = fmaxf(x, ot_dpp<0x4E>(x)); x = fmaxf(x, ot_dpp<0x141>(x)); x = fmaxf(x, ot_dpp<0x140>(x));
-    float y = x; ot_swap16(x, y); x = fmaxf(x, y);
-    y = x; ot_swap32(x, y); x = fmaxf(x, y);
-    return x;
-}
-static __device__ __forceinline__ float ot_wave_sum(float x)
-{
-    x += ot_dpp<0xB1>(x); x += ot_dpp<0x4E>(x); x += ot_dpp<0x141>(x); x += ot_dpp<0x140>(x);
-    float y = x; ot_swap16(x, y); x += y;
-    y = x; ot_swap32(x, y); x += y;
-    return x;
-}
-
-static __device__ __forceinline__ void ot_load4(const float *__restrict__ p, int j0, int nval, bool vec, float fill, float x[4])
-{
-    if (nval == 4 && vec) {
-        const float4 t = *(const float4 *)(p + j0);
-        x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x[k] = k < nval ? p[j0 + k] : fill;
-    }
-}
 
 // ---- variant 0: one sweep per iteration -----------------------------------------------------------------------------------
 // grid (stripes, B), 256 threads.  v == NULL: the zero potentials of the first iteration (then ubin0 is stored as u_bin).
@@ -97,7 +53,7 @@ __global__ void __launch_bounds__(256) ot_sweep_kernel(const float *__restrict__
     const float *vb = v ? v + (size_t)b * (L1 + 1) : nullptr;
     int nval[NQ];
     float vv[NQ][4];
-    OtLse c[NQ][4];
+    LsePrecise c[NQ][4];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
         const int j0 = q * OT_CB + 4 * tid;
@@ -117,7 +73,7 @@ __global__ void __launch_bounds__(256) ot_sweep_kernel(const float *__restrict__
         for (int r = 0; r < OT_RU; ++r)
 #pragma unroll
             for (int q = 0; q < NQ; ++q)
-                if (r0 + r < nrows) ot_load4(base + (size_t)(r0 + r) * L1, q * OT_CB + 4 * tid, nval[q], vec, 0.f, x[r][q]);
+                if (r0 + r < nrows) load4(base + (size_t)(r0 + r) * L1, q * OT_CB + 4 * tid, nval[q], vec, 0.f, x[r][q]);
         // rows: the wavefront's maximum first, one v_exp_f32 per term (an absent column / row is -inf and contributes exp(-inf) = 0)
 #pragma unroll
         for (int r = 0; r < OT_RU; ++r) {
@@ -127,7 +83,7 @@ __global__ void __launch_bounds__(256) ot_sweep_kernel(const float *__restrict__
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
                     if (r0 + r < nrows && k < nval[q]) lm = fmaxf(lm, x[r][q][k] + vv[q][k]);
-            const float mx = ot_wave_max(lm);
+            const float mx = wave_max_dpp(lm);
             const float ms = (mx > -INFINITY) ? mx : 0.f;
             float ls = 0.f;
 #pragma unroll
@@ -135,7 +91,7 @@ __global__ void __launch_bounds__(256) ot_sweep_kernel(const float *__restrict__
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
                     if (r0 + r < nrows && k < nval[q]) ls += __expf((x[r][q][k] + vv[q][k]) - ms);
-            const float sm = ot_wave_sum(ls);
+            const float sm = wave_sum_dpp(ls);
             if (lane == 0) { wm[par][r][wid] = mx; wsum[par][r][wid] = sm; }
         }
         __syncthreads();          // (buffers alternate: the next group's writes cannot overtake this group's reads)
@@ -182,9 +138,9 @@ __global__ void __launch_bounds__(256) ot_colfold_kernel(int L0, int L1, int nst
 {
     const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
     if (j >= L1) return;
-    OtLse acc = { -INFINITY, 0.f };
-    for (int k = 0; k < nst; ++k) ot_lse_merge(acc, cpm[((size_t)b * nst + k) * L1 + j], cps[((size_t)b * nst + k) * L1 + j]);
-    ot_lse_merge(acc, a + u[(size_t)b * (L0 + 1) + L0], 1.f);
+    LsePrecise acc = { -INFINITY, 0.f };
+    for (int k = 0; k < nst; ++k) lse_precise_merge(acc, cpm[((size_t)b * nst + k) * L1 + j], cps[((size_t)b * nst + k) * L1 + j]);
+    lse_precise_merge(acc, a + u[(size_t)b * (L0 + 1) + L0], 1.f);
     v[(size_t)b * (L1 + 1) + j] = norm - (acc.m + logf(acc.s));
 }
 
@@ -194,16 +150,14 @@ static __device__ float ot_block_lse(const float *x, int n, float *red)
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     float m = -INFINITY;
     for (int i = tid; i < n; i += 256) m = fmaxf(m, x[i]);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    m = wave_max(m);
     __syncthreads();
     if (lane == 0) red[wid] = m;
     __syncthreads();
     m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     float s = 0.f;
     for (int i = tid; i < n; i += 256) s += expf(x[i] - m);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = wave_sum(s);
     __syncthreads();
     if (lane == 0) red[wid] = s;
     __syncthreads();
@@ -257,7 +211,7 @@ __global__ void __launch_bounds__(256) ot_best_kernel(const float *__restrict__ 
         for (int r = 0; r < OT_RU; ++r)
 #pragma unroll
             for (int q = 0; q < NQ; ++q)
-                if (r0 + r < nrows) ot_load4(base + (size_t)(r0 + r) * L1, q * OT_CB + 4 * tid, nval[q], vec, 0.f, x[r][q]);
+                if (r0 + r < nrows) load4(base + (size_t)(r0 + r) * L1, q * OT_CB + 4 * tid, nval[q], vec, 0.f, x[r][q]);
         float best[OT_RU]; int bj[OT_RU];
 #pragma unroll
         for (int r = 0; r < OT_RU; ++r) {
@@ -275,6 +229,7 @@ __global__ void __launch_bounds__(256) ot_best_kernel(const float *__restrict__ 
                         }
             }
         }
+        // (wave_argmax of the rows in flight, interleaved by hand as in loftr.hip's dsm_best_tile_kernel)
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) {
 #pragma unroll
@@ -323,15 +278,11 @@ __global__ void __launch_bounds__(256) ot_row_kernel(const float *__restrict__ S
     if (i >= L0) return;
     const float *row = S + ((size_t)b * L0 + i) * L1;
     const float *vb = v ? v + (size_t)b * (L1 + 1) : nullptr;
-    OtLse acc = { -INFINITY, 0.f };
-    for (int j = lane; j < L1; j += 64) ot_lse_add(acc, row[j] + (vb ? vb[j] : 0.f));
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float om = __shfl_xor(acc.m, off, 64), os = __shfl_xor(acc.s, off, 64);
-        ot_lse_merge(acc, om, os);
-    }
+    LsePrecise acc = { -INFINITY, 0.f };
+    for (int j = lane; j < L1; j += 64) lse_precise_add(acc, row[j] + (vb ? vb[j] : 0.f));
+    lse_precise_wave_merge(acc);
     if (lane == 0) {
-        ot_lse_merge(acc, a + (vb ? vb[L1] : 0.f), 1.f);
+        lse_precise_merge(acc, a + (vb ? vb[L1] : 0.f), 1.f);
         u[(size_t)b * (L0 + 1) + i] = norm - (acc.m + logf(acc.s));
     }
 }
@@ -342,16 +293,16 @@ __global__ void __launch_bounds__(1024) ot_col_kernel(const float *__restrict__ 
     __shared__ float sm[16][64], ss[16][64];
     const int b = blockIdx.y, lane = threadIdx.x & 63, g = threadIdx.x >> 6, j = blockIdx.x * 64 + lane;
     const float *ub = u + (size_t)b * (L0 + 1);
-    OtLse acc = { -INFINITY, 0.f };
+    LsePrecise acc = { -INFINITY, 0.f };
     if (j < L1) {
         const float *colp = S + (size_t)b * L0 * L1 + j;
-        for (int i = g; i < L0; i += 16) ot_lse_add(acc, colp[(size_t)i * L1] + ub[i]);
+        for (int i = g; i < L0; i += 16) lse_precise_add(acc, colp[(size_t)i * L1] + ub[i]);
     }
     sm[g][lane] = acc.m; ss[g][lane] = acc.s;
     __syncthreads();
     if (g == 0 && j < L1) {
-        for (int k = 1; k < 16; ++k) ot_lse_merge(acc, sm[k][lane], ss[k][lane]);
-        ot_lse_merge(acc, a + ub[L0], 1.f);
+        for (int k = 1; k < 16; ++k) lse_precise_merge(acc, sm[k][lane], ss[k][lane]);
+        lse_precise_merge(acc, a + ub[L0], 1.f);
         v[(size_t)b * (L1 + 1) + j] = norm - (acc.m + logf(acc.s));
     }
 }
@@ -369,11 +320,7 @@ __global__ void __launch_bounds__(256) ot_rowbest_kernel(const float *__restrict
         const float z = (row[j] + ui) + vb[j];
         if (z > best) { best = z; bj = j; }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ob = __shfl_xor(best, off, 64); const int oj = __shfl_xor(bj, off, 64);
-        if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }
-    }
+    wave_argmax(best, bj);
     if (lane == 0) { rbest[(size_t)b * L0 + i] = best; rarg[(size_t)b * L0 + i] = bj; }
 }
 
@@ -404,11 +351,9 @@ __global__ void __launch_bounds__(256) ot_match_kernel(int L0, int L1, int h0, i
                                                        const float *__restrict__ cbest, int *__restrict__ i_ids,
                                                        int *__restrict__ j_ids, float *__restrict__ mconf, int *__restrict__ n_match)
 {
-    __shared__ int wave_cnt[4];
-    __shared__ int base_s;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    if (tid == 0) base_s = 0;
-    __syncthreads();
+    __shared__ Compact256 cs;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int total = 0;
     for (int start = 0; start < L0; start += 256) {
         const int i = start + tid;
         bool valid = false; int j = 0; float c = 0.f;
@@ -423,24 +368,14 @@ __global__ void __launch_bounds__(256) ot_match_kernel(int L0, int L1, int h0, i
                 valid = (c > thr) && inb && (z == cbest[(size_t)b * L1 + j]);
             }
         }
-        const unsigned long long bal = __ballot(valid);
-        const int wpre = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_cnt[wid] = __popcll(bal);
-        __syncthreads();
-        int off = base_s;
-        for (int w = 0; w < wid; ++w) off += wave_cnt[w];
+        const int o = compact256_slot(cs, valid, total);
         if (valid) {
-            const int o = off + wpre;
             i_ids[(size_t)b * L0 + o] = i; j_ids[(size_t)b * L0 + o] = j; mconf[(size_t)b * L0 + o] = c;
         }
-        __syncthreads();
-        if (tid == 0) base_s = off + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-        __syncthreads();
     }
-    if (tid == 0) n_match[b] = base_s;
+    if (tid == 0) n_match[b] = total;
 }
 
-static inline size_t ot_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // rows per stripe of variant 0: 64 when that already gives every CU two workgroups, else 32 / 16 (a pure function of the shape: the fold order,
 // hence the result's bits, depends on B and L0 only)
 static inline int ot_stripe_rows(int B, int L0)
@@ -469,8 +404,8 @@ size_t mfr_loftr_ot_match_workspace_bytes(int B, int L0, int L1)
     if (B <= 0 || L0 <= 0 || L1 <= 0) return 0;
     const int rs = ot_stripe_rows(B, L0);
     const size_t nst = (size_t)(L0 + rs - 1) / rs;
-    return ot_align_up((size_t)B * (L0 + 1) * 4, 256) + ot_align_up((size_t)B * (L1 + 1) * 4, 256) + 2 * ot_align_up((size_t)B * L0 * 4, 256) +
-           ot_align_up((size_t)B * L1 * 4, 256) + 2 * ot_align_up((size_t)B * nst * L1 * 4, 256);
+    return align_up((size_t)B * (L0 + 1) * 4, 256) + align_up((size_t)B * (L1 + 1) * 4, 256) + 2 * align_up((size_t)B * L0 * 4, 256) +
+           align_up((size_t)B * L1 * 4, 256) + 2 * align_up((size_t)B * nst * L1 * 4, 256);
 }
 
 int mfr_loftr_ot_match(const float *S, int B, int h0, int w0, int h1, int w1, float bin_score, int iters, float thr, int border,
@@ -485,9 +420,9 @@ int mfr_loftr_ot_match(const float *S, int B, int h0, int w0, int h1, int w1, fl
     if (workspace_bytes < mfr_loftr_ot_match_workspace_bytes(B, L0, L1)) return MFR_E_WORKSPACE;
     const int rs = ot_stripe_rows(B, L0), nst = (L0 + rs - 1) / rs;
     char *ws = (char *)workspace;
-    const size_t au = ot_align_up((size_t)B * (L0 + 1) * 4, 256), av = ot_align_up((size_t)B * (L1 + 1) * 4, 256);
-    const size_t a0 = ot_align_up((size_t)B * L0 * 4, 256), a1 = ot_align_up((size_t)B * L1 * 4, 256);
-    const size_t ap = ot_align_up((size_t)B * nst * L1 * 4, 256);
+    const size_t au = align_up((size_t)B * (L0 + 1) * 4, 256), av = align_up((size_t)B * (L1 + 1) * 4, 256);
+    const size_t a0 = align_up((size_t)B * L0 * 4, 256), a1 = align_up((size_t)B * L1 * 4, 256);
+    const size_t ap = align_up((size_t)B * nst * L1 * 4, 256);
     float *u = u_out ? u_out : (float *)ws, *v = v_out ? v_out : (float *)(ws + au);
     float *rbest = (float *)(ws + au + av);
     int *rarg = (int *)(ws + au + av + a0);

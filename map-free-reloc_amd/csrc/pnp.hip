@@ -27,7 +27,6 @@
 
 using namespace mfr;
 
-#define MFR_NSEG 16          // depth-min partial segments per image
 // pnp_hyp_score_kernel: hypotheses per workgroup / threads per workgroup.  Round 5: 256 / 256 -> 64 / 256 -- a wavefront scored the 64 hypotheses its own
 // lanes had solved, one after the other (500 wavefronts on 1024 SIMDs at 1000 iterations x 32 pairs); now wavefront 0 solves a workgroup's 64
 // hypotheses and all four wavefronts score 16 each.  A hypothesis' count does not depend on the grouping.
@@ -71,21 +70,18 @@ __global__ void __launch_bounds__(256) pnp_lift_kernel(
     const void *__restrict__ K0, int k_dtype, double *__restrict__ xyz, double *__restrict__ obs,
     int32_t *__restrict__ src_idx, int32_t *__restrict__ n_valid)
 {
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     int n = n_corr[b];
     if (n > maxN) n = maxN;
-    __shared__ int wave_cnt[4];
-    __shared__ int base_s;
-    float dmin = partial_min[b * MFR_NSEG];
-    for (int s = 1; s < MFR_NSEG; ++s) { const float v = partial_min[b * MFR_NSEG + s]; if (v < dmin) dmin = v; }
+    __shared__ Compact256 cs;
+    const float dmin = depth_min_fold(partial_min, b);
     double Ki[4];
     kinv(K0, k_dtype, b, Ki);
     const float *p0 = pts0 + (size_t)b * maxN * 2, *p1 = pts1 + (size_t)b * maxN * 2;
     const float *dm = depth0 + (size_t)b * H * W;
     double *oxyz = xyz + (size_t)b * maxN * 3, *oobs = obs + (size_t)b * maxN * 2;
     int32_t *osrc = src_idx + (size_t)b * maxN;
-    if (tid == 0) base_s = 0;
-    __syncthreads();
+    int total = 0;
     for (int start = 0; start < n; start += 256) {
         const int i = start + tid;
         bool valid = false;
@@ -97,25 +93,16 @@ __global__ void __launch_bounds__(256) pnp_lift_kernel(
                 valid = d > dmin;                                         // :196 (Q6)
             }
         }
-        const unsigned long long bal = __ballot(valid);
-        const int wpre = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_cnt[wid] = __popcll(bal);
-        __syncthreads();
-        int off = base_s;
-        for (int w = 0; w < wid; ++w) off += wave_cnt[w];
+        const int m = compact256_slot(cs, valid, total);
         if (valid) {
-            const int m = off + wpre;
             double X[3];
             backproject(u, v, d, Ki, X);                                  // :206, :6-17
             oxyz[3 * m] = X[0]; oxyz[3 * m + 1] = X[1]; oxyz[3 * m + 2] = X[2];
             oobs[2 * m] = (double)p1[2 * i]; oobs[2 * m + 1] = (double)p1[2 * i + 1];
             osrc[m] = i;
         }
-        __syncthreads();
-        if (tid == 0) base_s = off + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-        __syncthreads();
     }
-    if (tid == 0) n_valid[b] = base_s;
+    if (tid == 0) n_valid[b] = total;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -200,20 +187,6 @@ __global__ void __launch_bounds__(HYP_THREADS) pnp_hyp_score_kernel(
 
 // ------------------------------------------------------------------------------------------
 // LM pieces (wave-parallel, deterministic wave64 reduction order)
-static __device__ __forceinline__ void quat_right_update(const double *R, const double *dw, double *Rn)
-{
-    const double hx = 0.5 * dw[0], hy = 0.5 * dw[1], hz = 0.5 * dw[2];
-    const double nn = sqrt(((hx * hx + hy * hy) + hz * hz) + 1.0);
-    const double w = 1.0 / nn, x = hx / nn, y = hy / nn, z = hz / nn;
-    double Q[9];
-    Q[0] = 1.0 - 2.0 * (y * y + z * z); Q[1] = 2.0 * (x * y - w * z);       Q[2] = 2.0 * (x * z + w * y);
-    Q[3] = 2.0 * (x * y + w * z);       Q[4] = 1.0 - 2.0 * (x * x + z * z); Q[5] = 2.0 * (y * z - w * x);
-    Q[6] = 2.0 * (x * z - w * y);       Q[7] = 2.0 * (y * z + w * x);       Q[8] = 1.0 - 2.0 * (x * x + y * y);
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j)
-            Rn[3 * i + j] = (R[3 * i] * Q[j] + R[3 * i + 1] * Q[3 + j]) + R[3 * i + 2] * Q[6 + j];
-}
-
 static __device__ __forceinline__ double pnp_cost(const double *X, const double *O, const int32_t *idx, int n,
                                                   const double *Kd, const double *R, const double *t)
 {
@@ -223,36 +196,6 @@ static __device__ __forceinline__ double pnp_cost(const double *X, const double 
         acc = acc + reproj_err2(R, t, X + 3 * (size_t)j, O + 2 * (size_t)j, Kd);
     }
     return wave_sum(acc);
-}
-
-static __device__ __forceinline__ int chol_solve6(const double *A, const double *bvec, double *x)
-{
-    double L[36];
-    for (int i = 0; i < 36; ++i) L[i] = 0.0;
-    for (int i = 0; i < 6; ++i) {
-        for (int j = 0; j <= i; ++j) {
-            double s = A[6 * i + j];
-            for (int k = 0; k < j; ++k) s = s - L[6 * i + k] * L[6 * j + k];
-            if (i == j) {
-                if (!(s > 0.0)) return -1;
-                L[6 * i + i] = sqrt(s);
-            } else {
-                L[6 * i + j] = s / L[6 * j + j];
-            }
-        }
-    }
-    double y[6];
-    for (int i = 0; i < 6; ++i) {
-        double s = bvec[i];
-        for (int k = 0; k < i; ++k) s = s - L[6 * i + k] * y[k];
-        y[i] = s / L[6 * i + i];
-    }
-    for (int i = 5; i >= 0; --i) {
-        double s = y[i];
-        for (int k = i + 1; k < 6; ++k) s = s - L[6 * k + i] * x[k];
-        x[i] = s / L[6 * i + i];
-    }
-    return 0;
 }
 
 // Levenberg-Marquardt on the reprojection error over the inlier list; stands in for the EPnP
@@ -495,9 +438,6 @@ __global__ void sample_kernel(uint64_t seed, const int64_t *pair_ids, int iters,
 
 // ------------------------------------------------------------------------------------------
 // C-ABI
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
-
 extern "C" {
 
 int mfr_abi_version(void) { return MFR_ABI_VERSION; }

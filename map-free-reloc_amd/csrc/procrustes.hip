@@ -18,8 +18,6 @@
 #include "geom_dev.h"
 
 using namespace mfr;
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
-#define PR_NSEG 16
 #define PR_TILE 512
 
 MFR_DEV void jacobi4_maxvec(double A[4][4], double q[4])
@@ -96,24 +94,17 @@ __global__ void __launch_bounds__(256) proc_lift_kernel(
     const float *__restrict__ pmin1, int H, int W, const void *__restrict__ K0, const void *__restrict__ K1, int k_dtype,
     double *__restrict__ P, double *__restrict__ Q, int32_t *__restrict__ n_valid)
 {
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     int n = n_corr[b];
     if (n > maxN) n = maxN;
-    __shared__ int wave_cnt[4];
-    __shared__ int base_s;
-    float m0 = pmin0[b * PR_NSEG], m1 = pmin1[b * PR_NSEG];
-    for (int s = 1; s < PR_NSEG; ++s) {
-        const float a = pmin0[b * PR_NSEG + s], c = pmin1[b * PR_NSEG + s];
-        if (a < m0) m0 = a;
-        if (c < m1) m1 = c;
-    }
+    __shared__ Compact256 cs;
+    const float m0 = depth_min_fold(pmin0, b), m1 = depth_min_fold(pmin1, b);
     double Ki0[4], Ki1[4];
     kinv(K0, k_dtype, b, Ki0); kinv(K1, k_dtype, b, Ki1);
     const float *p0 = pts0 + (size_t)b * maxN * 2, *p1 = pts1 + (size_t)b * maxN * 2;
     const float *d0m = depth0 + (size_t)b * H * W, *d1m = depth1 + (size_t)b * H * W;
     double *oP = P + (size_t)b * maxN * 3, *oQ = Q + (size_t)b * maxN * 3;
-    if (tid == 0) base_s = 0;
-    __syncthreads();
+    int total = 0;
     for (int start = 0; start < n; start += 256) {
         const int i = start + tid;
         bool valid = false;
@@ -126,24 +117,15 @@ __global__ void __launch_bounds__(256) proc_lift_kernel(
                 valid = (d0 > m0) && (d1 > m1);
             }
         }
-        const unsigned long long bal = __ballot(valid);
-        const int wpre = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_cnt[wid] = __popcll(bal);
-        __syncthreads();
-        int off = base_s;
-        for (int w = 0; w < wid; ++w) off += wave_cnt[w];
+        const int m = compact256_slot(cs, valid, total);
         if (valid) {
-            const int m = off + wpre;
             double a[3], c[3];
             backproject(u0, v0, d0, Ki0, a); backproject(u1, v1, d1, Ki1, c);
             oP[3 * m] = a[0]; oP[3 * m + 1] = a[1]; oP[3 * m + 2] = a[2];
             oQ[3 * m] = c[0]; oQ[3 * m + 1] = c[1]; oQ[3 * m + 2] = c[2];
         }
-        __syncthreads();
-        if (tid == 0) base_s = off + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-        __syncthreads();
     }
-    if (tid == 0) n_valid[b] = base_s;
+    if (tid == 0) n_valid[b] = total;
 }
 
 // grid (ceil(iters/256), B)
@@ -303,13 +285,12 @@ __global__ void __launch_bounds__(64) proc_select_kernel(
     }
 }
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 struct PrWs { size_t pm0, pm1, P, Q, nvalid, counts, err2, idx, total; };
 static PrWs pr_ws_layout(int B, int maxN, int iters)
 {
     PrWs w; size_t o = 0;
-    w.pm0 = o;    o = align_up(o + sizeof(float) * PR_NSEG * (size_t)B, 256);
-    w.pm1 = o;    o = align_up(o + sizeof(float) * PR_NSEG * (size_t)B, 256);
+    w.pm0 = o;    o = align_up(o + sizeof(float) * MFR_NSEG * (size_t)B, 256);
+    w.pm1 = o;    o = align_up(o + sizeof(float) * MFR_NSEG * (size_t)B, 256);
     w.P = o;      o = align_up(o + sizeof(double) * 3 * (size_t)B * maxN, 256);
     w.Q = o;      o = align_up(o + sizeof(double) * 3 * (size_t)B * maxN, 256);
     w.nvalid = o; o = align_up(o + sizeof(int32_t) * (size_t)B, 256);

@@ -26,7 +26,6 @@
 #include "geom_dev.h"
 
 using namespace mfr;
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
 #define ICP_NACC 17
 #define ICP_STATE 24          // doubles per pair: R[9] t[3] fit_prev rmse_prev done iters fit rmse nS nT ...
 

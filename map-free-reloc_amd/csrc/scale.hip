@@ -31,12 +31,11 @@ __global__ void __launch_bounds__(256) scale_lift_kernel(
     const double *__restrict__ Rin, const double *__restrict__ tin, const int32_t *__restrict__ in_status,
     double *__restrict__ scale, int32_t *__restrict__ n_scale)
 {
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     int n = n_corr[b];
     if (n > maxN) n = maxN;
     if (in_status && in_status[b] != MFR_ST_OK) n = 0;
-    __shared__ int wave_cnt[4];
-    __shared__ int base_s;
+    __shared__ Compact256 cs;
     double Ki0[4], Ki1[4];
     kinv(K0, k_dtype, b, Ki0);
     kinv(K1, k_dtype, b, Ki1);
@@ -47,8 +46,7 @@ __global__ void __launch_bounds__(256) scale_lift_kernel(
     const uint8_t *mk = emat_mask ? emat_mask + (size_t)b * maxN : nullptr;
     const float *d0m = depth0 + (size_t)b * H * W, *d1m = depth1 + (size_t)b * H * W;
     double *out = scale + (size_t)b * maxN;
-    if (tid == 0) base_s = 0;
-    __syncthreads();
+    int total = 0;
     for (int start = 0; start < n; start += 256) {
         const int i = start + tid;
         bool valid = false;
@@ -71,18 +69,10 @@ __global__ void __launch_bounds__(256) scale_lift_kernel(
                 }
             }
         }
-        const unsigned long long bal = __ballot(valid);
-        const int wpre = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_cnt[wid] = __popcll(bal);
-        __syncthreads();
-        int off = base_s;
-        for (int w = 0; w < wid; ++w) off += wave_cnt[w];
-        if (valid) out[off + wpre] = sc;
-        __syncthreads();
-        if (tid == 0) base_s = off + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-        __syncthreads();
+        const int o = compact256_slot(cs, valid, total);
+        if (valid) out[o] = sc;
     }
-    if (tid == 0) n_scale[b] = base_s;
+    if (tid == 0) n_scale[b] = total;
 }
 
 // grid (chunks, B): workgroup c owns hypotheses [c*256, c*256+256)
@@ -164,9 +154,6 @@ __global__ void scale_final_kernel(const double *__restrict__ scale, const int32
     }
     status[b] = st;
 }
-
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
 
 struct ScaleWs { size_t scale, nscale, pcnt, pidx, total; int nchunks; };
 static ScaleWs scale_ws_layout(int B, int maxN)

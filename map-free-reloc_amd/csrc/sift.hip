@@ -26,8 +26,9 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
+#include "wave_dev.h"
 
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
+using namespace mfr;
 
 #define SIFT_LAYERS 3            // nOctaveLayers
 #define SIFT_LEVELS 6            // Gaussian images per octave (nOctaveLayers + 3)
@@ -281,8 +282,7 @@ __global__ void __launch_bounds__(256) sift_orient_kernel(SiftPyr P, const SiftC
         const int l2 = lane < 2 ? lane + 34 : lane - 2, r2 = lane > 33 ? lane - 34 : lane + 2;
         const float tl1 = __shfl(h, l1, 64), tr1 = __shfl(h, r1, 64), tl2 = __shfl(h, l2, 64), tr2 = __shfl(h, r2, 64);
         const float hist = (tl2 + tr2) * (1.f / 16.f) + (tl1 + tr1) * (4.f / 16.f) + h * (6.f / 16.f);
-        float m = lane < 36 ? hist : -INFINITY;
-        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+        const float m = wave_max(lane < 36 ? hist : -INFINITY);
         const float mag_thr = m * 0.8f;
         const float hl = __shfl(hist, l1, 64), hr = __shfl(hist, r1, 64);
         if (lane < 36 && hist > hl && hist > hr && hist >= mag_thr) {

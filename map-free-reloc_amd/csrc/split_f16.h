@@ -1,4 +1,5 @@
-// split_f16.h -- the "f16x2" operand split of the matrix-core kernels (gemm_split.hip, winograd_split.hip, attention.hip).
+// split_f16.h -- the "f16x2" operand split of the matrix-core kernels (gemm_split.hip, winograd_split.hip, attention.hip), and at the end the
+// exact three-term "bf16x3" split it is measured against.
 //
 // An fp32 product on the gfx950 F16 matrix cores, fp32 accumulate, THREE v_mfma_f32_32x32x16_f16 per K block instead of the six
 // bf16 ones of the "bf16x3" split:
@@ -59,5 +60,17 @@ __device__ __forceinline__ float sf_feature_scale(float maxabs)
     k = k > 126 ? 126 : (k < -126 ? -126 : k);
     return ldexpf(1.0f, k);
 }
+
+// ---- the "bf16x3" split (the A/B baseline of the same kernels): x = h + m + l EXACTLY, three bf16 terms by truncation (8 + 8 + 8 significand
+// bits).  The upper 16 bits of each returned word are the term's bf16 pattern; the subtractions are exact, nothing here can contract.
+__device__ __forceinline__ void bf_split3(float x, unsigned &h, unsigned &m, unsigned &l)
+{
+    h = __float_as_uint(x);
+    const float r = x - __uint_as_float(h & 0xffff0000u);
+    m = __float_as_uint(r);
+    l = __float_as_uint(r - __uint_as_float(m & 0xffff0000u));
+}
+// pack the bf16 (upper) halves of two fp32 bit patterns: lo -> bits 15:0, hi -> bits 31:16
+__device__ __forceinline__ unsigned bf_pack_hi16(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
 
 #define SF_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(sf_f16x8, (a)), __builtin_bit_cast(sf_f16x8, (b)), (c), 0, 0, 0)

@@ -20,9 +20,10 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
+#include "wave_dev.h"
 #include "zero_fill.h"
 
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
+using namespace mfr;
 
 // u / v row stride: ldS + 1 entries (dustbin) padded to a multiple of 4 floats so that rows of v are 16-byte aligned
 #define SG_LDV(ldS) (((ldS) + 4) & ~3)
@@ -69,30 +70,6 @@ static __device__ __forceinline__ void lse_add4(Lse &a, float x0, float x1, floa
     lse_block4(x0, x1, x2, x3, bm, bs);
     lse_merge_block(a, bm, bs);
 }
-// wavefront-wide max / sum that leave the SAME bits in all 64 lanes (every step pairs two groups and a + b == b + a): DPP inside a row of
-// 16 lanes (quad_perm xor 1, xor 2, row_half_mirror, row_mirror), then gfx950's v_permlane16_swap / v_permlane32_swap across rows and halves
-// (two copies of x go in; one comes back holding the even rows' / lower half's values everywhere, the other the odd rows' / upper half's) --
-// no LDS round trip.  Inline asm: the builtin, given the same value twice, was compiled to x + x (hipcc 7.2).
-static __device__ __forceinline__ void sg_swap16(float &a, float &b) { asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
-static __device__ __forceinline__ void sg_swap32(float &a, float &b) { asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
-template <int CTRL> static __device__ __forceinline__ float sg_dpp(float x)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
-}
-static __device__ __forceinline__ float sg_wave_max(float x)
-{
-    x = fmaxf(x, sg_dpp<0xB1>(x)); x = fmaxf(x, sg_dpp<0x4E>(x)); x = fmaxf(x, sg_dpp<0x141>(x)); x = fmaxf(x, sg_dpp<0x140>(x));
-    float y = x; sg_swap16(x, y); x = fmaxf(x, y);
-    y = x; sg_swap32(x, y); x = fmaxf(x, y);
-    return x;
-}
-static __device__ __forceinline__ float sg_wave_sum(float x)
-{
-    x += sg_dpp<0xB1>(x); x += sg_dpp<0x4E>(x); x += sg_dpp<0x141>(x); x += sg_dpp<0x140>(x);
-    float y = x; sg_swap16(x, y); x += y;
-    y = x; sg_swap32(x, y); x += y;
-    return x;
-}
 // u_i of a row on the 16-byte fast path: x[k] = S_ij + v_j of this lane's 16 columns (-inf beyond n), vn = alpha + v_n (the dustbin column, a
 // 1025th term that lane 0 adds).  Round 5: the row's maximum first (wavefront-wide), then one exponential per term against it and a plain
 // wavefront sum -- rounds 1-4 merged 64 (max, sum) pairs in a butterfly of six rescaling steps, 84 instructions a row.
@@ -101,12 +78,12 @@ static __device__ __forceinline__ float sg_row_u(const float (&x)[16], float vn,
     float mx = x[0];
 #pragma unroll
     for (int k = 1; k < 16; ++k) mx = fmaxf(mx, x[k]);
-    mx = fmaxf(sg_wave_max(mx), vn);
+    mx = fmaxf(wave_max_dpp(mx), vn);
     float sum = 0.f;
 #pragma unroll
     for (int k = 0; k < 16; ++k) sum += __expf(x[k] - mx);
     const float sd = sum + __expf(vn - mx);
-    sum = sg_wave_sum(lane == 0 ? sd : sum);
+    sum = wave_sum_dpp(lane == 0 ? sd : sum);
     return log_mu - (mx + __logf(sum));
 }
 // rows of accumulator r (0 .. 3) of row group g (= i mod 16), in the order they are added: whole quads first (row g + 64 t + 16 r while
@@ -437,11 +414,7 @@ __global__ void __launch_bounds__(256) sg_rowmax_kernel(const float *__restrict_
         const float x = row[j] + vb[j];
         if (x > best) { best = x; bi = j; }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ob = __shfl_xor(best, off, 64); const int oi = __shfl_xor(bi, off, 64);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
+    wave_argmax(best, bi);
     if (lane == 0) { idx0[(size_t)b * ldS + i] = bi; val0[(size_t)b * ldS + i] = best; }
 }
 
@@ -483,12 +456,10 @@ __global__ void __launch_bounds__(256) sg_match_kernel(
     int *__restrict__ matches0, float *__restrict__ mscores0, float *__restrict__ pts0, float *__restrict__ pts1,
     int maxN, int *__restrict__ n_corr)
 {
-    __shared__ int wave_cnt[4];
-    __shared__ int base_s;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    __shared__ Compact256 cs;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int m = n0[b], n = n1[b];
-    if (tid == 0) base_s = 0;
-    __syncthreads();
+    int total = 0;
     const float norm = (m > 0 && n > 0) ? -__logf((float)(m + n)) : 0.f;
     for (int start = 0; start < ldS; start += 256) {
         const int i = start + tid;
@@ -507,14 +478,8 @@ __global__ void __launch_bounds__(256) sg_match_kernel(
             matches0[(size_t)b * ldS + i] = valid ? j : -1;
             mscores0[(size_t)b * ldS + i] = (i < m) ? sc : 0.f;
         }
-        const unsigned long long bal = __ballot(valid);
-        const int wpre = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_cnt[wid] = __popcll(bal);
-        __syncthreads();
-        int off = base_s;
-        for (int w = 0; w < wid; ++w) off += wave_cnt[w];
+        const int o = compact256_slot(cs, valid, total);
         if (valid) {
-            const int o = off + wpre;
             if (o < maxN) {
                 pts0[((size_t)b * maxN + o) * 2] = kpts0[((size_t)b * K + i) * 2];
                 pts0[((size_t)b * maxN + o) * 2 + 1] = kpts0[((size_t)b * K + i) * 2 + 1];
@@ -522,14 +487,10 @@ __global__ void __launch_bounds__(256) sg_match_kernel(
                 pts1[((size_t)b * maxN + o) * 2 + 1] = kpts1[((size_t)b * K + j) * 2 + 1];
             }
         }
-        __syncthreads();
-        if (tid == 0) base_s = off + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-        __syncthreads();
     }
-    if (tid == 0) n_corr[b] = min(base_s, maxN);
+    if (tid == 0) n_corr[b] = min(total, maxN);
 }
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 struct SgWs { size_t u, v, idx0, val0, idx1, part_m, part_s, total; };
 static SgWs sg_ws_layout(int B, int ldS)
 {

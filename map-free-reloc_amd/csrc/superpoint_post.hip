@@ -21,9 +21,10 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
+#include "wave_dev.h"
 #include "zero_fill.h"
 
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
+using namespace mfr;
 
 // ------------------------------------------------------------------------------------------
 // one thread per coarse cell; logits NCHW so lanes (adjacent x) read coalesced per channel
@@ -367,14 +368,12 @@ __global__ void __launch_bounds__(256) sp_sample_kernel(const float *__restrict_
         if (xs[c] < 0 || xs[c] >= Wc || ys[c] < 0 || ys[c] >= Hc) continue;       // zero padding
         const float4 v = *((const float4 *)(dense + (((size_t)b * Hc + ys[c]) * Wc + xs[c]) * 256) + lane);
         float ss = v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off, 64);
+        ss = wave_sum(ss);
         const float inv = ws[c] / fmaxf(sqrtf(ss), 1e-12f);                        // F.normalize eps
         acc.x += v.x * inv; acc.y += v.y * inv; acc.z += v.z * inv; acc.w += v.w * inv;
     }
     float ss = acc.x * acc.x + acc.y * acc.y + acc.z * acc.z + acc.w * acc.w;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off, 64);
+    ss = wave_sum(ss);
     const float inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
     *o = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
 }

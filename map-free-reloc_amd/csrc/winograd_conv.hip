@@ -37,9 +37,8 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
+#include "wave_dev.h"
 #include "zero_fill.h"
-
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -49,9 +48,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define WN_TX 16                 // tiles along x per workgroup
 #define WN_TY 4                  // tile rows per workgroup (= wavefronts)
 
-// dword3 of a raw buffer descriptor on gfx9-family CDNA (32-bit data format); out-of-range reads return 0,
-// which is how the zero padding of the convolution is produced: padded taps get an offset beyond the buffer
-#define WN_RSRC_FLAGS 0x00020000
+// zero padding of the convolution: padded taps get an offset beyond the buffer, which reads as 0 (MFR_RSRC_FLAGS, wave_dev.h)
 #define WN_OOB 0x80000000u
 
 // NBLK (16-cout MFMA blocks per workgroup) is 2: 128 accumulator registers, two workgroups per CU.  (A one-wavefront-per-SIMD
@@ -182,7 +179,7 @@ __global__ void __launch_bounds__(256, NBLK == 2 ? 2 : 1) wino_conv3x3_kernel(
     const int HW = H * W;
 
     // one buffer per image: [Cin, H, W] f32; lane byte offsets inside a 4-channel slab, chunk advance in soffset
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(x + (size_t)b * Cin * HW), 0, Cin * HW * 4, WN_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(x + (size_t)b * Cin * HW), 0, Cin * HW * 4, MFR_RSRC_FLAGS);
     constexpr int NOFF = PAIR ? 8 : 16;
     constexpr int NRAW = PAIR ? 12 : 16;
     unsigned off[NOFF];
@@ -362,10 +359,10 @@ __global__ void __launch_bounds__(256, 2) wino_conv3x3_pipe_kernel(
     const int ty = by * WN_TY + w, tx = bx * WN_TX + col;
     const int HW = H * W;
 
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(x + (size_t)b * Cin * HW), 0, Cin * HW * 4, WN_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(x + (size_t)b * Cin * HW), 0, Cin * HW * 4, MFR_RSRC_FLAGS);
     // packed filters as a buffer too: chunk prefetches past the end read zeros instead of needing a branch
     const int nchunks = Cin >> 2;
-    const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void *)upk, 0, nchunks * ncb * SLAB * 4, WN_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void *)upk, 0, nchunks * ncb * SLAB * 4, MFR_RSRC_FLAGS);
     unsigned off[8];
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
@@ -570,8 +567,8 @@ __global__ void __launch_bounds__(256, 2) wino_conv3x3_shared_kernel(
     const int HW = H * W;
     const int nchunks = Cin >> 2;
 
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(x + (size_t)b * Cin * HW), 0, Cin * HW * 4, WN_RSRC_FLAGS);
-    const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void *)upk, 0, nchunks * ncb32 * SLAB * 4, WN_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(x + (size_t)b * Cin * HW), 0, Cin * HW * 4, MFR_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void *)upk, 0, nchunks * ncb32 * SLAB * 4, MFR_RSRC_FLAGS);
     // patch rows this wavefront needs: slice 0 rows (0, 1, 2), slice 1 rows (3, 2, 1) of the 4x4 patch
     unsigned off[6];
 #pragma unroll

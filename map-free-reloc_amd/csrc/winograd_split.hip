@@ -37,10 +37,11 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
+#include "wave_dev.h"
 #include "split_f16.h"
 #include "guard.h"
 
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return MFR_E_LAUNCH; } while (0)
+using namespace mfr;
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -48,7 +49,6 @@ typedef float wb_f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) float wb_lds_f32;
 typedef __attribute__((address_space(3))) wb_f32x2 wb_lds_f32x2;
 
-#define WB_RSRC_FLAGS 0x00020000
 #define WB_OOB 0x80000000u
 #define WB_ROWS 10                 // input rows per workgroup (4 tile rows: 8 output rows + 2 halo)
 #define WB_RS 48                   // staged row stride (floats): 2 rows = 96 dwords = half the LDS banks apart
@@ -57,16 +57,6 @@ typedef __attribute__((address_space(3))) wb_f32x2 wb_lds_f32x2;
 #define WB_FRAGS_PER_KSTEP 96      // 4 i x 4 j x 2 cout blocks x 3 terms (both arithmetics)
 
 union WbFrag { bf16x8 v; unsigned u[4]; uint4 q; };
-
-__device__ __forceinline__ void wb_split3(float x, unsigned &h, unsigned &m, unsigned &l)
-{
-    // the upper 16 bits of each word are the bf16 term; h + m + l == x exactly
-    h = __float_as_uint(x);
-    const float r = x - __uint_as_float(h & 0xffff0000u);
-    m = __float_as_uint(r);
-    l = __float_as_uint(r - __uint_as_float(m & 0xffff0000u));
-}
-__device__ __forceinline__ unsigned wb_pack(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // filters: w [Cout, Cin, 3, 3] f32 -> U = G g G^T (fp64 arithmetic, rounded once to fp32), split into three 16-bit terms and
@@ -92,8 +82,7 @@ __global__ void __launch_bounds__(64) wb_filter_scale_kernel(const float *__rest
             const int ci = t >> 4, p = t & 15;
             mx = fmaxf(mx, fabsf(wb_u_value(w + ((size_t)co * Cin + ci) * 9, p >> 2, p & 3)));
         }
-#pragma unroll
-    for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    mx = wave_max(mx);
     if (lane == 0 && co < cpad) oscale[co] = 1.0f / sf_feature_scale(mx);
 }
 template <bool F16>
@@ -123,11 +112,11 @@ __global__ void __launch_bounds__(256) wb_filter_kernel(const float *__restrict_
             word[e] = (unsigned)(term == 0 ? uh : term == 1 ? ul : uq) << 16;
         } else {
             unsigned h, m, lo;
-            wb_split3(u, h, m, lo);
+            bf_split3(u, h, m, lo);
             word[e] = term == 0 ? h : term == 1 ? m : lo;
         }
     }
-    upk[t] = make_uint4(wb_pack(word[0], word[1]), wb_pack(word[2], word[3]), wb_pack(word[4], word[5]), wb_pack(word[6], word[7]));
+    upk[t] = make_uint4(bf_pack_hi16(word[0], word[1]), bf_pack_hi16(word[2], word[3]), bf_pack_hi16(word[4], word[5]), bf_pack_hi16(word[6], word[7]));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -206,7 +195,7 @@ __global__ void __launch_bounds__(512, 2) wino_split_p8_kernel(
         xdesc.x = __builtin_amdgcn_readfirstlane((unsigned)xa);
         xdesc.y = __builtin_amdgcn_readfirstlane((unsigned)(xa >> 32) & 0xffffu);
         xdesc.z = (unsigned)(Cin * HW) * 4u;                // channels >= Cin lie beyond the buffer: zeros
-        xdesc.w = WB_RSRC_FLAGS;
+        xdesc.w = MFR_RSRC_FLAGS;
     }
     const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) float *)lds;
     auto pdma = [&](int c, int buf) {
@@ -281,17 +270,17 @@ __global__ void __launch_bounds__(512, 2) wino_split_p8_kernel(
             if (F16) sf_split2(v[0], v[1], SF_LOW_SCALE, vf[0].u[k], vf[1].u[k]);
             else {
                 unsigned h[2], m[2], l[2];
-                wb_split3(v[0], h[0], m[0], l[0]); wb_split3(v[1], h[1], m[1], l[1]);
-                vf[0].u[k] = wb_pack(h[0], h[1]);
-                vf[1].u[k] = wb_pack(m[0], m[1]);
-                vf[2].u[k] = wb_pack(l[0], l[1]);
+                bf_split3(v[0], h[0], m[0], l[0]); bf_split3(v[1], h[1], m[1], l[1]);
+                vf[0].u[k] = bf_pack_hi16(h[0], h[1]);
+                vf[1].u[k] = bf_pack_hi16(m[0], m[1]);
+                vf[2].u[k] = bf_pack_hi16(l[0], l[1]);
             }
         }
     };
 
     // ---- filter fragments of positions (wi, 2 jp), (wi, 2 jp + 1): [jj][mb][term], 12 consecutive fragments of the packed layout.
     // Buffer loads: the fragment index is wave-uniform (scalar offset), the only vector address is lane * 16.
-    const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void *)upk, 0, (int)(ncg * nks * WB_FRAGS_PER_KSTEP * 1024), WB_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void *)upk, 0, (int)(ncg * nks * WB_FRAGS_PER_KSTEP * 1024), MFR_RSRC_FLAGS);
     const unsigned fbase = (unsigned)((cg * nks * WB_FRAGS_PER_KSTEP + wi * 24 + jp * 12) * 1024);
     const unsigned lane16 = (unsigned)lane * 16u;
     WbFrag F[2][2][3];
@@ -568,7 +557,7 @@ __global__ void __launch_bounds__(512, 2) wino_split_c1_kernel(
     const int col = lane & 15, tysub = (lane >> 4) & 1, kg = lane >> 5;
 
     // ---- filter fragments (requested below, once the gray window is in LDS: they land while the patch is computed)
-    const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void *)upk, 0, (int)(4 * WB_FRAGS_PER_KSTEP * 1024), WB_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void *)upk, 0, (int)(4 * WB_FRAGS_PER_KSTEP * 1024), MFR_RSRC_FLAGS);
     const unsigned fbase = (unsigned)((wi * 24 + jp * 12) * 1024);
     const unsigned lane16 = (unsigned)lane * 16u;
     WbFrag F[2][2][3];

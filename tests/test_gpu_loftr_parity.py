@@ -87,6 +87,32 @@ def test_coarse_match_vs_oracle(pair):
         np.testing.assert_allclose(gc[safe_g].numpy(), wc[safe_w].numpy(), rtol=2e-4)
 
 
+def test_coarse_match_pair_without_matches_between_pairs_with_some(pair):
+    """the ordered compaction with no survivor (a grid cannot have 0 cells, so this is its empty case): pair 1 has flat scores, every
+    confidence 1 / L^2; the counts and the neighbours' match sets come from the oracle"""
+    ref, hip = pair
+    g = torch.Generator().manual_seed(3)
+    h, w, B = 30, 22, 3
+    L = h * w
+    f0 = torch.randn(B, L, 256, generator=g) * 2.2
+    perm = torch.stack([torch.randperm(L, generator=g) for _ in range(B)])
+    f1 = torch.gather(f0, 1, perm[..., None].expand(-1, -1, 256)) + 0.3 * torch.randn(B, L, 256, generator=g)
+    f0[1] = 0.0
+    cm = LR.coarse_matching(f0, f1, (h, w), (h, w))
+    want = [int((cm["b_ids"] == k).sum()) for k in range(B)]
+    assert want[1] == 0 and want[0] > L // 4 and want[2] > L // 4
+    S = torch.bmm(f0 / 16.0, (f1 / 16.0).transpose(1, 2))
+    for variant in (0, 1):
+        i_ids, j_ids, mconf, n = [t.cpu() for t in hip.coarse_match(S.to(DEV), (h, w), (h, w), variant=variant)]
+        assert int(n[1]) == 0
+        for k in (0, 2):
+            sel = cm["b_ids"] == k
+            safe = (cm["mconf"][sel] - 0.2).abs() > 1e-3                  # (the band rule of test_coarse_match_vs_oracle)
+            got = set(zip(i_ids[k, :n[k]].tolist(), j_ids[k, :n[k]].tolist()))
+            sure = set(zip(cm["i_ids"][sel][safe].tolist(), cm["j_ids"][sel][safe].tolist()))
+            assert sure <= got and len(got) - len(sure) <= int((~safe).sum())
+
+
 @pytest.mark.parametrize("h,w,B", [(30, 22, 2), (90, 68, 1), (17, 13, 3)])
 def test_coarse_match_two_sweep_equals_four_sweep(pair, h, w, B):
     """the tiled two-sweep kernels (default) against the row / column kernels of round 1 on the same S: identical mutual matches
