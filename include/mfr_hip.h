@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define MFR_ABI_VERSION 6   /* 6 (round 6): mfr_conv3x3_direct_f16x2*, later (additive) the SIFT detector mfr_sift_*, the JPEG decoder mfr_jpeg_*, mfr_conv3x3s2_direct_f16x2, mfr_mlp_ln_*, mfr_loftr_ot_match (LoFTR's optimal-transport coarse matching); 5 (round 6): mfr_f16x2_guard_bind (the f16x2 range guard); 2: intrinsics as (const void *K, int k_dtype) instead of const float *; 3: mfr_emat_solve_batch takes the
+#define MFR_ABI_VERSION 6   /* 6 (round 6): mfr_conv3x3_direct_f16x2*, later (additive) the SIFT detector mfr_sift_*, the JPEG decoder mfr_jpeg_*, mfr_resize_gray_bilinear (the device image resize), mfr_conv3x3s2_direct_f16x2, mfr_mlp_ln_*, mfr_loftr_ot_match (LoFTR's optimal-transport coarse matching); 5 (round 6): mfr_f16x2_guard_bind (the f16x2 range guard); 2: intrinsics as (const void *K, int k_dtype) instead of const float *; 3: mfr_emat_solve_batch takes the
                              * model-quality method (MAGSAC++ / count) and its table; 4 (round 5): the f16x2 entry points (mfr_gemm_f16x2*,
                              * mfr_wino_f16x2_*, mfr_conv3x3_wino_f16x2, mfr_conv_igemm_f16x2), mfr_sg_attention_variant renumbered (0 f16x2,
                              * 1 exact fp32, 2 bf16x3), the measurement-only entry points (mfr_conv3x3_wino_bf16x3_variant,
@@ -525,7 +525,7 @@ int mfr_sift_detect(const uint8_t *gray, int B, int H, int W, int nfeatures, int
  *   mfr_jpeg_workspace_bytes  workspace of mfr_jpeg_decode for n images of H x W whose records are at most max_record_bytes,
  *                             at subsequence length subseq_bits (0 = the default); 0 for unsupported arguments
  *   mfr_jpeg_decode           headers [n] (device), records (device, offsets [n+1] i64 bytes, each a multiple of 16) ->
- *                             gray [n,1,H,W] f32, rgb [n,H,W,3] u8 (may be NULL), status [n] (0 ok; a parse code of the
+ *                             gray [n,1,H,W] f32 (may be NULL when rgb is given), rgb [n,H,W,3] u8 (may be NULL), status [n] (0 ok; a parse code of the
  *                             header passed through, its image untouched; MFR_JPEG_E_* bits from the device: that image's
  *                             planes are undefined), rounds [n] (may be NULL: the entropy stage's fixed-point rounds, a debug
  *                             counter).  subseq_bits: test-only subsequence length in bits (0 = default, >= 16 otherwise).
@@ -534,6 +534,23 @@ size_t mfr_jpeg_workspace_bytes(int n, int H, int W, long long max_record_bytes,
 int mfr_jpeg_decode(const void *headers, const uint8_t *records, const long long *offsets, int n, int H, int W,
                     long long max_record_bytes, float *gray, uint8_t *rgb, int32_t *status, int32_t *rounds, void *workspace,
                     size_t workspace_bytes, int subseq_bits, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Gray plane of decoded RGB images at another size (csrc/resize.hip): rgb [n,H,W,3] u8 (mfr_jpeg_decode's) -> out [n,1,h,w] f32,
+ * bit for bit datasets.gray_plane(rgb, (w, h)): luma (19595 R + 38470 G + 7471 B + 2^15) >> 16, that byte as f32, OpenCV-style
+ * INTER_LINEAR of the float plane (source coordinate (x + 0.5) * n_in / n_out - 0.5, taps clamped at the edges, no antialiasing)
+ * as top = a00 (1 - fx) + a01 fx, bot = a10 (1 - fx) + a11 fx, out = top (1 - fy) + bot fy with every product and sum rounded to
+ * f32, then / 255f.  Call site: jpeg_ops.JpegDecoder.decode(resize=) and the device JPEG route of the batched loaders for datasets
+ * whose files are not at the network size (ScanNet: 1296 x 968 -> 640 x 480).  Added to ABI v6 without a version bump (additive).
+ *   y0, y1 [h] i32, fy [h] f32, x0, x1 [w] i32, fx [w] f32 (device): the tap tables, computed by the caller in float64 with the
+ *     expression of datasets.resize_bilinear_f32 (jpeg_ops.resize_taps); indices are clamped to the image again on the device
+ *   status [n] i32 (device, may be NULL): a row whose status is not 0 is left untouched
+ * Any H, W, h, w >= 1, either direction, separate factors per axis; the same size reproduces byte / 255.
+ */
+int mfr_resize_gray_bilinear(const uint8_t *rgb, int n, int H, int W, const int32_t *status,
+                             const int32_t *y0, const int32_t *y1, const float *fy,
+                             const int32_t *x0, const int32_t *x1, const float *fx,
+                             int h, int w, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * 3x3 / stride 1 / pad 1 convolutions of the SuperPoint encoder (conv1b..conv4b, convPa, convDa; same

@@ -494,7 +494,7 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(const mfr_jpeg_header 
         lum = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16;
     }
     const size_t o = (size_t)img * H * W + i;
-    gray[o] = (float)lum / 255.0f;
+    if (gray) gray[o] = (float)lum / 255.0f;
     if (rgb) {
         rgb[3 * o] = (uint8_t)R; rgb[3 * o + 1] = (uint8_t)G; rgb[3 * o + 2] = (uint8_t)B;
     }
@@ -514,7 +514,7 @@ extern "C" int mfr_jpeg_decode(const void *headers, const uint8_t *records, cons
                                size_t workspace_bytes, int subseq_bits, void *stream)
 {
     JpegLayout L;
-    if (!headers || !records || !offsets || !gray || !status || !workspace) return MFR_E_ARG;
+    if (!headers || !records || !offsets || (!gray && !rgb) || !status || !workspace) return MFR_E_ARG;
     if (jpeg_layout(n, H, W, max_record_bytes, subseq_bits, &L) != 0) return MFR_E_ARG;
     if (workspace_bytes < (size_t)(L.stride * n)) return MFR_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;

@@ -90,6 +90,16 @@ def collate_batch1(sample):
     return out
 
 
+def bilinear_taps(n_out, n_in):
+    """taps of cv2's INTER_LINEAR along one axis: (i0, i1, f) per output sample -- source coordinate (x + 0.5) * (n_in / n_out) - 0.5 in
+    float64, its floor and the next index clamped to the image, the fraction rounded to float32.  Shared by the two host resizes below
+    and by the device resize (jpeg_ops.resize_taps uploads these very tables: csrc/resize.hip)"""
+    s = (np.arange(n_out, dtype=np.float64) + 0.5) * (n_in / n_out) - 0.5
+    i0 = np.floor(s).astype(np.int64)
+    f = (s - i0).astype(np.float32)
+    return np.clip(i0, 0, n_in - 1), np.clip(i0 + 1, 0, n_in - 1), f
+
+
 def resize_bilinear_u8(a, wh):
     """cv2.resize(img, (w, h)) with its default INTER_LINEAR on a uint8 [H,W,C] image: half-pixel-centre bilinear sampling WITHOUT
     antialiasing (source coordinate (x + 0.5) * scale - 0.5, edge-clamped), result rounded back to uint8.  At an exact 2x downscale
@@ -101,14 +111,8 @@ def resize_bilinear_u8(a, wh):
     w, h = int(wh[0]), int(wh[1])
     if (w, h) == (W, H):
         return a
-
-    def taps(n_out, n_in):
-        s = (np.arange(n_out, dtype=np.float64) + 0.5) * (n_in / n_out) - 0.5
-        i0 = np.floor(s).astype(np.int64)
-        f = (s - i0).astype(np.float32)
-        return np.clip(i0, 0, n_in - 1), np.clip(i0 + 1, 0, n_in - 1), f
-    y0, y1, fy = taps(h, H)
-    x0, x1, fx = taps(w, W)
+    y0, y1, fy = bilinear_taps(h, H)
+    x0, x1, fx = bilinear_taps(w, W)
     af = a.astype(np.float32)
     top = af[y0][:, x0] * (1 - fx)[None, :, None] + af[y0][:, x1] * fx[None, :, None]
     bot = af[y1][:, x0] * (1 - fx)[None, :, None] + af[y1][:, x1] * fx[None, :, None]
@@ -123,14 +127,8 @@ def resize_bilinear_f32(a, wh):
     w, h = int(wh[0]), int(wh[1])
     if (w, h) == (W, H):
         return a
-
-    def taps(n_out, n_in):
-        s = (np.arange(n_out, dtype=np.float64) + 0.5) * (n_in / n_out) - 0.5
-        i0 = np.floor(s).astype(np.int64)
-        f = (s - i0).astype(np.float32)
-        return np.clip(i0, 0, n_in - 1), np.clip(i0 + 1, 0, n_in - 1), f
-    y0, y1, fy = taps(h, H)
-    x0, x1, fx = taps(w, W)
+    y0, y1, fy = bilinear_taps(h, H)
+    x0, x1, fx = bilinear_taps(w, W)
     af = a.astype(np.float32, copy=False)
     top = af[y0][:, x0] * (1 - fx)[None, :] + af[y0][:, x1] * fx[None, :]
     bot = af[y1][:, x0] * (1 - fx)[None, :] + af[y1][:, x1] * fx[None, :]
@@ -515,6 +513,9 @@ def list_scenes(cfg, split="val"):
     scenes."""
     root = cfg.DATASET.DATA_ROOT
     syn = cfg.DATASET.SYNTHETIC if "SYNTHETIC" in cfg.DATASET else None
+    if not syn and cfg.DATASET.DATA_SOURCE == "ScanNet":        # any other value (None, 'MapFree') is the Map-free tree below
+        from .scannet import list_scannet_scenes
+        return list_scannet_scenes(cfg, split)
     if syn:
         n_scenes, frames = (int(syn[0]), int(syn[1])) if isinstance(syn, (list, tuple)) else (2, 4)
         return [SyntheticScene(s, frames, cfg.DATASET.HEIGHT or 720, cfg.DATASET.WIDTH or 540) for s in range(n_scenes)]
@@ -603,8 +604,10 @@ def check_jpeg_decode(mode):
 def _jpeg_reader(hdr, rec, row, info):
     """gray_pair reader of the device JPEG route for batch row `row`: the file's header + record go to hdr[row] / rec[row] and
     info[row] = (0, record bytes, path); a file the device does not take (unsupported, invalid, above the slot's cap) is decoded here as on the
-    host route, into the row's plane, and info[row] = (parse status, 0, path)"""
-    def read(path, out_g):
+    host route, into the row's plane, and info[row] = (parse status, 0, path).  resize = (w, h): the size of `out_g` when it is not the
+    file's (scenes whose files are larger than the network input, scannet.ScanNetScene): the device resizes what it decodes
+    (DevicePrefetcher._put_jpeg), the host fallback is read_gray_plane(path, resize)"""
+    def read(path, out_g, resize=None):
         from . import jpeg_ops as J
         with open(path, "rb") as f:
             data = f.read()
@@ -612,7 +615,7 @@ def _jpeg_reader(hdr, rec, row, info):
         if st == J.OK:
             info[row] = (0, nb, path)
         else:
-            read_gray_plane(path, None, out_g)
+            read_gray_plane(path, resize, out_g)
             info[row] = (st, 0, path)
         return out_g
     return read
@@ -812,12 +815,14 @@ class PairBatchLoader:
         # shapes / dtypes of the batch buffers come from the first pair; it is decoded on this thread before the pool gets the others (an
         # attempt to overlap the two -- pool tasks that decode, then pool tasks that wait for them and fill -- halved the loader's rate:
         # workers parked in .result() while the next batches' decodes queued behind them; tools/bench_fused_split.py, round 4)
-        first = get(items[0])
-        Hh, Ww = first["image0"].shape[-2:]
+        # (a scene that states its planes' layout -- batch_layout() -> (H, W, has depth): scannet.ScanNetScene -- is not asked for a generic
+        # sample at all: its generic sample resizes the 8-bit RGB image, a different plane from gray_pair's whenever a resize happens)
+        layout = getattr(self.scenes[items[0][0]], "batch_layout", None)
+        first = get(items[0]) if layout is None else None
+        Hh, Ww, has_depth = layout() if layout is not None else (*first["image0"].shape[-2:], first["depth0"].numel() > 0)
         mk = (lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, pin_memory=True)) if self.pin else \
              (lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype))
         images = mk(2 * b, 1, Hh, Ww)
-        has_depth = first["depth0"].numel() > 0
         depth0 = mk(b, Hh, Ww) if has_depth else None
         depth1 = mk(b, Hh, Ww) if has_depth else None
         # packing through the buffers' numpy views: plain memcpy on the worker's own thread (a torch copy_ of a 1.5 MB plane is
@@ -919,9 +924,13 @@ class PairBatchLoader:
         st = self.stats
         if self._proc is None:
             t0 = _t.perf_counter()
-            first = self.scenes[items[0][0]][items[0][1]]
-            Hh, Ww = first["image0"].shape[-2:]
-            self._proc = _ProcessDecoder(self.scenes, self.B, Hh, Ww, first["depth0"].numel() > 0, self.workers, max(self.prefetch, 0) + 4, self.pin,
+            layout = getattr(self.scenes[items[0][0]], "batch_layout", None)
+            if layout is not None:
+                Hh, Ww, has_depth = layout()
+            else:
+                first = self.scenes[items[0][0]][items[0][1]]
+                (Hh, Ww), has_depth = first["image0"].shape[-2:], first["depth0"].numel() > 0
+            self._proc = _ProcessDecoder(self.scenes, self.B, Hh, Ww, has_depth, self.workers, max(self.prefetch, 0) + 4, self.pin,
                                          jpeg_cap=self.jpeg_cap if self.jpeg_decode == "device" else 0)
             self._pool_map(_pw_ping, range(self.workers * 2))                          # every worker has started and imported its modules
             st["process_pool_start_s"] = _t.perf_counter() - t0
@@ -1020,7 +1029,7 @@ class DevicePrefetcher:
         self.loader, self.device = loader, torch.device(device)
         self.stream = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
 
-    _jdec = None
+    _jdec = _jres = None
 
     def _put(self, hb):
         if self.stream is None:
@@ -1041,7 +1050,9 @@ class DevicePrefetcher:
     def _put_jpeg(self, hb, db):
         """device JPEG route (on the side stream): host planes of the rows the host decoded, then the packed headers / records of the others
         and the decode kernels straight into the batch's device images, then the duplicated reference rows.  The per-image status goes to a
-        pinned word array that _ready checks when the batch is handed out."""
+        pinned word array that _ready checks when the batch is handed out.  When the files are not at the batch's size (the headers say so:
+        ScanNet's 1296 x 968 frames for a 640 x 480 batch) they are decoded at their own size into RGB scratch and resized into the batch's
+        rows on the device (jpeg_ops.GrayResizer: the plane read_gray_plane(path, (W, H)) gives on the host route, bit for bit)."""
         from . import jpeg_ops as J
         jp, images = hb["jpeg"], hb["images"]
         n2, (H, W) = images.shape[0], images.shape[-2:]
@@ -1067,7 +1078,16 @@ class DevicePrefetcher:
                 d_rec[r * cap:r * cap + rows[r][1]].copy_(rec[r, :rows[r][1]], non_blocking=True)
             d_off = torch.arange(n2 + 1, dtype=torch.int64, device=self.device) * cap
             d_st = torch.zeros(n2, dtype=torch.int32, device=self.device)
-            self._jdec.decode_device(d_hdr, d_rec, d_off, n2, H, W, cap, d_img, d_st)
+            fH, fW = (int(v) for v in hdr.numpy()[dev_rows[0], 4:12].view(np.int32)[::-1])     # mfr_jpeg_header: status, width, height
+            if (fH, fW) == (H, W):
+                self._jdec.decode_device(d_hdr, d_rec, d_off, n2, H, W, cap, d_img, d_st)
+            else:                                                   # (a row of yet another size reports E_SIZE, as on the plain route)
+                scratch = torch.empty((n2, fH, fW, 3), dtype=torch.uint8, device=self.device)
+                self._jdec.decode_device(d_hdr, d_rec, d_off, n2, fH, fW, cap, None, d_st, scratch)
+                if self._jres is None:
+                    self._jres = J.GrayResizer(self.device)
+                self._jres(scratch, d_img, d_st)
+                scratch.record_stream(torch.cuda.current_stream(self.device))
             h_status = torch.empty(n2, dtype=torch.int32, pin_memory=True)
             h_status.copy_(d_st, non_blocking=True)
         for r in range(n2):

@@ -117,8 +117,8 @@ def pack(files, H=None, W=None):
 
 
 class JpegDecoder:
-    """JpegDecoder(device).decode(files: list[bytes] | PackedBatch, out=None, rgb=False) -> (gray [n,1,H,W] f32, status [n] i32) on the
-    device (plus rgb [n,H,W,3] u8 with rgb=True).  status: 0 ok, 1 unsupported (host's to decode: its plane is left as it was), 2 / 3
+    """JpegDecoder(device).decode(files: list[bytes] | PackedBatch, out=None, rgb=False, resize=None) -> (gray [n,1,H,W] f32, status [n] i32)
+    on the device (plus rgb [n,H,W,3] u8 with rgb=True; resize=(w, h): gray [n,1,h,w], resized on the device).  status: 0 ok, 1 unsupported (host's to decode: its plane is left as it was), 2 / 3
     invalid / capacity at the parse, E_HUFF / E_TRUNC / E_SIZE bits from the device.  subseq_bits: test-only subsequence length (0 =
     default).  No CPU fallback: without libmfr_hip.so or a GPU it raises MfrLibraryError."""
 
@@ -126,6 +126,7 @@ class JpegDecoder:
         self.device = torch.device(device)
         self.subseq_bits = int(subseq_bits)
         self._ws = None
+        self._resizer = None
         self.rounds = None
 
     def workspace(self, n, H, W, max_record):
@@ -151,18 +152,68 @@ class JpegDecoder:
         ws.record_stream(cur)
         self.rounds.record_stream(cur)
 
-    def decode(self, files, out=None, rgb=False):
+    def decode(self, files, out=None, rgb=False, resize=None):
+        """resize = (w, h): the planes are datasets.read_gray_plane(path, (w, h)) -- the files are decoded at their own size into RGB scratch
+        and resized on the device (GrayResizer, csrc/resize.hip); `out` is then [n,1,h,w] and the RGB returned with rgb=True stays at the
+        files' size.  resize None (or the files' own size): the decoder's gray plane, as before."""
         _lib.load(require_gpu=True)
         pb = files if isinstance(files, PackedBatch) else pack(files)
         n, H, W = pb.n, pb.H, pb.W
         dev = self.device
+        resized = resize is not None and (int(resize[0]), int(resize[1])) != (W, H)
+        oh, ow = (int(resize[1]), int(resize[0])) if resized else (H, W)
         if out is None:
-            out = torch.zeros(n, 1, H, W, dtype=torch.float32, device=dev)
-        assert out.shape == (n, 1, H, W) and out.dtype == torch.float32 and out.is_contiguous()
-        rgb_t = torch.zeros(n, H, W, 3, dtype=torch.uint8, device=dev) if rgb else None
+            out = torch.zeros(n, 1, oh, ow, dtype=torch.float32, device=dev)
+        assert out.shape == (n, 1, oh, ow) and out.dtype == torch.float32 and out.is_contiguous()
+        rgb_t = torch.zeros(n, H, W, 3, dtype=torch.uint8, device=dev) if (rgb or resized) else None
         status = torch.from_numpy(pb.status.copy()).to(dev)
         if n and bool((pb.status == OK).any()):                # nothing the device takes (e.g. only progressive files): statuses only
             max_rec = max(16, int(np.max(np.diff(pb.offsets))))
             self.decode_device(torch.from_numpy(pb.headers).to(dev), torch.from_numpy(pb.records).to(dev),
-                               torch.from_numpy(pb.offsets).to(dev), n, H, W, max_rec, out, status, rgb_t)
+                               torch.from_numpy(pb.offsets).to(dev), n, H, W, max_rec, None if resized else out, status, rgb_t)
+            if resized:
+                if self._resizer is None:
+                    self._resizer = GrayResizer(dev)
+                self._resizer(rgb_t, out, status)
         return (out, status, rgb_t) if rgb else (out, status)
+
+
+def resize_taps(n_out, n_in):
+    """(i0, i1 int32 [n_out], f float32 [n_out]): the bilinear taps of datasets.resize_bilinear_f32 along one axis (the same float64
+    expression, datasets.bilinear_taps), in the types csrc/resize.hip reads"""
+    from .datasets import bilinear_taps
+    i0, i1, f = bilinear_taps(n_out, n_in)
+    return i0.astype(np.int32), i1.astype(np.int32), f
+
+
+class GrayResizer:
+    """GrayResizer(device)(rgb [n,H,W,3] u8, out [n,1,h,w] f32, status=None): datasets.gray_plane(rgb[i], (w, h)) of every row whose status
+    is 0 (all rows without a status), on torch's current stream (include/mfr_hip.h mfr_resize_gray_bilinear).  The tap tables of a size pair
+    are computed on the host once and kept on the device."""
+
+    def __init__(self, device="cuda"):
+        self.device = torch.device(device)
+        self._taps = {}
+
+    def taps(self, n_out, n_in):
+        key = (int(n_out), int(n_in))
+        t = self._taps.get(key)
+        if t is None:
+            t = self._taps[key] = tuple(torch.from_numpy(a).to(self.device) for a in resize_taps(*key))
+        return t
+
+    def __call__(self, rgb, out, status=None):
+        lib = _lib.load(require_gpu=True)
+        n, H, W, c = rgb.shape
+        h, w = out.shape[-2:]
+        assert c == 3 and rgb.dtype == torch.uint8 and out.dtype == torch.float32 and out.shape == (n, 1, h, w)
+        assert status is None or (status.dtype == torch.int32 and status.numel() == n)
+        y0, y1, fy = self.taps(h, H)
+        x0, x1, fx = self.taps(w, W)
+        cur = torch.cuda.current_stream(self.device)
+        _lib.check(lib.mfr_resize_gray_bilinear(_lib.ptr(rgb), n, H, W, _lib.ptr(status), _lib.ptr(y0), _lib.ptr(y1), _lib.ptr(fy),
+                                                _lib.ptr(x0), _lib.ptr(x1), _lib.ptr(fx), h, w, _lib.ptr(out), cur.cuda_stream),
+                   "mfr_resize_gray_bilinear")
+        for t in (y0, y1, fy, x0, x1, fx):
+            t.record_stream(cur)
+        return out
