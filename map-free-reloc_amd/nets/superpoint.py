@@ -159,15 +159,12 @@ class SuperPointHIP:
                    "mfr_sp_sample_descriptors")
         return desc
 
-    @torch.no_grad()
-    def __call__(self, image):
-        """image [B2,1,H,W] f32 in [0,1] on the GPU -> dict(kpts [B2,K,2] (x,y), scores [B2,K],
-        desc [B2,K,256] token-major, n [B2] i32).  Rows >= n are zero."""
-        x = self.encode(image)
-        logits = self._conv(self._conv(x, "convPa"), "convPb", relu=False)
-        scores = self.score_map(logits)
-        cand, cnt, _ = self.nms_candidates(scores)
-        kpts, sc, n = self.select(cand, cnt, scores.shape[2])
+    def logits(self, x):
+        """encoder output [B,128,Hc,Wc] -> the detector head's 65 logits per cell [B,65,Hc,Wc] (convPa + ReLU, convPb)"""
+        return self._conv(self._conv(x, "convPa"), "convPb", relu=False)
+
+    def descriptor_rows(self, x):
+        """encoder output [B,128,Hc,Wc] -> the descriptor head's output BEFORE normalisation, token-major [B,Hc,Wc,256] (convDa + ReLU, convDb)"""
         # 1x1 descriptor head (convDb) through the own GEMM: every row's K loop runs in the same order whatever the number of rows.  Round 6: convDa writes its
         # output token-major itself when the direct kernel runs it (mfr_conv3x3_direct_f16x2_rows); else NCHW -> rows by csrc/elementwise.hip
         cDa_rows = self.upk["convDa"].rows(x, act=1) if (self.use_wino and "convDa" in self.upk) else None
@@ -180,6 +177,15 @@ class SuperPointHIP:
             rows = torch.empty(B * Hc * Wc, C, dtype=torch.float32, device=cDa.device)
             _lib.check(_lib.load().mfr_nchw_to_rows(_lib.ptr(cDa.contiguous()), None, B, C, Hc * Wc, 0, _lib.ptr(rows), Hc * Wc * C, C, _lib.stream_ptr()),
                        "mfr_nchw_to_rows")
-        dense = self.convDb(rows)
-        desc = self.sample(dense.view(B, Hc, Wc, 256), kpts, n)
+        return self.convDb(rows).view(B, Hc, Wc, 256)
+
+    @torch.no_grad()
+    def __call__(self, image):
+        """image [B2,1,H,W] f32 in [0,1] on the GPU -> dict(kpts [B2,K,2] (x,y), scores [B2,K],
+        desc [B2,K,256] token-major, n [B2] i32).  Rows >= n are zero."""
+        x = self.encode(image)
+        scores = self.score_map(self.logits(x))
+        cand, cnt, _ = self.nms_candidates(scores)
+        kpts, sc, n = self.select(cand, cnt, scores.shape[2])
+        desc = self.sample(self.descriptor_rows(x), kpts, n)
         return dict(kpts=kpts, scores=sc, desc=desc, n=n)

@@ -10,6 +10,17 @@ idle), so the SuperGlue recipe is "structured random": the GNN updates and the k
 are scaled down (the network stays a mild perturbation of its input descriptors) and the final
 projection is scaled up so that the score matrix is peaky.  Accuracy of such weights is
 meaningless; shapes, arithmetic and control flow are exactly those of the trained network.
+
+What these recipes make TRIVIAL (a trained checkpoint has none of these properties, and a device module that drops, doubles or swaps
+one of the terms still agrees with the oracle on these weights):
+  * LoFTR: all 17 BatchNorms are the identity (gamma 1, beta 0, mean 0, var 1); every norm1 has gamma 1, beta 0; every norm2 a constant
+    gamma and beta 0; `fine_preprocess.down_proj.bias` and `fine_preprocess.merge_feat.bias` are zero;
+  * SuperPoint: all 12 convolution biases are zero;
+  * SuperGlue: `mlp.3.bias` of all 18 layers and `kenc.encoder.12.bias` are zero (so the offset nets/superglue.fold_weights carries from
+    layer to layer is identically 0), BatchNorm is within 5 % of the identity, `bin_score` is 1.0.
+tests/trained_like.py turns any of the three state dicts into one where every such term is non-trivial; the wiring of the device modules
+is tested on those (tests/test_gpu_matcher_wiring.py, tests/test_weight_folding_host.py).  The defaults here stay as they are: the
+benchmark, the parity census and every other test depend on these bits.
 """
 import torch
 

@@ -236,6 +236,14 @@ def test_superglue_weight_folding_is_exact_algebra():
             sd[k] = 0.1 * torch.randn(sd[k].shape, generator=g)
         if k.endswith("running_var"):
             sd[k] = 0.5 + torch.rand(sd[k].shape, generator=g)
+    # ... and the terms the recipe leaves trivial: the last keypoint-encoder bias (zero), gamma / beta of the keypoint encoder's
+    # BatchNorms (1 +- 0.05 / 0.05) and the dustbin score (1.0)
+    sd["kenc.encoder.12.bias"] = 0.1 * torch.randn(256, generator=g)
+    for i in (1, 4, 7, 10):
+        c = sd[f"kenc.encoder.{i}.weight"].numel()
+        sd[f"kenc.encoder.{i}.weight"] = 0.5 + torch.rand(c, generator=g)
+        sd[f"kenc.encoder.{i}.bias"] = 0.2 * torch.randn(c, generator=g)
+    sd["bin_score"] = torch.tensor(2.37)
     ref = nets_ref.SuperGlueRef().double().eval()
     ref.load_state_dict({k: v.double() for k, v in sd.items()})
     n0, n1, H, W = 37, 29, 120, 160
@@ -246,6 +254,7 @@ def test_superglue_weight_folding_is_exact_algebra():
     out = ref(k0, s0, d0, k1, s1, d1, (H, W))
 
     fw = fold_weights(sd)
+    assert fw["bin_score"] == float(torch.tensor(2.37)) == float(ref.bin_score.detach())
 
     def run(kp, sc, de, kp_o, sc_o, de_o):
         def enc(kp, sc, de):
