@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define MFR_ABI_VERSION 6   /* 6 (round 6): mfr_conv3x3_direct_f16x2*, later (additive) the SIFT detector mfr_sift_*, the JPEG decoder mfr_jpeg_*, mfr_resize_gray_bilinear (the device image resize), mfr_conv3x3s2_direct_f16x2, mfr_mlp_ln_*, mfr_loftr_ot_match (LoFTR's optimal-transport coarse matching); 5 (round 6): mfr_f16x2_guard_bind (the f16x2 range guard); 2: intrinsics as (const void *K, int k_dtype) instead of const float *; 3: mfr_emat_solve_batch takes the
+#define MFR_ABI_VERSION 6   /* 6 (round 6): mfr_conv3x3_direct_f16x2*, later (additive) the SIFT detector mfr_sift_*, the JPEG decoder mfr_jpeg_*, mfr_resize_gray_bilinear (the device image resize), mfr_conv3x3s2_direct_f16x2, mfr_mlp_ln_*, mfr_loftr_ot_match (LoFTR's optimal-transport coarse matching), mfr_abs_pose_fuse (7Scenes: absolute pose from relative poses); 5 (round 6): mfr_f16x2_guard_bind (the f16x2 range guard); 2: intrinsics as (const void *K, int k_dtype) instead of const float *; 3: mfr_emat_solve_batch takes the
                              * model-quality method (MAGSAC++ / count) and its table; 4 (round 5): the f16x2 entry points (mfr_gemm_f16x2*,
                              * mfr_wino_f16x2_*, mfr_conv3x3_wino_f16x2, mfr_conv_igemm_f16x2), mfr_sg_attention_variant renumbered (0 f16x2,
                              * 1 exact fp32, 2 bf16x3), the measurement-only entry points (mfr_conv3x3_wino_bf16x3_variant,
@@ -145,6 +145,39 @@ int mfr_scale_from_depth_batch(const float *pts0, const float *pts1, const uint8
                                void *workspace, size_t workspace_bytes,
                                double *t_metric, double *best_scale, int32_t *n_inliers, int32_t *status,
                                void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Absolute pose of a query from its relative poses to several database images (7Scenes): lib/utils/localize.py
+ *   per pair (RelaPosePair :942-964, AbsPose :896-918): q = mat2quat(R), r = quat2mat(q), x_te, abs_q_pred, abs_c_pred
+ *   mode 0  cal_abs_pose_err_metric (:352-421): Weiszfeld geometric median of abs_c_pred (stop |y - y1| < 1e-5, at most
+ *           MFR_AP_WEISZFELD_CAP iterations: then the current iterate, status | MFR_AP_ITER_CAP) + chordal mean rotation
+ *   mode 1  ransac(pair_type='relapose') (:471-635): every pair of neighbours in combinations order, triangulation +
+ *           raw quaternion mean, find_inliers at thr_deg, local_optimisation at thr_mult * thr_deg with lo_iters random
+ *           subsets (Philox keyed by seed, query, LO call, iteration); no winner -> the first pair's database pose,
+ *           MFR_AP_APPROXIMATED, inlier mask {0}.  At most MFR_AP_MAX_PAIRS neighbours per query (else MFR_AP_TOO_MANY).
+ * All pointers are device memory.  train_q [P,4] wxyz, train_c [P,3], pred_R [P,9], pred_t [P,3] f64 (the caller drops pairs
+ * without a finite pose); pairs of query i are offsets[i] .. offsets[i+1] (offsets [Q+1] i32, ascending, last <= P).
+ * thr_mult >= 1 (else MFR_E_ARG): the local optimisation refits over the inliers at thr_mult * thr_deg, a superset of the >= 2 inliers
+ * at thr_deg, so that set is never empty (the reference raises on an empty one).  0 <= lo_iters <= MFR_AP_MAX_LO_ITERS.
+ * Outputs abs_q [Q,4] wxyz (mode 1: the unnormalised mean), abs_c [Q,3] (NaN without pairs), inlier_mask [P] i32, status [Q].
+ * ------------------------------------------------------------------------------------------ */
+#define MFR_AP_OK            0
+#define MFR_AP_APPROXIMATED  1
+#define MFR_AP_NO_PAIRS      2
+#define MFR_AP_TOO_MANY      3
+#define MFR_AP_BAD_OFFSETS   4
+#define MFR_AP_ITER_CAP      16   /* bit, mode 0 */
+#define MFR_AP_MAX_PAIRS     64
+#define MFR_AP_MAX_LO_ITERS  62
+#define MFR_AP_WEISZFELD_CAP 256
+size_t mfr_abs_pose_workspace_bytes(int P);
+int mfr_abs_pose_fuse(const double *train_q, const double *train_c, const double *pred_R, const double *pred_t, int P,
+                      const int32_t *offsets, int Q, int mode, double thr_deg, double thr_mult, int lo_iters, uint64_t seed,
+                      void *workspace, size_t workspace_bytes,
+                      double *abs_q, double *abs_c, int32_t *inlier_mask, int32_t *status, void *stream);
+/* test hook: the local optimisation's random subsets as bit masks, out[(q * calls + c) * iters + it] = the nsub (<= 14) members drawn from
+ * the set bits of base[q] for (seed, query q, LO call c, iteration it); 0 where base[q] holds fewer than nsub.  Device pointers. */
+int mfr_test_abs_pose_subset(uint64_t seed, const uint64_t *base, int n, int calls, int iters, int nsub, uint64_t *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Essential-matrix path: EssentialMatrixSolver.estimate_pose, lib/models/matching/pose_solver.py:29-61

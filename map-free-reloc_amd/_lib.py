@@ -120,6 +120,9 @@ SIGNATURES = {
     "mfr_scale_workspace_bytes": (_sz, [_i, _i]),
     "mfr_scale_from_depth_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp,
                                         _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "mfr_abs_pose_workspace_bytes": (_sz, [_i]),
+    "mfr_test_abs_pose_subset": (_i, [_u64, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "mfr_abs_pose_fuse": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _d, _d, _i, _u64, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -81,8 +81,12 @@ def collate_batch1(sample):
     for k, v in sample.items():
         if isinstance(v, torch.Tensor):
             out[k] = v[None]
+        elif isinstance(v, np.ndarray):                      # (the 7Scenes sample: intrinsics and absolute poses are numpy arrays)
+            out[k] = torch.from_numpy(v)[None]
         elif isinstance(v, (int, np.integer)):
             out[k] = torch.tensor([int(v)])
+        elif isinstance(v, float):
+            out[k] = torch.tensor([v], dtype=torch.float64)
         elif isinstance(v, tuple):
             out[k] = [[x] for x in v]
         else:
@@ -516,6 +520,9 @@ def list_scenes(cfg, split="val"):
     if not syn and cfg.DATASET.DATA_SOURCE == "ScanNet":        # any other value (None, 'MapFree') is the Map-free tree below
         from .scannet import list_scannet_scenes
         return list_scannet_scenes(cfg, split)
+    if not syn and cfg.DATASET.DATA_SOURCE == "7Scenes":
+        from .sevenscenes import list_sevenscenes_scenes
+        return list_sevenscenes_scenes(cfg, split)
     if syn:
         n_scenes, frames = (int(syn[0]), int(syn[1])) if isinstance(syn, (list, tuple)) else (2, 4)
         return [SyntheticScene(s, frames, cfg.DATASET.HEIGHT or 720, cfg.DATASET.WIDTH or 540) for s in range(n_scenes)]
