@@ -20,7 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
-#include "geom_dev.h"
+#include "solver_dev.h"
 
 using namespace mfr;
 
@@ -35,58 +35,7 @@ using namespace mfr;
 #define AP_SWEEPS 12
 #define AP_WAVES 4               // queries per workgroup (mode 1)
 
-// ---------------------------------------------------------------- symmetric 4x4 eigenproblem
-// cyclic Jacobi, AP_SWEEPS sweeps over the 6 off-diagonal entries; on return the diagonal of A holds the eigenvalues and the COLUMNS of V
-// the eigenvectors.  A rotation whose angle underflows (theta^2 = inf) is the identity; NaN input gives NaN output after the same work.
-MFR_DEV void jacobi4(double A[4][4], double V[4][4])
-{
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < AP_SWEEPS; ++sweep) {
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) {
-                const double apq = A[p][q];
-                if (apq == 0.0) continue;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-                const double at = theta < 0.0 ? -theta : theta;
-                double t = 1.0 / (at + sqrt(theta * theta + 1.0));
-                if (theta < 0.0) t = -t;
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const double akp = A[k][p], akq = A[k][q];
-                    A[k][p] = c * akp - s * akq; A[k][q] = s * akp + c * akq;
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const double apk = A[p][k], aqk = A[q][k];
-                    A[p][k] = c * apk - s * aqk; A[q][k] = s * apk + c * aqk;
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - s * vkq; V[k][q] = s * vkp + c * vkq;
-                }
-            }
-    }
-}
-// column of the largest (want_max) or smallest eigenvalue, first index on ties (np.argmax / the last row of vh)
-MFR_DEV void jacobi4_pick(double A[4][4], bool want_max, double v[4])
-{
-    double V[4][4];
-    jacobi4(A, V);
-    int best = 0;
-#pragma unroll
-    for (int i = 1; i < 4; ++i)
-        if (want_max ? (A[i][i] > A[best][best]) : (A[i][i] < A[best][best])) best = i;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = (best == 0) ? V[k][0] : (best == 1) ? V[k][1] : (best == 2) ? V[k][2] : V[k][3];
-}
-
+// ---------------------------------------------------------------- quaternions
 // transforms3d.quaternions.quat2mat: divides by the squared norm, identity below eps
 MFR_DEV void quat2mat(const double q[4], double R[9])
 {
@@ -114,7 +63,7 @@ MFR_DEV void mat2quat(const double M[9], double q[4])
     K[3][0] = (Qyz - Qzy) / 3.0; K[3][1] = (Qzx - Qxz) / 3.0; K[3][2] = (Qxy - Qyx) / 3.0; K[3][3] = ((Qxx + Qyy) + Qzz) / 3.0;
     K[0][1] = K[1][0]; K[0][2] = K[2][0]; K[0][3] = K[3][0]; K[1][2] = K[2][1]; K[1][3] = K[3][1]; K[2][3] = K[3][2];
     double v[4];
-    jacobi4_pick(K, true, v);
+    jacobi4_pick<AP_SWEEPS>(K, true, v);
     q[0] = v[3]; q[1] = v[0]; q[2] = v[1]; q[3] = v[2];
     if (q[0] < 0.0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
 }
@@ -193,7 +142,7 @@ MFR_DEV void ap_estimate(const double *__restrict__ pw, int k, uint64_t mask, Ap
 #pragma unroll
         for (int b = 0; b < a; ++b) M[a][b] = M[b][a];
     double X[4];
-    jacobi4_pick(M, false, X);
+    jacobi4_pick<AP_SWEEPS>(M, false, X);
     h.c[0] = X[0] / X[3]; h.c[1] = X[1] / X[3]; h.c[2] = X[2] / X[3];
     const double dn = (double)n;
 #pragma unroll
@@ -422,7 +371,7 @@ __global__ void __launch_bounds__(64) abs_pose_median_kernel(
 #pragma unroll
         for (int b = 0; b < a; ++b) M[a][b] = M[b][a];
     double v[4], Rm[9], qo[4];
-    jacobi4_pick(M, true, v);
+    jacobi4_pick<AP_SWEEPS>(M, true, v);
     quat2mat(v, Rm);                                                    // .as_matrix(), then mat2quat (:397-398)
     mat2quat(Rm, qo);
     for (int a = 0; a < 4; ++a) abs_q[4 * (size_t)qi + a] = qo[a];

@@ -266,7 +266,7 @@ static __device__ __forceinline__ double emat_cost(SelRed &rd, const double *p0,
 static __device__ __forceinline__ int emat_refine(SelRed &rd, const double *p0, const double *p1, const int32_t *idx, int n,
                                                int max_iter, double *R, double *t)
 {
-    double lambda = 1e-3;
+    LmDamping lm;
     double cost = emat_cost(rd, p0, p1, idx, n, R, t);
     if (!(cost == cost)) return -1;
     for (int it = 0; it < max_iter; ++it) {
@@ -277,46 +277,18 @@ static __device__ __forceinline__ int emat_refine(SelRed &rd, const double *p0, 
         for (int q = 0; q < 27; ++q) acc[q] = 0.0;
         for (int i = (int)threadIdx.x; i < n; i += EM_SEL_THREADS) {
             const int j = idx[i];
-            const double a = p0[2 * (size_t)j], b = p0[2 * (size_t)j + 1], c = p1[2 * (size_t)j], d = p1[2 * (size_t)j + 1];
-            const double Ex0 = (E[0] * a + E[1] * b) + E[2], Ex1 = (E[3] * a + E[4] * b) + E[5], Ex2 = (E[6] * a + E[7] * b) + E[8];
-            const double Et0 = (E[0] * c + E[3] * d) + E[6], Et1 = (E[1] * c + E[4] * d) + E[7];
-            const double num = (c * Ex0 + d * Ex1) + Ex2;
-            const double den = ((Ex0 * Ex0 + Ex1 * Ex1) + Et0 * Et0) + Et1 * Et1;
-            const double wgt = 1.0 / sqrt(den);
-            const double q[3] = { c, d, 1.0 }, p[3] = { a, b, 1.0 };
-            const double txq[3] = { t[1] * q[2] - t[2] * q[1], t[2] * q[0] - t[0] * q[2], t[0] * q[1] - t[1] * q[0] };
-            const double u[3] = { -((R[0] * txq[0] + R[3] * txq[1]) + R[6] * txq[2]),
-                                  -((R[1] * txq[0] + R[4] * txq[1]) + R[7] * txq[2]),
-                                  -((R[2] * txq[0] + R[5] * txq[1]) + R[8] * txq[2]) };
-            const double Rp[3] = { (R[0] * p[0] + R[1] * p[1]) + R[2] * p[2], (R[3] * p[0] + R[4] * p[1]) + R[5] * p[2],
-                                   (R[6] * p[0] + R[7] * p[1]) + R[8] * p[2] };
-            double J[6];
-            J[0] = (p[1] * u[2] - p[2] * u[1]) * wgt; J[1] = (p[2] * u[0] - p[0] * u[2]) * wgt; J[2] = (p[0] * u[1] - p[1] * u[0]) * wgt;
-            J[3] = (Rp[1] * q[2] - Rp[2] * q[1]) * wgt; J[4] = (Rp[2] * q[0] - Rp[0] * q[2]) * wgt; J[5] = (Rp[0] * q[1] - Rp[1] * q[0]) * wgt;
-            const double r = num * wgt;
-            int qq = 0;
-#pragma unroll
-            for (int rr = 0; rr < 6; ++rr)
-#pragma unroll
-                for (int cc = rr; cc < 6; ++cc, ++qq) acc[qq] = acc[qq] + J[rr] * J[cc];
-#pragma unroll
-            for (int rr = 0; rr < 6; ++rr, ++qq) acc[qq] = acc[qq] + J[rr] * r;
+            double J[6], r;
+            sampson_jac(E, R, t, p0[2 * (size_t)j], p0[2 * (size_t)j + 1], p1[2 * (size_t)j], p1[2 * (size_t)j + 1], J, r);
+            lm6_accumulate(acc, J, r);
         }
         block_sum(rd, acc);
-        double H[36], g[6];
-        {
-            int qq = 0;
-            for (int rr = 0; rr < 6; ++rr)
-                for (int cc = rr; cc < 6; ++cc, ++qq) { H[6 * rr + cc] = acc[qq]; H[6 * cc + rr] = acc[qq]; }
-            for (int rr = 0; rr < 6; ++rr, ++qq) g[rr] = -acc[qq];
-        }
-        for (int rr = 0; rr < 6; ++rr) H[6 * rr + rr] = H[6 * rr + rr] + lambda * H[6 * rr + rr];
-        for (int rr = 0; rr < 3; ++rr)
+        double H[36], g[6], dl[6];
+        lm6_unpack(acc, H, g);
+        lm.damp(H);
+        for (int rr = 0; rr < 3; ++rr)                      // gauge term t t^T: E does not see the length of t
             for (int cc = 0; cc < 3; ++cc) H[6 * (3 + rr) + 3 + cc] = H[6 * (3 + rr) + 3 + cc] + t[rr] * t[cc];
-        double dl[6];
         if (chol_solve6(H, g, dl)) {
-            lambda = lambda * 10.0;
-            if (lambda > 1e12) break;
+            if (lm.reject()) break;
             continue;
         }
         double Rn[9], tn[3];
@@ -324,28 +296,19 @@ static __device__ __forceinline__ int emat_refine(SelRed &rd, const double *p0, 
         tn[0] = t[0] + dl[3]; tn[1] = t[1] + dl[4]; tn[2] = t[2] + dl[5];
         const double nt = sqrt((tn[0] * tn[0] + tn[1] * tn[1]) + tn[2] * tn[2]);
         if (!(nt > 0.0)) {
-            lambda = lambda * 10.0;
-            if (lambda > 1e12) break;
+            if (lm.reject()) break;
             continue;
         }
         tn[0] = tn[0] / nt; tn[1] = tn[1] / nt; tn[2] = tn[2] / nt;
         const double cn = emat_cost(rd, p0, p1, idx, n, Rn, tn);
-        double mx = 0.0;
-        for (int k = 0; k < 6; ++k) { const double v = dl[k] < 0.0 ? -dl[k] : dl[k]; if (v > mx) mx = v; }
         if (cn < cost) {
-            const double dec = cost - cn;
             for (int k = 0; k < 9; ++k) R[k] = Rn[k];
             for (int k = 0; k < 3; ++k) t[k] = tn[k];
-            const bool done = (dec <= 1e-14 * cost);
+            const bool done = lm.accept(cost - cn, 1e-14 * cost);
             cost = cn;
-            lambda = lambda * 0.1;
-            if (lambda < 1e-12) lambda = 1e-12;
             if (done) break;
-        } else {
-            lambda = lambda * 10.0;
-            if (lambda > 1e12) break;
-        }
-        if (mx < 1e-13) break;
+        } else if (lm.reject()) break;
+        if (lm6_max_abs(dl) < 1e-13) break;
     }
     return 0;
 }
@@ -430,57 +393,27 @@ static __device__ __forceinline__ int magsac_lo_block(SelRed &rd, const Magsac &
     int cnt;
     double loss = magsac_score_block(rd, ms, E, p0, p1, n, &cnt);
     if (!(loss == loss)) return -1;
-    double lambda = 1e-3;
+    LmDamping lm;
     for (int it = 0; it < MAGSAC_LO_ITERS; ++it) {
         double acc[27];
 #pragma unroll
         for (int q = 0; q < 27; ++q) acc[q] = 0.0;
         for (int i = (int)threadIdx.x; i < n; i += EM_SEL_THREADS) {
             const double a = p0[2 * (size_t)i], b = p0[2 * (size_t)i + 1], c = p1[2 * (size_t)i], d = p1[2 * (size_t)i + 1];
-            const double Ex0 = (E[0] * a + E[1] * b) + E[2], Ex1 = (E[3] * a + E[4] * b) + E[5], Ex2 = (E[6] * a + E[7] * b) + E[8];
-            const double Et0 = (E[0] * c + E[3] * d) + E[6], Et1 = (E[1] * c + E[4] * d) + E[7];
-            const double num = (c * Ex0 + d * Ex1) + Ex2;
-            const double den = ((Ex0 * Ex0 + Ex1 * Ex1) + Et0 * Et0) + Et1 * Et1;
-            const double r2 = (num * num) / den;
+            const double r2 = sampson2(E, a, b, c, d);
             if (!(r2 < ms.cut)) continue;
-            const double pw = magsac_interp(ms.lut + 1, 2, ms.M, ms.scale, r2);
-            const double wgt = 1.0 / sqrt(den);
-            const double q[3] = { c, d, 1.0 }, p[3] = { a, b, 1.0 };
-            const double txq[3] = { t[1] * q[2] - t[2] * q[1], t[2] * q[0] - t[0] * q[2], t[0] * q[1] - t[1] * q[0] };
-            const double u[3] = { -((R[0] * txq[0] + R[3] * txq[1]) + R[6] * txq[2]),
-                                  -((R[1] * txq[0] + R[4] * txq[1]) + R[7] * txq[2]),
-                                  -((R[2] * txq[0] + R[5] * txq[1]) + R[8] * txq[2]) };
-            const double Rp[3] = { (R[0] * p[0] + R[1] * p[1]) + R[2] * p[2], (R[3] * p[0] + R[4] * p[1]) + R[5] * p[2],
-                                   (R[6] * p[0] + R[7] * p[1]) + R[8] * p[2] };
-            double J[6];
-            J[0] = (p[1] * u[2] - p[2] * u[1]) * wgt; J[1] = (p[2] * u[0] - p[0] * u[2]) * wgt; J[2] = (p[0] * u[1] - p[1] * u[0]) * wgt;
-            J[3] = (Rp[1] * q[2] - Rp[2] * q[1]) * wgt; J[4] = (Rp[2] * q[0] - Rp[0] * q[2]) * wgt; J[5] = (Rp[0] * q[1] - Rp[1] * q[0]) * wgt;
-            const double r = num * wgt;
-            int qq = 0;
-#pragma unroll
-            for (int rr = 0; rr < 6; ++rr) {
-                const double wj = pw * J[rr];
-#pragma unroll
-                for (int cc = rr; cc < 6; ++cc, ++qq) acc[qq] = acc[qq] + wj * J[cc];
-            }
-#pragma unroll
-            for (int rr = 0; rr < 6; ++rr, ++qq) acc[qq] = acc[qq] + (pw * J[rr]) * r;
+            double J[6], r;
+            sampson_jac(E, R, t, a, b, c, d, J, r);
+            lm6_accumulate(acc, J, r, magsac_interp(ms.lut + 1, 2, ms.M, ms.scale, r2));
         }
         block_sum(rd, acc);
-        double H[36], g[6];
-        {
-            int qq = 0;
-            for (int rr = 0; rr < 6; ++rr)
-                for (int cc = rr; cc < 6; ++cc, ++qq) { H[6 * rr + cc] = acc[qq]; H[6 * cc + rr] = acc[qq]; }
-            for (int rr = 0; rr < 6; ++rr, ++qq) g[rr] = -acc[qq];
-        }
-        for (int rr = 0; rr < 6; ++rr) H[6 * rr + rr] = H[6 * rr + rr] + lambda * H[6 * rr + rr];
-        for (int rr = 0; rr < 3; ++rr)
+        double H[36], g[6], dl[6];
+        lm6_unpack(acc, H, g);
+        lm.damp(H);
+        for (int rr = 0; rr < 3; ++rr)                      // gauge term t t^T: E does not see the length of t
             for (int cc = 0; cc < 3; ++cc) H[6 * (3 + rr) + 3 + cc] = H[6 * (3 + rr) + 3 + cc] + t[rr] * t[cc];
-        double dl[6];
         if (chol_solve6(H, g, dl)) {
-            lambda = lambda * 10.0;
-            if (lambda > 1e12) break;
+            if (lm.reject()) break;
             continue;
         }
         double Rn[9], tn[3], En[9];
@@ -488,30 +421,21 @@ static __device__ __forceinline__ int magsac_lo_block(SelRed &rd, const Magsac &
         tn[0] = t[0] + dl[3]; tn[1] = t[1] + dl[4]; tn[2] = t[2] + dl[5];
         const double nt = sqrt((tn[0] * tn[0] + tn[1] * tn[1]) + tn[2] * tn[2]);
         if (!(nt > 0.0)) {
-            lambda = lambda * 10.0;
-            if (lambda > 1e12) break;
+            if (lm.reject()) break;
             continue;
         }
         tn[0] = tn[0] / nt; tn[1] = tn[1] / nt; tn[2] = tn[2] / nt;
         skew_mul(tn, Rn, En);
         int cn;
         const double ln = magsac_score_block(rd, ms, En, p0, p1, n, &cn);
-        double mx = 0.0;
-        for (int k = 0; k < 6; ++k) { const double v = dl[k] < 0.0 ? -dl[k] : dl[k]; if (v > mx) mx = v; }
         if (ln < loss) {
-            const double dec = loss - ln, mag = loss < 0.0 ? -loss : loss;
             for (int k = 0; k < 9; ++k) { R[k] = Rn[k]; E[k] = En[k]; }
             for (int k = 0; k < 3; ++k) t[k] = tn[k];
-            const bool done = (dec <= 1e-12 * mag);
+            const bool done = lm.accept(loss - ln, 1e-12 * (loss < 0.0 ? -loss : loss));
             loss = ln; cnt = cn;
-            lambda = lambda * 0.1;
-            if (lambda < 1e-12) lambda = 1e-12;
             if (done) break;
-        } else {
-            lambda = lambda * 10.0;
-            if (lambda > 1e12) break;
-        }
-        if (mx < 1e-13) break;
+        } else if (lm.reject()) break;
+        if (lm6_max_abs(dl) < 1e-13) break;
     }
     for (int k = 0; k < 9; ++k) Eout[k] = E[k];
     *loss_out = loss; *cnt_out = cnt;
@@ -598,35 +522,7 @@ __global__ void __launch_bounds__(EM_SEL_THREADS) emat_select_kernel(
         if (n == 5) {
             run = 1;
             if (cnt[0] > 0) { best = cnt[0]; bit = 0; }
-        } else {
-            int niters = max_iters, carry = 4;
-            bool stop = false;
-            for (int c0 = 0; c0 < max_iters && !stop && c0 < niters; c0 += 64) {
-                const int it = c0 + lane;
-                const int v = (it < max_iters) ? cnt[it] : -1;
-                int incl = v;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const int o = __shfl_up(incl, off, 64);
-                    if (lane >= off && o > incl) incl = o;
-                }
-                int excl = __shfl_up(incl, 1, 64);
-                if (lane == 0 || excl < carry) excl = carry;
-                unsigned long long rec = __ballot(v > excl);
-                while (rec) {
-                    const int l = __ffsll((long long)rec) - 1;
-                    rec &= rec - 1;
-                    const int itr = c0 + l;
-                    if (itr >= niters) { stop = true; break; }
-                    best = __shfl(v, l, 64);
-                    bit = itr;
-                    niters = update_num_iters(conf, (double)(n - best) / (double)n, 5, niters);
-                }
-                const int last = __shfl(incl, 63, 64);
-                if (last > carry) carry = last;
-            }
-            run = (bit + 1 > niters) ? bit + 1 : niters;
-        }
+        } else run = ransac_replay_counts(cnt, max_iters, n, conf, 5, best, bit);
         if (bit < 0) st = MFR_ST_NO_MODEL;
     }
     double R[9], t[3];
@@ -654,10 +550,8 @@ __global__ void __launch_bounds__(EM_SEL_THREADS) emat_select_kernel(
                     const double r2 = sampson2(Eb, p0[2 * (size_t)i], p0[2 * (size_t)i + 1], p1[2 * (size_t)i], p1[2 * (size_t)i + 1]);
                     in = MAGSAC ? (r2 < thr2) : (r2 <= thr2);
                 }
-                const unsigned long long bal = __ballot(in);
-                if (in) idx[m + __popcll(bal & ((1ull << lane) - 1ull))] = i;
+                wave_compact_append(in, i, idx, m);
                 if (i < n) rm[i] = in ? 1 : 0;
-                m += __popcll(bal);
             }
             if (lane == 0) rd.i[0] = m;
         }
@@ -739,21 +633,23 @@ __global__ void __launch_bounds__(EM_SEL_THREADS) emat_select_kernel(
     }
 }
 
-struct EmWs { size_t x0, x1, thr2, Es, nsol, counts, bestm, losses, idx, rm, total; };
-static EmWs em_ws_layout(int B, int maxN, int iters)
+struct EmWs { double *x0, *x1, *thr2, *Es; int32_t *nsol, *counts, *bestm; double *losses; int32_t *idx; uint8_t *rm; size_t total; };
+static EmWs em_ws(void *base, int B, int maxN, int iters)
 {
-    EmWs w; size_t o = 0;
-    w.x0 = o;     o = align_up(o + sizeof(double) * 2 * (size_t)B * maxN, 256);
-    w.x1 = o;     o = align_up(o + sizeof(double) * 2 * (size_t)B * maxN, 256);
-    w.thr2 = o;   o = align_up(o + sizeof(double) * (size_t)B, 256);
-    w.Es = o;     o = align_up(o + sizeof(double) * 90 * (size_t)B * iters, 256);
-    w.nsol = o;   o = align_up(o + sizeof(int32_t) * (size_t)B * iters, 256);
-    w.counts = o; o = align_up(o + sizeof(int32_t) * (size_t)B * iters, 256);
-    w.bestm = o;  o = align_up(o + sizeof(int32_t) * (size_t)B * iters, 256);
-    w.losses = o; o = align_up(o + sizeof(double) * (size_t)B * iters, 256);
-    w.idx = o;    o = align_up(o + sizeof(int32_t) * (size_t)B * maxN, 256);
-    w.rm = o;     o = align_up(o + (size_t)B * maxN, 256);
-    w.total = o;
+    WsCarver c(base);
+    EmWs w;
+    const size_t b = (size_t)B;
+    w.x0 = c.take<double>(2 * b * maxN);
+    w.x1 = c.take<double>(2 * b * maxN);
+    w.thr2 = c.take<double>(b);
+    w.Es = c.take<double>(90 * b * iters);
+    w.nsol = c.take<int32_t>(b * iters);
+    w.counts = c.take<int32_t>(b * iters);
+    w.bestm = c.take<int32_t>(b * iters);
+    w.losses = c.take<double>(b * iters);
+    w.idx = c.take<int32_t>(b * maxN);
+    w.rm = c.take<uint8_t>(b * maxN);
+    w.total = c.off;
     return w;
 }
 
@@ -763,7 +659,7 @@ size_t mfr_emat_workspace_bytes(int B, int maxN, int max_iters)
 {
     if (B <= 0 || maxN <= 0) return 0;
     if (max_iters < 1) max_iters = 1;
-    return em_ws_layout(B, maxN, max_iters).total;
+    return em_ws(nullptr, B, maxN, max_iters).total;
 }
 
 // host: the table of the normalised MAGSAC++ loss and IRLS weight (lut[2 j], lut[2 j + 1]) over u_j = j / M = r^2 / (k sigma_max)^2,
@@ -807,15 +703,12 @@ int mfr_emat_solve_batch(const float *pts0, const float *pts1, const int32_t *n_
     if (!magsac && score_method != MFR_EMAT_SCORE_COUNT) return MFR_E_ARG;
     if (magsac && (!magsac_lut || lut_m < 2 || lut_m > MAGSAC_MAX_M || !(max_thr_ratio >= 1.0))) return MFR_E_ARG;
     if (max_iters < 1) max_iters = 1;
-    const EmWs w = em_ws_layout(B, maxN, max_iters);
+    const EmWs w = em_ws(workspace, B, maxN, max_iters);
     if (workspace_bytes < w.total) return MFR_E_WORKSPACE;
-    char *ws = (char *)workspace;
     hipStream_t s = (hipStream_t)stream;
-    double *x0 = (double *)(ws + w.x0), *x1 = (double *)(ws + w.x1), *thr2 = (double *)(ws + w.thr2);
-    double *Es = (double *)(ws + w.Es), *losses = (double *)(ws + w.losses);
-    int32_t *nsol = (int32_t *)(ws + w.nsol), *counts = (int32_t *)(ws + w.counts), *bestm = (int32_t *)(ws + w.bestm);
-    int32_t *idx = (int32_t *)(ws + w.idx);
-    uint8_t *rm = (uint8_t *)(ws + w.rm);
+    double *x0 = w.x0, *x1 = w.x1, *thr2 = w.thr2, *Es = w.Es, *losses = w.losses;
+    int32_t *nsol = w.nsol, *counts = w.counts, *bestm = w.bestm, *idx = w.idx;
+    uint8_t *rm = w.rm;
     const double ratio2 = max_thr_ratio * max_thr_ratio;
     hipLaunchKernelGGL(emat_prep_kernel, dim3((maxN + 255) / 256, B), dim3(256), 0, s, pts0, pts1, n_corr, maxN, K0, K1, k_dtype,
                        pix_thr, x0, x1, thr2);

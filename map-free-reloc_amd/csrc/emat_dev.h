@@ -3,7 +3,7 @@
 // cv.findEssentialMat / cv.recoverPose restated from the published algorithms, see emat.hip).
 // Same FP contract as geom_dev.h (binary64, + - * / sqrt only, no FMA contraction, fixed order).
 #pragma once
-#include "geom_dev.h"
+#include "solver_dev.h"
 
 namespace mfr {
 
@@ -189,6 +189,27 @@ MFR_DEV double sampson2(const double *E, double a, double b, double c, double d)
     const double num = (c * Ex0 + d * Ex1) + Ex2;
     const double den = ((Ex0 * Ex0 + Ex1 * Ex1) + Et0 * Et0) + Et1 * Et1;
     return (num * num) / den;
+}
+
+// the Sampson residual r = num / sqrt(den) of one correspondence (a, b) <-> (c, d) under E = [t]x R, and its Jacobian J[6] with respect
+// to a right rotation update (J[0..2]) and a translation update (J[3..5]); r * r = sampson2(E, a, b, c, d) up to rounding
+MFR_DEV void sampson_jac(const double *E, const double *R, const double *t, double a, double b, double c, double d, double J[6], double &r)
+{
+    const double Ex0 = (E[0] * a + E[1] * b) + E[2], Ex1 = (E[3] * a + E[4] * b) + E[5], Ex2 = (E[6] * a + E[7] * b) + E[8];
+    const double Et0 = (E[0] * c + E[3] * d) + E[6], Et1 = (E[1] * c + E[4] * d) + E[7];
+    const double num = (c * Ex0 + d * Ex1) + Ex2;
+    const double den = ((Ex0 * Ex0 + Ex1 * Ex1) + Et0 * Et0) + Et1 * Et1;
+    const double wgt = 1.0 / sqrt(den);
+    const double q[3] = { c, d, 1.0 }, p[3] = { a, b, 1.0 };
+    const double txq[3] = { t[1] * q[2] - t[2] * q[1], t[2] * q[0] - t[0] * q[2], t[0] * q[1] - t[1] * q[0] };
+    const double u[3] = { -((R[0] * txq[0] + R[3] * txq[1]) + R[6] * txq[2]),
+                          -((R[1] * txq[0] + R[4] * txq[1]) + R[7] * txq[2]),
+                          -((R[2] * txq[0] + R[5] * txq[1]) + R[8] * txq[2]) };
+    const double Rp[3] = { (R[0] * p[0] + R[1] * p[1]) + R[2] * p[2], (R[3] * p[0] + R[4] * p[1]) + R[5] * p[2],
+                           (R[6] * p[0] + R[7] * p[1]) + R[8] * p[2] };
+    J[0] = (p[1] * u[2] - p[2] * u[1]) * wgt; J[1] = (p[2] * u[0] - p[0] * u[2]) * wgt; J[2] = (p[0] * u[1] - p[1] * u[0]) * wgt;
+    J[3] = (Rp[1] * q[2] - Rp[2] * q[1]) * wgt; J[4] = (Rp[2] * q[0] - Rp[0] * q[2]) * wgt; J[5] = (Rp[0] * q[1] - Rp[1] * q[0]) * wgt;
+    r = num * wgt;
 }
 
 MFR_DEV void skew_mul(const double *t, const double *R, double *E)

@@ -23,7 +23,7 @@
 
 #include "../../include/mfr_hip.h"
 #include "zero_fill.h"
-#include "geom_dev.h"
+#include "solver_dev.h"
 
 using namespace mfr;
 
@@ -47,11 +47,7 @@ __global__ void __launch_bounds__(256) depth_min_kernel(const float *__restrict_
         const float v = d[i];
         if (v < m) m = v;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float o = __shfl_xor(m, off, 64);
-        if (o < m) m = o;
-    }
+    m = wave_min(m);
     __shared__ float sm[4];
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -84,19 +80,10 @@ __global__ void __launch_bounds__(256) pnp_lift_kernel(
     int total = 0;
     for (int start = 0; start < n; start += 256) {
         const int i = start + tid;
-        bool valid = false;
-        int u = 0, v = 0;
-        float d = 0.f;
-        if (i < n) {
-            if (pix_trunc(p0[2 * i], W, u) && pix_trunc(p0[2 * i + 1], H, v)) {   // np.int32 truncation (:186, Q1)
-                d = dm[v * W + u];                                        // :193
-                valid = d > dmin;                                         // :196 (Q6)
-            }
-        }
+        double X[3];
+        const bool valid = i < n && lift_point(p0[2 * i], p0[2 * i + 1], dm, H, W, dmin, Ki, X);   // :186-206 (Q1, Q6), :6-17
         const int m = compact256_slot(cs, valid, total);
         if (valid) {
-            double X[3];
-            backproject(u, v, d, Ki, X);                                  // :206, :6-17
             oxyz[3 * m] = X[0]; oxyz[3 * m + 1] = X[1]; oxyz[3 * m + 2] = X[2];
             oobs[2 * m] = (double)p1[2 * i]; oobs[2 * m + 1] = (double)p1[2 * i + 1];
             osrc[m] = i;
@@ -203,7 +190,7 @@ static __device__ __forceinline__ double pnp_cost(const double *X, const double 
 static __device__ __noinline__ int pnp_lm(const double *X, const double *O, const int32_t *idx, int n_idx,
                                           const double *Kd, int max_iter, double *R, double *t)
 {
-    double lambda = 1e-3;
+    LmDamping lm;
     double cost = pnp_cost(X, O, idx, n_idx, Kd, R, t);
     if (!(cost == cost) || !(cost < 1e300)) return -1;
     for (int it = 0; it < max_iter; ++it) {
@@ -246,40 +233,25 @@ static __device__ __noinline__ int pnp_lm(const double *X, const double *O, cons
         }
 #pragma unroll
         for (int q = 0; q < 27; ++q) acc[q] = wave_sum(acc[q]);
-        double Hm[36], g[6];
-        {
-            int q = 0;
-            for (int r = 0; r < 6; ++r)
-                for (int c = r; c < 6; ++c, ++q) { Hm[6 * r + c] = acc[q]; Hm[6 * c + r] = acc[q]; }
-            for (int r = 0; r < 6; ++r, ++q) g[r] = -acc[q];
-        }
-        for (int r = 0; r < 6; ++r) Hm[6 * r + r] = Hm[6 * r + r] + lambda * Hm[6 * r + r];
-        double dlt[6];
+        double Hm[36], g[6], dlt[6];
+        lm6_unpack(acc, Hm, g);
+        lm.damp(Hm);
         if (chol_solve6(Hm, g, dlt)) {
-            lambda = lambda * 10.0;
-            if (lambda > 1e12) break;
+            if (lm.reject()) break;
             continue;
         }
         double Rn[9], tn[3];
         quat_right_update(R, dlt, Rn);
         tn[0] = t[0] + dlt[3]; tn[1] = t[1] + dlt[4]; tn[2] = t[2] + dlt[5];
         const double cn = pnp_cost(X, O, idx, n_idx, Kd, Rn, tn);
-        double mx = 0.0;
-        for (int k = 0; k < 6; ++k) { const double a = dlt[k] < 0.0 ? -dlt[k] : dlt[k]; if (a > mx) mx = a; }
         if (cn < cost) {
-            const double dec = cost - cn;
             for (int k = 0; k < 9; ++k) R[k] = Rn[k];
             for (int k = 0; k < 3; ++k) t[k] = tn[k];
-            const bool done = (dec <= 1e-14 * cost);
+            const bool done = lm.accept(cost - cn, 1e-14 * cost);
             cost = cn;
-            lambda = lambda * 0.1;
-            if (lambda < 1e-12) lambda = 1e-12;
             if (done) break;
-        } else {
-            lambda = lambda * 10.0;
-            if (lambda > 1e12) break;
-        }
-        if (mx < 1e-13) break;
+        } else if (lm.reject()) break;
+        if (lm6_max_abs(dlt) < 1e-13) break;
     }
     return 0;
 }
@@ -316,35 +288,7 @@ __global__ void __launch_bounds__(64) pnp_select_kernel(
             const int s[4] = { 0, 1, 2, 3 };
             if (pnp_hypothesis(X, O, s, Kd, R, t)) { bit = 0; best = 4; run = 1; } else st = MFR_ST_NO_MODEL;
         } else {
-            // records of the running max, then sequential replay of the iteration cap
-            int niters = max_iters, carry = 3;
-            bool stop = false;
-            const int32_t *cnt = counts + (size_t)b * max_iters;
-            for (int c0 = 0; c0 < max_iters && !stop && c0 < niters; c0 += 64) {
-                const int it = c0 + lane;
-                const int v = (it < max_iters) ? cnt[it] : -1;
-                int incl = v;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const int o = __shfl_up(incl, off, 64);
-                    if (lane >= off && o > incl) incl = o;
-                }
-                int excl = __shfl_up(incl, 1, 64);
-                if (lane == 0 || excl < carry) excl = carry;
-                unsigned long long rec = __ballot(v > excl);
-                while (rec) {
-                    const int l = __ffsll((long long)rec) - 1;
-                    rec &= rec - 1;
-                    const int itr = c0 + l;
-                    if (itr >= niters) { stop = true; break; }
-                    best = __shfl(v, l, 64);
-                    bit = itr;
-                    niters = update_num_iters(conf, (double)(n - best) / (double)n, 4, niters);
-                }
-                const int last = __shfl(incl, 63, 64);
-                if (last > carry) carry = last;
-            }
-            run = (bit + 1 > niters) ? bit + 1 : niters;   // loop exit index of the sequential form
+            run = ransac_replay_counts(counts + (size_t)b * max_iters, max_iters, n, conf, 4, best, bit);
             if (bit < 0) st = MFR_ST_NO_MODEL;
             else {
                 int s[4];
@@ -359,10 +303,8 @@ __global__ void __launch_bounds__(64) pnp_select_kernel(
             const int i = i0 + lane;
             bool in = false;
             if (i < n) in = (n == 4) ? true : (reproj_err2(R, t, X + 3 * (size_t)i, O + 2 * (size_t)i, Kd) <= thr2);
-            const unsigned long long bal = __ballot(in);
-            if (in) idx[m + __popcll(bal & ((1ull << lane) - 1ull))] = i;
+            wave_compact_append(in, i, idx, m);
             if (mask_valid && i < n) mask_valid[(size_t)b * maxN + i] = in ? 1 : 0;
-            m += __popcll(bal);
         }
         __threadfence();          // idx[] written by other lanes of this wave is read below
         if (n > 4) {
@@ -436,6 +378,15 @@ __global__ void sample_kernel(uint64_t seed, const int64_t *pair_ids, int iters,
     for (int k = 0; k < K; ++k) out[((size_t)b * iters + it) * K + k] = s[k];
 }
 
+// one wavefront per row of counts: ransac_replay_counts alone (n points per row, confidence conf)
+__global__ void __launch_bounds__(64) replay_counts_kernel(const int32_t *counts, int max_iters, int n, double conf, int model_points,
+                                                           int32_t *out)
+{
+    int best, bit;
+    const int run = ransac_replay_counts(counts + (size_t)blockIdx.x * max_iters, max_iters, n, conf, model_points, best, bit);
+    if (threadIdx.x == 0) { out[3 * blockIdx.x] = best; out[3 * blockIdx.x + 1] = bit; out[3 * blockIdx.x + 2] = run; }
+}
+
 // ------------------------------------------------------------------------------------------
 // C-ABI
 extern "C" {
@@ -458,6 +409,15 @@ int mfr_test_sample(uint64_t seed, const int64_t *pair_ids, int B, int iters, in
     dim3 grid((iters + 255) / 256, B);
     if (k == 4) hipLaunchKernelGGL(sample_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, seed, pair_ids, iters, n, out);
     else hipLaunchKernelGGL(sample_kernel<5>, grid, dim3(256), 0, (hipStream_t)stream, seed, pair_ids, iters, n, out);
+    CHECK_LAUNCH();
+    return 0;
+}
+
+// test hook of the shared count replay, kept out of the public header: counts [B,max_iters] -> out [B,3] = (best, bit, run)
+int mfr_test_replay_counts(const int32_t *counts, int B, int max_iters, int n, double conf, int model_points, int32_t *out, void *stream)
+{
+    if (!counts || !out || B <= 0 || max_iters <= 0 || n < model_points || (model_points != 4 && model_points != 5)) return MFR_E_ARG;
+    hipLaunchKernelGGL(replay_counts_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, counts, max_iters, n, conf, model_points, out);
     CHECK_LAUNCH();
     return 0;
 }
@@ -517,21 +477,23 @@ int mfr_pnp_ransac(const double *xyz, const double *obs, const int32_t *n_valid,
                          counts, inl_idx, R, t, n_inliers, status, mask_valid, best_iter, iters_run, (hipStream_t)stream);
 }
 
-// workspace layout of mfr_pnp_solve_batch (all 256-B aligned)
-struct PnpWs { size_t partial, xyz, obs, src, nvalid, pre, counts, inl, maskv, total; };
-static PnpWs pnp_ws_layout(int B, int maxN, int max_iters)
+// workspace of mfr_pnp_solve_batch
+struct PnpWs { float *partial; double *xyz, *obs; int32_t *src, *nvalid, *pre, *counts, *inl; uint8_t *maskv; size_t total; };
+static PnpWs pnp_ws(void *base, int B, int maxN, int max_iters)
 {
-    PnpWs w; size_t o = 0;
-    w.partial = o; o = align_up(o + sizeof(float) * MFR_NSEG * (size_t)B, 256);
-    w.xyz = o;     o = align_up(o + sizeof(double) * 3 * (size_t)B * maxN, 256);
-    w.obs = o;     o = align_up(o + sizeof(double) * 2 * (size_t)B * maxN, 256);
-    w.src = o;     o = align_up(o + sizeof(int32_t) * (size_t)B * maxN, 256);
-    w.nvalid = o;  o = align_up(o + sizeof(int32_t) * (size_t)B, 256);
-    w.pre = o;     o = align_up(o + sizeof(int32_t) * (size_t)B, 256);
-    w.counts = o;  o = align_up(o + sizeof(int32_t) * (size_t)B * max_iters, 256);
-    w.inl = o;     o = align_up(o + sizeof(int32_t) * (size_t)B * maxN, 256);
-    w.maskv = o;   o = align_up(o + (size_t)B * maxN, 256);
-    w.total = o;
+    WsCarver c(base);
+    PnpWs w;
+    const size_t b = (size_t)B;
+    w.partial = c.take<float>(MFR_NSEG * b);
+    w.xyz = c.take<double>(3 * b * maxN);
+    w.obs = c.take<double>(2 * b * maxN);
+    w.src = c.take<int32_t>(b * maxN);
+    w.nvalid = c.take<int32_t>(b);
+    w.pre = c.take<int32_t>(b);
+    w.counts = c.take<int32_t>(b * max_iters);
+    w.inl = c.take<int32_t>(b * maxN);
+    w.maskv = c.take<uint8_t>(b * maxN);
+    w.total = c.off;
     return w;
 }
 
@@ -539,7 +501,7 @@ size_t mfr_pnp_workspace_bytes(int B, int maxN, int max_iters)
 {
     if (B <= 0 || maxN <= 0) return 0;
     if (max_iters < 1) max_iters = 1;
-    return pnp_ws_layout(B, maxN, max_iters).total;
+    return pnp_ws(nullptr, B, maxN, max_iters).total;
 }
 
 int mfr_pnp_solve_batch(const float *pts0, const float *pts1, const int32_t *n_corr, int B, int maxN,
@@ -551,28 +513,22 @@ int mfr_pnp_solve_batch(const float *pts0, const float *pts1, const int32_t *n_c
     if (!pts0 || !pts1 || !n_corr || !depth0 || !K0 || !K1 || !pair_ids || !workspace || !R || !t || !n_inliers ||
         !status || B <= 0 || maxN <= 0 || H <= 0 || W <= 0 || !k_dtype_ok(k_dtype)) return MFR_E_ARG;
     if (max_iters < 1) max_iters = 1;
-    const PnpWs w = pnp_ws_layout(B, maxN, max_iters);
+    const PnpWs w = pnp_ws(workspace, B, maxN, max_iters);
     if (workspace_bytes < w.total) return MFR_E_WORKSPACE;
-    char *ws = (char *)workspace;
     hipStream_t s = (hipStream_t)stream;
-    float *partial = (float *)(ws + w.partial);
-    double *xyz = (double *)(ws + w.xyz), *obs = (double *)(ws + w.obs);
-    int32_t *src = (int32_t *)(ws + w.src), *nvalid = (int32_t *)(ws + w.nvalid), *pre = (int32_t *)(ws + w.pre);
-    int32_t *counts = (int32_t *)(ws + w.counts), *inl = (int32_t *)(ws + w.inl);
-    uint8_t *maskv = (uint8_t *)(ws + w.maskv);
 
-    int rc = mfr_depth_min(depth0, B, H, W, partial, stream);
+    int rc = mfr_depth_min(depth0, B, H, W, w.partial, stream);
     if (rc) return rc;
-    rc = mfr_pnp_lift(pts0, pts1, n_corr, B, maxN, depth0, partial, H, W, K0, k_dtype, xyz, obs, src, nvalid, stream);
+    rc = mfr_pnp_lift(pts0, pts1, n_corr, B, maxN, depth0, w.partial, H, W, K0, k_dtype, w.xyz, w.obs, w.src, w.nvalid, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(pnp_prestatus_kernel, dim3((B + 63) / 64), dim3(64), 0, s, n_corr, nvalid, B, pre);
+    hipLaunchKernelGGL(pnp_prestatus_kernel, dim3((B + 63) / 64), dim3(64), 0, s, n_corr, w.nvalid, B, w.pre);
     CHECK_LAUNCH();
-    rc = launch_ransac(xyz, obs, nvalid, pre, B, maxN, K1, k_dtype, max_iters, reproj_thr, confidence, seed, pair_ids, counts,
-                       inl, R, t, n_inliers, status, inlier_mask ? maskv : nullptr, nullptr, nullptr, s);
+    rc = launch_ransac(w.xyz, w.obs, w.nvalid, w.pre, B, maxN, K1, k_dtype, max_iters, reproj_thr, confidence, seed, pair_ids, w.counts,
+                       w.inl, R, t, n_inliers, status, inlier_mask ? w.maskv : nullptr, nullptr, nullptr, s);
     if (rc) return rc;
     if (inlier_mask) {
         if (mfr_zero_async(inlier_mask, (size_t)B * maxN, s) != hipSuccess) return MFR_E_LAUNCH;
-        hipLaunchKernelGGL(pnp_mask_scatter_kernel, dim3((maxN + 255) / 256, B), dim3(256), 0, s, maskv, src, nvalid,
+        hipLaunchKernelGGL(pnp_mask_scatter_kernel, dim3((maxN + 255) / 256, B), dim3(256), 0, s, w.maskv, w.src, w.nvalid,
                            status, maxN, inlier_mask);
         CHECK_LAUNCH();
     }

@@ -15,55 +15,10 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
-#include "geom_dev.h"
+#include "solver_dev.h"
 
 using namespace mfr;
 #define PR_TILE 512
-
-MFR_DEV void jacobi4_maxvec(double A[4][4], double q[4])
-{
-    double V[4][4];
-    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 10; ++sweep)
-        for (int p = 0; p < 3; ++p)
-            for (int r = p + 1; r < 4; ++r) {
-                const double apq = A[p][r];
-                if (apq == 0.0) continue;
-                const double theta = (A[r][r] - A[p][p]) / (2.0 * apq);
-                const double at = theta < 0.0 ? -theta : theta;
-                double t = 1.0 / (at + sqrt(theta * theta + 1.0));
-                if (theta < 0.0) t = -t;
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < 4; ++k) { const double akp = A[k][p], akq = A[k][r]; A[k][p] = c * akp - s * akq; A[k][r] = s * akp + c * akq; }
-                for (int k = 0; k < 4; ++k) { const double apk = A[p][k], aqk = A[r][k]; A[p][k] = c * apk - s * aqk; A[r][k] = s * apk + c * aqk; }
-                for (int k = 0; k < 4; ++k) { const double vkp = V[k][p], vkq = V[k][r]; V[k][p] = c * vkp - s * vkq; V[k][r] = s * vkp + c * vkq; }
-            }
-    int b = 0;
-    for (int i = 1; i < 4; ++i) if (A[i][i] > A[b][b]) b = i;
-    const double nn = sqrt(((V[0][b] * V[0][b] + V[1][b] * V[1][b]) + V[2][b] * V[2][b]) + V[3][b] * V[3][b]);
-    for (int i = 0; i < 4; ++i) q[i] = V[i][b] / nn;
-}
-
-MFR_DEV_NOINLINE void kabsch_from_moments(const double *s, double *R, double *t)
-{
-    const double n = s[0], pc[3] = { s[1] / n, s[2] / n, s[3] / n }, qc[3] = { s[4] / n, s[5] / n, s[6] / n };
-    double S[3][3];
-    for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) S[a][b] = s[7 + 3 * a + b] - n * pc[a] * qc[b];
-    double N[4][4];
-    N[0][0] = (S[0][0] + S[1][1]) + S[2][2];
-    N[0][1] = S[1][2] - S[2][1]; N[0][2] = S[2][0] - S[0][2]; N[0][3] = S[0][1] - S[1][0];
-    N[1][1] = (S[0][0] - S[1][1]) - S[2][2]; N[1][2] = S[0][1] + S[1][0]; N[1][3] = S[2][0] + S[0][2];
-    N[2][2] = (-S[0][0] + S[1][1]) - S[2][2]; N[2][3] = S[1][2] + S[2][1];
-    N[3][3] = (-S[0][0] - S[1][1]) + S[2][2];
-    for (int i = 0; i < 4; ++i) for (int j = 0; j < i; ++j) N[i][j] = N[j][i];
-    double q[4];
-    jacobi4_maxvec(N, q);
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
-    R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
-    R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
-    for (int i = 0; i < 3; ++i) t[i] = qc[i] - ((R[3 * i] * pc[0] + R[3 * i + 1] * pc[1]) + R[3 * i + 2] * pc[2]);
-}
 
 MFR_DEV double dist2(const double *R, const double *t, double p0, double p1, double p2, double q0, double q1, double q2)
 {
@@ -107,20 +62,15 @@ __global__ void __launch_bounds__(256) proc_lift_kernel(
     int total = 0;
     for (int start = 0; start < n; start += 256) {
         const int i = start + tid;
+        double a[3], c[3];
         bool valid = false;
-        int u0 = 0, v0 = 0, u1 = 0, v1 = 0;
-        float d0 = 0.f, d1 = 0.f;
         if (i < n) {
-            if (pix_trunc(p0[2 * i], W, u0) && pix_trunc(p0[2 * i + 1], H, v0) && pix_trunc(p1[2 * i], W, u1) &&
-                pix_trunc(p1[2 * i + 1], H, v1)) {
-                d0 = d0m[v0 * W + u0]; d1 = d1m[v1 * W + u1];
-                valid = (d0 > m0) && (d1 > m1);
-            }
+            const bool v0 = lift_point(p0[2 * i], p0[2 * i + 1], d0m, H, W, m0, Ki0, a);
+            const bool v1 = lift_point(p1[2 * i], p1[2 * i + 1], d1m, H, W, m1, Ki1, c);
+            valid = v0 && v1;
         }
         const int m = compact256_slot(cs, valid, total);
         if (valid) {
-            double a[3], c[3];
-            backproject(u0, v0, d0, Ki0, a); backproject(u1, v1, d1, Ki1, c);
             oP[3 * m] = a[0]; oP[3 * m + 1] = a[1]; oP[3 * m + 2] = a[2];
             oQ[3 * m] = c[0]; oQ[3 * m + 1] = c[1]; oQ[3 * m + 2] = c[2];
         }
@@ -245,9 +195,7 @@ __global__ void __launch_bounds__(64) proc_select_kernel(
                 const int i = i0 + lane;
                 const bool in = (i < n) && (dist2(R, t, Pb[3 * (size_t)i], Pb[3 * (size_t)i + 1], Pb[3 * (size_t)i + 2],
                                                   Qb[3 * (size_t)i], Qb[3 * (size_t)i + 1], Qb[3 * (size_t)i + 2]) < thr2);
-                const unsigned long long bal = __ballot(in);
-                if (in) idx[m + __popcll(bal & ((1ull << lane) - 1ull))] = i;
-                m += __popcll(bal);
+                wave_compact_append(in, i, idx, m);
             }
             __threadfence();
             double acc[16];
@@ -285,19 +233,21 @@ __global__ void __launch_bounds__(64) proc_select_kernel(
     }
 }
 
-struct PrWs { size_t pm0, pm1, P, Q, nvalid, counts, err2, idx, total; };
-static PrWs pr_ws_layout(int B, int maxN, int iters)
+struct PrWs { float *pm0, *pm1; double *P, *Q; int32_t *nvalid, *counts; double *err2; int32_t *idx; size_t total; };
+static PrWs pr_ws(void *base, int B, int maxN, int iters)
 {
-    PrWs w; size_t o = 0;
-    w.pm0 = o;    o = align_up(o + sizeof(float) * MFR_NSEG * (size_t)B, 256);
-    w.pm1 = o;    o = align_up(o + sizeof(float) * MFR_NSEG * (size_t)B, 256);
-    w.P = o;      o = align_up(o + sizeof(double) * 3 * (size_t)B * maxN, 256);
-    w.Q = o;      o = align_up(o + sizeof(double) * 3 * (size_t)B * maxN, 256);
-    w.nvalid = o; o = align_up(o + sizeof(int32_t) * (size_t)B, 256);
-    w.counts = o; o = align_up(o + sizeof(int32_t) * (size_t)B * iters, 256);
-    w.err2 = o;   o = align_up(o + sizeof(double) * (size_t)B * iters, 256);
-    w.idx = o;    o = align_up(o + sizeof(int32_t) * (size_t)B * maxN, 256);
-    w.total = o;
+    WsCarver c(base);
+    PrWs w;
+    const size_t b = (size_t)B;
+    w.pm0 = c.take<float>(MFR_NSEG * b);
+    w.pm1 = c.take<float>(MFR_NSEG * b);
+    w.P = c.take<double>(3 * b * maxN);
+    w.Q = c.take<double>(3 * b * maxN);
+    w.nvalid = c.take<int32_t>(b);
+    w.counts = c.take<int32_t>(b * iters);
+    w.err2 = c.take<double>(b * iters);
+    w.idx = c.take<int32_t>(b * maxN);
+    w.total = c.off;
     return w;
 }
 
@@ -307,7 +257,7 @@ size_t mfr_procrustes_workspace_bytes(int B, int maxN, int max_iters)
 {
     if (B <= 0 || maxN <= 0) return 0;
     if (max_iters < 1) max_iters = 1;
-    return pr_ws_layout(B, maxN, max_iters).total;
+    return pr_ws(nullptr, B, maxN, max_iters).total;
 }
 
 int mfr_procrustes_solve_batch(const float *pts0, const float *pts1, const int32_t *n_corr, int B, int maxN,
@@ -319,13 +269,12 @@ int mfr_procrustes_solve_batch(const float *pts0, const float *pts1, const int32
     if (!pts0 || !pts1 || !n_corr || !depth0 || !depth1 || !K0 || !K1 || !pair_ids || !workspace || !R || !t || !n_inliers ||
         !status || B <= 0 || maxN <= 0 || H <= 0 || W <= 0 || !(max_corr_dist > 0.0) || !k_dtype_ok(k_dtype)) return MFR_E_ARG;
     if (max_iters < 1) max_iters = 1;
-    const PrWs w = pr_ws_layout(B, maxN, max_iters);
+    const PrWs w = pr_ws(workspace, B, maxN, max_iters);
     if (workspace_bytes < w.total) return MFR_E_WORKSPACE;
-    char *ws = (char *)workspace;
     hipStream_t s = (hipStream_t)stream;
-    float *pm0 = (float *)(ws + w.pm0), *pm1 = (float *)(ws + w.pm1);
-    double *P = (double *)(ws + w.P), *Q = (double *)(ws + w.Q), *err2 = (double *)(ws + w.err2);
-    int32_t *nvalid = (int32_t *)(ws + w.nvalid), *counts = (int32_t *)(ws + w.counts), *idx = (int32_t *)(ws + w.idx);
+    float *pm0 = w.pm0, *pm1 = w.pm1;
+    double *P = w.P, *Q = w.Q, *err2 = w.err2;
+    int32_t *nvalid = w.nvalid, *counts = w.counts, *idx = w.idx;
     int rc = mfr_depth_min(depth0, B, H, W, pm0, stream);
     if (rc) return rc;
     rc = mfr_depth_min(depth1, B, H, W, pm1, stream);

@@ -23,57 +23,11 @@
 
 #include "../../include/mfr_hip.h"
 #include "zero_fill.h"
-#include "geom_dev.h"
+#include "solver_dev.h"
 
 using namespace mfr;
 #define ICP_NACC 17
 #define ICP_STATE 24          // doubles per pair: R[9] t[3] fit_prev rmse_prev done iters fit rmse nS nT ...
-
-// identical arithmetic to procrustes.hip / oracle kabsch_from_moments (Horn quaternion, fixed-sweep Jacobi)
-MFR_DEV void icp_jacobi4_maxvec(double A[4][4], double q[4])
-{
-    double V[4][4];
-    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 10; ++sweep)
-        for (int p = 0; p < 3; ++p)
-            for (int r = p + 1; r < 4; ++r) {
-                const double apq = A[p][r];
-                if (apq == 0.0) continue;
-                const double theta = (A[r][r] - A[p][p]) / (2.0 * apq);
-                const double at = theta < 0.0 ? -theta : theta;
-                double t = 1.0 / (at + sqrt(theta * theta + 1.0));
-                if (theta < 0.0) t = -t;
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < 4; ++k) { const double akp = A[k][p], akq = A[k][r]; A[k][p] = c * akp - s * akq; A[k][r] = s * akp + c * akq; }
-                for (int k = 0; k < 4; ++k) { const double apk = A[p][k], aqk = A[r][k]; A[p][k] = c * apk - s * aqk; A[r][k] = s * apk + c * aqk; }
-                for (int k = 0; k < 4; ++k) { const double vkp = V[k][p], vkq = V[k][r]; V[k][p] = c * vkp - s * vkq; V[k][r] = s * vkp + c * vkq; }
-            }
-    int b = 0;
-    for (int i = 1; i < 4; ++i) if (A[i][i] > A[b][b]) b = i;
-    const double nn = sqrt(((V[0][b] * V[0][b] + V[1][b] * V[1][b]) + V[2][b] * V[2][b]) + V[3][b] * V[3][b]);
-    for (int i = 0; i < 4; ++i) q[i] = V[i][b] / nn;
-}
-
-MFR_DEV_NOINLINE void icp_kabsch_from_moments(const double *s, double *R, double *t)
-{
-    const double n = s[0], pc[3] = { s[1] / n, s[2] / n, s[3] / n }, qc[3] = { s[4] / n, s[5] / n, s[6] / n };
-    double S[3][3];
-    for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) S[a][b] = s[7 + 3 * a + b] - n * pc[a] * qc[b];
-    double N[4][4];
-    N[0][0] = (S[0][0] + S[1][1]) + S[2][2];
-    N[0][1] = S[1][2] - S[2][1]; N[0][2] = S[2][0] - S[0][2]; N[0][3] = S[0][1] - S[1][0];
-    N[1][1] = (S[0][0] - S[1][1]) - S[2][2]; N[1][2] = S[0][1] + S[1][0]; N[1][3] = S[2][0] + S[0][2];
-    N[2][2] = (-S[0][0] + S[1][1]) - S[2][2]; N[2][3] = S[1][2] + S[2][1];
-    N[3][3] = (-S[0][0] - S[1][1]) + S[2][2];
-    for (int i = 0; i < 4; ++i) for (int j = 0; j < i; ++j) N[i][j] = N[j][i];
-    double q[4];
-    icp_jacobi4_maxvec(N, q);
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
-    R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
-    R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
-    for (int i = 0; i < 3; ++i) t[i] = qc[i] - ((R[3 * i] * pc[0] + R[3 * i + 1] * pc[1]) + R[3 * i + 2] * pc[2]);
-}
 
 // grid (ceil(HW/256), B)
 __global__ void __launch_bounds__(256) icp_prep_kernel(const float *__restrict__ depth0, const float *__restrict__ depth1, int HW, int W,
@@ -233,7 +187,7 @@ __global__ void __launch_bounds__(64) icp_update_kernel(const double *__restrict
         for (int j = 0; j < 16; ++j) m[j] = tot[j];
         for (int j = 0; j < 9; ++j) R[j] = st[j];
         for (int j = 0; j < 3; ++j) t[j] = st[9 + j];
-        icp_kabsch_from_moments(m, U, Ut);
+        kabsch_from_moments(m, U, Ut);
         for (int i = 0; i < 3; ++i) {
             for (int j = 0; j < 3; ++j) Rn[3 * i + j] = (U[3 * i] * R[j] + U[3 * i + 1] * R[3 + j]) + U[3 * i + 2] * R[6 + j];
             tn[i] = ((U[3 * i] * t[0] + U[3 * i + 1] * t[1]) + U[3 * i + 2] * t[2]) + Ut[i];
@@ -266,16 +220,26 @@ __global__ void __launch_bounds__(64) icp_finish_kernel(const double *__restrict
     if (iters) iters[b] = (int)st[15];
 }
 
-static inline size_t icp_align(size_t x) { return (x + 255) / 256 * 256; }
+struct IcpWs { double *Tc, *partial, *state; int32_t *cnt; size_t total; };
+static IcpWs icp_ws(void *base, int B, int H, int W)
+{
+    WsCarver c(base);
+    IcpWs w;
+    const size_t hw = (size_t)H * W, nblk = (hw + 255) / 256;
+    w.Tc = c.take<double>(3 * hw * B);
+    w.partial = c.take<double>(ICP_NACC * nblk * B);
+    w.state = c.take<double>((size_t)ICP_STATE * B);
+    w.cnt = c.take<int32_t>(2 * (size_t)B);
+    w.total = c.off;
+    return w;
+}
 
 extern "C" {
 
 size_t mfr_procrustes_icp_workspace_bytes(int B, int H, int W)
 {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    const size_t hw = (size_t)H * W, nblk = (hw + 255) / 256;
-    return icp_align(sizeof(double) * 3 * hw * B) + icp_align(sizeof(double) * ICP_NACC * nblk * B) + icp_align(sizeof(double) * ICP_STATE * B) +
-           icp_align(sizeof(int32_t) * 2 * B);
+    return icp_ws(nullptr, B, H, W).total;
 }
 
 int mfr_procrustes_icp_refine(const float *depth0, const float *depth1, int B, int H, int W, const void *K0, const void *K1, int k_dtype,
@@ -285,13 +249,11 @@ int mfr_procrustes_icp_refine(const float *depth0, const float *depth1, int B, i
 {
     if (!depth0 || !depth1 || !K0 || !K1 || !workspace || !R || !t || !n_inliers || B <= 0 || H <= 0 || W <= 0 || !(max_corr_dist > 0.0) ||
         max_iter < 0 || (size_t)H * W > 0x3fffffffu || !k_dtype_ok(k_dtype)) return MFR_E_ARG;
-    if (workspace_bytes < mfr_procrustes_icp_workspace_bytes(B, H, W)) return MFR_E_WORKSPACE;
+    const IcpWs w = icp_ws(workspace, B, H, W);
+    if (workspace_bytes < w.total) return MFR_E_WORKSPACE;
     const int HW = H * W, nblk = (HW + 255) / 256;
-    char *ws = (char *)workspace;
-    double *Tc = (double *)ws;                 ws += icp_align(sizeof(double) * 3 * (size_t)HW * B);
-    double *partial = (double *)ws;            ws += icp_align(sizeof(double) * ICP_NACC * (size_t)nblk * B);
-    double *state = (double *)ws;              ws += icp_align(sizeof(double) * ICP_STATE * B);
-    int32_t *cnt = (int32_t *)ws;
+    double *Tc = w.Tc, *partial = w.partial, *state = w.state;
+    int32_t *cnt = w.cnt;
     hipStream_t s = (hipStream_t)stream;
     if (mfr_zero_async(cnt, sizeof(int32_t) * 2 * B, s) != hipSuccess) return MFR_E_LAUNCH;
     hipLaunchKernelGGL(icp_prep_kernel, dim3(nblk, B), dim3(256), 0, s, depth0, depth1, HW, W, K1, k_dtype, R, t, status, Tc, cnt, state);

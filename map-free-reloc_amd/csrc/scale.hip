@@ -17,7 +17,7 @@
 #include <stdint.h>
 
 #include "../../include/mfr_hip.h"
-#include "geom_dev.h"
+#include "solver_dev.h"
 
 using namespace mfr;
 
@@ -52,21 +52,16 @@ __global__ void __launch_bounds__(256) scale_lift_kernel(
         bool valid = false;
         double sc = 0.0;
         if (i < n && (!mk || mk[i] == 1)) {
-            int u0, v0, u1, v1;
-            if (pix_trunc(p0[2 * i], W, u0) && pix_trunc(p0[2 * i + 1], H, v0) && pix_trunc(p1[2 * i], W, u1) &&
-                pix_trunc(p1[2 * i + 1], H, v1)) {
-                const float d0 = d0m[v0 * W + u0], d1 = d1m[v1 * W + u1];
-                if (d0 > 0.f && d1 > 0.f) {
-                    valid = true;
-                    double a[3], c[3], ra[3];
-                    backproject(u0, v0, d0, Ki0, a);
-                    backproject(u1, v1, d1, Ki1, c);
-                    ra[0] = (R[0] * a[0] + R[1] * a[1]) + R[2] * a[2];
-                    ra[1] = (R[3] * a[0] + R[4] * a[1]) + R[5] * a[2];
-                    ra[2] = (R[6] * a[0] + R[7] * a[1]) + R[8] * a[2];
-                    const double d[3] = { c[0] - ra[0], c[1] - ra[1], c[2] - ra[2] };
-                    sc = dot3(d, t);
-                }
+            double a[3], c[3], ra[3];
+            const bool v0 = lift_point(p0[2 * i], p0[2 * i + 1], d0m, H, W, 0.f, Ki0, a);
+            const bool v1 = lift_point(p1[2 * i], p1[2 * i + 1], d1m, H, W, 0.f, Ki1, c);
+            if (v0 && v1) {
+                valid = true;
+                ra[0] = (R[0] * a[0] + R[1] * a[1]) + R[2] * a[2];
+                ra[1] = (R[3] * a[0] + R[4] * a[1]) + R[5] * a[2];
+                ra[2] = (R[6] * a[0] + R[7] * a[1]) + R[8] * a[2];
+                const double d[3] = { c[0] - ra[0], c[1] - ra[1], c[2] - ra[2] };
+                sc = dot3(d, t);
             }
         }
         const int o = compact256_slot(cs, valid, total);
@@ -155,16 +150,18 @@ __global__ void scale_final_kernel(const double *__restrict__ scale, const int32
     status[b] = st;
 }
 
-struct ScaleWs { size_t scale, nscale, pcnt, pidx, total; int nchunks; };
-static ScaleWs scale_ws_layout(int B, int maxN)
+struct ScaleWs { double *scale; int32_t *nscale, *pcnt, *pidx; size_t total; int nchunks; };
+static ScaleWs scale_ws(void *base, int B, int maxN)
 {
-    ScaleWs w; size_t o = 0;
+    WsCarver c(base);
+    ScaleWs w;
+    const size_t b = (size_t)B;
     w.nchunks = (maxN + SC_BLOCK - 1) / SC_BLOCK;
-    w.scale = o;  o = align_up(o + sizeof(double) * (size_t)B * maxN, 256);
-    w.nscale = o; o = align_up(o + sizeof(int32_t) * (size_t)B, 256);
-    w.pcnt = o;   o = align_up(o + sizeof(int32_t) * (size_t)B * w.nchunks, 256);
-    w.pidx = o;   o = align_up(o + sizeof(int32_t) * (size_t)B * w.nchunks, 256);
-    w.total = o;
+    w.scale = c.take<double>(b * maxN);
+    w.nscale = c.take<int32_t>(b);
+    w.pcnt = c.take<int32_t>(b * w.nchunks);
+    w.pidx = c.take<int32_t>(b * w.nchunks);
+    w.total = c.off;
     return w;
 }
 
@@ -173,7 +170,7 @@ extern "C" {
 size_t mfr_scale_workspace_bytes(int B, int maxN)
 {
     if (B <= 0 || maxN <= 0) return 0;
-    return scale_ws_layout(B, maxN).total;
+    return scale_ws(nullptr, B, maxN).total;
 }
 
 int mfr_scale_from_depth_batch(const float *pts0, const float *pts1, const uint8_t *emat_mask,
@@ -186,12 +183,11 @@ int mfr_scale_from_depth_batch(const float *pts0, const float *pts1, const uint8
 {
     if (!pts0 || !pts1 || !n_corr || !depth0 || !depth1 || !K0 || !K1 || !R || !t || !workspace || !t_metric ||
         !best_scale || !n_inliers || !status || B <= 0 || maxN <= 0 || H <= 0 || W <= 0 || !k_dtype_ok(k_dtype)) return MFR_E_ARG;
-    const ScaleWs w = scale_ws_layout(B, maxN);
+    const ScaleWs w = scale_ws(workspace, B, maxN);
     if (workspace_bytes < w.total) return MFR_E_WORKSPACE;
-    char *ws = (char *)workspace;
     hipStream_t s = (hipStream_t)stream;
-    double *scale = (double *)(ws + w.scale);
-    int32_t *nscale = (int32_t *)(ws + w.nscale), *pcnt = (int32_t *)(ws + w.pcnt), *pidx = (int32_t *)(ws + w.pidx);
+    double *scale = w.scale;
+    int32_t *nscale = w.nscale, *pcnt = w.pcnt, *pidx = w.pidx;
     hipLaunchKernelGGL(scale_lift_kernel, dim3(B), dim3(256), 0, s, pts0, pts1, emat_mask, n_corr, maxN, depth0,
                        depth1, H, W, K0, K1, k_dtype, R, t, in_status, scale, nscale);
     CHECK_LAUNCH();

@@ -1,5 +1,5 @@
-// wave_dev.h -- the wavefront (64 lanes) and workgroup primitives the kernels share, plus the three host-side one-liners every TU
-// needs (CHECK_LAUNCH, align_up, the raw-buffer descriptor word).  gfx950.
+// wave_dev.h -- the wavefront (64 lanes) and workgroup primitives the kernels share, plus the host-side pieces every TU needs
+// (CHECK_LAUNCH, align_up and the workspace carver, the raw-buffer descriptor word).  gfx950.
 //
 // ONE definition of each: the solvers equal the CPU oracle bit for bit and the matchers compare values for equality between their row and
 // their column side, so two copies of a reduction that drift apart are a wrong result, not a style problem.
@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stddef.h>
+#include <stdint.h>
 
 #include "../../include/mfr_hip.h"
 
@@ -26,6 +27,20 @@
 namespace mfr {
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// a workspace as consecutive 256-byte-aligned arrays.  A solver states its layout ONCE, as the takes of one function: run on a null
+// base it sizes the workspace (`off` after the last take), run on the caller's buffer it hands out the same pointers
+struct WsCarver {
+    char *base;
+    size_t off = 0;
+    explicit WsCarver(void *b) : base((char *)b) {}
+    template <class T> T *take(size_t count)
+    {
+        T *p = base ? (T *)(base + off) : nullptr;
+        off = align_up(off + sizeof(T) * count, 256);
+        return p;
+    }
+};
 
 MFR_DEV int lane_id() { return (int)(threadIdx.x & 63); }
 
@@ -48,6 +63,17 @@ MFR_DEV float wave_max(float v)
 {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+// comparisons only (`if (o < v) v = o`, no fminf): the same value in every lane; a NaN never passes the test, so it is skipped like in the
+// sequential loop, unless it is the lane's own start value
+MFR_DEV float wave_min(float v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float o = __shfl_xor(v, off, 64);
+        if (o < v) v = o;
+    }
     return v;
 }
 
@@ -110,6 +136,15 @@ MFR_DEV int compact256_slot(Compact256 &c, bool valid, int &total)
     total += c.wave_cnt[0] + c.wave_cnt[1] + c.wave_cnt[2] + c.wave_cnt[3];
     __syncthreads();
     return slot;
+}
+
+// one wavefront's step of a sequential `if (in) idx[m++] = i`: the lanes whose `in` is set append their `i` in lane order; `m` (wave-uniform)
+// advances by their number.  A later read of idx[] by other lanes needs a __threadfence() first.
+MFR_DEV void wave_compact_append(bool in, int i, int32_t *__restrict__ idx, int &m)
+{
+    const unsigned long long bal = __ballot(in);
+    if (in) idx[m + __popcll(bal & ((1ull << lane_id()) - 1ull))] = i;
+    m += __popcll(bal);
 }
 
 // ---------------------------------------------------------------- precise online log-sum-exp

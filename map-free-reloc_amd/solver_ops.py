@@ -9,8 +9,10 @@ import torch
 
 from . import _lib
 
-ST_OK, ST_TOO_FEW, ST_BAD_DEPTH, ST_NO_MODEL, ST_DEGENERATE = range(5)
-NSEG = 16
+# values of include/mfr_hip.h, stated here once for the package
+ST_OK, ST_TOO_FEW, ST_BAD_DEPTH, ST_NO_MODEL, ST_DEGENERATE = range(5)      # MFR_ST_*
+K_F32, K_F64 = 0, 1                                                         # MFR_K_F32 / MFR_K_F64
+NSEG = 16                                                                   # partial minima per image of mfr_depth_min
 
 
 def _chk(t, dtype, name):
@@ -19,9 +21,6 @@ def _chk(t, dtype, name):
     if t.dtype != dtype:
         raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
     return t.contiguous()
-
-
-K_F32, K_F64 = 0, 1        # include/mfr_hip.h MFR_K_F32 / MFR_K_F64
 
 
 def _chk_K(K0, K1=None):
@@ -39,8 +38,32 @@ def _chk_K(K0, K1=None):
     return out[0], out[1], (K_F64 if dt == torch.float64 else K_F32)
 
 
-def _ws(nbytes, device):
-    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+def _chk_corr(pts0, pts1, n_corr):
+    """the correspondence triple every solver takes -> (pts0, pts1, n_corr, B, maxN, device)"""
+    pts0 = _chk(pts0, torch.float32, "pts0"); pts1 = _chk(pts1, torch.float32, "pts1")
+    n_corr = _chk(n_corr, torch.int32, "n_corr")
+    B, maxN, _ = pts0.shape
+    return pts0, pts1, n_corr, B, maxN, pts0.device
+
+
+def _pose_out(B, dev):
+    """R [B,3,3] f64, t [B,3] f64, n_inliers [B] i32, status [B] i32"""
+    return (torch.empty(B, 3, 3, dtype=torch.float64, device=dev), torch.empty(B, 3, dtype=torch.float64, device=dev),
+            torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+
+
+def _i32(dev, *shape):
+    return torch.empty(*shape, dtype=torch.int32, device=dev)
+
+
+class _Workspace:
+    """what the batched ops share: a grow-only scratch buffer, replaced when the device changes"""
+    _buf = None
+
+    def _ws(self, nbytes, dev):
+        if self._buf is None or self._buf.numel() < nbytes or self._buf.device != dev:
+            self._buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+        return self._buf
 
 
 def depth_min_partials(depth):
@@ -56,12 +79,10 @@ def depth_min_partials(depth):
 def pnp_lift(pts0, pts1, n_corr, depth0, K0):
     """pose_solver.py:186-206: returns xyz [B,maxN,3] f64, obs [B,maxN,2] f64, src_idx, n_valid."""
     lib = _lib.load(require_gpu=True)
-    pts0 = _chk(pts0, torch.float32, "pts0"); pts1 = _chk(pts1, torch.float32, "pts1")
-    n_corr = _chk(n_corr, torch.int32, "n_corr"); depth0 = _chk(depth0, torch.float32, "depth0")
+    pts0, pts1, n_corr, B, maxN, dev = _chk_corr(pts0, pts1, n_corr)
+    depth0 = _chk(depth0, torch.float32, "depth0")
     K0, _, kdt = _chk_K(K0)
-    B, maxN, _ = pts0.shape
     _, H, W = depth0.shape
-    dev = pts0.device
     part = depth_min_partials(depth0)
     xyz = torch.zeros(B, maxN, 3, dtype=torch.float64, device=dev)
     obs = torch.zeros(B, maxN, 2, dtype=torch.float64, device=dev)
@@ -83,15 +104,10 @@ def pnp_ransac(xyz, obs, n_valid, K1, pair_ids, max_iters=1000, thr=3.0, conf=0.
     B, maxN, _ = xyz.shape
     dev = xyz.device
     max_iters = max(int(max_iters), 1)
-    counts = torch.empty(B, max_iters, dtype=torch.int32, device=dev)
-    inl = torch.empty(B, maxN, dtype=torch.int32, device=dev)
-    R = torch.empty(B, 3, 3, dtype=torch.float64, device=dev)
-    t = torch.empty(B, 3, dtype=torch.float64, device=dev)
-    ni = torch.empty(B, dtype=torch.int32, device=dev)
-    st = torch.empty(B, dtype=torch.int32, device=dev)
+    counts, inl = _i32(dev, B, max_iters), _i32(dev, B, maxN)
+    R, t, ni, st = _pose_out(B, dev)
     mask = torch.empty(B, maxN, dtype=torch.uint8, device=dev)
-    bi = torch.empty(B, dtype=torch.int32, device=dev)
-    ir = torch.empty(B, dtype=torch.int32, device=dev)
+    bi, ir = _i32(dev, B), _i32(dev, B)
     _lib.check(lib.mfr_pnp_ransac(_lib.ptr(xyz), _lib.ptr(obs), _lib.ptr(n_valid), B, maxN, _lib.ptr(K1), kdt, max_iters,
                                   float(thr), float(conf), int(seed), _lib.ptr(pair_ids), _lib.ptr(counts),
                                   _lib.ptr(inl), _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(st), _lib.ptr(mask),
@@ -99,7 +115,7 @@ def pnp_ransac(xyz, obs, n_valid, K1, pair_ids, max_iters=1000, thr=3.0, conf=0.
     return dict(R=R, t=t, n_inliers=ni, status=st, mask=mask, best_iter=bi, iters_run=ir, counts=counts)
 
 
-class PnPBatchSolver:
+class PnPBatchSolver(_Workspace):
     """PnPSolver.estimate_pose (pose_solver.py:184-235) for a batch of pairs, one C-ABI call."""
 
     def __init__(self, max_iters=1000, reproj_thr=3.0, confidence=0.9999, seed=0):
@@ -107,29 +123,21 @@ class PnPBatchSolver:
         self.reproj_thr = float(reproj_thr)
         self.confidence = float(confidence)
         self.seed = int(seed)
-        self._ws = None
 
     def __call__(self, pts0, pts1, n_corr, depth0, K0, K1, pair_ids, want_mask=False):
         lib = _lib.load(require_gpu=True)
-        pts0 = _chk(pts0, torch.float32, "pts0"); pts1 = _chk(pts1, torch.float32, "pts1")
-        n_corr = _chk(n_corr, torch.int32, "n_corr"); depth0 = _chk(depth0, torch.float32, "depth0")
+        pts0, pts1, n_corr, B, maxN, dev = _chk_corr(pts0, pts1, n_corr)
+        depth0 = _chk(depth0, torch.float32, "depth0")
         K0, K1, kdt = _chk_K(K0, K1)
         pair_ids = _chk(pair_ids, torch.int64, "pair_ids")
-        B, maxN, _ = pts0.shape
         _, H, W = depth0.shape
-        dev = pts0.device
-        need = lib.mfr_pnp_workspace_bytes(B, maxN, self.max_iters)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = _ws(need, dev)
-        R = torch.empty(B, 3, 3, dtype=torch.float64, device=dev)
-        t = torch.empty(B, 3, dtype=torch.float64, device=dev)
-        ni = torch.empty(B, dtype=torch.int32, device=dev)
-        st = torch.empty(B, dtype=torch.int32, device=dev)
+        ws = self._ws(lib.mfr_pnp_workspace_bytes(B, maxN, self.max_iters), dev)
+        R, t, ni, st = _pose_out(B, dev)
         mask = torch.empty(B, maxN, dtype=torch.uint8, device=dev) if want_mask else None
         _lib.check(lib.mfr_pnp_solve_batch(
             _lib.ptr(pts0), _lib.ptr(pts1), _lib.ptr(n_corr), B, maxN, _lib.ptr(depth0), H, W, _lib.ptr(K0),
             _lib.ptr(K1), kdt, self.max_iters, self.reproj_thr, self.confidence, self.seed, _lib.ptr(pair_ids),
-            _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(st),
+            _lib.ptr(ws), ws.numel(), _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(st),
             _lib.ptr(mask), _lib.stream_ptr()), "mfr_pnp_solve_batch")
         out = dict(R=R, t=t, n_inliers=ni, status=st)
         if want_mask:
@@ -149,7 +157,7 @@ def magsac_lut_host(M=MAGSAC_LUT_M):
     return t
 
 
-class EssentialBatchSolver:
+class EssentialBatchSolver(_Workspace):
     """EssentialMatrixSolver.estimate_pose (pose_solver.py:29-61) for a batch of pairs.  score 'magsac' (default) = what the
     reference asks OpenCV for (cv.USAC_MAGSAC, :46-48): MAGSAC++ model quality + sigma-consensus++; 'count' = inlier count + LM
     polish (rounds 1-3, kept for A/B)."""
@@ -162,7 +170,6 @@ class EssentialBatchSolver:
         self.pix_thr, self.confidence = float(pix_thr), float(confidence)
         self.seed, self.max_iters = int(seed), max(int(max_iters), 1)
         self.score, self.max_thr_ratio = EMAT_SCORE[score], float(max_thr_ratio)
-        self._ws = None
         self._lut = None
 
     def _table(self, dev):
@@ -172,31 +179,21 @@ class EssentialBatchSolver:
 
     def __call__(self, pts0, pts1, n_corr, K0, K1, pair_ids, diagnostics=False):
         lib = _lib.load(require_gpu=True)
-        pts0 = _chk(pts0, torch.float32, "pts0"); pts1 = _chk(pts1, torch.float32, "pts1")
-        n_corr = _chk(n_corr, torch.int32, "n_corr")
+        pts0, pts1, n_corr, B, maxN, dev = _chk_corr(pts0, pts1, n_corr)
         K0, K1, kdt = _chk_K(K0, K1)
         pair_ids = _chk(pair_ids, torch.int64, "pair_ids")
-        B, maxN, _ = pts0.shape
-        dev = pts0.device
-        need = lib.mfr_emat_workspace_bytes(B, maxN, self.max_iters)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = _ws(need, dev)
+        ws = self._ws(lib.mfr_emat_workspace_bytes(B, maxN, self.max_iters), dev)
         lut = self._table(dev) if self.score == 0 else None
-        R = torch.empty(B, 3, 3, dtype=torch.float64, device=dev)
-        t = torch.empty(B, 3, dtype=torch.float64, device=dev)
-        ni = torch.empty(B, dtype=torch.int32, device=dev)
-        st = torch.empty(B, dtype=torch.int32, device=dev)
+        R, t, ni, st = _pose_out(B, dev)
         mask = torch.empty(B, maxN, dtype=torch.uint8, device=dev)
         bi = ir = cnt = los = lo = None
         if diagnostics:
-            bi = torch.empty(B, dtype=torch.int32, device=dev); ir = torch.empty(B, dtype=torch.int32, device=dev)
-            lo = torch.empty(B, dtype=torch.int32, device=dev)
-            cnt = torch.empty(B, self.max_iters, dtype=torch.int32, device=dev)
+            bi, ir, lo, cnt = _i32(dev, B), _i32(dev, B), _i32(dev, B), _i32(dev, B, self.max_iters)
             los = torch.zeros(B, self.max_iters, dtype=torch.float64, device=dev)
         _lib.check(lib.mfr_emat_solve_batch(
             _lib.ptr(pts0), _lib.ptr(pts1), _lib.ptr(n_corr), B, maxN, _lib.ptr(K0), _lib.ptr(K1), kdt, self.pix_thr,
             self.confidence, self.max_iters, self.seed, _lib.ptr(pair_ids), self.score, _lib.ptr(lut), MAGSAC_LUT_M,
-            self.max_thr_ratio, _lib.ptr(self._ws), self._ws.numel(),
+            self.max_thr_ratio, _lib.ptr(ws), ws.numel(),
             _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(st), _lib.ptr(mask), _lib.ptr(bi), _lib.ptr(ir),
             _lib.ptr(cnt), _lib.ptr(los), _lib.ptr(lo), _lib.stream_ptr()), "mfr_emat_solve_batch")
         out = dict(R=R, t=t, n_inliers=ni, status=st, mask=mask)
@@ -205,39 +202,29 @@ class EssentialBatchSolver:
         return out
 
 
-class ProcrustesBatchSolver:
+class ProcrustesBatchSolver(_Workspace):
     """ProcrustesSolver.estimate_pose (pose_solver.py:238-320, REFINE False) for a batch of pairs."""
 
     def __init__(self, max_corr_dist=0.05, confidence=0.999, seed=0, max_iters=4096):
         self.max_corr_dist, self.confidence = float(max_corr_dist), float(confidence)
         self.seed, self.max_iters = int(seed), max(int(max_iters), 1)
-        self._ws = None
 
     def __call__(self, pts0, pts1, n_corr, depth0, depth1, K0, K1, pair_ids, diagnostics=False):
         lib = _lib.load(require_gpu=True)
-        pts0 = _chk(pts0, torch.float32, "pts0"); pts1 = _chk(pts1, torch.float32, "pts1")
-        n_corr = _chk(n_corr, torch.int32, "n_corr")
+        pts0, pts1, n_corr, B, maxN, dev = _chk_corr(pts0, pts1, n_corr)
         depth0 = _chk(depth0, torch.float32, "depth0"); depth1 = _chk(depth1, torch.float32, "depth1")
         K0, K1, kdt = _chk_K(K0, K1)
         pair_ids = _chk(pair_ids, torch.int64, "pair_ids")
-        B, maxN, _ = pts0.shape
         _, H, W = depth0.shape
-        dev = pts0.device
-        need = lib.mfr_procrustes_workspace_bytes(B, maxN, self.max_iters)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = _ws(need, dev)
-        R = torch.empty(B, 3, 3, dtype=torch.float64, device=dev)
-        t = torch.empty(B, 3, dtype=torch.float64, device=dev)
-        ni = torch.empty(B, dtype=torch.int32, device=dev)
-        st = torch.empty(B, dtype=torch.int32, device=dev)
+        ws = self._ws(lib.mfr_procrustes_workspace_bytes(B, maxN, self.max_iters), dev)
+        R, t, ni, st = _pose_out(B, dev)
         bi = ir = cnt = None
         if diagnostics:
-            bi = torch.empty(B, dtype=torch.int32, device=dev); ir = torch.empty(B, dtype=torch.int32, device=dev)
-            cnt = torch.empty(B, self.max_iters, dtype=torch.int32, device=dev)
+            bi, ir, cnt = _i32(dev, B), _i32(dev, B), _i32(dev, B, self.max_iters)
         _lib.check(lib.mfr_procrustes_solve_batch(
             _lib.ptr(pts0), _lib.ptr(pts1), _lib.ptr(n_corr), B, maxN, _lib.ptr(depth0), _lib.ptr(depth1), H, W, _lib.ptr(K0),
             _lib.ptr(K1), kdt, self.max_corr_dist, self.confidence, self.max_iters, self.seed, _lib.ptr(pair_ids),
-            _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(st), _lib.ptr(bi),
+            _lib.ptr(ws), ws.numel(), _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(st), _lib.ptr(bi),
             _lib.ptr(ir), _lib.ptr(cnt), _lib.stream_ptr()), "mfr_procrustes_solve_batch")
         out = dict(R=R, t=t, n_inliers=ni, status=st)
         if diagnostics:
@@ -245,14 +232,13 @@ class ProcrustesBatchSolver:
         return out
 
 
-class ProcrustesIcpRefine:
+class ProcrustesIcpRefine(_Workspace):
     """PROCRUSTES.REFINE (pose_solver.py:290-319): whole-cloud point-to-point ICP from the RANSAC transform, for a batch of
     pairs (csrc/procrustes_icp.hip).  R [B,3,3], t [B,3] f64 are refined IN PLACE; returns n_inliers / fitness / rmse / iters."""
 
     def __init__(self, max_corr_dist=0.05, rel_fitness=1e-4, rel_rmse=1e-4, max_iter=30):
         self.max_corr_dist, self.rel_fitness, self.rel_rmse = float(max_corr_dist), float(rel_fitness), float(rel_rmse)
         self.max_iter = int(max_iter)
-        self._ws = None
 
     def __call__(self, depth0, depth1, K0, K1, R, t, status=None):
         lib = _lib.load(require_gpu=True)
@@ -263,30 +249,25 @@ class ProcrustesIcpRefine:
             status = _chk(status, torch.int32, "status")
         B, H, W = depth0.shape
         dev = depth0.device
-        need = lib.mfr_procrustes_icp_workspace_bytes(B, H, W)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = _ws(need, dev)
-        ni = torch.empty(B, dtype=torch.int32, device=dev)
+        ws = self._ws(lib.mfr_procrustes_icp_workspace_bytes(B, H, W), dev)
+        ni, it = _i32(dev, B), _i32(dev, B)
         fit = torch.empty(B, dtype=torch.float64, device=dev); rm = torch.empty(B, dtype=torch.float64, device=dev)
-        it = torch.empty(B, dtype=torch.int32, device=dev)
         _lib.check(lib.mfr_procrustes_icp_refine(_lib.ptr(depth0), _lib.ptr(depth1), B, H, W, _lib.ptr(K0), _lib.ptr(K1), kdt, self.max_corr_dist,
-                                                 self.rel_fitness, self.rel_rmse, self.max_iter, _lib.ptr(status), _lib.ptr(self._ws),
-                                                 self._ws.numel(), _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(fit), _lib.ptr(rm),
+                                                 self.rel_fitness, self.rel_rmse, self.max_iter, _lib.ptr(status), _lib.ptr(ws),
+                                                 ws.numel(), _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(fit), _lib.ptr(rm),
                                                  _lib.ptr(it), _lib.stream_ptr()), "mfr_procrustes_icp_refine")
         return dict(R=R, t=t, n_inliers=ni, fitness=fit, rmse=rm, iters=it)
 
 
-class ScaleFromDepthBatch:
+class ScaleFromDepthBatch(_Workspace):
     """EssentialMatrixMetricSolver's own part (pose_solver.py:137-172) for a batch of pairs."""
 
     def __init__(self, scale_thr=0.1):
         self.scale_thr = float(scale_thr)
-        self._ws = None
 
     def __call__(self, pts0, pts1, emat_mask, n_corr, depth0, depth1, K0, K1, R, t, in_status=None):
         lib = _lib.load(require_gpu=True)
-        pts0 = _chk(pts0, torch.float32, "pts0"); pts1 = _chk(pts1, torch.float32, "pts1")
-        n_corr = _chk(n_corr, torch.int32, "n_corr")
+        pts0, pts1, n_corr, B, maxN, dev = _chk_corr(pts0, pts1, n_corr)
         depth0 = _chk(depth0, torch.float32, "depth0"); depth1 = _chk(depth1, torch.float32, "depth1")
         K0, K1, kdt = _chk_K(K0, K1)
         R = _chk(R, torch.float64, "R"); t = _chk(t, torch.float64, "t")
@@ -294,20 +275,15 @@ class ScaleFromDepthBatch:
             emat_mask = _chk(emat_mask, torch.uint8, "emat_mask")
         if in_status is not None:
             in_status = _chk(in_status, torch.int32, "in_status")
-        B, maxN, _ = pts0.shape
         _, H, W = depth0.shape
-        dev = pts0.device
-        need = lib.mfr_scale_workspace_bytes(B, maxN)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = _ws(need, dev)
+        ws = self._ws(lib.mfr_scale_workspace_bytes(B, maxN), dev)
         tm = torch.empty(B, 3, dtype=torch.float64, device=dev)
         bs = torch.empty(B, dtype=torch.float64, device=dev)
-        ni = torch.empty(B, dtype=torch.int32, device=dev)
-        st = torch.empty(B, dtype=torch.int32, device=dev)
+        ni, st = _i32(dev, B), _i32(dev, B)
         _lib.check(lib.mfr_scale_from_depth_batch(
             _lib.ptr(pts0), _lib.ptr(pts1), _lib.ptr(emat_mask), _lib.ptr(n_corr), B, maxN, _lib.ptr(depth0),
             _lib.ptr(depth1), H, W, _lib.ptr(K0), _lib.ptr(K1), kdt, _lib.ptr(R), _lib.ptr(t), _lib.ptr(in_status),
-            self.scale_thr, _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(tm), _lib.ptr(bs), _lib.ptr(ni),
+            self.scale_thr, _lib.ptr(ws), ws.numel(), _lib.ptr(tm), _lib.ptr(bs), _lib.ptr(ni),
             _lib.ptr(st), _lib.stream_ptr()), "mfr_scale_from_depth_batch")
         return dict(t_metric=tm, best_scale=bs, n_inliers=ni, status=st)
 
@@ -328,4 +304,19 @@ def test_sample(seed, pair_ids, iters, n, k):
     out = torch.empty(B, iters, k, dtype=torch.int32, device=pair_ids.device)
     _lib.check(lib.mfr_test_sample(int(seed), _lib.ptr(pair_ids), B, iters, n, k, _lib.ptr(out), _lib.stream_ptr()),
                "mfr_test_sample")
+    return out
+
+
+def test_replay_counts(counts, n, conf, model_points):
+    """ransac_replay_counts (csrc/solver_dev.h) alone: counts [B,max_iters] i32 -> [B,3] i32 (best, bit, run).  A test hook the public
+    header does not declare, so it is bound here."""
+    import ctypes as C
+    lib = _lib.load(require_gpu=True)
+    fn = lib.mfr_test_replay_counts
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
+    counts = _chk(counts, torch.int32, "counts")
+    B, max_iters = counts.shape
+    out = _i32(counts.device, B, 3)
+    _lib.check(fn(_lib.ptr(counts), B, max_iters, int(n), float(conf), int(model_points), _lib.ptr(out), _lib.stream_ptr()),
+               "mfr_test_replay_counts")
     return out
