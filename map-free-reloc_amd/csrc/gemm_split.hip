@@ -82,19 +82,68 @@ __device__ __forceinline__ void gb_xsplit_store(uint4 *lds, const float4 &p, con
 
 // the partial products of one 16-wide K block into the 2 x 2 accumulator tiles, small terms first; a: X terms, b: W terms
 #define GB_MFMA_BF(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-template <bool F16>
+// SWAP (mlp_ln_kernel, phase 1): the W fragment is the MFMA's first operand -- acc[fi][rj] holds features along the registers, rows along the lanes
+template <bool F16, bool SWAP>
 __device__ __forceinline__ void gb_products(f32x16 (&acc)[2][2], const GbFrag (&a)[2][3], const GbFrag (&b)[2][3])
 {
 #define GB_P4(ta, tb) do { \
-        if (F16) { acc[0][0] = SF_MFMA(a[0][ta].q, b[0][tb].q, acc[0][0]); acc[0][1] = SF_MFMA(a[0][ta].q, b[1][tb].q, acc[0][1]); \
-                   acc[1][0] = SF_MFMA(a[1][ta].q, b[0][tb].q, acc[1][0]); acc[1][1] = SF_MFMA(a[1][ta].q, b[1][tb].q, acc[1][1]); } \
-        else     { acc[0][0] = GB_MFMA_BF(a[0][ta].v, b[0][tb].v, acc[0][0]); acc[0][1] = GB_MFMA_BF(a[0][ta].v, b[1][tb].v, acc[0][1]); \
-                   acc[1][0] = GB_MFMA_BF(a[1][ta].v, b[0][tb].v, acc[1][0]); acc[1][1] = GB_MFMA_BF(a[1][ta].v, b[1][tb].v, acc[1][1]); } } while (0)
+        _Pragma("unroll") for (int i = 0; i < 2; ++i) \
+            _Pragma("unroll") for (int j = 0; j < 2; ++j) { \
+                const GbFrag &p = SWAP ? b[i][tb] : a[i][ta], &q = SWAP ? a[j][ta] : b[j][tb]; \
+                if (F16) acc[i][j] = SF_MFMA(p.q, q.q, acc[i][j]); else acc[i][j] = GB_MFMA_BF(p.v, q.v, acc[i][j]); } } while (0)
     if (F16) { GB_P4(1, 2); GB_P4(0, 1); GB_P4(0, 0); }                              // xl wq, xh wl, xh wh
     else     { GB_P4(1, 1); GB_P4(0, 2); GB_P4(2, 0); GB_P4(0, 1); GB_P4(1, 0); GB_P4(0, 0); }
 #undef GB_P4
 }
 #define GB_XT(F16) ((F16) ? 2 : 3)
+
+// ---- tile geometry, K step, guard: ONE definition for every kernel of this file ---------------------------------------------------------------
+// Macros where the text lands in a kernel's K loop or epilogue: hipcc's register allocation and schedule of these kernels move with ANY helper
+// function there, even one inlined at once (the accumulator zeroing, the fragment rows or the K step as a function each change the code of all
+// 14 gemm_split_d_kernel instantiations, register counts included); a macro is the token stream of the hand-written code.  Functions where the
+// code stays the same (gb_products, gb_wdst, gb_xload).  The macros use the kernel's own names (tid, lane, wm, wn, lds, arow, brow, XT, WT).
+// accumulator register r of MFMA tile (i, j) of a wavefront: tile row 64 wm + 32 i + (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column 64 wn + 32 j + (lane & 31)
+#define GB_ACC_ROW(i, r) (32 * (i) + ((r) & 3) + 8 * ((r) >> 2))                                       /* without the wavefront / lane part */
+#define GB_TILE_ROW(base, i, r) ((base) + 32 * (i) + ((r) & 3) + 8 * ((r) >> 2) + 4 * (lane >> 5))    /* base: ... + 64 wm */
+// fragment addresses: operand row (token / feature) = 64 w + 32 t + (lane & 31), k group = 2 ks + (lane >> 5); kg_stride: 16-byte units per k group
+#define GB_FRAG_ROW(w, kg_stride) ((lane >> 5) * (kg_stride) + 64 * (w) + (lane & 31))
+// X staging: unit u = tid + 256 i -> (row = u >> 2, k group = u & 3), 8 floats = two 16-byte loads; GB_XSRC: where unit i of row block mb starts
+// (rows beyond M: a valid row is read and its results are never stored)
+#define GB_XSTAGE() \
+    int xdst[2], xr[2], xk[2]; \
+    _Pragma("unroll") for (int i = 0; i < 2; ++i) { \
+        const int u = tid + 256 * i; \
+        xr[i] = u >> 2; xk[i] = 8 * (u & 3); \
+        xdst[i] = (u & 3) * GB_KG_STRIDE + xr[i]; \
+    }
+#define GB_XSRC(mb, i) (X + (size_t)min((mb) * GB_BM + xr[i], M - 1) * ldx + xk[i])
+// register-staged W: unit u = tid + 256 i, i = 0 .. 2 WT - 1 -> straight copy of the packed tile image (term, k group, feature) behind the X terms
+__device__ __forceinline__ int gb_wdst(int tid, int i, int xt)
+{
+    const int u = tid + 256 * i, term = u / 512, kg = (u % 512) / 128, f = u % 128;
+    return (xt + term) * GB_TERM_UNITS + kg * GB_KG_STRIDE + f;
+}
+// one K step of 32 on the staged operands: the A / B fragments of its two k groups (wq formed here) and their products.  WIDX: the W unit of
+// (term t, k group 2 ks, tile i) -- GB_WIDX_REG: register-staged (padded like X, behind the X terms); GD_WIDX(P): LDS-DMA stage P (the packed image as it is)
+#define GB_WIDX_REG ((XT + t) * GB_TERM_UNITS + 2 * ks * GB_KG_STRIDE + brow + 32 * i)
+#define GB_MMA_KSTEP(acc, SWAP, WIDX) do { \
+        _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) { \
+            GbFrag a[2][3], b[2][3]; \
+            _Pragma("unroll") for (int i = 0; i < 2; ++i) { \
+                _Pragma("unroll") for (int t = 0; t < XT; ++t) a[i][t].q = lds[t * GB_TERM_UNITS + 2 * ks * GB_KG_STRIDE + arow + 32 * i]; \
+                _Pragma("unroll") for (int t = 0; t < WT; ++t) b[i][t].q = lds[WIDX]; \
+                if (F16) b[i][2].q = gb_wq(b[i][0].q); } \
+            gb_products<F16, SWAP>(acc, a, b); } } while (0)
+#define GB_ZERO(acc) do { \
+        _Pragma("unroll") for (int i = 0; i < 2; ++i) \
+            _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) \
+                _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[i][jj][r] = 0.f; } while (0)
+// range guard (guard.h): an out-of-range x[m, k] makes EVERY accumulator of output row m non-finite, so one column per row is enough:
+// column block jj = 0 of every (i, r) covers the tile's 128 rows (lanes / the two wn wavefronts repeat them)
+#define GB_GUARD_ROWS(acc, chk) do { \
+        _Pragma("unroll") for (int i = 0; i < 2; ++i) \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) MFR_GUARD_ACC(chk, acc[i][0][r]); \
+        mfr_guard_commit(guard, chk); } while (0)
 // batched launches (gridDim.y problems that share shapes: the matchers' score / similarity products, one packed "weight" per pair): element
 // strides of X and Y, 16-byte-unit stride of the packed operand (its 1 / scale tail moves with it)
 #define GB_BATCH_OFFSETS() do { const size_t bz_ = blockIdx.y; X += bz_ * (size_t)xs; Wp += bz_ * (size_t)ws; Y += bz_ * (size_t)ys; if (F16) oscale += bz_ * (size_t)ws * 4; } while (0)
@@ -164,8 +213,6 @@ __global__ void __launch_bounds__(256, 2) gemm_split_kernel(const float *__restr
     const int m0 = mb * GB_BM;
     const int nkb = K / GB_BK;
 
-    // staging assignment.  X: unit u = tid + 256 i -> (row = u >> 2, k group = u & 3), 8 floats = two 16-byte loads.
-    // W: unit u = tid + 256 i, i = 0..5 -> straight copy of the packed tile image.
     const float *xrow[2];
     int xdst[2];
 #pragma unroll
@@ -177,10 +224,7 @@ __global__ void __launch_bounds__(256, 2) gemm_split_kernel(const float *__restr
     }
     int wdst[2 * WT];
 #pragma unroll
-    for (int i = 0; i < 2 * WT; ++i) {
-        const int u = tid + 256 * i, term = u / 512, kg = (u % 512) / 128, f = u % 128;
-        wdst[i] = (XT + term) * GB_TERM_UNITS + kg * GB_KG_STRIDE + f;
-    }
+    for (int i = 0; i < 2 * WT; ++i) wdst[i] = gb_wdst(tid, i, XT);
     const uint4 *wtile = Wp + (size_t)nb * nkb * GB_W_TILE_UNITS(F16) + tid;
 
     // (named registers, not arrays: hipcc keeps a lambda-captured array that is written under a condition in scratch memory)
@@ -193,16 +237,9 @@ __global__ void __launch_bounds__(256, 2) gemm_split_kernel(const float *__restr
         w0 = wt_[0]; w1 = wt_[256]; w2 = wt_[512]; w3 = wt_[768]; if (WT == 3) { w4 = wt_[1024]; w5 = wt_[1280]; } } while (0)
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    // fragment addresses: operand row (token / feature) = 64 w + 32 t + (lane & 31), k group = 2 ks + (lane >> 5)
-    const int arow = (lane >> 5) * GB_KG_STRIDE + 64 * wm + (lane & 31);
-    const int brow = (lane >> 5) * GB_KG_STRIDE + 64 * wn + (lane & 31);
+    GB_ZERO(acc);
+    const int arow = GB_FRAG_ROW(wm, GB_KG_STRIDE);
+    const int brow = GB_FRAG_ROW(wn, GB_KG_STRIDE);
 
     GB_GLOAD(0);
     for (int kb = 0; kb < nkb; ++kb) {
@@ -215,31 +252,11 @@ __global__ void __launch_bounds__(256, 2) gemm_split_kernel(const float *__restr
         // without this fence hipcc sinks the loads BELOW the MFMAs (ten live 16-byte registers fewer across them) and every K step
         // pays the full memory latency before its split: load -> wait -> split -> store -> MFMA, nothing overlapped inside a workgroup
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            GbFrag a[2][3], b[2][3];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-#pragma unroll
-                for (int t = 0; t < XT; ++t) a[i][t].q = lds[t * GB_TERM_UNITS + 2 * ks * GB_KG_STRIDE + arow + 32 * i];
-#pragma unroll
-                for (int t = 0; t < WT; ++t) b[i][t].q = lds[(XT + t) * GB_TERM_UNITS + 2 * ks * GB_KG_STRIDE + brow + 32 * i];
-                if (F16) b[i][2].q = gb_wq(b[i][0].q);
-            }
-            gb_products<F16>(acc, a, b);
-        }
+        GB_MMA_KSTEP(acc, false, GB_WIDX_REG);
     }
 #undef GB_GLOAD
 
-    if (F16 && guard) {                                     // range guard (guard.h): one column block covers the tile's rows
-        float chk = 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) MFR_GUARD_ACC(chk, acc[i][0][r]);
-        mfr_guard_commit(guard, chk);
-    }
-    // epilogue: accumulator register r of tile (i, j): token row 64 wm + 32 i + (r & 3) + 8 (r >> 2) + 4 (lane >> 5), feature 64 wn + 32 j + (lane & 31)
+    if (F16 && guard) { float chk = 0.f; GB_GUARD_ROWS(acc, chk); }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int n = nb * GB_BN + 64 * wn + 32 * j + (lane & 31);
@@ -250,7 +267,7 @@ __global__ void __launch_bounds__(256, 2) gemm_split_kernel(const float *__restr
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m0 + 64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int m = GB_TILE_ROW(m0 + 64 * wm, i, r);
                 if (m >= M) continue;
                 float *yp = Y + (size_t)m * ldy + n;
                 float v = F16 ? __builtin_fmaf(acc[i][j][r], os, bv) : acc[i][j][r] + bv;
@@ -262,6 +279,99 @@ __global__ void __launch_bounds__(256, 2) gemm_split_kernel(const float *__restr
     }
 }
 
+// ---- what the persistent kernels below share: tile walk, output tile, epilogues (macros: see above; names of the kernel: nnb, nmb, Y, ldy, M, N) -----
+// Work items of one XCD: (local row block, feature block), feature block innermost; item j of this XCD -> tile (mb, nb).  Row blocks beyond nmb do
+// not exist (they can only be the last local row block: the walk ends there).  Declares j, this workgroup's first item (none: the kernel returns),
+// and next_item(jj): the item after jj in this workgroup's walk, or jj itself at the end (the streams then re-read valid memory that is never used).
+// (gemm_split_pk_kernel steps by hand: with next_item its f16x2 instantiations measured 0.5 - 1.7 % slower, profiles/gemm_split_refactor_ab.jsonl.)
+#define GB_TILE(j, mb_, nb_) const int nb_ = (j) % nnb, mb_ = ((j) / nnb) * 8 + xcd
+#define GB_WALK() \
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd = gridDim.x >> 3; \
+    const int items = ((nmb + 7) >> 3) * nnb; \
+    int j = slot; \
+    if (j >= items) return; \
+    { GB_TILE(j, mb, nb); (void)nb; if (mb >= nmb) return; }
+#define GB_WALK_NEXT() \
+    auto next_item = [&](int jj) { int jn = jj + per_xcd; if (jn < items) { GB_TILE(jn, mbn, nbn); (void)nbn; if (mbn >= nmb) jn = items; } return jn < items ? jn : jj; }
+// a wavefront's part of output tile (row block at m0, feature block nb): the tile's rows of Y as one buffer (rows beyond M fall outside it: reads
+// return 0, stores are dropped); register r of accumulator tile (i, jj) lives at yoff + 128 jj, scalar offset GB_SOFF(i, r); n0: the thread's first column
+#define GB_YTILE(nb) \
+    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void *)(Y + (size_t)m0 * ldy), 0, (int)((unsigned)min(GB_BM, M - m0) * rowb), MFR_RSRC_FLAGS); \
+    const int n0 = (nb) * GB_BN + 64 * wn + (lane & 31); \
+    const unsigned yoff = (unsigned)(64 * wm + 4 * (lane >> 5)) * rowb + 4u * (unsigned)n0
+#define GB_SOFF(i, r) ((unsigned)GB_ACC_ROW(i, r) * rowb)                                              /* rowb: bytes per row of Y */
+// the tile of Y for the accumulating epilogues (issued during the last K step)
+#define GB_PREFETCH_Y() do { \
+        _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) \
+            _Pragma("unroll") for (int i = 0; i < 2; ++i) \
+                _Pragma("unroll") for (int r = 0; r < 16; ++r) \
+                    ov[i][jj][r] = __builtin_amdgcn_raw_buffer_load_b32(ry, yoff + 128u * jj, GB_SOFF(i, r), 0); } while (0)
+// per-column bias and scale (f16x2: 1 / scale of the feature) as buffers (no bias / bf16x3: every read returns 0) and those of the thread's two
+// columns n0, n0 + 32
+#define GB_COLS() \
+    const __amdgpu_buffer_rsrc_t rbias = __builtin_amdgcn_make_buffer_rsrc((void *)bias, 0, bias ? N * 4 : 0, MFR_RSRC_FLAGS); \
+    const __amdgpu_buffer_rsrc_t rscale = __builtin_amdgcn_make_buffer_rsrc((void *)oscale, 0, F16 ? nnb * GB_BN * 4 : 0, MFR_RSRC_FLAGS)
+#define GB_COLS_LOAD() \
+    const float bv0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rbias, 4u * (unsigned)n0, 0, 0)); \
+    const float bv1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rbias, 4u * (unsigned)n0 + 128u, 0, 0)); \
+    const float os0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rscale, 4u * (unsigned)n0, 0, 0)); \
+    const float os1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rscale, 4u * (unsigned)n0 + 128u, 0, 0))
+// the X stream's loads of one K step into a register set (named registers: see gemm_split_kernel), pointers advanced to the next step
+__device__ __forceinline__ void gb_xload(const float *&lx0, const float *&lx1, float4 &p0, float4 &p1, float4 &q0, float4 &q1)
+{
+    p0 = *(const float4 *)lx0; p1 = *(const float4 *)(lx0 + 4); q0 = *(const float4 *)lx1; q1 = *(const float4 *)(lx1 + 4);
+    lx0 += GB_BK; lx1 += GB_BK;
+}
+// Y (+)= act(acc os + bias), the columns' bv0 / bv1 / os0 / os1 of GB_COLS_LOAD; ROW_BIAS(v, i, jj, r): gemm_split_d_kernel<FLAGS & 8>'s per-window bias
+#define GB_NO_ROW_BIAS(v, i, jj, r) (void)0
+#define GB_STORE_PLAIN(acc, ROW_BIAS) do { \
+        _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) { \
+            if (n0 + 32 * jj >= N) continue; \
+            const float bv = jj ? bv1 : bv0, os = jj ? os1 : os0; \
+            _Pragma("unroll") for (int i = 0; i < 2; ++i) \
+                _Pragma("unroll") for (int r = 0; r < 16; ++r) { \
+                    float v = F16 ? __builtin_fmaf(acc[i][jj][r], os, bv) : acc[i][jj][r] + bv; \
+                    if (FLAGS & 1) v = fmaxf(v, 0.f); \
+                    if (FLAGS & 2) v += __builtin_bit_cast(float, ov[i][jj][r]); \
+                    ROW_BIAS(v, i, jj, r); \
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, yoff + 128u * jj, GB_SOFF(i, r), 0); \
+                } } } while (0)
+// Y (+)= LayerNorm (g0, g1, be0, be1, ln_eps) over the N = 128 output features of acc S + B.  Row statistics: the thread's two columns, a butterfly over the 32 lanes
+// that hold the row's other columns of this wavefront, the two wavefronts of a row exchanged through 2 KB of LDS (lnx[512], summed in the fixed
+// order wn = 0, 1); mean first, then the centred squares (the two-pass form of layernorm_kernel, loftr_fused.hip).
+#define GB_LN_ROW_SUMS(at) do { \
+        _Pragma("unroll") for (int m = 1; m <= 16; m <<= 1) \
+            _Pragma("unroll") for (int i = 0; i < 2; ++i) \
+                _Pragma("unroll") for (int r = 0; r < 16; ++r) part[i][r] += __shfl_xor(part[i][r], m, 64); \
+        if ((lane & 31) == 0) { \
+            _Pragma("unroll") for (int i = 0; i < 2; ++i) \
+                _Pragma("unroll") for (int r = 0; r < 16; ++r) lnx[(at) + wn * 128 + GB_TILE_ROW(64 * wm, i, r)] = part[i][r]; \
+        } \
+        __syncthreads(); } while (0)
+#define GB_STORE_LAYERNORM(acc, ACCUMULATE, B0, B1, S0, S1) do { \
+        float part[2][16]; \
+        _Pragma("unroll") for (int i = 0; i < 2; ++i) \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) { \
+                acc[i][0][r] = F16 ? __builtin_fmaf(acc[i][0][r], S0, B0) : acc[i][0][r] + B0; \
+                acc[i][1][r] = F16 ? __builtin_fmaf(acc[i][1][r], S1, B1) : acc[i][1][r] + B1; \
+                part[i][r] = acc[i][0][r] + acc[i][1][r]; \
+            } \
+        GB_LN_ROW_SUMS(0); \
+        _Pragma("unroll") for (int i = 0; i < 2; ++i) \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) { \
+                const float mean = (lnx[GB_TILE_ROW(64 * wm, i, r)] + lnx[128 + GB_TILE_ROW(64 * wm, i, r)]) * (1.0f / 128.0f); \
+                acc[i][0][r] -= mean; acc[i][1][r] -= mean; \
+                part[i][r] = acc[i][0][r] * acc[i][0][r] + acc[i][1][r] * acc[i][1][r]; \
+            } \
+        GB_LN_ROW_SUMS(256); \
+        _Pragma("unroll") for (int i = 0; i < 2; ++i) \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) { \
+                const float rstd = rsqrtf((lnx[256 + GB_TILE_ROW(64 * wm, i, r)] + lnx[384 + GB_TILE_ROW(64 * wm, i, r)]) * (1.0f / 128.0f) + ln_eps); \
+                float y0 = acc[i][0][r] * rstd * g0 + be0, y1 = acc[i][1][r] * rstd * g1 + be1; \
+                if (ACCUMULATE) { y0 = __builtin_bit_cast(float, ov[i][0][r]) + y0; y1 = __builtin_bit_cast(float, ov[i][1][r]) + y1; } \
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y0), ry, yoff, GB_SOFF(i, r), 0); \
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y1), ry, yoff + 128u, GB_SOFF(i, r), 0); \
+            } } while (0)
 
 // ---- round 4: PERSISTENT workgroups -------------------------------------------------------------------------------------------------------
 // Measured on the SuperGlue shapes (M = 65536; profiles/r04_bench_sg_pnp_kernel_stats.csv) the one-tile-per-workgroup kernel above takes
@@ -283,32 +393,16 @@ __global__ void __launch_bounds__(256, 2) gemm_split_pk_kernel(const float *__re
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wm = wid >> 1, wn = wid & 1;
     const int nkb = K / GB_BK;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
-    const int items = ((nmb + 7) >> 3) * nnb;               // work items of one XCD: (local row block, feature block), feature block innermost
-    // item j of this XCD -> tile; row blocks beyond nmb do not exist (they can only be the last local row block: the walk ends there)
-#define GB_TILE(j, mb_, nb_) const int nb_ = (j) % nnb, mb_ = ((j) / nnb) * 8 + xcd
-    int j = slot;
-    if (j >= items) return;
-    { GB_TILE(j, mb, nb); (void)nb; if (mb >= nmb) return; }
+    GB_WALK();
 
-    int xdst[2], xr[2], xk[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int u = tid + 256 * i;
-        xr[i] = u >> 2; xk[i] = 8 * (u & 3);
-        xdst[i] = (u & 3) * GB_KG_STRIDE + xr[i];
-    }
+    GB_XSTAGE();
     int wdst[2 * WT];
 #pragma unroll
-    for (int i = 0; i < 2 * WT; ++i) {
-        const int u = tid + 256 * i, term = u / 512, kg = (u % 512) / 128, f = u % 128;
-        wdst[i] = (XT + term) * GB_TERM_UNITS + kg * GB_KG_STRIDE + f;
-    }
-    const int arow = (lane >> 5) * GB_KG_STRIDE + 64 * wm + (lane & 31);
-    const int brow = (lane >> 5) * GB_KG_STRIDE + 64 * wn + (lane & 31);
+    for (int i = 0; i < 2 * WT; ++i) wdst[i] = gb_wdst(tid, i, XT);
+    const int arow = GB_FRAG_ROW(wm, GB_KG_STRIDE);
+    const int brow = GB_FRAG_ROW(wn, GB_KG_STRIDE);
     const unsigned rowb = (unsigned)ldy * 4u;              // bytes per row of Y
-    const __amdgpu_buffer_rsrc_t rbias = __builtin_amdgcn_make_buffer_rsrc((void *)bias, 0, bias ? N * 4 : 0, MFR_RSRC_FLAGS);   // no bias: every read returns 0
-    const __amdgpu_buffer_rsrc_t rscale = __builtin_amdgcn_make_buffer_rsrc((void *)oscale, 0, F16 ? nnb * GB_BN * 4 : 0, MFR_RSRC_FLAGS);
+    GB_COLS();
 
     // the LOAD stream runs one K step ahead of the multiply, across tile boundaries
     const float *lx0, *lx1;
@@ -316,8 +410,8 @@ __global__ void __launch_bounds__(256, 2) gemm_split_pk_kernel(const float *__re
     int lk, lj = j;                                        // K step / item the load stream is at
     auto load_tile_start = [&](int jj) {
         GB_TILE(jj, mb, nb);
-        lx0 = X + (size_t)min(mb * GB_BM + xr[0], M - 1) * ldx + xk[0];      // rows beyond M: a valid row is read, its results are never stored
-        lx1 = X + (size_t)min(mb * GB_BM + xr[1], M - 1) * ldx + xk[1];
+        lx0 = GB_XSRC(mb, 0);
+        lx1 = GB_XSRC(mb, 1);
         lw = Wp + (size_t)nb * nkb * GB_W_TILE_UNITS(F16) + tid;
         lk = 0;
     };
@@ -328,32 +422,19 @@ __global__ void __launch_bounds__(256, 2) gemm_split_pk_kernel(const float *__re
         w0 = lw[0]; w1 = lw[256]; w2 = lw[512]; w3 = lw[768]; if (WT == 3) { w4 = lw[1024]; w5 = lw[1280]; } \
         lx0 += GB_BK; lx1 += GB_BK; lw += GB_W_TILE_UNITS(F16); \
         if (++lk == nkb) { int jn = lj + per_xcd; if (jn < items) { GB_TILE(jn, mbn_, nbn_); (void)nbn_; if (mbn_ >= nmb) jn = items; } \
-                           if (jn < items) lj = jn; load_tile_start(lj); } } while (0)        /* no next tile: the last load re-reads this tile's start */
+                           if (jn < items) lj = jn; load_tile_start(lj); } } while (0)            /* no next tile: the last load re-reads this tile's start */
 
     f32x16 acc[2][2];
     unsigned ov[2][2][16];                                 // FLAGS & 2: the tile of Y fetched during the last K step
-    // accumulator register r of tile (i, jj) of a wavefront: row 32 i + (r & 3) + 8 (r >> 2) (+ 64 wm + 4 (lane >> 5): the lane offset), feature + 32 jj
-#define GB_SOFF(i, r) ((unsigned)(32 * (i) + ((r) & 3) + 8 * ((r) >> 2)) * rowb)
 
     load_tile_start(j);
     GB_PLOAD();
     for (;;) {
         GB_TILE(j, mb, nb);
         const int m0 = mb * GB_BM;
-        // this tile's rows of Y as one buffer (rows beyond M fall outside it: reads return 0, stores are dropped)
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void *)(Y + (size_t)m0 * ldy), 0, (int)((unsigned)min(GB_BM, M - m0) * rowb), MFR_RSRC_FLAGS);
-        const int n0 = nb * GB_BN + 64 * wn + (lane & 31);
-        const unsigned yoff = (unsigned)(64 * wm + 4 * (lane >> 5)) * rowb + 4u * (unsigned)n0;
-        const float bv0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rbias, 4u * (unsigned)n0, 0, 0));
-        const float bv1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rbias, 4u * (unsigned)n0 + 128u, 0, 0));
-        const float os0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rscale, 4u * (unsigned)n0, 0, 0));
-        const float os1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rscale, 4u * (unsigned)n0 + 128u, 0, 0));
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][jj][r] = 0.f;
+        GB_YTILE(nb);
+        GB_COLS_LOAD();
+        GB_ZERO(acc);
 #define GB_PSTEP(LAST) do { \
             __syncthreads(); \
             gb_xsplit_store<F16>(lds, xa0, xa1, xdst[0]); gb_xsplit_store<F16>(lds, xb0, xb1, xdst[1]); \
@@ -361,54 +442,21 @@ __global__ void __launch_bounds__(256, 2) gemm_split_pk_kernel(const float *__re
             if (WT == 3) { lds[wdst[2 * WT - 2]] = w4; lds[wdst[2 * WT - 1]] = w5; } \
             __syncthreads(); \
             GB_PLOAD(); \
-            if ((LAST) && (FLAGS & 2)) { \
-                _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) \
-                    _Pragma("unroll") for (int i = 0; i < 2; ++i) \
-                        _Pragma("unroll") for (int r = 0; r < 16; ++r) \
-                            ov[i][jj][r] = __builtin_amdgcn_raw_buffer_load_b32(ry, yoff + 128u * jj, GB_SOFF(i, r), 0); } \
+            if ((LAST) && (FLAGS & 2)) GB_PREFETCH_Y(); \
             __builtin_amdgcn_sched_barrier(0); \
-            _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) { \
-                GbFrag a[2][3], b[2][3]; \
-                _Pragma("unroll") for (int i = 0; i < 2; ++i) { \
-                    _Pragma("unroll") for (int t = 0; t < XT; ++t) a[i][t].q = lds[t * GB_TERM_UNITS + 2 * ks * GB_KG_STRIDE + arow + 32 * i]; \
-                    _Pragma("unroll") for (int t = 0; t < WT; ++t) b[i][t].q = lds[(XT + t) * GB_TERM_UNITS + 2 * ks * GB_KG_STRIDE + brow + 32 * i]; \
-                    if (F16) b[i][2].q = gb_wq(b[i][0].q); } \
-                gb_products<F16>(acc, a, b); } } while (0)
+            GB_MMA_KSTEP(acc, false, GB_WIDX_REG); } while (0)
         for (int kb = 0; kb < nkb - 1; ++kb) GB_PSTEP(false);
         GB_PSTEP(true);
 
-        if (F16 && guard) {                                 // range guard (guard.h): one column block covers the tile's rows
-            float chk = 0.f;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) MFR_GUARD_ACC(chk, acc[i][0][r]);
-            mfr_guard_commit(guard, chk);
-        }
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            if (n0 + 32 * jj >= N) continue;
-            const float bv = jj ? bv1 : bv0, os = jj ? os1 : os0;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float v = F16 ? __builtin_fmaf(acc[i][jj][r], os, bv) : acc[i][jj][r] + bv;
-                    if (FLAGS & 1) v = fmaxf(v, 0.f);
-                    if (FLAGS & 2) v += __builtin_bit_cast(float, ov[i][jj][r]);
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, yoff + 128u * jj, GB_SOFF(i, r), 0);
-                }
-        }
-        // next item of this workgroup
-        int jn = j + per_xcd;
+        if (F16 && guard) { float chk = 0.f; GB_GUARD_ROWS(acc, chk); }
+        GB_STORE_PLAIN(acc, GB_NO_ROW_BIAS);
+        int jn = j + per_xcd;                              // next item of this workgroup
         if (jn >= items) break;
         { GB_TILE(jn, mbn, nbn); (void)nbn; if (mbn >= nmb) break; }
         j = jn;
     }
 #undef GB_PSTEP
 #undef GB_PLOAD
-#undef GB_TILE
-#undef GB_SOFF
 }
 
 // ---- the default (K % 64 == 0): persistent 128 x 128 workgroups, W by LDS-DMA, X two K steps ahead -----------------------------------
@@ -431,6 +479,27 @@ __device__ unsigned long long gd_prof[4][64];
 #else
 #define GD_STAMP(k) do { } while (0)
 #endif
+// W stream: GD_WDESC declares a buffer descriptor over a whole packed weight; GD_WDMA_ISSUE: the 2 WT `buffer_load_dwordx4 ... lds` (LOAD:
+// GD_WDMA_LOAD of the descriptor) per wavefront that copy the packed tile image at byte offset img of it into W stage `stage` (scalar offset =
+// tile image + this wavefront's chunks)
+typedef unsigned gd_u32x4 __attribute__((ext_vector_type(4)));
+#define GD_WDESC(wdesc, Wp, wp_bytes) \
+    gd_u32x4 wdesc; \
+    wdesc.x = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)Wp); \
+    wdesc.y = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)Wp >> 32) & 0xffffu); \
+    wdesc.z = wp_bytes; \
+    wdesc.w = MFR_RSRC_FLAGS
+#define GD_WDMA_LANE() \
+    const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) uint4 *)lds; \
+    const unsigned lane16 = 16u * (unsigned)lane
+#define GD_WDMA_LOAD(wdesc) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(m0v), "v"(lane16), "s"(wdesc), "s"(so) : "memory")
+#define GD_WDMA_ISSUE(img, stage, LOAD) do { \
+        _Pragma("unroll") for (int q = 0; q < 2 * WT; ++q) { \
+            const unsigned so = __builtin_amdgcn_readfirstlane(img + (unsigned)(64 * (wid + 4 * q)) * 16u); \
+            const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + 16u * (unsigned)(XT * GB_TERM_UNITS + stage * WSTAGE + 64 * (wid + 4 * q))); \
+            LOAD; \
+        } } while (0)
+#define GD_WIDX(P) ((P) * WSTAGE + t * 512 + 2 * ks * 128 + brow + 32 * i)                             /* GB_MMA_KSTEP's W unit in stage P */
 // FLAGS & 8 (round 6): the X rows are the tokens of LoFTR's fine-level 5x5 WINDOWS, read straight from the NHWC fine map (row g = window g / W^2,
 // token g % W^2 -> pixel (cell centre - W / 2 + token offset) of image img_ids[window]; outside the map: the zero row = F.unfold's padding), and the
 // epilogue adds one bias row PER WINDOW (the coarse half of merge_feat, constant over a window's tokens).  Replaces fine_gather_kernel + the
@@ -455,54 +524,28 @@ __global__ void __launch_bounds__(256, 2) gemm_split_d_kernel(const float *__res
     // FLAGS & 4 (round 6): LayerNorm over the N = 128 output features in the epilogue (LoFTR's fine-level encoder layers: norm1 behind `merge`,
     // norm2 (+ residual, FLAGS & 2: Y += ...) behind the MLP's second layer -- upstream LoFTREncoderLayer.forward).  At the fine level every one of
     // these kernels is HBM-bound (2.4 M rows x 128 floats per tensor), so the separate LayerNorm pass cost its full read + write of the tensor;
-    // the ~700 extra instructions per tile of the in-register reduction below are free.  Row statistics: the thread's two columns, a butterfly
-    // over the 32 lanes that hold the row's other columns of this wavefront, the two wavefronts of a row exchanged through 2 KB of LDS (summed
-    // in the fixed order wn = 0, 1); mean first, then the centred squares (the two-pass form of layernorm_kernel, loftr_fused.hip).
+    // the ~700 extra instructions per tile of the in-register reduction (GB_STORE_LAYERNORM) are free.
     __shared__ float lnx[(FLAGS & 4) ? 512 : 1];
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wid >> 1, wn = wid & 1;
     const int nkb = K / GB_BK;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
-    const int items = ((nmb + 7) >> 3) * nnb;
-#define GD_TILE(j, mb_, nb_) const int nb_ = (j) % nnb, mb_ = ((j) / nnb) * 8 + xcd
-    int j = slot;
-    if (j >= items) return;
-    { GD_TILE(j, mb, nb); (void)nb; if (mb >= nmb) return; }
-    // the item after jj in this workgroup's walk, or jj itself at the end (the streams then re-read valid memory that is never used)
-    auto next_item = [&](int jj) { int jn = jj + per_xcd; if (jn < items) { GD_TILE(jn, mbn, nbn); (void)nbn; if (mbn >= nmb) jn = items; } return jn < items ? jn : jj; };
+    GB_WALK();
+    GB_WALK_NEXT();
 
-    int xdst[2], xr[2], xk[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int u = tid + 256 * i;
-        xr[i] = u >> 2; xk[i] = 8 * (u & 3);
-        xdst[i] = (u & 3) * GB_KG_STRIDE + xr[i];
-    }
-    const int arow = (lane >> 5) * GB_KG_STRIDE + 64 * wm + (lane & 31);
-    const int brow = XT * GB_TERM_UNITS + (lane >> 5) * 128 + 64 * wn + (lane & 31);
+    GB_XSTAGE();
+    const int arow = GB_FRAG_ROW(wm, GB_KG_STRIDE);
+    const int brow = XT * GB_TERM_UNITS + GB_FRAG_ROW(wn, 128);
     const unsigned rowb = (unsigned)ldy * 4u;
-    const __amdgpu_buffer_rsrc_t rbias = __builtin_amdgcn_make_buffer_rsrc((void *)bias, 0, bias ? N * 4 : 0, MFR_RSRC_FLAGS);
-    const __amdgpu_buffer_rsrc_t rscale = __builtin_amdgcn_make_buffer_rsrc((void *)oscale, 0, F16 ? nnb * GB_BN * 4 : 0, MFR_RSRC_FLAGS);
+    GB_COLS();
 
-    // W stream (LDS-DMA, one step ahead): descriptor over the whole packed weight, scalar offset = tile image + this wavefront's chunks
-    typedef unsigned gd_u32x4 __attribute__((ext_vector_type(4)));
-    gd_u32x4 wdesc;
-    wdesc.x = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)Wp);
-    wdesc.y = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)Wp >> 32) & 0xffffu);
-    wdesc.z = wp_bytes;
-    wdesc.w = MFR_RSRC_FLAGS;
-    const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) uint4 *)lds;
-    const unsigned lane16 = 16u * (unsigned)lane;
+    // W stream (LDS-DMA, one step ahead)
+    GD_WDESC(wdesc, Wp, wp_bytes);
+    GD_WDMA_LANE();
     int wj = j, wk = 0;                                    // item / K step the W stream is at
     auto wdma = [&](int stage) {
-        GD_TILE(wj, mbw, nbw); (void)mbw;
+        GB_TILE(wj, mbw, nbw); (void)mbw;
         const unsigned img = (unsigned)(nbw * nkb + wk) * (unsigned)(WSTAGE * 16);
-#pragma unroll
-        for (int q = 0; q < 2 * WT; ++q) {
-            const unsigned so = __builtin_amdgcn_readfirstlane(img + (unsigned)(64 * (wid + 4 * q)) * 16u);
-            const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + 16u * (unsigned)(XT * GB_TERM_UNITS + stage * WSTAGE + 64 * (wid + 4 * q)));
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(m0v), "v"(lane16), "s"(wdesc), "s"(so) : "memory");
-        }
+        GD_WDMA_ISSUE(img, stage, GD_WDMA_LOAD(wdesc));
         if (++wk == nkb) { wk = 0; wj = next_item(wj); }
     };
     // X stream (registers, two steps ahead)
@@ -515,19 +558,18 @@ __global__ void __launch_bounds__(256, 2) gemm_split_d_kernel(const float *__res
         return (y >= 0 && y < wnd.Hf && x >= 0 && x < wnd.Wf) ? X + (((size_t)img * wnd.Hf + y) * wnd.Wf + x) * (size_t)ldx : wnd.zero;
     };
     auto x_tile_start = [&](int jj) {
-        GD_TILE(jj, mb, nb); (void)nb;
+        GB_TILE(jj, mb, nb); (void)nb;
         if constexpr ((FLAGS & 8) != 0) {
             lx0 = window_row(min(mb * GB_BM + xr[0], M - 1)) + xk[0];
             lx1 = window_row(min(mb * GB_BM + xr[1], M - 1)) + xk[1];
         } else {
-            lx0 = X + (size_t)min(mb * GB_BM + xr[0], M - 1) * ldx + xk[0];
-            lx1 = X + (size_t)min(mb * GB_BM + xr[1], M - 1) * ldx + xk[1];
+            lx0 = GB_XSRC(mb, 0);
+            lx1 = GB_XSRC(mb, 1);
         }
     };
     float4 xa0, xa1, xb0, xb1, xc0, xc1, xd0, xd1;         // set 0: xa (rows u >> 2), xb (+ 64 rows); set 1: xc, xd
 #define GD_XLOAD(p0, p1, q0, q1) do { \
-        p0 = *(const float4 *)lx0; p1 = *(const float4 *)(lx0 + 4); q0 = *(const float4 *)lx1; q1 = *(const float4 *)(lx1 + 4); \
-        lx0 += GB_BK; lx1 += GB_BK; \
+        gb_xload(lx0, lx1, p0, p1, q0, q1); \
         if (++lk == nkb) { lk = 0; lj = next_item(lj); x_tile_start(lj); } } while (0)
 
     f32x16 acc[2][2];
@@ -538,7 +580,6 @@ __global__ void __launch_bounds__(256, 2) gemm_split_d_kernel(const float *__res
 #else
 #define GD_PSTEP_INC (void)0
 #endif
-#define GD_SOFF(i, r) ((unsigned)(32 * (i) + ((r) & 3) + 8 * ((r) >> 2)) * rowb)
     // step of parity P: X register set P -> the X stage; W stage P (filled by the DMA of the previous step) is multiplied; the DMA of the next
     // step's W goes to stage P ^ 1 and set P is reloaded with the X of two steps ahead.  Younger than the DMA this step waits for: the previous
     // step's 4 X loads, this step's 2 WT DMAs and 4 X loads.
@@ -549,24 +590,13 @@ __global__ void __launch_bounds__(256, 2) gemm_split_d_kernel(const float *__res
         gb_xsplit_store<F16>(lds, p0, p1, xdst[0]); gb_xsplit_store<F16>(lds, q0, q1, xdst[1]); \
         wdma((P) ^ 1); GD_XLOAD(p0, p1, q0, q1); \
         GD_STAMP(2); \
-        if ((LAST) && (FLAGS & 2)) { \
-            _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) \
-                _Pragma("unroll") for (int i = 0; i < 2; ++i) \
-                    _Pragma("unroll") for (int r = 0; r < 16; ++r) \
-                        ov[i][jj][r] = __builtin_amdgcn_raw_buffer_load_b32(ry, yoff + 128u * jj, GD_SOFF(i, r), 0); \
-            GD_VMCNT(63); } \
+        if ((LAST) && (FLAGS & 2)) { GB_PREFETCH_Y(); GD_VMCNT(63); } \
         else GD_VMCNT(8 + 2 * WT); \
         GD_STAMP(3); \
         __syncthreads(); \
         GD_STAMP(4); \
         __builtin_amdgcn_sched_barrier(0); \
-        _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) { \
-            GbFrag a[2][3], b[2][3]; \
-            _Pragma("unroll") for (int i = 0; i < 2; ++i) { \
-                _Pragma("unroll") for (int t = 0; t < XT; ++t) a[i][t].q = lds[t * GB_TERM_UNITS + 2 * ks * GB_KG_STRIDE + arow + 32 * i]; \
-                _Pragma("unroll") for (int t = 0; t < WT; ++t) b[i][t].q = lds[(P) * WSTAGE + t * 512 + 2 * ks * 128 + brow + 32 * i]; \
-                if (F16) b[i][2].q = gb_wq(b[i][0].q); } \
-            gb_products<F16>(acc, a, b); } \
+        GB_MMA_KSTEP(acc, false, GD_WIDX(P)); \
         GD_PSTEP_INC; } while (0)
 
     x_tile_start(j);
@@ -574,112 +604,29 @@ __global__ void __launch_bounds__(256, 2) gemm_split_d_kernel(const float *__res
     GD_XLOAD(xa0, xa1, xb0, xb1);
     GD_XLOAD(xc0, xc1, xd0, xd1);
     for (;;) {
-        GD_TILE(j, mb, nb);
+        GB_TILE(j, mb, nb);
         const int m0 = mb * GB_BM;
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void *)(Y + (size_t)m0 * ldy), 0, (int)((unsigned)min(GB_BM, M - m0) * rowb), MFR_RSRC_FLAGS);
-        const int n0 = nb * GB_BN + 64 * wn + (lane & 31);
-        const unsigned yoff = (unsigned)(64 * wm + 4 * (lane >> 5)) * rowb + 4u * (unsigned)n0;
-        const float bv0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rbias, 4u * (unsigned)n0, 0, 0));
-        const float bv1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rbias, 4u * (unsigned)n0 + 128u, 0, 0));
-        const float os0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rscale, 4u * (unsigned)n0, 0, 0));
-        const float os1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rscale, 4u * (unsigned)n0 + 128u, 0, 0));
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][jj][r] = 0.f;
+        GB_YTILE(nb);
+        GB_COLS_LOAD();
+        GB_ZERO(acc);
         for (int kb = 0; kb < nkb - 2; kb += 2) { GD_STEP(0, xa0, xa1, xb0, xb1, false); GD_STEP(1, xc0, xc1, xd0, xd1, false); }
         GD_STEP(0, xa0, xa1, xb0, xb1, false);
         GD_STEP(1, xc0, xc1, xd0, xd1, true);
-        if (F16 && guard) {
-            // range guard (guard.h): an out-of-range x[m, k] makes EVERY accumulator of output row m non-finite, so one column per row is enough:
-            // column block jj = 0 of every (i, r) covers the tile's 128 rows (lanes / the two wn wavefronts repeat them)
-            float chk = 0.f;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) MFR_GUARD_ACC(chk, acc[i][0][r]);
-            mfr_guard_commit(guard, chk);
-        }
+        if (F16 && guard) { float chk = 0.f; GB_GUARD_ROWS(acc, chk); }
         if constexpr ((FLAGS & 4) != 0) {
             const float g0 = ln_gamma[n0], g1 = ln_gamma[n0 + 32], be0 = ln_beta[n0], be1 = ln_beta[n0 + 32];
-            float part[2][16];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    acc[i][0][r] = F16 ? __builtin_fmaf(acc[i][0][r], os0, bv0) : acc[i][0][r] + bv0;
-                    acc[i][1][r] = F16 ? __builtin_fmaf(acc[i][1][r], os1, bv1) : acc[i][1][r] + bv1;
-                    part[i][r] = acc[i][0][r] + acc[i][1][r];
-                }
-#pragma unroll
-            for (int m = 1; m <= 16; m <<= 1)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) part[i][r] += __shfl_xor(part[i][r], m, 64);
-#define GD_LNROW(i, r) (64 * wm + 32 * (i) + ((r) & 3) + 8 * ((r) >> 2) + 4 * (lane >> 5))
-            if ((lane & 31) == 0) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) lnx[wn * 128 + GD_LNROW(i, r)] = part[i][r];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float mean = (lnx[GD_LNROW(i, r)] + lnx[128 + GD_LNROW(i, r)]) * (1.0f / 128.0f);
-                    acc[i][0][r] -= mean; acc[i][1][r] -= mean;
-                    part[i][r] = acc[i][0][r] * acc[i][0][r] + acc[i][1][r] * acc[i][1][r];
-                }
-#pragma unroll
-            for (int m = 1; m <= 16; m <<= 1)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) part[i][r] += __shfl_xor(part[i][r], m, 64);
-            if ((lane & 31) == 0) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) lnx[256 + wn * 128 + GD_LNROW(i, r)] = part[i][r];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float rstd = rsqrtf((lnx[256 + GD_LNROW(i, r)] + lnx[384 + GD_LNROW(i, r)]) * (1.0f / 128.0f) + ln_eps);
-                    float y0 = acc[i][0][r] * rstd * g0 + be0, y1 = acc[i][1][r] * rstd * g1 + be1;
-                    if (FLAGS & 2) { y0 = __builtin_bit_cast(float, ov[i][0][r]) + y0; y1 = __builtin_bit_cast(float, ov[i][1][r]) + y1; }
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y0), ry, yoff, GD_SOFF(i, r), 0);
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y1), ry, yoff + 128u, GD_SOFF(i, r), 0);
-                }
-#undef GD_LNROW
+            GB_STORE_LAYERNORM(acc, FLAGS & 2, bv0, bv1, os0, os1);
         } else {
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            if (n0 + 32 * jj >= N) continue;
-            const float bv = jj ? bv1 : bv0, os = jj ? os1 : os0;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float v = F16 ? __builtin_fmaf(acc[i][jj][r], os, bv) : acc[i][jj][r] + bv;
-                    if (FLAGS & 1) v = fmaxf(v, 0.f);
-                    if (FLAGS & 2) v += __builtin_bit_cast(float, ov[i][jj][r]);
-                    if constexpr ((FLAGS & 8) != 0) {
-                        if (wnd.rgb) {
-                            const int g = min(m0 + 64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), M - 1);
-                            v += wnd.rgb[(size_t)(g / (wnd.win * wnd.win)) * N + n0 + 32 * jj];
-                        }
-                    }
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, yoff + 128u * jj, GD_SOFF(i, r), 0);
-                }
-        }
+            // FLAGS & 8: the window's bias row (rows beyond M: a valid window is read, nothing is stored)
+#define GD_WINDOW_BIAS(v, i, jj, r) \
+            if constexpr ((FLAGS & 8) != 0) { \
+                if (wnd.rgb) { \
+                    const int g = min(GB_TILE_ROW(m0 + 64 * wm, i, r), M - 1); \
+                    v += wnd.rgb[(size_t)(g / (wnd.win * wnd.win)) * N + n0 + 32 * jj]; \
+                } \
+            }
+            GB_STORE_PLAIN(acc, GD_WINDOW_BIAS);
+#undef GD_WINDOW_BIAS
         }
         const int jn = next_item(j);
         if (jn == j) break;
@@ -687,9 +634,7 @@ __global__ void __launch_bounds__(256, 2) gemm_split_d_kernel(const float *__res
     }
     GD_VMCNT(0);                                           // the streams' last (unused) DMA must not land in the LDS of the next workgroup
 #undef GD_STEP
-#undef GD_SOFF
 #undef GD_XLOAD
-#undef GD_TILE
 }
 
 // ---- round 6: the MLP of a fine-level LoFTR encoder layer in ONE kernel ------------------------------------------------------------------------
@@ -709,20 +654,6 @@ __global__ void __launch_bounds__(256, 2) gemm_split_d_kernel(const float *__res
 // The W stream is the same 2 (K1 / 32 + 4) tile images for every row tile (W1 half 0, W2 first half, W1 half 1, W2 second half): 384 KB per tile from L2.
 // Every output element is the same sum of the same products in the same order as the two-launch path, so the result agrees with it to the rounding of
 // the MFMA's internal adder under operand exchange (tests/test_gpu_gemm_split.py holds both to the float64 bars).
-template <bool F16>
-__device__ __forceinline__ void gb_products_t(f32x16 (&acc)[2][2], const GbFrag (&a)[2][3], const GbFrag (&b)[2][3])
-{
-    // acc[fi][rj] (features x rows) += W-fragment fi (first operand) x X-fragment rj (second operand); same term order as gb_products
-#define GB_T4(ta, tb) do { \
-        if (F16) { acc[0][0] = SF_MFMA(b[0][tb].q, a[0][ta].q, acc[0][0]); acc[0][1] = SF_MFMA(b[0][tb].q, a[1][ta].q, acc[0][1]); \
-                   acc[1][0] = SF_MFMA(b[1][tb].q, a[0][ta].q, acc[1][0]); acc[1][1] = SF_MFMA(b[1][tb].q, a[1][ta].q, acc[1][1]); } \
-        else     { acc[0][0] = GB_MFMA_BF(b[0][tb].v, a[0][ta].v, acc[0][0]); acc[0][1] = GB_MFMA_BF(b[0][tb].v, a[1][ta].v, acc[0][1]); \
-                   acc[1][0] = GB_MFMA_BF(b[1][tb].v, a[0][ta].v, acc[1][0]); acc[1][1] = GB_MFMA_BF(b[1][tb].v, a[1][ta].v, acc[1][1]); } } while (0)
-    if (F16) { GB_T4(1, 2); GB_T4(0, 1); GB_T4(0, 0); }
-    else     { GB_T4(1, 1); GB_T4(0, 2); GB_T4(2, 0); GB_T4(0, 1); GB_T4(1, 0); GB_T4(0, 0); }
-#undef GB_T4
-}
-
 static __device__ __forceinline__ void gb_swap32(float &a, float &b) { asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
 
 template <bool F16, bool ACC>
@@ -740,65 +671,42 @@ __global__ void __launch_bounds__(256, 2) mlp_ln_kernel(const float *__restrict_
     const int wm = wid >> 1, wn = wid & 1;
     const int nkb1 = K1 / GB_BK;                           // even (K1 % 64 == 0)
     const int half_steps = nkb1 + 4, steps = 2 * half_steps;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
-    const int items = (nmb + 7) >> 3;
-    int j = slot;
-    if (j >= items || j * 8 + xcd >= nmb) return;
-    auto next_item = [&](int jj) { const int jn = jj + per_xcd; return (jn < items && jn * 8 + xcd < nmb) ? jn : jj; };
+    constexpr int nnb = 1;                                 // the walk is over row blocks only
+    GB_WALK();
+    GB_WALK_NEXT();
 
-    int xdst[2], xr[2], xk[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int u = tid + 256 * i;
-        xr[i] = u >> 2; xk[i] = 8 * (u & 3);
-        xdst[i] = (u & 3) * GB_KG_STRIDE + xr[i];
-    }
-    const int arow = (lane >> 5) * GB_KG_STRIDE + 64 * wm + (lane & 31);
-    const int brow = XT * GB_TERM_UNITS + (lane >> 5) * 128 + 64 * wn + (lane & 31);
+    GB_XSTAGE();
+    const int arow = GB_FRAG_ROW(wm, GB_KG_STRIDE);
+    const int brow = XT * GB_TERM_UNITS + GB_FRAG_ROW(wn, 128);
     const unsigned rowb = (unsigned)ldy * 4u;
 
     // W stream: the same `steps` tile images for every row tile
-    typedef unsigned gd_u32x4 __attribute__((ext_vector_type(4)));
-    gd_u32x4 wdesc1, wdesc2;
-    wdesc1.x = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)W1p);
-    wdesc1.y = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)W1p >> 32) & 0xffffu);
-    wdesc1.z = w1_bytes; wdesc1.w = MFR_RSRC_FLAGS;
-    wdesc2.x = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)W2p);
-    wdesc2.y = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)W2p >> 32) & 0xffffu);
-    wdesc2.z = w2_bytes; wdesc2.w = MFR_RSRC_FLAGS;
-    const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) uint4 *)lds;
-    const unsigned lane16 = 16u * (unsigned)lane;
+    GD_WDESC(wdesc1, W1p, w1_bytes);
+    GD_WDESC(wdesc2, W2p, w2_bytes);
+    GD_WDMA_LANE();
     int wstep = 0;
     auto wdma = [&](int stage) {
         const int half = wstep >= half_steps ? 1 : 0, r = wstep - half * half_steps;
         const bool first = r < nkb1;
         const unsigned img = (unsigned)(first ? half * nkb1 + r : 4 * half + (r - nkb1)) * (unsigned)(WSTAGE * 16);
-#pragma unroll
-        for (int q = 0; q < 2 * WT; ++q) {
-            const unsigned so = __builtin_amdgcn_readfirstlane(img + (unsigned)(64 * (wid + 4 * q)) * 16u);
-            const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + 16u * (unsigned)(XT * GB_TERM_UNITS + stage * WSTAGE + 64 * (wid + 4 * q)));
-            if (first) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(m0v), "v"(lane16), "s"(wdesc1), "s"(so) : "memory");
-            else       asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(m0v), "v"(lane16), "s"(wdesc2), "s"(so) : "memory");
-        }
+        GD_WDMA_ISSUE(img, stage, if (first) GD_WDMA_LOAD(wdesc1); else GD_WDMA_LOAD(wdesc2));
         if (++wstep == steps) wstep = 0;
     };
     // X stream (registers, two steps ahead): the tile's K1 / 32 steps twice (once per hidden half), then the next tile
     const float *lx0, *lx1;
     int xstep = 0, lj = j;
     auto x_tile_start = [&](int jj) {
-        const int mb = jj * 8 + xcd;
-        lx0 = X + (size_t)min(mb * GB_BM + xr[0], M - 1) * ldx + xk[0];
-        lx1 = X + (size_t)min(mb * GB_BM + xr[1], M - 1) * ldx + xk[1];
+        GB_TILE(jj, mb, nb); (void)nb;
+        lx0 = GB_XSRC(mb, 0);
+        lx1 = GB_XSRC(mb, 1);
     };
     float4 xa0, xa1, xb0, xb1, xc0, xc1, xd0, xd1;
 #define ML_XLOAD(p0, p1, q0, q1) do { \
-        p0 = *(const float4 *)lx0; p1 = *(const float4 *)(lx0 + 4); q0 = *(const float4 *)lx1; q1 = *(const float4 *)(lx1 + 4); \
-        lx0 += GB_BK; lx1 += GB_BK; ++xstep; \
+        gb_xload(lx0, lx1, p0, p1, q0, q1); ++xstep; \
         if (xstep == nkb1) { lx0 -= K1; lx1 -= K1; } \
         else if (xstep == 2 * nkb1) { xstep = 0; lj = next_item(lj); x_tile_start(lj); } } while (0)
 
     f32x16 acc1[2][2], acc2[2][2];
-#define ML_SOFF(i, r) ((unsigned)(32 * (i) + ((r) & 3) + 8 * ((r) >> 2)) * rowb)
     // phase-1 step of parity P (X register set P, W stage P); FIRST: no X loads of a previous phase-1 step are in flight behind this step's DMA
 #define ML_STEP1(P, p0, p1, q0, q1, FIRST) do { \
         __syncthreads(); \
@@ -807,13 +715,7 @@ __global__ void __launch_bounds__(256, 2) mlp_ln_kernel(const float *__restrict_
         if (FIRST) GD_VMCNT(4 + 2 * WT); else GD_VMCNT(8 + 2 * WT); \
         __syncthreads(); \
         __builtin_amdgcn_sched_barrier(0); \
-        _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) { \
-            GbFrag a[2][3], b[2][3]; \
-            _Pragma("unroll") for (int i = 0; i < 2; ++i) { \
-                _Pragma("unroll") for (int t = 0; t < XT; ++t) a[i][t].q = lds[t * GB_TERM_UNITS + 2 * ks * GB_KG_STRIDE + arow + 32 * i]; \
-                _Pragma("unroll") for (int t = 0; t < WT; ++t) b[i][t].q = lds[(P) * WSTAGE + t * 512 + 2 * ks * 128 + brow + 32 * i]; \
-                if (F16) b[i][2].q = gb_wq(b[i][0].q); } \
-            gb_products_t<F16>(acc1, a, b); } } while (0)
+        GB_MMA_KSTEP(acc1, true, GD_WIDX(P)); } while (0)
 
     x_tile_start(j);
     wdma(0);
@@ -822,35 +724,24 @@ __global__ void __launch_bounds__(256, 2) mlp_ln_kernel(const float *__restrict_
     const float g0 = ln_gamma[64 * wn + (lane & 31)], g1 = ln_gamma[64 * wn + 32 + (lane & 31)];
     const float be0 = ln_beta[64 * wn + (lane & 31)], be1 = ln_beta[64 * wn + 32 + (lane & 31)];
     for (;;) {
-        const int mb = j * 8 + xcd, m0 = mb * GB_BM;
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void *)(Y + (size_t)m0 * ldy), 0, (int)((unsigned)min(GB_BM, M - m0) * rowb), MFR_RSRC_FLAGS);
-        const int n0 = 64 * wn + (lane & 31);
-        const unsigned yoff = (unsigned)(64 * wm + 4 * (lane >> 5)) * rowb + 4u * (unsigned)n0;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc2[i][jj][r] = 0.f;
+        GB_TILE(j, mb, nb);
+        const int m0 = mb * GB_BM;
+        GB_YTILE(nb);
+        GB_ZERO(acc2);
         float chk = 0.f;
         for (int h = 0; h < 2; ++h) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc1[i][jj][r] = 0.f;
+            GB_ZERO(acc1);
             ML_STEP1(0, xa0, xa1, xb0, xb1, true);
             ML_STEP1(1, xc0, xc1, xd0, xd1, false);
             for (int kb = 2; kb < nkb1; kb += 2) { ML_STEP1(0, xa0, xa1, xb0, xb1, false); ML_STEP1(1, xc0, xc1, xd0, xd1, false); }
             // range guard (guard.h): an out-of-range x poisons every hidden feature of its row: one register per (feature block 0, row block)
             if (F16 && guard) { MFR_GUARD_ACC(chk, acc1[0][0][0]); MFR_GUARD_ACC(chk, acc1[0][1][0]); }
-            // scale / bias / ReLU: register r of acc1[fi][rj] is hidden feature 128 h + 64 wn + 32 fi + (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+            // scale / bias / ReLU: register r of acc1[fi][rj] is hidden feature 128 h + the tile row of (wn, fi, r): the operands are swapped
 #pragma unroll
             for (int fi = 0; fi < 2; ++fi)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int f = 128 * h + 64 * wn + 32 * fi + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    const int f = GB_TILE_ROW(128 * h + 64 * wn, fi, r);
                     const float bv = b1 ? b1[f] : 0.f;
                     const float os = F16 ? os1[f] : 1.0f;
 #pragma unroll
@@ -890,96 +781,17 @@ __global__ void __launch_bounds__(256, 2) mlp_ln_kernel(const float *__restrict_
                 GD_VMCNT(2 * WT);
                 __syncthreads();
                 __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    GbFrag a[2][3], b[2][3];
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-                        for (int t = 0; t < XT; ++t) a[i][t].q = lds[t * GB_TERM_UNITS + 2 * ks * GB_KG_STRIDE + arow + 32 * i];
-#pragma unroll
-                        for (int t = 0; t < WT; ++t) b[i][t].q = lds[(c & 1) * WSTAGE + t * 512 + 2 * ks * 128 + brow + 32 * i];
-                        if (F16) b[i][2].q = gb_wq(b[i][0].q);
-                    }
-                    gb_products<F16>(acc2, a, b);
-                }
+                GB_MMA_KSTEP(acc2, false, GD_WIDX(c & 1));
             }
         }
         // ---- epilogue: out = acc2 / scale + bias -> LayerNorm (+ residual) -> Y
         unsigned ov[2][2][16];
-        if (ACC) {
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) ov[i][jj][r] = __builtin_amdgcn_raw_buffer_load_b32(ry, yoff + 128u * jj, ML_SOFF(i, r), 0);
-        }
-        if (F16 && guard) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) MFR_GUARD_ACC(chk, acc2[i][0][r]);
-            mfr_guard_commit(guard, chk);
-        }
+        if (ACC) GB_PREFETCH_Y();
+        if (F16 && guard) GB_GUARD_ROWS(acc2, chk);
         {
             const float bv0 = b2 ? b2[n0] : 0.f, bv1 = b2 ? b2[n0 + 32] : 0.f;
             const float os0 = F16 ? os2[n0] : 1.f, os1v = F16 ? os2[n0 + 32] : 1.f;
-            float part[2][16];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    acc2[i][0][r] = F16 ? __builtin_fmaf(acc2[i][0][r], os0, bv0) : acc2[i][0][r] + bv0;
-                    acc2[i][1][r] = F16 ? __builtin_fmaf(acc2[i][1][r], os1v, bv1) : acc2[i][1][r] + bv1;
-                    part[i][r] = acc2[i][0][r] + acc2[i][1][r];
-                }
-#pragma unroll
-            for (int m = 1; m <= 16; m <<= 1)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) part[i][r] += __shfl_xor(part[i][r], m, 64);
-#define ML_LNROW(i, r) (64 * wm + 32 * (i) + ((r) & 3) + 8 * ((r) >> 2) + 4 * (lane >> 5))
-            if ((lane & 31) == 0) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) lnx[wn * 128 + ML_LNROW(i, r)] = part[i][r];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float mean = (lnx[ML_LNROW(i, r)] + lnx[128 + ML_LNROW(i, r)]) * (1.0f / 128.0f);
-                    acc2[i][0][r] -= mean; acc2[i][1][r] -= mean;
-                    part[i][r] = acc2[i][0][r] * acc2[i][0][r] + acc2[i][1][r] * acc2[i][1][r];
-                }
-#pragma unroll
-            for (int m = 1; m <= 16; m <<= 1)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) part[i][r] += __shfl_xor(part[i][r], m, 64);
-            if ((lane & 31) == 0) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) lnx[256 + wn * 128 + ML_LNROW(i, r)] = part[i][r];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float rstd = rsqrtf((lnx[256 + ML_LNROW(i, r)] + lnx[384 + ML_LNROW(i, r)]) * (1.0f / 128.0f) + ln_eps);
-                    float y0 = acc2[i][0][r] * rstd * g0 + be0, y1 = acc2[i][1][r] * rstd * g1 + be1;
-                    if (ACC) { y0 = __builtin_bit_cast(float, ov[i][0][r]) + y0; y1 = __builtin_bit_cast(float, ov[i][1][r]) + y1; }
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y0), ry, yoff, ML_SOFF(i, r), 0);
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y1), ry, yoff + 128u, ML_SOFF(i, r), 0);
-                }
-#undef ML_LNROW
+            GB_STORE_LAYERNORM(acc2, ACC, bv0, bv1, os0, os1v);
         }
         const int jn = next_item(j);
         if (jn == j) break;
@@ -987,7 +799,6 @@ __global__ void __launch_bounds__(256, 2) mlp_ln_kernel(const float *__restrict_
     }
     GD_VMCNT(0);                                           // the streams' last (unused) DMA must not land in the LDS of the next workgroup
 #undef ML_STEP1
-#undef ML_SOFF
 #undef ML_XLOAD
 }
 
@@ -1040,10 +851,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_f16x2_kernel(const float *_
     }
     int wdst[2 * WT];
 #pragma unroll
-    for (int i = 0; i < 2 * WT; ++i) {
-        const int u = tid + 256 * i, term = u / 512, kgw = (u % 512) / 128, f = u % 128;
-        wdst[i] = (XT + term) * GB_TERM_UNITS + kgw * GB_KG_STRIDE + f;
-    }
+    for (int i = 0; i < 2 * WT; ++i) wdst[i] = gb_wdst(tid, i, XT);
     const uint4 *wtile = Wp + (size_t)nb * nkb * GB_W_TILE_UNITS(true) + tid;
 
     float xr[2][8];
@@ -1089,14 +897,9 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_f16x2_kernel(const float *_
     };
 
     f32x16 acc[2][2];                                       // [channel block i][pixel block j]
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    const int wrow = (lane >> 5) * GB_KG_STRIDE + 64 * wm + (lane & 31);      // weight fragment rows (channels)
-    const int prow = (lane >> 5) * GB_KG_STRIDE + 64 * wn + (lane & 31);      // X fragment rows (pixels)
+    GB_ZERO(acc);
+    const int wrow = GB_FRAG_ROW(wm, GB_KG_STRIDE);         // weight fragment rows (channels)
+    const int prow = GB_FRAG_ROW(wn, GB_KG_STRIDE);         // X fragment rows (pixels)
 
     gload(0);
     for (int kb = 0; kb < nkb; ++kb) {
@@ -1155,7 +958,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_f16x2_kernel(const float *_
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int co = nb * GB_BN + 64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int co = GB_TILE_ROW(nb * GB_BN + 64 * wm, i, r);
             osv[i][r] = oscale[co];                                              // (padded to nnb * 128 entries)
             bvv[i][r] = bias ? bias[min(co, Cout - 1)] : 0.f;
             cho[i][r] = co < Cout ? (unsigned)co : 0x10000000u;                  // in ELEMENTS of a plane (x plane size x 4 below)
@@ -1216,23 +1019,47 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_f16x2_kernel(const float *_
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------
 static size_t gb_tile_bytes(int N, int K, bool f16) { return (size_t)((N + GB_BN - 1) / GB_BN) * (K / GB_BK) * GB_W_TILE_UNITS(f16) * 16; }
 
+// what a launch derives from a packed weight [N, K]: its tile images (tb bytes; the LDS-DMA kernels address them with 32 bits), the per-feature
+// 1 / scale behind them (f16x2) and the range-guard flag (f16x2)
+template <bool F16>
+struct GbOperand {
+    const uint4 *wp;
+    size_t tb;
+    const float *oscale;
+    GbOperand(const void *packed_w, int N, int K) : wp((const uint4 *)packed_w), tb(gb_tile_bytes(N, K, F16)), oscale(F16 ? (const float *)((const char *)packed_w + tb) : nullptr) {}
+    bool dma_ok() const { return tb < 0xffffffffull; }
+    static int *guard() { return F16 ? mfr_guard_current() : (int *)nullptr; }
+};
+// the persistent kernels' grid: `cap` workgroups per XCD (64 = 2 per CU on 256 CUs), fewer when there are fewer tiles (multiple of 8: one share per XCD)
+static unsigned gb_persistent_grid(int nmb, int nnb, long long cap = 64)
+{
+    const long long per_xcd = (long long)((nmb + 7) / 8) * nnb;
+    return 8u * (unsigned)(per_xcd < cap ? per_xcd : cap);
+}
+// the default kernel; the batch strides, the LayerNorm epilogue (FLAGS & 4) and the windows (FLAGS & 8) are filled in where a launch has none
+template <int FLAGS, bool F16>
+static void gb_launch_d(hipStream_t st, unsigned grid, const float *x, int ldx, const GbOperand<F16> &w, const float *bias, float *y, int ldy, int M, int N, int K,
+                        int nbatch = 1, long long xs = 0, long long ws = 0, long long ys = 0, const float *ln_gamma = nullptr, const float *ln_beta = nullptr,
+                        float ln_eps = 0.f, const GdWindows &wnd = GdWindows{})
+{
+    hipLaunchKernelGGL((gemm_split_d_kernel<FLAGS, F16>), dim3(grid, (unsigned)nbatch), dim3(256), 0, st, x, ldx, w.wp, (unsigned)w.tb, w.oscale, bias, y, ldy, M, N, K,
+                       (N + GB_BN - 1) / GB_BN, (M + GB_BM - 1) / GB_BM, xs, ws, ys, GbOperand<F16>::guard(), ln_gamma, ln_beta, ln_eps, wnd);
+}
+
 template <bool F16>
 static int gb_launch(const float *x, int ldx, const void *packed_w, const float *bias, float *y, int ldy, int M, int N, int K, int flags, void *stream,
                      int nbatch = 1, long long xs = 0, long long ws_bytes = 0, long long ys = 0, const float *ln_gamma = nullptr, const float *ln_beta = nullptr,
                      float ln_eps = 0.f)
 {
+    hipStream_t st = (hipStream_t)stream;
     if (ln_gamma) {
         // LayerNorm epilogue: the default (LDS-DMA) kernel only, one 128-feature block; flags: 0 or 2 (Y += LayerNorm(...))
         if (!ln_beta || N != GB_BN || (K % 64) || (flags & ~2) || nbatch != 1 || !x || !packed_w || !y || M <= 0 || (ldx & 3) || ldx < K || ldy < N || ((uintptr_t)x & 15)) return MFR_E_ARG;
-        const size_t tb = gb_tile_bytes(N, K, F16);
-        if (tb >= 0xffffffffull) return MFR_E_ARG;
-        const int nmb = (M + GB_BM - 1) / GB_BM;
-        const long long per_xcd = (long long)((nmb + 7) / 8);
-        const unsigned grid = 8u * (unsigned)(per_xcd < 64 ? per_xcd : 64);
-        const float *oscale = F16 ? (const float *)((const char *)packed_w + tb) : nullptr;
-        int *g = F16 ? mfr_guard_current() : (int *)nullptr;
-        if (flags & 2) hipLaunchKernelGGL((gemm_split_d_kernel<6, F16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx, (const uint4 *)packed_w, (unsigned)tb, oscale, bias, y, ldy, M, N, K, 1, nmb, 0ll, 0ll, 0ll, g, ln_gamma, ln_beta, ln_eps, GdWindows{});
-        else           hipLaunchKernelGGL((gemm_split_d_kernel<4, F16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx, (const uint4 *)packed_w, (unsigned)tb, oscale, bias, y, ldy, M, N, K, 1, nmb, 0ll, 0ll, 0ll, g, ln_gamma, ln_beta, ln_eps, GdWindows{});
+        const GbOperand<F16> w(packed_w, N, K);
+        if (!w.dma_ok()) return MFR_E_ARG;
+        const unsigned grid = gb_persistent_grid((M + GB_BM - 1) / GB_BM, 1);
+        if (flags & 2) gb_launch_d<6, F16>(st, grid, x, ldx, w, bias, y, ldy, M, N, K, 1, 0, 0, 0, ln_gamma, ln_beta, ln_eps);
+        else           gb_launch_d<4, F16>(st, grid, x, ldx, w, bias, y, ldy, M, N, K, 1, 0, 0, 0, ln_gamma, ln_beta, ln_eps);
         CHECK_LAUNCH();
         return 0;
     }
@@ -1244,31 +1071,25 @@ static int gb_launch(const float *x, int ldx, const void *packed_w, const float 
     if (((uintptr_t)x & 15)) return MFR_E_ARG;
     const int f = flags & 3, one_tile = flags & 4;
     int pk = flags & 8;
-    const size_t tb = gb_tile_bytes(N, K, F16);
-    if (!one_tile && !pk && ((K % 64) || tb >= 0xffffffffull)) pk = 8;
+    const GbOperand<F16> w(packed_w, N, K);
+    if (!one_tile && !pk && ((K % 64) || !w.dma_ok())) pk = 8;
     const int nnb = (N + GB_BN - 1) / GB_BN, nmb = (M + GB_BM - 1) / GB_BM;
     const long long tiles = (long long)nmb * nnb;
     if (tiles > 0x7fffffffll) return MFR_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const uint4 *wp = (const uint4 *)packed_w;
-    const float *oscale = F16 ? (const float *)((const char *)packed_w + tb) : nullptr;
-    // 2 workgroups per CU on 256 CUs; fewer when there are fewer tiles (multiple of 8: one share per XCD)
-    const long long per_xcd = (long long)((nmb + 7) / 8) * nnb;
     // f16x2 without the accumulating epilogue: 158 registers, 48 KB of LDS -> three workgroups per CU (0.119 -> 0.099 ms on the 256 -> 768 layer,
     // profiles/r05_ab_gemm.json); the others: two
-    const long long cap = (F16 && !(f & 2) && !pk) ? 96 : 64;
-    const unsigned grid = 8u * (unsigned)(per_xcd < cap ? per_xcd : cap);
+    const unsigned grid = gb_persistent_grid(nmb, nnb, (F16 && !(f & 2) && !pk) ? 96 : 64);
 #define GB_SW(GO) switch (f) { case 0: GO(0); break; case 1: GO(1); break; case 2: GO(2); break; default: GO(3); break; }
     if (one_tile) {
-#define GB_GO(F) hipLaunchKernelGGL((gemm_split_kernel<F, F16>), dim3((unsigned)tiles, (unsigned)nbatch), dim3(256), 0, st, x, ldx, wp, oscale, bias, y, ldy, M, N, K, nnb, xs, ws, ys, F16 ? mfr_guard_current() : (int *)nullptr)
+#define GB_GO(F) hipLaunchKernelGGL((gemm_split_kernel<F, F16>), dim3((unsigned)tiles, (unsigned)nbatch), dim3(256), 0, st, x, ldx, w.wp, w.oscale, bias, y, ldy, M, N, K, nnb, xs, ws, ys, w.guard())
         GB_SW(GB_GO)
 #undef GB_GO
     } else if (pk) {
-#define GB_GO(F) hipLaunchKernelGGL((gemm_split_pk_kernel<F, F16>), dim3(grid, (unsigned)nbatch), dim3(256), 0, st, x, ldx, wp, oscale, bias, y, ldy, M, N, K, nnb, nmb, xs, ws, ys, F16 ? mfr_guard_current() : (int *)nullptr)
+#define GB_GO(F) hipLaunchKernelGGL((gemm_split_pk_kernel<F, F16>), dim3(grid, (unsigned)nbatch), dim3(256), 0, st, x, ldx, w.wp, w.oscale, bias, y, ldy, M, N, K, nnb, nmb, xs, ws, ys, w.guard())
         GB_SW(GB_GO)
 #undef GB_GO
     } else {
-#define GB_GO(F) hipLaunchKernelGGL((gemm_split_d_kernel<F, F16>), dim3(grid, (unsigned)nbatch), dim3(256), 0, st, x, ldx, wp, (unsigned)tb, oscale, bias, y, ldy, M, N, K, nnb, nmb, xs, ws, ys, F16 ? mfr_guard_current() : (int *)nullptr, (const float *)nullptr, (const float *)nullptr, 0.f, GdWindows{})
+#define GB_GO(F) gb_launch_d<F, F16>(st, grid, x, ldx, w, bias, y, ldy, M, N, K, nbatch, xs, ws, ys)
         GB_SW(GB_GO)
 #undef GB_GO
     }
@@ -1283,17 +1104,14 @@ static int gb_mlp_ln(const float *x, int ldx, int K1, const void *packed_w1, con
 {
     // hidden width 256 (two 128-feature blocks), output width 128: the fine-level LoFTR encoder layer (d_model 128)
     if (!x || !packed_w1 || !packed_w2 || !gamma || !beta || !y || M <= 0 || K1 <= 0 || (K1 % 64) || (ldx & 3) || ldx < K1 || ldy < GB_BN || ((uintptr_t)x & 15)) return MFR_E_ARG;
-    const size_t tb1 = gb_tile_bytes(2 * GB_BN, K1, F16), tb2 = gb_tile_bytes(GB_BN, 2 * GB_BN, F16);
-    if (tb1 >= 0xffffffffull) return MFR_E_ARG;
+    const GbOperand<F16> w1(packed_w1, 2 * GB_BN, K1), w2(packed_w2, GB_BN, 2 * GB_BN);
+    if (!w1.dma_ok()) return MFR_E_ARG;
     const int nmb = (M + GB_BM - 1) / GB_BM;
-    const long long per_xcd = (long long)((nmb + 7) / 8);
-    const unsigned grid = 8u * (unsigned)(per_xcd < 64 ? per_xcd : 64);
-    const float *os1 = F16 ? (const float *)((const char *)packed_w1 + tb1) : nullptr, *os2 = F16 ? (const float *)((const char *)packed_w2 + tb2) : nullptr;
-    int *g = F16 ? mfr_guard_current() : (int *)nullptr;
-    if (accumulate) hipLaunchKernelGGL((mlp_ln_kernel<F16, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx, K1, (const uint4 *)packed_w1, (unsigned)tb1, os1, b1,
-                                       (const uint4 *)packed_w2, (unsigned)tb2, os2, b2, gamma, beta, eps, y, ldy, M, nmb, g);
-    else            hipLaunchKernelGGL((mlp_ln_kernel<F16, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx, K1, (const uint4 *)packed_w1, (unsigned)tb1, os1, b1,
-                                       (const uint4 *)packed_w2, (unsigned)tb2, os2, b2, gamma, beta, eps, y, ldy, M, nmb, g);
+    const unsigned grid = gb_persistent_grid(nmb, 1);
+#define GB_GO(A) hipLaunchKernelGGL((mlp_ln_kernel<F16, A>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx, K1, w1.wp, (unsigned)w1.tb, w1.oscale, b1, \
+                                    w2.wp, (unsigned)w2.tb, w2.oscale, b2, gamma, beta, eps, y, ldy, M, nmb, w1.guard())
+    if (accumulate) GB_GO(true); else GB_GO(false);
+#undef GB_GO
     CHECK_LAUNCH();
     return 0;
 }
@@ -1308,15 +1126,11 @@ static int gb_windows(const float *feat, int Bimg, int Hf, int Wf, int C, const 
     const long long Mll = (long long)nwin * win * win;
     if (Mll > 0x7fffffffll) return MFR_E_ARG;
     const int M = (int)Mll, K = C;
-    const size_t tb = gb_tile_bytes(N, K, F16);
-    if (tb >= 0xffffffffull) return MFR_E_ARG;
-    const int nnb = (N + GB_BN - 1) / GB_BN, nmb = (M + GB_BM - 1) / GB_BM;
-    const long long per_xcd = (long long)((nmb + 7) / 8) * nnb;
-    const unsigned grid = 8u * (unsigned)(per_xcd < 64 ? per_xcd : 64);
-    const float *oscale = F16 ? (const float *)((const char *)packed_w + tb) : nullptr;
-    GdWindows w{img_ids, cell_ids, zero_row, window_bias, wc, stride, Hf, Wf, win};
-    hipLaunchKernelGGL((gemm_split_d_kernel<8, F16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, feat, C, (const uint4 *)packed_w, (unsigned)tb, oscale, bias, y, ldy, M, N, K,
-                       nnb, nmb, 0ll, 0ll, 0ll, F16 ? mfr_guard_current() : (int *)nullptr, (const float *)nullptr, (const float *)nullptr, 0.f, w);
+    const GbOperand<F16> w(packed_w, N, K);
+    if (!w.dma_ok()) return MFR_E_ARG;
+    const unsigned grid = gb_persistent_grid((M + GB_BM - 1) / GB_BM, (N + GB_BN - 1) / GB_BN);
+    gb_launch_d<8, F16>((hipStream_t)stream, grid, feat, C, w, bias, y, ldy, M, N, K, 1, 0, 0, 0, nullptr, nullptr, 0.f,
+                        GdWindows{img_ids, cell_ids, zero_row, window_bias, wc, stride, Hf, Wf, win});
     CHECK_LAUNCH();
     return 0;
 }

@@ -163,9 +163,9 @@ class IgemmConv:
         self.direct_s2 = DirectConv3x3(w, self.b) if (kh, kw, self.stride, self.pad) == (3, 3, 2, 1) and ci > 1 else None
 
     def __call__(self, x, relu=False, up_add=None):
+        """up_add [B, Cout, Ho / 2, Wo / 2]: y = conv(x) + bias + its 2x bilinear up-sampling (align_corners=True) in the same launch (LoFTR's FPN merge)"""
         if self.direct_s2 is not None and up_add is None and options.get("CONV_KERNEL") in ("auto", "direct"):
             return self.direct_s2.strided(x, act=1 if relu else 0)
-        """up_add [B, Cout, Ho / 2, Wo / 2]: y = conv(x) + bias + its 2x bilinear up-sampling (align_corners=True) in the same launch (LoFTR's FPN merge)"""
         lib = _lib.load()
         x = x.contiguous()
         B, C, H, W = x.shape
