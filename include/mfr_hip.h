@@ -626,6 +626,13 @@ int mfr_conv3x3_direct_f16x2(const float *x, const void *packed, const float *bi
  *                                           of 4) -- what the 1x1 / linear layer behind the convolution reads (SuperPoint convDa -> convDb, models/superpoint.py; LoFTR
  *                                           layer1_outconv2 -> FinePreprocess' unfold, matchers.py:50): replaces the NCHW store + mfr_nchw_to_rows.  No residual, no pool. */
 int mfr_conv3x3_direct_f16x2_rows(const float *x, const void *packed, const float *bias, int B, int Cin, int Cout, int H, int W, int act, float *yrows, int ldy, void *stream);
+/*   mfr_conv3x3_direct_f16x2_tiled          both of the above with the PIXEL TILING chosen by the caller (A/B tool, tests; the entries above pass 0): tile_mode 0 = auto (the
+ *                                           table in dc_conv), 1 = the 2-D tile (8 rows x 32 columns), 2 = the LINEAR tile: 256 consecutive units of the image as one padded
+ *                                           linear space of pitch `pitch` >= W + 1 (0 = W + 1; <= 159), which computes ceil(H pitch / 256) * 256 positions per image instead
+ *                                           of ceil(W / 32) * 32 * ceil(H / 8) * 8.  Same K loop, same products in the same order: bitwise the same output.  Mode 2 exists
+ *                                           for Cout > 64, no pool; MFR_E_ARG otherwise.  ldrows > 0: token-major output as _rows (then no residual, no pool), 0: NCHW. */
+int mfr_conv3x3_direct_f16x2_tiled(const float *x, const void *packed, const float *bias, const float *residual, int B, int Cin, int Cout, int H, int W,
+                                   int act, int pool, float *y, int ldrows, int tile_mode, int pitch, void *stream);
 /*   mfr_conv3x3s2_direct_f16x2              the STRIDE-2 3x3 / pad 1 layer (LoFTR's layer2.0 / layer3.0 conv1, `nn.Conv2d(k=3, s=2, p=1)` + folded BatchNorm + ReLU;
  *                                           un-vendored loftr/backbone/resnet_fpn.py, call site matchers.py:50) through the same kernel: the (2 TR + 1) x 65 patch is staged
  *                                           with its columns de-interleaved by parity, so every tap is again 32 consecutive LDS units; same packed filter as the

@@ -33,6 +33,11 @@
 //     channel) and leaves as four unconditional 16-byte buffer stores of eight full 128-byte lines; scale / bias / residual are fetched ahead of the
 //     stores (one in-order counter for loads and stores).  Pooling: rows pair in registers before the exchange, columns pair inside a lane after it.
 //   * grid: 1-D, XCD-aware: workgroup id & 7 = XCD; the channel groups of one spatial tile run back to back on the same XCD (its L2 holds the halo).
+//   * narrow maps (template parameter LIN, see DcGeom): the TR x 32 tile computes ceil(W / 32) * 32 columns -- 96 for the 67-pixel maps of SuperPoint's 1/8
+//     level, 35 % of those layers' MFMAs on pixels that do not exist.  The LINEAR tile takes 256 consecutive units of the image as one padded linear
+//     space of pitch W + 1 instead; same blocking, same K loop (the row shift of a tap becomes a run-time base), same epilogues, bitwise the same output.
+//     conv4a / 4b / Pa / Da 0.39 -> 0.30 / 0.77 -> 0.57 ms, conv3a 0.79 -> 0.70 ms, LoFTR's 68- and 136-pixel levels -18 % / -8 % at the bench batches
+//     (profiles/ab_direct_tiles.json); which shape class runs which tiling: dc_lin_auto below.
 // What bounds it: the matrix pipe at the chip's power limit (62-74 % busy at 1.25-1.29 GHz, profiles/r06_pmc_dconv_*.json).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -72,14 +77,24 @@ extern "C" int *mfr_guard_current(void) { return nullptr; }
 // parity -- row = [33 even columns | 33 odd columns] -- so that tap (dy, dx) of a row of 32 outputs is again 32 consecutive 16-byte units (row 2 r + dy,
 // half dx & 1, column c + (dx >> 1)).  Four times the patch per output: MG = 4 (all four wavefronts share 4 rows, 256 channels per workgroup) keeps
 // two stages within 80 KB.
-template <int MG, int NW, int STR> struct DcGeom {
+//
+// LIN > 0: the LINEAR pixel geometry for narrow maps (stride 1, no pooling, MG = 2).  The 2-D tile computes ceil(W / 32) * 32 columns: 96 for SuperPoint's
+// 67-pixel 1/8 level (35 % of the MFMAs on pixels that do not exist with the rows), 160 for 135.  Here an image is ONE padded linear space of pitch
+// Pw >= W + 1, u = y Pw + x: the columns x >= W are zeros and serve as the right border of row y and the left border of row y + 1 at once, the input
+// neighbour (dy, dx) of output u is u + (dy - 1) Pw + (dx - 1) for every pixel, and a tile is DC_LT = 256 consecutive u (8 blocks of 32 lanes, as the
+// 2 x 4 and 3 x 2 blockings have): ceil(H Pw / 256) tiles per image, waste <= one tile + H (Pw - W) positions.  The patch is the units
+// [u0 - Pw - 1, u0 + 256 + Pw + 1): 258 + 2 Pw of them, staged in the SAME layout, so a B operand is still 32 consecutive 16-byte units and only the row
+// shift dy Pw is a run-time value (three per-lane row bases).  LIN is the plane stride PPAD (compile-time, % 64 == 0): 448 (Pw <= 95) or 576 (Pw <= 159).
+// The K loop is the 2-D one instruction for instruction: every output sums the same products in the same order, the results are bitwise equal.
+#define DC_LT 256
+template <int MG, int NW, int STR, int LIN = 0> struct DcGeom {
     static constexpr int NT = 64 * NW;                 // threads per workgroup
     static constexpr int NGW = NW / MG;                // row groups (4 rows each) per workgroup
     static constexpr int TR = 4 * NGW;                 // output rows per tile
     static constexpr int PR = STR == 1 ? TR + 2 : 2 * TR + 1;      // patch rows
     static constexpr int PCW = STR == 1 ? DC_PC : 66;  // staged row width (pixels)
-    static constexpr int P = PR * PCW;                 // patch pixels
-    static constexpr int PPAD = (P + 63) / 64 * 64;    // plane stride (16-byte units)
+    static constexpr int P = PR * PCW;                 // patch pixels (LIN: 258 + 2 Pw, a run-time value)
+    static constexpr int PPAD = LIN ? LIN : (P + 63) / 64 * 64;    // plane stride (16-byte units)
     static constexpr int STAGE = 4 * PPAD;             // [term][channel half][pixel]
     static constexpr int R = (2 * PPAD + NT - 1) / NT; // staging rounds: item = (channel half, pixel), NT per round
 };
@@ -124,13 +139,15 @@ __global__ void __launch_bounds__(256) dc_pack_kernel(const float *__restrict__ 
 }
 
 // ---- the convolution ----------------------------------------------------------------------------------------------------------------------------
-template <int MG, int NW, bool POOL, int STR>
+template <int MG, int NW, bool POOL, int STR, int LIN = 0>
 __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_direct_f16x2_kernel(
     const float *__restrict__ x, const uint4 *__restrict__ wp, unsigned wp_bytes, const float *__restrict__ oscale, const float *__restrict__ bias,
-    const float *__restrict__ residual, float *__restrict__ y, int Cin, int Cout, int H, int W, int nbx, int nby, int S, int ncgw, int nks, int act, int *guard, int ldrows)
+    const float *__restrict__ residual, float *__restrict__ y, int Cin, int Cout, int H, int W, int nbx, int nby, int S, int ncgw, int nks, int act, int *guard, int ldrows,
+    int Pw)                                              // LIN: the pitch of the padded linear pixel space (nbx = tiles per image, nby = 1); else unused
 {
     static_assert(STR == 1 || (STR == 2 && !POOL), "stride 1 or 2; no pooled strided variant");
-    using G = DcGeom<MG, NW, STR>;
+    static_assert(LIN == 0 || (MG == 2 && NW == 4 && !POOL && STR == 1 && LIN % 64 == 0), "linear geometry: MG = 2, stride 1, no pooling");
+    using G = DcGeom<MG, NW, STR, LIN>;
     __shared__ __attribute__((aligned(16))) uint4 lds[2 * G::STAGE];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -139,6 +156,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_direct_f16x2_kernel(
     if (s >= S) return;
     const int bx = s % nbx, by = (s / nbx) % nby, b = s / (nbx * nby);
     const int x0 = 32 * bx, y0 = G::TR * by;            // (output coordinates)
+    const int u0 = DC_LT * bx;                          // LIN: the tile's first unit of the padded linear space
     const int HW = H * W;
     const int Hout = STR == 1 ? H : (H - 1) / 2 + 1, Wout = STR == 1 ? W : (W - 1) / 2 + 1;
     // Wavefront blocking: MB channel blocks x NB pixel rows.  Standard (2 x 4): channel pair mg = w % MG, row group ng = w / MG of four rows.  TAIL (3 x 2;
@@ -155,6 +173,20 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_direct_f16x2_kernel(
     for (int r = 0; r < G::R; ++r) {
         const int h = (G::NT * r + 64 * w) / G::PPAD;     // >= 2: this wavefront has no item in the (last, partial) round -- it stages zeros into the planes' padding
         const int p = G::NT * r + tid - h * G::PPAD;     // (no branch: the K loop stays ONE basic block and the scheduler spreads the staging over the MFMAs)
+        if constexpr (LIN > 0) {
+            // patch unit p is unit U = u0 - Pw - 1 + p of the padded linear space: pixel (U / Pw, U % Pw); rows -1 and H and the columns >= W are zeros.  The
+            // patch may fill the whole plane (no padding to park a write in): a wavefront without an item (wavefronts 2, 3 in the last round) repeats the item
+            // of the wavefront two below it, which that one stages in the same step from the same memory -- the same value twice, and every write address
+            // of a thread stays tid + a constant (one register for all rounds but the last).
+            const int il = G::NT * r + tid - (h < 2 ? 0 : 128), hl = (G::NT * r + 64 * w - (h < 2 ? 0 : 128)) / G::PPAD, pl = il - hl * G::PPAD;
+            const int U = u0 - Pw - 1 + pl;
+            const int yy = (int)((unsigned)max(U, 0) / (unsigned)Pw), xx = max(U, 0) - yy * Pw;
+            const bool ok = pl < DC_LT + 2 + 2 * Pw && U >= 0 && yy < H && xx < W;
+            voff[r] = ok ? (unsigned)(yy * W + xx) * 4u : DC_OOB;
+            hh[r] = hl;
+            wdst[r] = il;
+            continue;
+        }
         const int pr = p / G::PCW, q = p - pr * G::PCW;
         const int pc = STR == 1 ? q : 2 * (q % 33) + q / 33;                        // patch column of the staged unit (STR 2: [even | odd] halves)
         const int gy = STR * y0 - 1 + pr, gx = STR * x0 - 1 + pc;
@@ -191,8 +223,9 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_direct_f16x2_kernel(
         const int mbg = mb0 + m;
         return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsW, lane16, (unsigned)(mbg >> 1) * kstride + (unsigned)(((c * 9 + tap) * 2 + (mbg & 1)) * 3 + term) * 1024u, 0));
     };
-    const int rdb = (lane >> 5) * G::PPAD + (STR * NB * ng) * G::PCW + (lane & 31);
-    auto tapoff = [](int n, int dy, int dx) { return STR == 1 ? (n + dy) * G::PCW + dx : (2 * n + dy) * G::PCW + (dx & 1) * 33 + (dx >> 1); };
+    // LIN: block j = NB ng + n covers the units u0 + 32 j + (0 .. 31); tap (dy, dx) of unit u is patch unit (u - u0) + dy Pw + dx
+    const int rdb = (lane >> 5) * G::PPAD + (LIN ? 32 * NB * ng : (STR * NB * ng) * G::PCW) + (lane & 31);
+    auto tapoff = [](int n, int dy, int dx) { return LIN ? 32 * n + dx : STR == 1 ? (n + dy) * G::PCW + dx : (2 * n + dy) * G::PCW + (dx & 1) * 33 + (dx >> 1); };
 
     DC_STAMP(0);
     // ---- prologue: stage 0 (all rounds' loads in flight together: the accumulators are not live yet), the first two taps' weights
@@ -225,16 +258,18 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_direct_f16x2_kernel(
 
     // staging of step c + 1 inside step c, in phase units (27 per step): round r is requested in phase SL(r) and split + written in phase SW(r) -- four
     // or more phases (~1 k cycles) later, ONE register set (the next round is requested after this one is written)
-#define DC_SL(r) (G::R == 5 ? 5 * (r) : 8 * (r))
-#define DC_SW(r) (G::R == 5 ? ((r) == 4 ? 26 : 5 * (r) + 4) : ((r) == 2 ? 24 : 8 * (r) + 6))
+    // (R = 4, the linear geometry's PPAD 448: requests in phases 0, 6, 12, 18, writes five phases later, the last in phase 23)
+#define DC_SL(r) (G::R == 5 ? 5 * (r) : G::R == 4 ? 6 * (r) : 8 * (r))
+#define DC_SW(r) (G::R == 5 ? ((r) == 4 ? 26 : 5 * (r) + 4) : G::R == 4 ? 6 * (r) + 5 : ((r) == 2 ? 24 : 8 * (r) + 6))
     DC_STAMP(1);
     for (int c = 0; c < nks; ++c) {
         DC_STAMP(2 + 4 * (c & 7));
         __syncthreads();                                 // stage c complete (written during step c - 1 / the prologue); stage c - 1's buffer is free
         const uint4 *st = lds + (c & 1) * G::STAGE + rdb;
+        const uint4 *const strow[3] = {st, LIN ? st + Pw : st, LIN ? st + 2 * Pw : st};      // LIN: the row shift dy Pw is the one run-time part of a tap's address
         const int nbuf = (c + 1) & 1;
 #pragma unroll
-        for (int n = 0; n < NB; ++n) Bl[n] = st[2 * G::PPAD + tapoff(n, 0, 0)];
+        for (int n = 0; n < NB; ++n) Bl[n] = strow[0][2 * G::PPAD + tapoff(n, 0, 0)];
         DC_STAMP(3 + 4 * (c & 7));
         auto stage_event = [&](int phi) {
 #pragma unroll
@@ -249,7 +284,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_direct_f16x2_kernel(
             constexpr int dyn = (tap + 1) / 3, dxn = (tap + 1) - 3 * dyn;
             // phase 1: wq . xl  |  requests: this tap's xh, the OTHER set's wh (tap + 1)
 #pragma unroll
-            for (int n = 0; n < NB; ++n) Bh[n] = st[tapoff(n, dy, dx)];
+            for (int n = 0; n < NB; ++n) Bh[n] = strow[dy][tapoff(n, dy, dx)];
             __builtin_amdgcn_sched_barrier(0);           // the reads first: phase 2 needs them 8 MFMAs from here
 #pragma unroll
             for (int m = 0; m < MB; ++m) Ao[m][0] = aload(c, tap + 1, m, 0);
@@ -264,7 +299,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_direct_f16x2_kernel(
             for (int m = 0; m < MB; ++m) A[m][2] = aload(c, tap + 2, m, 2);
             if (tap < 8) {
 #pragma unroll
-                for (int n = 0; n < NB; ++n) Bl[n] = st[2 * G::PPAD + tapoff(n, dyn, dxn)];
+                for (int n = 0; n < NB; ++n) Bl[n] = strow[dyn % 3][2 * G::PPAD + tapoff(n, dyn, dxn)];
             }
             stage_event(3 * tap + 1);
 #pragma unroll
@@ -296,14 +331,25 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_direct_f16x2_kernel(
     const int H = Hout, W = Wout, HW = Hout * Wout;      // from here on: the OUTPUT image (they shadow the input's; the staging lambdas above keep the input's)
     // ---- epilogue: lane = pixel (row y0 + 4 ng + n, column x0 + (lane & 31)), register r of block m = channel cg64 * 64 + 32 m + (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     DC_STAMP(34);
+    // output pixel (oy, ox) of block n, pixel lp of the block's 32.  LIN: unit u = u0 + 32 (NB ng + n) + lp of the padded space; the positions with x >= W
+    // (the shared border columns) and y >= H (the last tile's overhang) are computed and discarded
+    auto opix = [&](int n, int lp, int &oy, int &ox) {
+        const int u = u0 + 32 * (NB * ng + n) + lp; oy = (int)((unsigned)u / (unsigned)Pw); ox = u - oy * Pw;
+    };
     float gchk = 0.f;
     if (guard) {
+        bool real[NB];                                   // LIN: a discarded position sums real neighbours of TWO rows -- not an output, not the guard's business
+#pragma unroll
+        for (int n = 0; n < NB; ++n) {
+            real[n] = true;
+            if constexpr (LIN > 0) { int oy, ox; opix(n, lane & 31, oy, ox); real[n] = oy < H && ox < W; }
+        }
 #pragma unroll
         for (int m = 0; m < MB; ++m)
 #pragma unroll
             for (int n = 0; n < NB; ++n)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) MFR_GUARD_ACC(gchk, acc[m][n][r]);      // before bias / residual / activation (guard.h)
+                for (int r = 0; r < 16; ++r) MFR_GUARD_ACC(gchk, LIN > 0 && !real[n] ? 0.f : acc[m][n][r]);      // before bias / residual / activation (guard.h)
         mfr_guard_commit(guard, gchk);
     }
     // The store tail.  Measured on the first versions (profiles/r06_dconv_timeline_*.json): (1) gfx950 returns loads AND stores through one in-order
@@ -313,7 +359,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_direct_f16x2_kernel(
     // INSTRUCTION, not per byte.  Hence: scale / bias are fetched once, before any store; every store is an unconditional buffer store; and where the
     // image width allows it (W % 4 == 0) each 32 x 32 accumulator block goes through 4 KB of wave-private LDS (lane = pixel -> lane = four consecutive
     // pixels of one channel) and leaves as FOUR 16-byte stores of eight full 128-byte lines instead of sixteen 4-byte ones.
-    const int px = x0 + (lane & 31);
+    const int px0 = x0 + (lane & 31);
     const int half = lane >> 5;
     const int Ho = POOL ? (H >> 1) : H, Wo = POOL ? (W >> 1) : W;
     const size_t cstride = (size_t)Ho * Wo;
@@ -330,7 +376,8 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_direct_f16x2_kernel(
         unsigned pixrow[NB];
 #pragma unroll
         for (int n = 0; n < NB; ++n) {
-            const int oy = y0 + NB * ng + n;
+            int oy = y0 + NB * ng + n, px = px0;
+            if constexpr (LIN > 0) opix(n, lane & 31, oy, px);
             pixrow[n] = (oy < H && px < W) ? (unsigned)(oy * W + px) * (unsigned)ldrows * 4u : DC_OOB;
         }
         DC_STAMP(36);
@@ -351,7 +398,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_direct_f16x2_kernel(
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(dc_u32x4, v), rsQ, cpart + pixrow[n], 0, 0);
                 }
             }
-    } else if (!(W & 3)) {
+    } else if (!(W & 3) && (LIN == 0 || !(Pw & 3))) {      // (LIN: Pw % 4 == 0 keeps four consecutive units in one row, all real or all discarded)
         const int L8 = lane >> 3, L7 = lane & 7;
         float os[MB][4], bv[MB][4];
         unsigned cho[MB][4];
@@ -367,7 +414,8 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_direct_f16x2_kernel(
         unsigned pix[NB];
 #pragma unroll
         for (int n = 0; n < NB; ++n) {
-            const int oy = y0 + NB * ng + n, xg = x0 + 4 * L7;
+            int oy = y0 + NB * ng + n, xg = x0 + 4 * L7;
+            if constexpr (LIN > 0) opix(n, 4 * L7, oy, xg);
             if (POOL) pix[n] = ((oy >> 1) < Ho && (xg >> 1) < Wo) ? (unsigned)((oy >> 1) * Wo + (xg >> 1)) * 4u : DC_OOB;      // (n even; W % 4 == 0: a pair is in or out as a whole)
             else      pix[n] = (oy < H && xg < W) ? (unsigned)(oy * W + xg) * 4u : DC_OOB;
         }
@@ -427,7 +475,8 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_direct_f16x2_kernel(
         unsigned pixoff[NB];
 #pragma unroll
         for (int n = 0; n < NB; ++n) {
-            const int oy = y0 + NB * ng + n;
+            int oy = y0 + NB * ng + n, px = px0;
+            if constexpr (LIN > 0) opix(n, lane & 31, oy, px);
             if (POOL) pixoff[n] = (!(lane & 1) && (oy >> 1) < Ho && (px >> 1) < Wo) ? (unsigned)((oy >> 1) * Wo + (px >> 1)) * 4u : DC_OOB;      // (n even)
             else      pixoff[n] = (oy < H && px < W) ? (unsigned)(oy * W + px) * 4u : DC_OOB;
         }
@@ -521,8 +570,30 @@ int mfr_conv3x3_direct_f16x2_filter_pack(const float *w, int Cin, int Cout, void
     return 0;
 }
 
+// What tile_mode 0 (auto) resolves to, per shape class: W range x Cout class (> 64: the only one with the geometry) x NCHW / rows output.  Filled from the A/B
+// record profiles/ab_direct_tiles.json (tools/ab_direct_tiles.py; 64 SuperPoint / 32 LoFTR images): a class is linear only where its median launch time
+// beat the 2-D tile's by more than the spread of the 2-D median over three repetitions.  A W range is the part of a 32-column band in which the 2-D
+// tile wastes at least what it wastes at the measured widths' far end (96 / 80, 160 / 144 columns computed per real one); every other shape keeps the 2-D tile.
+//     W          Cout                 output   2-D -> linear (ms)                                          measured at
+//     65 .. 80   128, 256             NCHW     0.394 -> 0.296, 0.765 -> 0.573, 0.744 -> 0.607 (residual)   W = 67, 68
+//     65 .. 80   256                  rows     0.747 -> 0.587                                              W = 67
+//    129 .. 144  128, 196, 256        NCHW     0.786 -> 0.700, 1.883 -> 1.738, 2.423 -> 2.218, 2.237 -> 2.046   W = 135, 136
+//    129 .. 144  any                  rows     not measured: 2-D
+// Pitch: W + 1.  W + 4 (16-byte rows, the LDS-exchange stores) measured within +-1.6 % of it on the W % 4 == 0 maps, faster on two shapes, slower on one.
+static bool dc_lin_auto(int W, int Cout, int ldrows)
+{
+    if (Cout <= 64) return false;
+    if (W >= 65 && W <= 80) return true;
+    if (W >= 129 && W <= 144) return ldrows == 0;
+    return false;
+}
+#define DC_LIN_AUTO(W, Cout, ldrows) dc_lin_auto(W, Cout, ldrows)
+// Largest pitch of the linear geometry per instantiation: 258 + 2 Pw patch units must fit the plane stride
+#define DC_LIN_PW_SMALL ((448 - DC_LT - 2) / 2)           /* 95 */
+#define DC_LIN_PW_LARGE ((576 - DC_LT - 2) / 2)           /* 159 */
+// tile_mode: 0 auto, 1 the 2-D tile (TR rows x 32 columns), 2 the linear tile (256 units of the padded space of pitch `pitch`; 0 = the default pitch)
 static int dc_conv(const float *x, const void *packed, const float *bias, const float *residual, int B, int Cin, int Cout, int H, int W,
-                   int act, int pool, float *y, int ldrows, void *stream)
+                   int act, int pool, float *y, int ldrows, int tile_mode, int pitch, void *stream)
 {
     if (!x || !packed || !y || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || act < 0 || act > 2) return MFR_E_ARG;
     if (pool && (H < 2 || W < 2 || residual)) return MFR_E_ARG;
@@ -533,16 +604,30 @@ static int dc_conv(const float *x, const void *packed, const float *bias, const 
     const float *oscale = (const float *)((const char *)packed + fb);
     const int mg = Cout > 64 ? 2 : 1;
     const int tr = 4 * DC_NW / mg;
-    const int nbx = (W + 31) / 32, nby = (H + tr - 1) / tr, ncgw = (Cout + 64 * mg - 1) / (64 * mg);
+    if (tile_mode < 0 || tile_mode > 2 || pitch < 0) return MFR_E_ARG;
+    // the linear geometry exists for the 2 x 4 / 3 x 2 blockings of four wavefronts, stride 1, no pooling, up to W = 158
+    const bool lin_ok = DC_NW == 4 && mg == 2 && !pool && W + 1 <= DC_LIN_PW_LARGE;
+    if (tile_mode == 0) tile_mode = (lin_ok && DC_LIN_AUTO(W, Cout, ldrows)) ? 2 : 1;
+    int nbx = (W + 31) / 32, nby = (H + tr - 1) / tr;
+    const int ncgw = (Cout + 64 * mg - 1) / (64 * mg);
+    if (tile_mode == 2) {
+        if (!pitch) pitch = W + 1;
+        if (!lin_ok || pitch < W + 1 || pitch > DC_LIN_PW_LARGE) return MFR_E_ARG;
+        nbx = (int)(((long long)H * pitch + DC_LT - 1) / DC_LT), nby = 1;      // tiles per image
+    }
     const long long S = (long long)nbx * nby * B;
     const long long grid = ((S + 7) / 8) * 8 * ncgw;
     if (grid > 0x7fffffffll) return MFR_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     int *guard = mfr_guard_current();
-#define DC_LAUNCH(MGV, POOLV) hipLaunchKernelGGL((conv_direct_f16x2_kernel<MGV, DC_NW, POOLV, 1>), dim3((unsigned)grid), dim3(64 * DC_NW), 0, st, x, (const uint4 *)packed, (unsigned)fb, oscale, bias, \
-                                                  residual, y, Cin, Cout, H, W, nbx, nby, (int)S, ncgw, nks, act, guard, ldrows)
-    if (mg == 1) { if (pool) DC_LAUNCH(1, true); else DC_LAUNCH(1, false); }
-    else         { if (pool) DC_LAUNCH(2, true); else DC_LAUNCH(2, false); }
+#define DC_LAUNCH(MGV, POOLV, LINV) hipLaunchKernelGGL((conv_direct_f16x2_kernel<MGV, DC_NW, POOLV, 1, LINV>), dim3((unsigned)grid), dim3(64 * DC_NW), 0, st, x, (const uint4 *)packed, (unsigned)fb, oscale, bias, \
+                                                        residual, y, Cin, Cout, H, W, nbx, nby, (int)S, ncgw, nks, act, guard, ldrows, pitch)
+#if DC_NW == 4
+    if (tile_mode == 2) { if (pitch <= DC_LIN_PW_SMALL) DC_LAUNCH(2, false, 448); else DC_LAUNCH(2, false, 576); }
+    else
+#endif
+    if (mg == 1) { if (pool) DC_LAUNCH(1, true, 0); else DC_LAUNCH(1, false, 0); }
+    else         { if (pool) DC_LAUNCH(2, true, 0); else DC_LAUNCH(2, false, 0); }
 #undef DC_LAUNCH
     CHECK_LAUNCH();
     return 0;
@@ -551,13 +636,20 @@ static int dc_conv(const float *x, const void *packed, const float *bias, const 
 int mfr_conv3x3_direct_f16x2(const float *x, const void *packed, const float *bias, const float *residual, int B, int Cin, int Cout, int H, int W,
                              int act, int pool, float *y, void *stream)
 {
-    return dc_conv(x, packed, bias, residual, B, Cin, Cout, H, W, act, pool, y, 0, stream);
+    return dc_conv(x, packed, bias, residual, B, Cin, Cout, H, W, act, pool, y, 0, 0, 0, stream);
+}
+
+int mfr_conv3x3_direct_f16x2_tiled(const float *x, const void *packed, const float *bias, const float *residual, int B, int Cin, int Cout, int H, int W,
+                                   int act, int pool, float *y, int ldrows, int tile_mode, int pitch, void *stream)
+{
+    if (ldrows < 0 || (ldrows > 0 && (ldrows < Cout || (ldrows & 3) || (Cout & 3) || pool || residual || H <= 0 || W <= 0 || (size_t)4 * ldrows * H * W >= 0x40000000ull))) return MFR_E_ARG;
+    return dc_conv(x, packed, bias, residual, B, Cin, Cout, H, W, act, pool, y, ldrows, tile_mode, pitch, stream);
 }
 
 int mfr_conv3x3_direct_f16x2_rows(const float *x, const void *packed, const float *bias, int B, int Cin, int Cout, int H, int W, int act, float *yrows, int ldy, void *stream)
 {
     if (ldy < Cout || (ldy & 3) || (Cout & 3) || H <= 0 || W <= 0 || (size_t)4 * ldy * H * W >= 0x40000000ull) return MFR_E_ARG;
-    return dc_conv(x, packed, bias, nullptr, B, Cin, Cout, H, W, act, 0, yrows, ldy, stream);
+    return dc_conv(x, packed, bias, nullptr, B, Cin, Cout, H, W, act, 0, yrows, ldy, 0, 0, stream);
 }
 
 int mfr_conv3x3s2_direct_f16x2(const float *x, const void *packed, const float *bias, int B, int Cin, int Cout, int H, int W, int act, float *y, void *stream)
@@ -574,7 +666,7 @@ int mfr_conv3x3s2_direct_f16x2(const float *x, const void *packed, const float *
     const long long grid = ((S + 7) / 8) * 8 * ncgw;
     if (grid > 0x7fffffffll) return MFR_E_ARG;
     hipLaunchKernelGGL((conv_direct_f16x2_kernel<4, 4, false, 2>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, (const uint4 *)packed, (unsigned)fb, oscale, bias,
-                       (const float *)nullptr, y, Cin, Cout, H, W, nbx, nby, (int)S, ncgw, nks, act, mfr_guard_current(), 0);
+                       (const float *)nullptr, y, Cin, Cout, H, W, nbx, nby, (int)S, ncgw, nks, act, mfr_guard_current(), 0, 0);
     CHECK_LAUNCH();
     return 0;
 }

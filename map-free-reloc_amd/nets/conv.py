@@ -8,6 +8,10 @@ Three hand-written kernels compute the same layer (include/mfr_hip.h):
                              splitting; the arithmetic is `HIP.SPLIT` ('f16x2', the default: three partial products; 'bf16x3': six),
                              resolved when the layer's filters are packed;
   * mfr_conv3x3_wino         (csrc/winograd_conv.hip)    the same transform on the exact-fp32 matrix cores.
+The direct kernel has two pixel tilings of the same K loop (`HIP.CONV_TILE`; bitwise the same output): the 2-D tile of 8 rows x 32 columns, and for
+the narrow maps (SuperPoint's 67- and 135-pixel levels, LoFTR's 68 and 136: 96 / 160 columns computed for 67 / 135) a LINEAR tile of 256 consecutive
+units of the image taken as one padded linear space (pitch W + 1), which computes ceil(H (W + 1) / 256) * 256 positions per image; which shape class
+runs which is a table in dc_conv (csrc/conv_direct.hip), filled from profiles/ab_direct_tiles.json (tools/ab_direct_tiles.py).
 All meet the same parity bar (<= 2e-5 against a float64 convolution, tests/test_gpu_winograd_*.py).  The split kernel tiles the image in
 blocks of 16 Winograd tiles along x; for the narrow odd-width maps of SuperPoint's 1/8 level (67 pixels = 34 tiles -> 48 computed) the
 exact-fp32 kernel's linear tiling wastes nothing, so the choice is made per layer shape, once, here (`HIP.CONV_KERNEL` forces one)."""
@@ -88,9 +92,20 @@ class WinoConv3x3:
         return y
 
 
+LINEAR_MAX_W = 158                  # widest map of the direct kernel's linear tiling (pitch W + 1 <= 159, csrc/conv_direct.hip)
+
+
 class DirectConv3x3:
     """the same 3x3 / stride 1 / pad 1 layer as a direct implicit GEMM with an LDS-staged halo tile (csrc/conv_direct.hip, mfr_conv3x3_direct_f16x2;
     f16x2 arithmetic only).  Same call signature as WinoConv3x3."""
+
+    def _tile_mode(self, W, pool):
+        """HIP.CONV_TILE -> tile_mode of mfr_conv3x3_direct_f16x2_tiled: 0 auto (the library's table), 1 the 2-D tile, 2 the linear tile.  'linear' means
+        linear wherever that geometry exists -- the other layers (pooled, Cout <= 64, wide maps) have the 2-D tile only"""
+        tile = options.get("CONV_TILE")
+        if tile == "linear":
+            return 2 if (self.co > 64 and not pool and W <= LINEAR_MAX_W) else 1
+        return 1 if tile == "rows" else 0
 
     def __init__(self, weight, bias):
         lib = _lib.load(require_gpu=True)
@@ -108,6 +123,11 @@ class DirectConv3x3:
         B, C, H, W = x.shape
         assert C == self.ci and x.dtype == torch.float32 and self.co % 4 == 0
         y = torch.empty(B, H, W, self.co, dtype=torch.float32, device=x.device)
+        mode = self._tile_mode(W, False)
+        if mode:
+            _lib.check(lib.mfr_conv3x3_direct_f16x2_tiled(_lib.ptr(x), _lib.ptr(self.packed), _lib.ptr(self.b), None, B, C, self.co, H, W, int(act), 0, _lib.ptr(y),
+                                                          self.co, mode, 0, _lib.stream_ptr()), "mfr_conv3x3_direct_f16x2_tiled")
+            return y
         _lib.check(lib.mfr_conv3x3_direct_f16x2_rows(_lib.ptr(x), _lib.ptr(self.packed), _lib.ptr(self.b), B, C, self.co, H, W, int(act), _lib.ptr(y), self.co,
                                                      _lib.stream_ptr()), "mfr_conv3x3_direct_f16x2_rows")
         return y
@@ -130,6 +150,11 @@ class DirectConv3x3:
         assert C == self.ci and x.dtype == torch.float32
         y = torch.empty((B, self.co, H // 2, W // 2) if pool else (B, self.co, H, W), dtype=torch.float32, device=x.device)
         res = _lib.ptr(residual.contiguous()) if residual is not None else None
+        mode = self._tile_mode(W, pool)
+        if mode:
+            _lib.check(lib.mfr_conv3x3_direct_f16x2_tiled(_lib.ptr(x), _lib.ptr(self.packed), _lib.ptr(self.b), res, B, C, self.co, H, W, int(act), int(pool),
+                                                          _lib.ptr(y), 0, mode, 0, _lib.stream_ptr()), "mfr_conv3x3_direct_f16x2_tiled")
+            return y
         _lib.check(lib.mfr_conv3x3_direct_f16x2(_lib.ptr(x), _lib.ptr(self.packed), _lib.ptr(self.b), res, B, C, self.co, H, W, int(act), int(pool),
                                                 _lib.ptr(y), _lib.stream_ptr()), "mfr_conv3x3_direct_f16x2")
         return y

@@ -9,6 +9,10 @@ merge) through `apply_cfg(cfg)`, or directly by a tool / test (`options.set("CON
   CONV              'wino' (own Winograd kernels) | 'miopen' (library convolution + own epilogue kernels): 3x3 layers of the matchers
   CONV_KERNEL       'auto' (nets/conv.py: f16x2 -> the direct halo-staged kernel, round 6; bf16x3 -> split / exact Winograd per layer shape) | 'direct'
                     (csrc/conv_direct.hip, f16x2 only) | 'split' (the operand-splitting Winograd kernel, arithmetic = SPLIT) | 'exact' (fp32 Winograd): which own 3x3 kernel
+  CONV_TILE         'auto' | 'rows' | 'linear': pixel tiling of the direct 3x3 kernel (csrc/conv_direct.hip).  'rows' = the 2-D tile of 8 rows x 32 columns
+                    everywhere; 'linear' = 256 consecutive units of the padded linear pixel space wherever that geometry exists (Cout > 64, no pooling,
+                    W <= 158: the narrow maps, where the 2-D tile computes up to 35 % positions that do not exist), 2-D elsewhere; 'auto' = the per-shape
+                    table in dc_conv, from profiles/ab_direct_tiles.json.  The same bits either way
   FUSED_CONV1       SuperPoint conv1a + conv1b (+ ReLUs, max-pool) as ONE kernel that builds conv1b's input patches in LDS (True, f16x2 only) or as
                     two launches through the 6.4 GB intermediate (False); the same bits either way
   FUSED_CONV_RELU   SuperPoint conv1a through the fused first-layer kernel with ReLU folded (True / False)
@@ -23,6 +27,7 @@ _SPEC = {
     "SPLIT": ("f16x2", ("f16x2", "bf16x3")),
     "CONV": ("wino", ("wino", "miopen")),
     "CONV_KERNEL": ("auto", ("auto", "split", "exact", "direct")),
+    "CONV_TILE": ("auto", ("auto", "rows", "linear")),
     "FUSED_CONV1": (True, (False, True)),
     "FUSED_CONV_RELU": (False, (False, True)),
     "RPR_CONV": ("hip", ("hip", "miopen")),

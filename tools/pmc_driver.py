@@ -1,5 +1,6 @@
 """One isolated kernel, launched a few times, for `rocprofv3 --pmc` passes (tools/pmc_kernel.sh): python tools/pmc_driver.py <what> [split]
 what: conv1ab (SuperPoint conv1a fused into conv1b, 64 images 720x540), gemm (the 512 -> 512 + ReLU layer at M = 65536), gemm_qkv (256 -> 768), conv1b (64 -> 64 channels, 64 images 720x540, pooled), attention (64 images x 4 heads x 1024),
+      dconv_conv4a / dconv_conv3a[_rows2d | _linear] (the direct kernel on SuperPoint's 90x67 / 180x135 maps, either pixel tiling),
       loftr_l1out2 (196 -> 196 at 360x272, 32 images), loftr_gemm (256 -> 256 at M = 195840), sinkhorn (32 pairs x 1024^2, 20 sweeps)"""
 import os
 import sys
@@ -32,6 +33,14 @@ elif what in ("dconv_l1", "dconv_conv2a", "dconv_l1out2"):      # the direct hal
     r = torch.randn(B, co, H, W, device=dev) if res else None
     cv = DirectConv3x3(w, b)
     fn = lambda: cv(x, act=act, residual=r)
+elif what.startswith(("dconv_conv4a", "dconv_conv3a")):      # SuperPoint's narrow maps at the bench batch; suffix _rows2d / _linear forces HIP.CONV_TILE (default: auto)
+    from mapfree_reloc_amd.nets.conv import DirectConv3x3
+    B, ci, co, H, W = (64, 128, 128, 90, 67) if "conv4a" in what else (64, 64, 128, 180, 135)
+    if what.endswith(("_rows2d", "_linear")):
+        options.set("CONV_TILE", "rows" if what.endswith("_rows2d") else "linear")
+    x = torch.randn(B, ci, H, W, device=dev); w = torch.randn(co, ci, 3, 3, device=dev) / (3.0 * ci ** 0.5); b = torch.randn(co, device=dev)
+    cv = DirectConv3x3(w, b)
+    fn = lambda: cv(x, act=1)
 elif what == "conv1ab":
     from mapfree_reloc_amd.nets.superpoint import SuperPointHIP
     from mapfree_reloc_amd.nets import weights as WT
