@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define MFR_ABI_VERSION 6   /* 6 (round 6): mfr_conv3x3_direct_f16x2*, later (additive) the SIFT detector mfr_sift_*, the JPEG decoder mfr_jpeg_*, mfr_resize_gray_bilinear (the device image resize), mfr_conv3x3s2_direct_f16x2, mfr_mlp_ln_*, mfr_loftr_ot_match (LoFTR's optimal-transport coarse matching), mfr_abs_pose_fuse (7Scenes: absolute pose from relative poses); 5 (round 6): mfr_f16x2_guard_bind (the f16x2 range guard); 2: intrinsics as (const void *K, int k_dtype) instead of const float *; 3: mfr_emat_solve_batch takes the
+#define MFR_ABI_VERSION 6   /* 6 (round 6): mfr_conv3x3_direct_f16x2*, later (additive) the SIFT detector mfr_sift_*, the JPEG decoder mfr_jpeg_*, the depth PNG decoder mfr_png_depth_*, mfr_resize_gray_bilinear (the device image resize), mfr_conv3x3s2_direct_f16x2, mfr_mlp_ln_*, mfr_loftr_ot_match (LoFTR's optimal-transport coarse matching), mfr_abs_pose_fuse (7Scenes: absolute pose from relative poses); 5 (round 6): mfr_f16x2_guard_bind (the f16x2 range guard); 2: intrinsics as (const void *K, int k_dtype) instead of const float *; 3: mfr_emat_solve_batch takes the
                              * model-quality method (MAGSAC++ / count) and its table; 4 (round 5): the f16x2 entry points (mfr_gemm_f16x2*,
                              * mfr_wino_f16x2_*, mfr_conv3x3_wino_f16x2, mfr_conv_igemm_f16x2), mfr_sg_attention_variant renumbered (0 f16x2,
                              * 1 exact fp32, 2 bf16x3), the measurement-only entry points (mfr_conv3x3_wino_bf16x3_variant,
@@ -567,6 +567,25 @@ size_t mfr_jpeg_workspace_bytes(int n, int H, int W, long long max_record_bytes,
 int mfr_jpeg_decode(const void *headers, const uint8_t *records, const long long *offsets, int n, int H, int W,
                     long long max_record_bytes, float *gray, uint8_t *rgb, int32_t *status, int32_t *rounds, void *workspace,
                     size_t workspace_bytes, int subseq_bits, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * 16-bit gray (millimetre depth) PNG decode (csrc/png.hip): non-interlaced colour type 0 / bit depth 16 files -> the loaders'
+ * depth plane, bit for bit datasets.read_depth_plane(path): float32(uint16 / 1000.0).  Call site: the batched loaders of
+ * predict_fused with HIP.DEPTH_DECODE 'device' (datasets.PairBatchLoader / DevicePrefetcher, png_ops.DepthPngDecoder).  The host
+ * half is csrc/host_decode.c mfr_host_png_parse (libmfr_host.so), which writes one mfr_png_header and one record (the joined IDAT
+ * payloads) per file (include/mfr_png.h).  Added to ABI v6 without a version bump (purely additive).
+ *   mfr_png_depth_workspace_bytes  scratch of mfr_png_depth_decode for n images of H x W (the filtered scanlines, H (1 + 2 W) bytes
+ *                                per image, 256-aligned); 0 for unsupported arguments (H or W above 65535, H (1 + 2 W) >= 2^31)
+ *   mfr_png_depth_decode         headers [n] (device), records (device, offsets [n+1] i64 bytes, each a multiple of 16; record i
+ *                                lies in [offsets[i], offsets[i+1]) and ends with >= 8 bytes after its stream) -> out [n,H,W] f32,
+ *                                status [n] (0 ok; a parse code of the header passed through; MFR_PNG_E_* from the device).  A row
+ *                                whose status is not 0 keeps its out plane untouched.  One wavefront per image: inflate (RFC 1950 /
+ *                                1951: stored, fixed and dynamic blocks), size and Adler-32 check, filters 0-4, big-endian sample
+ *                                / 1000.0 in f64 rounded to f32.  No input makes it read or write out of bounds or loop forever.
+ */
+size_t mfr_png_depth_workspace_bytes(int n, int H, int W);
+int mfr_png_depth_decode(const void *headers, const uint8_t *records, const long long *offsets, int n, int H, int W,
+                         long long max_record_bytes, void *scratch, size_t scratch_bytes, float *out, int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Gray plane of decoded RGB images at another size (csrc/resize.hip): rgb [n,H,W,3] u8 (mfr_jpeg_decode's) -> out [n,1,h,w] f32,

@@ -117,6 +117,8 @@ SIGNATURES = {
     "mfr_sift_detect": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mfr_jpeg_workspace_bytes": (_sz, [_i, _i, _i, C.c_longlong, _i]),
     "mfr_jpeg_decode": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
+    "mfr_png_depth_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mfr_png_depth_decode": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_longlong, _vp, _sz, _vp, _vp, _vp]),
     "mfr_resize_gray_bilinear": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "mfr_scale_workspace_bytes": (_sz, [_i, _i]),
     "mfr_scale_from_depth_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp,

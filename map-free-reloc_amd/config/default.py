@@ -21,6 +21,11 @@ keys this implementation adds (declared here because unknown keys are rejected o
                      'device' has them only parse baseline JPEGs into packed slots that DevicePrefetcher decodes on the GPU (jpeg_ops.py,
                      csrc/jpeg.hip; same planes bit for bit); other files, depth PNGs and resized / synthetic scenes stay on the host route;
                      validated by datasets.check_jpeg_decode;
+                     DEPTH_DECODE: 'host' | 'device' -- orthogonal to both: 'host' (default) decodes the 16-bit depth PNGs with PIL + zlib on the
+                     workers; 'device' has them only join the IDAT chunks of non-interlaced 16-bit gray files into the row's own depth plane,
+                     and DevicePrefetcher inflates, unfilters and converts them on the GPU (png_ops.py, csrc/png.hip; same planes bit for bit);
+                     other PNGs and every other route (generic samples, multi-frame / resized scenes, ScanNet / 7Scenes, regression loaders)
+                     stay on the host; validated by datasets.check_depth_decode;
                      CONV / CONV_KERNEL / FUSED_CONV_RELU / RPR_CONV / RPR_CONV_BWD / RPR_CONV_ORDER / RPR_WGRAD_SPLITS: which of two
                      implementations of a layer runs (A/B measurement, parity tests) -- options.py lists values and defaults
   LOFTR.WEIGHTS      checkpoint of the online LoFTR matcher ('LoFTR' feature matching)
@@ -84,7 +89,7 @@ def get_cfg_defaults():
     # ---- additions of this implementation ----
     c.RANSAC = CN(); c.RANSAC.SEED = 0
     c.HIP = CN(); c.HIP.BATCH_PAIRS = 16; c.HIP.MAX_KEYPOINTS = 1024; c.HIP.MAX_CORRESPONDENCES = 8192; c.HIP.GRAPH_BATCH1 = True; c.HIP.GRAPH_FUSED = False
-    c.HIP.EMAT_SCORE = 'magsac'; c.HIP.MAGSAC_MAX_THR_RATIO = 1.0; c.HIP.REF_FEATURE_CACHE = True; c.HIP.LOADER_DECODE = 'process'; c.HIP.JPEG_DECODE = 'host'; c.HIP.LOADER_WORKERS = 0
+    c.HIP.EMAT_SCORE = 'magsac'; c.HIP.MAGSAC_MAX_THR_RATIO = 1.0; c.HIP.REF_FEATURE_CACHE = True; c.HIP.LOADER_DECODE = 'process'; c.HIP.JPEG_DECODE = 'host'; c.HIP.DEPTH_DECODE = 'host'; c.HIP.LOADER_WORKERS = 0
     from .. import options as _opt                     # kernel-selection options (options.py): declared with their defaults, applied by apply_cfg
     for _k in _opt.names():
         c.HIP[_k] = _opt.default(_k)

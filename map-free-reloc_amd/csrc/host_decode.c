@@ -7,7 +7,8 @@
  * the SAME rounded values the numpy expressions produce (the tables are built by numpy in datasets.py); what this file saves is the
  * intermediate arrays and, for the caller, one copy: the results are written straight into the batch slot.  Plain C, no dependencies;
  * not a compute path of the GPU product (that is libmfr_hip.so) -- without this library datasets.py runs the numpy expressions.
- * Since ABI 3 it also holds the host half of the device JPEG decoder (mfr_host_jpeg_parse below; jpeg_ops.py).
+ * Since ABI 3 it also holds the host half of the device JPEG decoder (mfr_host_jpeg_parse below; jpeg_ops.py), since ABI 4 that of
+ * the device depth PNG decoder (mfr_host_png_parse at the end; png_ops.py).
  */
 #include <stddef.h>
 #include <stdint.h>
@@ -25,7 +26,7 @@ void mfr_host_depth_from_u16(const uint16_t *d, size_t n, const float *lut, floa
     for (size_t i = 0; i < n; ++i) out[i] = lut[d[i]];
 }
 
-int mfr_host_abi_version(void) { return 3; }   /* 3: mfr_host_jpeg_parse */
+int mfr_host_abi_version(void) { return 4; }   /* 3: mfr_host_jpeg_parse; 4: mfr_host_png_parse */
 
 /* ---- baseline JPEG: header parse + entropy-segment preparation for the device decoder (csrc/jpeg.hip) ----
  * ITU-T T.81: markers B.1, frame / scan headers B.2, tables B.2.4, restart intervals B.2.4.4 and F.1.2.3, canonical Huffman codes C.
@@ -275,3 +276,82 @@ int mfr_host_jpeg_parse(const uint8_t *buf, size_t n, mfr_jpeg_header *h, uint8_
 /* worst-case record size of a file of n bytes with up to nseg restart segments */
 size_t mfr_host_jpeg_record_bound(size_t n, int nseg) { return (((size_t)nseg * 8 + 15) & ~(size_t)15) + n + 48; }
 size_t mfr_host_jpeg_header_bytes(void) { return sizeof(mfr_jpeg_header); }
+
+/* ---- 16-bit gray PNG: chunk walk + IDAT concatenation for the device decoder (csrc/png.hip) ----
+ * PNG 1.2: signature 3.1, chunk layout 3.2, IHDR 4.1.1, IDAT 4.1.3 (consecutive), IEND 4.1.4; the zlib header RFC 1950 2.2.
+ * Chunk CRCs are NOT verified (the stream's Adler-32 is, on the device).  Ancillary chunks are skipped; trailing bytes after IEND are
+ * ignored.  Every read is bounded by n, every write by cap.  Layout: include/mfr_png.h. */
+#include "mfr_png.h"
+
+static uint32_t be32at(const uint8_t *b) { return ((uint32_t)b[0] << 24) | ((uint32_t)b[1] << 16) | ((uint32_t)b[2] << 8) | b[3]; }
+
+/* buf[0..n) -> *h and the record out[0..cap); *rec_bytes = the record's size.  Returns MFR_PNG_OK / _UNSUPPORTED / _INVALID / _CAPACITY
+ * (also in h->status).  Two walks over the chunks: the first validates and sizes, the second copies. */
+int mfr_host_png_parse(const uint8_t *buf, size_t n, mfr_png_header *h, uint8_t *out, size_t cap, size_t *rec_bytes)
+{
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+    memset(h, 0, sizeof(*h));
+    *rec_bytes = 0;
+#define FAIL(code) do { h->status = (code); return (code); } while (0)
+    if (n < 8 || memcmp(buf, sig, 8)) FAIL(MFR_PNG_INVALID);
+    size_t pos = 8, first_idat = 0, stream = 0;
+    int idat = 0, end = 0, first = 1;                                    /* idat: 0 none yet, 1 inside the run, 2 the run is over */
+    uint8_t zh[2] = {0, 0};                                              /* the stream's first two bytes (they may lie in two chunks) */
+    while (!end) {
+        if (n - pos < 12) FAIL(MFR_PNG_INVALID);
+        const uint32_t len = be32at(buf + pos);
+        const uint8_t *type = buf + pos + 4;
+        if (len > 0x7FFFFFFFu || (size_t)len > n - pos - 12) FAIL(MFR_PNG_INVALID);
+        const uint8_t *d = buf + pos + 8;
+        if (first) {
+            if (memcmp(type, "IHDR", 4) || len != 13) FAIL(MFR_PNG_INVALID);
+            const uint32_t w = be32at(d), ht = be32at(d + 4);
+            if (w == 0 || ht == 0 || w > 0x7FFFFFFFu || ht > 0x7FFFFFFFu) FAIL(MFR_PNG_INVALID);
+            const int bd = d[8], ct = d[9];
+            const int ok = ct == 0 ? (bd == 1 || bd == 2 || bd == 4 || bd == 8 || bd == 16)
+                         : ct == 3 ? (bd == 1 || bd == 2 || bd == 4 || bd == 8)
+                         : (ct == 2 || ct == 4 || ct == 6) ? (bd == 8 || bd == 16) : 0;
+            if (!ok || d[10] != 0 || d[11] != 0 || d[12] > 1) FAIL(MFR_PNG_INVALID);
+            h->width = (int32_t)w; h->height = (int32_t)ht; h->bit_depth = bd; h->color_type = ct; h->interlace = d[12];
+            first = 0;
+        } else if (!memcmp(type, "IHDR", 4)) {
+            FAIL(MFR_PNG_INVALID);
+        } else if (!memcmp(type, "IDAT", 4)) {
+            if (idat == 2) FAIL(MFR_PNG_INVALID);                        /* another chunk between two IDATs */
+            if (idat == 0) first_idat = pos;
+            idat = 1;
+            for (uint32_t k = 0; k < len && stream + k < 2; ++k) zh[stream + k] = d[k];
+            stream += len;
+            if (stream > 0x7FFFFFFFu) FAIL(MFR_PNG_INVALID);
+        } else if (!memcmp(type, "IEND", 4)) {
+            if (idat == 0 || len != 0) FAIL(MFR_PNG_INVALID);
+            end = 1;
+        } else {
+            if (idat == 1) idat = 2;
+            if (!(type[0] & 0x20) && memcmp(type, "PLTE", 4)) FAIL(MFR_PNG_INVALID);   /* an unknown critical chunk */
+        }
+        pos += 12 + (size_t)len;
+    }
+    if (stream < 2 || (zh[0] & 15) != 8 || ((zh[0] << 8) | zh[1]) % 31 != 0) FAIL(MFR_PNG_INVALID);
+    if (h->color_type != 0 || h->bit_depth != 16 || h->interlace != 0) FAIL(MFR_PNG_UNSUPPORTED);
+    if ((zh[0] >> 4) > 7 || (zh[1] & 0x20)) FAIL(MFR_PNG_UNSUPPORTED);   /* window above 32 KiB, preset dictionary */
+    const size_t rec = (stream + 8 + 15) & ~(size_t)15;
+    if (cap < rec) FAIL(MFR_PNG_CAPACITY);
+    size_t o = 0;
+    for (pos = first_idat; o < stream; ) {                               /* the run was validated above: consecutive, inside [0, n) */
+        const uint32_t len = be32at(buf + pos);
+        memcpy(out + o, buf + pos + 8, len);
+        o += len;
+        pos += 12 + (size_t)len;
+    }
+    memset(out + o, 0, rec - o);
+    h->stream_bytes = (int32_t)stream;
+    h->record_bytes = (int32_t)rec;
+    *rec_bytes = rec;
+#undef FAIL
+    return MFR_PNG_OK;
+}
+
+/* record size of a file of n bytes (always enough: the stream is shorter than the file) */
+size_t mfr_host_png_record_bound(size_t n) { return (n + 8 + 15) & ~(size_t)15; }
+size_t mfr_host_png_header_bytes(void) { return sizeof(mfr_png_header); }

@@ -180,7 +180,7 @@ _HOST_LIB = False           # False = not looked for yet, None = absent (numpy e
 
 
 def _host_lib():
-    """csrc/libmfr_host.so (host_decode.c: the loaders' two per-pixel loops in C, ABI 3: and the JPEG parse of jpeg_ops), or None -- then the
+    """csrc/libmfr_host.so (host_decode.c: the loaders' two per-pixel loops in C, ABI 4: and the JPEG / PNG parses of jpeg_ops / png_ops), or None -- then the
     numpy expressions run"""
     global _HOST_LIB
     if _HOST_LIB is False:
@@ -194,7 +194,10 @@ def _host_lib():
             lib.mfr_host_jpeg_parse.argtypes = [vp, sz, vp, vp, sz, vp]; lib.mfr_host_jpeg_parse.restype = ctypes.c_int
             lib.mfr_host_jpeg_record_bound.argtypes = [sz, ctypes.c_int]; lib.mfr_host_jpeg_record_bound.restype = sz
             lib.mfr_host_jpeg_header_bytes.argtypes = []; lib.mfr_host_jpeg_header_bytes.restype = sz
-            _HOST_LIB = lib if lib.mfr_host_abi_version() == 3 else None
+            lib.mfr_host_png_parse.argtypes = [vp, sz, vp, vp, sz, vp]; lib.mfr_host_png_parse.restype = ctypes.c_int
+            lib.mfr_host_png_record_bound.argtypes = [sz]; lib.mfr_host_png_record_bound.restype = sz
+            lib.mfr_host_png_header_bytes.argtypes = []; lib.mfr_host_png_header_bytes.restype = sz
+            _HOST_LIB = lib if lib.mfr_host_abi_version() == 4 else None
         except (OSError, AttributeError):
             _HOST_LIB = None
     return _HOST_LIB
@@ -358,12 +361,17 @@ class MapFreeScene:
                     _FRAME_CACHE.popitem(last=False)
         return img, d
 
-    def _gray_frame(self, rel, keep=False, out_g=None, out_d=None, reader=None):
+    def _gray_frame(self, rel, keep=False, out_g=None, out_d=None, reader=None, depth_reader=None):
         """(gray plane [h,w] f32, depth [h,w] f32 or None) of one frame as numpy arrays -- to_gray(image) / depth of _frame(rel), bit for bit at
         the file's own size (gray_pair, the only caller, refuses other sizes), without the float RGB image, decoded straight into out_g / out_d when given; keep=True: the same small least-recently-used cache as
-        _frame under its own keys (the cached arrays are copied into out_g / out_d)"""
+        _frame under its own keys (the cached arrays are copied into out_g / out_d).  depth_reader: a callable (path, out_d) that takes
+        the place of read_depth_plane (the device depth route, _png_reader): the depth map is then neither cached nor returned"""
         path = os.path.join(self.scene_root, rel)
         dpath = path.replace(".jpg", f".{self.estimated_depth}.png") if self.estimated_depth is not None else None
+        if depth_reader is not None:
+            if dpath and out_d is not None:
+                depth_reader(dpath, out_d)
+            dpath = None                                        # below: the gray plane alone (cached under a key of its own)
         if reader is not None:                                  # the device JPEG route: the reader prepares the file for the device
             return (reader(path, out_g) if out_g is not None else None), (read_depth_plane(dpath, out_d) if dpath else None)
         if not keep:
@@ -373,7 +381,7 @@ class MapFreeScene:
             ident = (st.st_mtime_ns, st.st_size)
         except OSError:
             ident = None
-        key = ("gray", self.scene_root, rel, ident, tuple(self.resize) if self.resize is not None else None, self.estimated_depth)
+        key = ("gray", self.scene_root, rel, ident, tuple(self.resize) if self.resize is not None else None, self.estimated_depth if dpath else None)
         with _FRAME_LOCK:
             hit = _FRAME_CACHE.get(key)
             if hit is not None:
@@ -392,6 +400,7 @@ class MapFreeScene:
         return g, d
 
     has_gray_pair = True        # the loaders' fast path (an explicit capability: subclasses whose pairs are not (frame, frame) switch it off)
+    has_depth_readers = True    # gray_pair takes depth_readers (the device depth route); readers with a gray_pair of their own do not
 
     def resize_is_native(self):
         """is cfg's (W, H) the size the files have (Map-free: 540 x 720, config/mapfree.yaml)?  Only then is the gray plane route-independent: the
@@ -401,21 +410,23 @@ class MapFreeScene:
         route, so the batched loaders, the reference-view cache and the per-pair plugin see ONE plane."""
         return self.resize is None or all(sz == (int(self.resize[0]), int(self.resize[1])) for sz in self._file_sizes)
 
-    def gray_pair(self, index, want_ref=True, out=None, readers=None):
+    def gray_pair(self, index, want_ref=True, out=None, readers=None, depth_readers=None):
         """what the batched loaders need of sample `index`: (gray0 or None, depth0, gray1, depth1, K0, K1, pair_id, (name0, name1)), numpy arrays
         with the values of to_gray(self[index]['image0' / 'image1']) and its depth maps -- bit for bit AT THE FILES' OWN SIZE, the only case this
         route serves (resize_is_native(); otherwise None).  out = (g0, d0, g1, d1) destination arrays (entries
         may be None): the planes are then decoded / copied straight into them.  Returns None when this scene's images are not plain RGB reads
         (black_white training transform): the caller takes the generic sample then.  readers = (reader0, reader1): callables (path, out_g)
-        that take the place of read_gray_plane for the two frames (the device JPEG route, _jpeg_reader); depth is read as usual."""
+        that take the place of read_gray_plane for the two frames (the device JPEG route, _jpeg_reader); depth_readers = (reader0, reader1):
+        callables (path, out_d) that take the place of read_depth_plane (the device depth route, _png_reader; d0 / d1 are then None)."""
         if self.black_white or not self.resize_is_native():
             return None
         sa, ia, sb, ib = self.pairs[index]
         p1, p2 = f"seq{sa}/frame_{ia:05}.jpg", f"seq{sb}/frame_{ib:05}.jpg"
         og0, od0, og1, od1 = out if out is not None else (None, None, None, None)
         r0, r1 = readers if readers is not None else (None, None)
-        g0, d0 = self._gray_frame(p1, keep=True, out_g=og0 if want_ref else None, out_d=od0, reader=r0)
-        g1, d1 = self._gray_frame(p2, out_g=og1, out_d=od1, reader=r1)
+        dr0, dr1 = depth_readers if depth_readers is not None else (None, None)
+        g0, d0 = self._gray_frame(p1, keep=True, out_g=og0 if want_ref else None, out_d=od0, reader=r0, depth_reader=dr0)
+        g1, d1 = self._gray_frame(p2, out_g=og1, out_d=od1, reader=r1, depth_reader=dr1)
         return (g0 if want_ref else None, d0, g1, d1, self.K[p1].copy(), self.K[p2].copy(), index * self.sample_factor, (p1, p2))
 
     def __getitem__(self, index):
@@ -628,6 +639,65 @@ def _jpeg_reader(hdr, rec, row, info):
     return read
 
 
+DEPTH_DECODE_MODES = ("host", "device")
+
+
+def check_depth_decode(mode):
+    """HIP.DEPTH_DECODE: 'host' (PIL + zlib on the decode workers, the default) | 'device' (workers join the PNG's IDAT chunks, png_ops
+    inflates, unfilters and converts on the GPU)"""
+    if mode not in DEPTH_DECODE_MODES:
+        raise ValueError(f"HIP.DEPTH_DECODE must be one of {DEPTH_DECODE_MODES}, got {mode!r}")
+    return mode
+
+
+def _png_reader(row, info):
+    """gray_pair depth reader of the device depth route for row `row` = (0 | 1: depth0 / depth1, pair position): the file's record (its zlib
+    stream) goes into the row's own float plane -- H W 4 bytes always hold the stream of an H x W 16-bit image -- and info[row] = (0, record
+    bytes, path, header bytes); a file the device does not take (unsupported, invalid, a record above the plane's size) is decoded here as
+    on the host route, into the plane, and info[row] = (parse status, 0, path, None)"""
+    def read(path, out_d):
+        from . import png_ops as P
+        with open(path, "rb") as f:
+            data = f.read()
+        assert out_d.dtype == np.float32 and out_d.flags["C_CONTIGUOUS"]
+        slot = out_d.reshape(-1).view(np.uint8)
+        hdr = np.zeros(P.HEADER_BYTES, dtype=np.uint8)
+        st, nb = P.parse_into(data, hdr, slot[:slot.size // 16 * 16])
+        if st == P.OK:
+            info[row] = (0, nb, path, hdr.tobytes())
+        else:
+            read_depth_plane(path, out_d)
+            info[row] = (st, 0, path, None)
+        return out_d
+    return read
+
+
+def _png_skip(path, out_d):
+    """depth reader of a reference view that another row of the batch decodes (the device duplicates it)"""
+    return out_d
+
+
+def _png_rows(b, want, first_of_p, infos, mk):
+    """the device depth route's part of a batch of b pairs: rows 0..b-1 are depth0's, b..2b-1 depth1's.  rows[r] = None (the plane holds
+    host-decoded depth), (0, record bytes, path) (it holds the file's record) or ("dup", source row); headers u8 [2b, HEADER_BYTES], rows
+    the device must not touch marked unsupported.  infos[p]: pair p's _png_reader entries (empty: the pair took the generic route)"""
+    from . import png_ops as P
+    headers = mk(2 * b, P.HEADER_BYTES, dtype=torch.uint8)
+    h_np = headers.numpy()
+    h_np[...] = 0
+    h_np[:, :4].view(np.int32)[:, 0] = P.UNSUPPORTED
+    rows = [None] * (2 * b)
+    for p, info in enumerate(infos):
+        for (which, _), v in info.items():
+            if v[0] == 0:
+                r = which * b + p
+                rows[r] = v[:3]
+                h_np[r] = np.frombuffer(v[3], dtype=np.uint8)
+        if info and not want[p]:
+            rows[p] = ("dup", first_of_p[p])
+    return dict(headers=headers, rows=rows)
+
+
 def _slot_views(flat, n_slots, B, Hh, Ww, has_depth):
     """carve the ring's batch slots out of ONE shared tensor (one shared-memory segment = one descriptor per worker)"""
     per = 2 * B * Hh * Ww + (2 * B * Hh * Ww if has_depth else 0)
@@ -649,7 +719,7 @@ def _jpeg_views(jflat, n_slots, B, cap):
             for k in range(n_slots)]
 
 
-def _pw_init(scenes, flat, layout, jflat=None, jcap=0):
+def _pw_init(scenes, flat, layout, jflat=None, jcap=0, png=False):
     # Everything inherited from the parent becomes permanent in this process: a garbage-collection pass of the child must never finalise the
     # PARENT's objects -- a dead multiprocessing.Pool of an earlier loader among them, whose __del__ writes to a queue under a lock that a
     # thread of the parent may have held at fork time (the child then waits for it for ever: round 5's first full CPU test run hung exactly
@@ -659,6 +729,7 @@ def _pw_init(scenes, flat, layout, jflat=None, jcap=0):
     torch.set_num_threads(1)
     _PW["scenes"], _PW["slots"] = scenes, _slot_views(flat, *layout)
     _PW["jslots"] = _jpeg_views(jflat, layout[0], layout[1], jcap) if jflat is not None else None
+    _PW["png"] = bool(png)
 
 
 def _pw_fill(task):
@@ -675,11 +746,14 @@ def _pw_fill(task):
         if _PW["jslots"] is not None:                        # device JPEG route: headers + records into the slot's packed buffers
             hdr, rec = (t.numpy() for t in _PW["jslots"][k])
             readers = (_jpeg_reader(hdr, rec, 2 * p, info), _jpeg_reader(hdr, rec, 2 * p + 1, info))
+        pinfo, kw = {}, {}
+        if _PW["png"] and has_d and getattr(sc, "has_depth_readers", False):     # device depth route: the records into the depth planes
+            kw = dict(depth_readers=(_png_reader((0, p), pinfo) if want_ref else _png_skip, _png_reader((1, p), pinfo)))
         fast = sc.gray_pair(i, want_ref, out=(im[2 * p, 0], sl["depth0"].numpy()[p] if has_d else None, im[2 * p + 1, 0],
-                                              sl["depth1"].numpy()[p] if has_d else None), readers=readers)
+                                              sl["depth1"].numpy()[p] if has_d else None), readers=readers, **kw)
         if fast is not None:
             _, _, _, _, K0, K1, pid, (n0, n1) = fast
-            return (np.asarray(K0), np.asarray(K1), int(pid), n1, n0, _t.perf_counter() - t0, info)
+            return (np.asarray(K0), np.asarray(K1), int(pid), n1, n0, _t.perf_counter() - t0, info, pinfo)
     smp = sc[i]
     npv = lambda t: t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
     if want_ref:
@@ -688,7 +762,7 @@ def _pw_fill(task):
     if sl["depth0"] is not None and smp["depth0"].numel() > 0:
         sl["depth0"].numpy()[p] = npv(smp["depth0"]); sl["depth1"].numpy()[p] = npv(smp["depth1"])
     return (np.asarray(smp["K_color0"]), np.asarray(smp["K_color1"]), int(smp["pair_id"]), smp["pair_names"][1], smp["pair_names"][0],
-            _t.perf_counter() - t0, {})
+            _t.perf_counter() - t0, {}, {})
 
 
 def _pw_ping(i):
@@ -699,7 +773,7 @@ class _ProcessDecoder:
     """pool of decode processes + ring of shared-memory batch slots (see above).  A slot is reused only after the H2D copies issued from it
     have completed (DevicePrefetcher stores its event in `events[k]`)."""
 
-    def __init__(self, scenes, B, Hh, Ww, has_depth, workers, n_slots, pin, jpeg_cap=0):
+    def __init__(self, scenes, B, Hh, Ww, has_depth, workers, n_slots, pin, jpeg_cap=0, png=False):
         import torch.multiprocessing as mp
         layout = (n_slots, B, Hh, Ww, has_depth)
         per = 2 * B * Hh * Ww + (2 * B * Hh * Ww if has_depth else 0)
@@ -724,7 +798,7 @@ class _ProcessDecoder:
         # FORK, like torch's DataLoader workers: the children inherit the scene objects and the shared segment without re-importing anything
         # (spawned workers each re-imported torch: 36 s to start 32 of them under a 16-CPU container quota, tools/bench_fused_split.py) and
         # never touch the HIP runtime -- they run PIL / zlib / numpy only
-        self.pool = mp.get_context("fork").Pool(workers, initializer=_pw_init, initargs=(scenes, self.flat, layout, self.jflat, jpeg_cap))
+        self.pool = mp.get_context("fork").Pool(workers, initializer=_pw_init, initargs=(scenes, self.flat, layout, self.jflat, jpeg_cap, png))
         self.next = 0
 
     def acquire(self):
@@ -762,12 +836,17 @@ class PairBatchLoader:
     this batch), scene_id / scene_root / last_of_scene (of the batch's last pair, kept for single-scene consumers))."""
 
     def __init__(self, scenes, batch_pairs=32, prefetch=2, pin=None, global_offsets=None, workers=8, span_scenes=True, decode="thread",
-                 jpeg_decode="host", jpeg_cap=JPEG_RECORD_CAP):
+                 jpeg_decode="host", jpeg_cap=JPEG_RECORD_CAP, depth_decode="host"):
         """workers: decode threads per batch (PIL / zlib / numpy release the GIL): a pair is two JPEGs + one or two 16-bit PNGs,
         ~12 ms of decode on one core, so one thread feeds ~80 pairs/s where the fused pipeline consumes ~700.
         jpeg_decode 'device' (HIP.JPEG_DECODE): on the fast route (gray_pair: MapFreeScene files at their own size) the workers only parse
         the JPEGs into packed header / record slots of `jpeg_cap` bytes per frame and the batch carries them under "jpeg"; DevicePrefetcher
-        decodes them on the GPU (jpeg_ops).  Frames the device does not take are decoded on the host as before; other routes are unchanged."""
+        decodes them on the GPU (jpeg_ops).  Frames the device does not take are decoded on the host as before; other routes are unchanged.
+        depth_decode 'device' (HIP.DEPTH_DECODE, orthogonal): on the same fast route (scenes with has_depth_readers) the workers only join the
+        IDAT chunks of each 16-bit depth PNG into its record, written into the row's own depth0 / depth1 plane (no larger ring), and the batch
+        carries the headers and the row table under "png"; DevicePrefetcher copies the records and decodes them on the GPU (png_ops).  A
+        scene's shared reference depth is decoded once per batch and duplicated on the device.  Files the device does not take are decoded
+        on the host into the same row."""
         self.scenes, self.B, self.prefetch = list(scenes), int(batch_pairs), int(prefetch)
         self.workers = max(1, int(workers))
         self._pool = None
@@ -776,6 +855,7 @@ class PairBatchLoader:
         self.decode, self._proc = decode, None
         self.jpeg_decode = check_jpeg_decode(jpeg_decode)
         self.jpeg_cap = (int(jpeg_cap) + 15) // 16 * 16
+        self.depth_decode = check_depth_decode(depth_decode)
         self.stats = {}                                        # process decoder: pool start, time in pool.map, summed worker task time, ...
         self.pin = torch.cuda.is_available() if pin is None else pin
         self.offsets = global_offsets
@@ -840,17 +920,22 @@ class PairBatchLoader:
         gray_of = {}                                           # id(map-frame tensor) -> (the tensor, its gray plane): one conversion per scene
                                                                # keyframe; the tensor is held so that its id cannot be reused inside the batch
         jp = self._jpeg_batch(items, mk) if self.jpeg_decode == "device" else None
+        png = self.depth_decode == "device" and has_depth
+        first_of, want_ref = self._ref_plan(items)
+        pinfos = [{} for _ in range(b)]
 
         def fill(p, smp=None):
             sc_ = self.scenes[items[p][0]]
             if smp is None and getattr(sc_, "has_gray_pair", False):      # gray planes / depth straight from the files' bytes into the batch buffers
-                want, readers = True, None
+                want, readers, kw = True, None, {}
                 if jp is not None:
                     want = jp["want"][p]
                     h_np, r_np = jp["headers"].numpy(), jp["records"].numpy()
                     readers = (_jpeg_reader(h_np, r_np, 2 * p, jp["rows"]), _jpeg_reader(h_np, r_np, 2 * p + 1, jp["rows"]))
+                if png and getattr(sc_, "has_depth_readers", False):
+                    kw = dict(depth_readers=(_png_reader((0, p), pinfos[p]) if want_ref[p] else _png_skip, _png_reader((1, p), pinfos[p])))
                 fast = sc_.gray_pair(items[p][1], want, out=(im_np[2 * p, 0], d0_np[p] if has_depth else None, im_np[2 * p + 1, 0],
-                                                             d1_np[p] if has_depth else None), readers=readers)
+                                                             d1_np[p] if has_depth else None), readers=readers, **kw)
                 if fast is not None:
                     if not want:
                         jp["rows"][2 * p] = ("dup", 2 * jp["first_of"][jp["key"][p]])
@@ -883,6 +968,8 @@ class PairBatchLoader:
         sc = self.scenes[items[-1][0]]
         done = [self.scenes[si].scene_id for si, i in items if i == len(self.scenes[si]) - 1]
         extra = {} if jp is None else dict(jpeg=dict(headers=jp["headers"], records=jp["records"], rows=jp["rows"]))
+        if png:
+            extra["png"] = _png_rows(b, want_ref, first_of, pinfos, mk)
         return dict(images=images, depth0=depth0, depth1=depth1, K0=K0, K1=K1, **extra,
                     seed_ids=torch.tensor([m[2] for m in meta], dtype=torch.int64),
                     global_ids=torch.tensor([self.offsets[si] + i for si, i in items], dtype=torch.int64),
@@ -894,6 +981,16 @@ class PairBatchLoader:
                     ref_keys=[self._ref_key(si, m[4]) if getattr(self.scenes[si], "shared_reference", False) else None
                               for (si, _), m in zip(items, meta)],
                     scene_id=sc.scene_id, scene_root=sc.scene_root, scene_index=items[-1][0], last_of_scene=bool(done and done[-1] == sc.scene_id))
+
+    def _ref_plan(self, items):
+        """(first_of [b], want [b]): want[p] = pair p is the first of the batch with its reference view (one per distinct scene that shares
+        its reference; every pair of other scenes), first_of[p] = the position of that first pair"""
+        seen, first_of, want = {}, [], []
+        for p, (si, i) in enumerate(items):
+            k = si if getattr(self.scenes[si], "shared_reference", False) else ("pair", p)
+            want.append(k not in seen)
+            first_of.append(seen.setdefault(k, p))
+        return first_of, want
 
     def _jpeg_batch(self, items, mk=None, slot=None):
         """device JPEG route of one batch: packed buffers (fresh pinned ones, or a process slot's), the row table (None = host plane in
@@ -938,7 +1035,8 @@ class PairBatchLoader:
                 first = self.scenes[items[0][0]][items[0][1]]
                 (Hh, Ww), has_depth = first["image0"].shape[-2:], first["depth0"].numel() > 0
             self._proc = _ProcessDecoder(self.scenes, self.B, Hh, Ww, has_depth, self.workers, max(self.prefetch, 0) + 4, self.pin,
-                                         jpeg_cap=self.jpeg_cap if self.jpeg_decode == "device" else 0)
+                                         jpeg_cap=self.jpeg_cap if self.jpeg_decode == "device" else 0,
+                                         png=self.depth_decode == "device")
             self._pool_map(_pw_ping, range(self.workers * 2))                          # every worker has started and imported its modules
             st["process_pool_start_s"] = _t.perf_counter() - t0
         pr = self._proc
@@ -977,6 +1075,9 @@ class PairBatchLoader:
         done = [self.scenes[si].scene_id for si, i in items if i == len(self.scenes[si]) - 1]
         has_depth = sl["depth0"] is not None
         extra = {} if jp is None else dict(jpeg=dict(headers=jp["headers"], records=jp["records"], rows=jp["rows"]))
+        if self.depth_decode == "device" and has_depth:
+            mk = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, pin_memory=bool(self.pin and torch.cuda.is_available()))
+            extra["png"] = _png_rows(b, want, [first_of[items[p][0]] if not want[p] else p for p in range(b)], [m[7] for m in meta], mk)
         return dict(images=sl["images"][:2 * b], depth0=sl["depth0"][:b] if has_depth else None, depth1=sl["depth1"][:b] if has_depth else None,
                     K0=K0, K1=K1, **extra, seed_ids=torch.tensor([m[2] for m in meta], dtype=torch.int64),
                     global_ids=torch.tensor([self.offsets[si] + i for si, i in items], dtype=torch.int64),
@@ -1036,18 +1137,18 @@ class DevicePrefetcher:
         self.loader, self.device = loader, torch.device(device)
         self.stream = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
 
-    _jdec = _jres = None
+    _jdec = _jres = _pdec = None
 
     def _put(self, hb):
         if self.stream is None:
-            if "jpeg" in hb:
+            if "jpeg" in hb or "png" in hb:
                 from ._lib import MfrLibraryError
-                raise MfrLibraryError("the device JPEG route needs a HIP device (there is no CPU fallback)")
+                raise MfrLibraryError(f"the device {'JPEG' if 'jpeg' in hb else 'depth PNG'} route needs a HIP device (there is no CPU fallback)")
             return dict(hb), None, None
         with torch.cuda.stream(self.stream):
-            skip = ("_slot", "jpeg", "images") if "jpeg" in hb else ("_slot",)
+            skip = ("_slot",) + (("jpeg", "images") if "jpeg" in hb else ()) + (("png", "depth0", "depth1") if "png" in hb else ())
             db = {k: (v.to(self.device, non_blocking=True) if isinstance(v, torch.Tensor) else v) for k, v in hb.items() if k not in skip}
-            check = self._put_jpeg(hb, db) if "jpeg" in hb else None
+            check = [c for c in (self._put_jpeg(hb, db) if "jpeg" in hb else None, self._put_png(hb, db) if "png" in hb else None) if c is not None]
             ev = torch.cuda.Event(); ev.record(self.stream)
             if "_slot" in hb:                                  # shared-memory slot of the process decoder: reusable once these copies are done
                 pr, k = hb["_slot"]
@@ -1101,7 +1202,42 @@ class DevicePrefetcher:
             if rows[r] is not None and rows[r][0] == "dup":
                 d_img[r].copy_(d_img[rows[r][1]], non_blocking=True)
         db["images"] = d_img
-        return (h_status, [(r, rows[r][2]) for r in dev_rows]) if dev_rows else None
+        return (h_status, [(r, rows[r][2]) for r in dev_rows], "JPEG") if dev_rows else None
+
+    def _put_png(self, hb, db):
+        """device depth route (on the side stream): the planes of the rows the host decoded, then the records of the others (each lies at the
+        start of its own pinned depth plane; only its bytes are copied) with the headers, the decode kernel straight into the batch's device
+        depth maps, then the duplicated reference rows.  The per-image status goes to a pinned word array that _ready checks."""
+        from . import png_ops as P
+        pg, d0, d1 = hb["png"], hb["depth0"], hb["depth1"]
+        b, (H, W) = d0.shape[0], d0.shape[-2:]
+        rows, n2 = pg["rows"], 2 * b
+        plane = lambda r: d0[r] if r < b else d1[r - b]
+        d_depth = torch.empty((n2, H, W), dtype=torch.float32, device=self.device)
+        dev_rows = [r for r in range(n2) if rows[r] is not None and rows[r][0] == 0]
+        for r in range(n2):
+            if rows[r] is None:
+                d_depth[r].copy_(plane(r), non_blocking=True)
+        h_status = None
+        if dev_rows:
+            if self._pdec is None:
+                self._pdec = P.DepthPngDecoder(self.device)
+            cap = max(rows[r][1] for r in dev_rows)                 # record sizes are multiples of 16
+            d_hdr = pg["headers"].to(self.device, non_blocking=True)
+            d_rec = torch.empty(n2 * cap + 16, dtype=torch.uint8, device=self.device)
+            for r in dev_rows:
+                nb = rows[r][1]
+                d_rec[r * cap:r * cap + nb].copy_(plane(r).reshape(-1).view(torch.uint8)[:nb], non_blocking=True)
+            d_off = torch.arange(n2 + 1, dtype=torch.int64, device=self.device) * cap
+            d_st = torch.zeros(n2, dtype=torch.int32, device=self.device)
+            self._pdec.decode_device(d_hdr, d_rec, d_off, n2, H, W, cap, d_depth, d_st)
+            h_status = torch.empty(n2, dtype=torch.int32, pin_memory=True)
+            h_status.copy_(d_st, non_blocking=True)
+        for r in range(n2):
+            if rows[r] is not None and rows[r][0] == "dup":
+                d_depth[r].copy_(d_depth[rows[r][1]], non_blocking=True)
+        db["depth0"], db["depth1"] = d_depth[:b], d_depth[b:]
+        return (h_status, [(r, rows[r][2]) for r in dev_rows], "depth PNG") if dev_rows else None
 
     def __iter__(self):
         nxt = None
@@ -1114,12 +1250,12 @@ class DevicePrefetcher:
 
     def _ready(self, item):
         db, ev, check = item
-        if check is not None:                                  # device JPEG statuses of this batch (its side-stream work is done first)
+        for h_status, paths, what in check or ():              # device decode statuses of this batch (its side-stream work is done first)
             ev.synchronize()
-            st = check[0].numpy()
-            bad = [(path, int(st[r])) for r, path in check[1] if st[r] != 0]
+            st = h_status.numpy()
+            bad = [(path, int(st[r])) for r, path in paths if st[r] != 0]
             if bad:
-                raise OSError(f"device JPEG decode failed for {bad[0][0]} (status {bad[0][1]:#x}; {len(bad)} frame(s) of the batch)")
+                raise OSError(f"device {what} decode failed for {bad[0][0]} (status {bad[0][1]:#x}; {len(bad)} frame(s) of the batch)")
         if ev is not None:
             torch.cuda.current_stream(self.device).wait_event(ev)
             for v in db.values():

@@ -58,7 +58,7 @@ def _host():
     from . import datasets
     lib = datasets._host_lib()
     if lib is None:
-        raise _lib.MfrLibraryError("csrc/libmfr_host.so (ABI 3) not found: build it with __graft_entry__.build()")
+        raise _lib.MfrLibraryError("csrc/libmfr_host.so (ABI 4) not found: build it with __graft_entry__.build()")
     assert lib.mfr_host_jpeg_header_bytes() == HEADER_BYTES, "jpeg_ops.Header does not mirror include/mfr_jpeg.h"
     return lib
 

@@ -85,7 +85,8 @@ def collect_fused(cfg, batch_pairs=None, pipeline=None, hook=None):
     where = [(sc, i) for sc in scenes for i in range(len(sc))]                             # global id -> (scene, index)
     workers = int(cfg.HIP.LOADER_WORKERS) if int(cfg.HIP.LOADER_WORKERS) > 0 else max(2, min(32, usable_cpus()))
     loader = PairBatchLoader(scenes, int(batch_pairs or cfg.HIP.BATCH_PAIRS), pin=device.type == 'cuda', workers=workers,
-                             decode=str(cfg.HIP.LOADER_DECODE), jpeg_decode=str(cfg.HIP.JPEG_DECODE))
+                             decode=str(cfg.HIP.LOADER_DECODE), jpeg_decode=str(cfg.HIP.JPEG_DECODE),
+                             depth_decode=str(cfg.HIP.DEPTH_DECODE))   # (this reader's depth maps stay on the host route)
     rows = {}
     try:
         for batch in DevicePrefetcher(loader, device):

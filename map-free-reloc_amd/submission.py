@@ -220,8 +220,10 @@ def predict_fused(cfg, split, output_root, pipeline=None, batch_pairs=None, resu
         workers = int(cfg.HIP.LOADER_WORKERS)
     decode = str(cfg.HIP.LOADER_DECODE) if 'LOADER_DECODE' in cfg.HIP else 'process'
     jpeg_decode = str(cfg.HIP.JPEG_DECODE) if 'JPEG_DECODE' in cfg.HIP else 'host'
+    depth_decode = str(cfg.HIP.DEPTH_DECODE) if 'DEPTH_DECODE' in cfg.HIP else 'host'
     loader = PairBatchLoader([scenes[i] for i in todo], B, prefetch=prefetch, pin=device.type == 'cuda',
-                             global_offsets=[int(offsets[i]) for i in todo], workers=workers, decode=decode, jpeg_decode=jpeg_decode)
+                             global_offsets=[int(offsets[i]) for i in todo], workers=workers, decode=decode, jpeg_decode=jpeg_decode,
+                             depth_decode=depth_decode)
     recs, names, acc = [], {}, []
     stats = dict(pairs=0, batches=0, loader_wait_s=0.0, issue_s=0.0, gpu_busy_s=0.0, t0=time.perf_counter())
     it = iter(DevicePrefetcher(loader, device))
@@ -327,7 +329,7 @@ def predict_fused(cfg, split, output_root, pipeline=None, batch_pairs=None, resu
     loader.close()                                          # decode processes / shared-memory slots of this run
     stats['close_s'] = time.perf_counter() - tc
     stats['seconds'] = time.perf_counter() - stats.pop('t0')
-    LAST_RUN_STATS.clear(); LAST_RUN_STATS.update(stats, rank=rank, world=world, scenes_computed=len(todo), decode_workers=workers, decode=decode, jpeg_decode=jpeg_decode, batch_pairs=B, loader_stats=dict(getattr(loader, 'stats', {})))
+    LAST_RUN_STATS.clear(); LAST_RUN_STATS.update(stats, rank=rank, world=world, scenes_computed=len(todo), decode_workers=workers, decode=decode, jpeg_decode=jpeg_decode, depth_decode=depth_decode, batch_pairs=B, loader_stats=dict(getattr(loader, 'stats', {})))
     try:                                                    # one line per call and rank: the run's own record (pairs, seconds, stalls), next to the pose files
         line = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in LAST_RUN_STATS.items() if isinstance(v, (int, float, str, bool, dict))}
         line['unix_time'] = round(time.time(), 1)

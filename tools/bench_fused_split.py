@@ -60,6 +60,7 @@ def main():
     ap.add_argument("--no-resume-legs", action="store_true")
     ap.add_argument("--decode", default="process", help="thread | process (HIP.LOADER_DECODE)")
     ap.add_argument("--jpeg-decode", default="host", help="host | device (HIP.JPEG_DECODE)")
+    ap.add_argument("--depth-decode", default="host", help="host | device (HIP.DEPTH_DECODE)")
     ap.add_argument("--workers", type=int, default=0, help="decode workers (HIP.LOADER_WORKERS; 0 = the granted CPUs)")
     ap.add_argument("--ref-cache", type=int, default=1, help="0: HIP.REF_FEATURE_CACHE off (SuperPoint on the reference view of every pair)")
     a = ap.parse_args()
@@ -86,6 +87,7 @@ def main():
         cfg.HIP.REF_FEATURE_CACHE = bool(a.ref_cache)
         cfg.HIP.LOADER_DECODE = a.decode
         cfg.HIP.JPEG_DECODE = a.jpeg_decode
+        cfg.HIP.DEPTH_DECODE = a.depth_decode
         cfg.HIP.LOADER_WORKERS = a.workers
         if name == "sg_pnp":
             cfg.FEATURE_MATCHING, cfg.POSE_SOLVER = "SuperGlue", "PNP"
@@ -109,7 +111,7 @@ def main():
         base = dict(pairs=st["pairs"], seconds=round(dt, 2), pairs_per_s=round(st["pairs"] / dt, 1), batch_pairs=B, batches=st["batches"], graph=bool(a.graph),
                     loader_wait_s=round(st["loader_wait_s"], 2), loader_stall_fraction=round(st["loader_wait_s"] / st["seconds"], 4),
                     issue_s=round(st["issue_s"], 2), gpu_busy_s=round(st["gpu_busy_s"], 2), gpu_busy_fraction=round(st["gpu_busy_s"] / st["seconds"], 4),
-                    decode_workers=st["decode_workers"], ref_feature_cache=bool(a.ref_cache), decode=a.decode, jpeg_decode=a.jpeg_decode, loader_stats={k: round(v, 3) for k, v in st.get("loader_stats", {}).items()},
+                    decode_workers=st["decode_workers"], ref_feature_cache=bool(a.ref_cache), decode=a.decode, jpeg_decode=a.jpeg_decode, depth_decode=a.depth_decode, loader_stats={k: round(v, 3) for k, v in st.get("loader_stats", {}).items()},
                     phases_s=dict(predict_fused_call=round(dt, 2), inside_the_batch_loop=round(st["seconds"], 2), until_first_batch=round(st.get("first_batch_s", 0.0), 2),
                                   loop_incl_last_records=round(st.get("loop_s", 0.0), 2), loader_close=round(st.get("close_s", 0.0), 2)))
         if a.no_resume_legs:
