@@ -671,8 +671,8 @@ int mfr_wino_filter_transform(const float *w, int Cin, int Cout, float *upk, voi
 int mfr_conv3x3_wino(const float *x, const float *upk, const float *bias, const float *residual, int B, int Cin, int Cout,
                      int H, int W, int act, int pool, float *y, void *stream);
 /* the same convolution through a named kernel variant: 0 default, 1 classic, 2 software-pipelined K loop (bit-identical to 1),
- * 4 shared-transform (two cout slices split every patch transform; bias folded into an accumulator: f32-roundoff differences);
- * other values are timing ablations of tools/tune_wino.py -- for A/B timing and parity tests */
+ * 3 = 2 with the instruction placement left to the compiler, 4 shared-transform (two cout slices split every patch transform; bias
+ * folded into an accumulator: f32-roundoff differences) -- for A/B timing (tools/tune_wino.py) and parity tests; other values: MFR_E_ARG */
 int mfr_conv3x3_wino_variant(const float *x, const float *upk, const float *bias, const float *residual, int B, int Cin, int Cout,
                              int H, int W, int act, int pool, int variant, float *y, void *stream);
 

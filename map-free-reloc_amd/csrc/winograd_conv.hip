@@ -56,7 +56,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // prologue / epilogue cost more than the halved transform work saved -- and is no longer built.)  The packed-filter layout
 // depends on NBLK only, so it is a compile-time constant of the library: no environment variable, no hidden state.
 #define WN_NBLK 2
-static inline int wn_nblk(int) { return WN_NBLK; }
 
 // packed U_xi[cout][cin]: [chunk c = cin/4][cout block cb][q = xi/4][blk][lane = (cin%4)*16 + cout%16][e = xi%4]
 __global__ void __launch_bounds__(256) wino_filter_kernel(const float *__restrict__ w, int Cin, int Cout, int CoutP, int nblk, float *__restrict__ upk)
@@ -336,9 +335,7 @@ __global__ void __launch_bounds__(256, NBLK == 2 ? 2 : 1) wino_conv3x3_kernel(
 #define WN_M_DS_WR 0x200
 
 // MODE 0: pinned interleave (sched_group_barrier); MODE 1: the same software pipeline, placement left to the compiler
-// ABL (timing ablations, results are WRONG when != 0; tools/tune_wino.py only): 1 = no output transform / stores,
-// 2 = no workgroup barrier in the K loop, 4 = no input transform arithmetic, 8 = no patch loads
-template <bool POOL, int LOAD, int MODE, int ABL = 0>
+template <bool POOL, int LOAD, int MODE>
 __global__ void __launch_bounds__(256, 2) wino_conv3x3_pipe_kernel(
     const float *__restrict__ x, const float *__restrict__ upk, const float *__restrict__ bias, float *__restrict__ y,
     const float *__restrict__ residual, int Cin, int Cout, int H, int W, int nbx, int nby, int S, int Sx, int ncb, int act)
@@ -381,11 +378,6 @@ __global__ void __launch_bounds__(256, 2) wino_conv3x3_pipe_kernel(
     struct Patch { unsigned p0[4], p1[4], h[4]; };                   // 4 rows: own column pair + halo element
     auto gload = [&](Patch &r, int c) {
         const unsigned so = (unsigned)c * cstep;
-        if (ABL & 8) {
-#pragma unroll
-            for (int a = 0; a < 4; ++a) { r.p0[a] = so + a; r.p1[a] = so ^ a; r.h[a] = so; }
-            return;
-        }
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             const auto pr = __builtin_amdgcn_raw_buffer_load_b64(rs, off[a], so, 0);
@@ -395,14 +387,6 @@ __global__ void __launch_bounds__(256, 2) wino_conv3x3_pipe_kernel(
     };
     auto transform = [&](const Patch &r, float (&v)[16]) {
         float d[16];
-        if (ABL & 4) {
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                v[4 * a] = __builtin_bit_cast(float, r.p0[a]); v[4 * a + 1] = __builtin_bit_cast(float, r.p1[a]);
-                v[4 * a + 2] = __builtin_bit_cast(float, r.h[a]); v[4 * a + 3] = __builtin_bit_cast(float, r.p0[a] ^ r.h[a]);
-            }
-            return;
-        }
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             const int p0 = (int)r.p0[a], hv = (int)r.h[a];
@@ -479,7 +463,7 @@ __global__ void __launch_bounds__(256, 2) wino_conv3x3_pipe_kernel(
             if (i == 20 || i == 24) WN_SGB(WN_M_DS_WR, 1);
         }
         }
-        if (!(ABL & 2)) __syncthreads();
+        __syncthreads();
         __builtin_amdgcn_sched_barrier(0);          // the next step's transform must not be hoisted above its patch loads' latency
     };
 
@@ -499,15 +483,6 @@ __global__ void __launch_bounds__(256, 2) wino_conv3x3_pipe_kernel(
         kstep(c + 1, pa, pb, vb, va, u0, u1);      // chunk c+1: transforms c+2 (in pa) -> va, prefetches c+3 -> pb
     }
     if (nchunks & 1) kstep(c, pb, pa, va, vb, u0, u1);   // odd chunk count: one more step (its look-ahead work is discarded)
-    if (ABL & 1) {
-        f32x4 t = acc[0][0];
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-#pragma unroll
-            for (int k = 0; k < NBLK; ++k) if (i | k) t += acc[i][k];
-        if (t[0] + t[1] + t[2] + t[3] == 12345.678f) y[tid] = t[0];
-        return;
-    }
     wn_epilogue<POOL, LOAD, NBLK>(acc, bias, y, residual, Cout, H, W, act, b, cb, kq, ty, tx);
 }
 
@@ -526,7 +501,7 @@ __global__ void __launch_bounds__(256, 2) wino_conv3x3_pipe_kernel(
 //     outputs: no bias instruction in the epilogue.
 // K loop software-pipelined and pinned like the pipelined kernel; one barrier per chunk.
 // ---------------------------------------------------------------------------------------------------------------------
-template <bool POOL, int LOAD, int ABL = 0, int ACT = -1>
+template <bool POOL, int LOAD, int ACT = -1>
 __global__ void __launch_bounds__(256, 2) wino_conv3x3_shared_kernel(
     const float *__restrict__ x, const float *__restrict__ upk, const float *__restrict__ bias, float *__restrict__ y,
     const float *__restrict__ residual, int Cin, int Cout, int H, int W, int nbx, int nby, int S, int Sx, int ncb, int ncb32, int act)
@@ -592,11 +567,6 @@ __global__ void __launch_bounds__(256, 2) wino_conv3x3_shared_kernel(
     struct Patch { unsigned p0[3], p1[3], h[3]; };
     auto gload = [&](Patch &r, int c) {
         const unsigned so = (unsigned)c * cstep;
-        if (ABL & 8) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) { r.p0[a] = so + a; r.p1[a] = so ^ a; r.h[a] = so; }
-            return;
-        }
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             const auto pr = __builtin_amdgcn_raw_buffer_load_b64(rs, off[a], so, 0);
@@ -670,15 +640,12 @@ __global__ void __launch_bounds__(256, 2) wino_conv3x3_shared_kernel(
 #pragma unroll
         for (int i = 0; i < 8; ++i) a[i] = us[i * 64];
         float o[8];
-        if (!(ABL & 4)) htransform(pin, o);
-        else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) o[i] = __builtin_bit_cast(float, pin.p0[i % 3] ^ pin.h[i % 3] + i);
-        }
+        htransform(pin, o);
         vstore((c + 1) & 1, o);
         const int cn = min(c + 2, nchunks - 1);      // prefetch index clamped (scalar): never reads past the tensors
         gload(pout, cn);
-        if (!(ABL & 16)) { ustore((c + 1) & 1, ur); uload(ur, cn); }
+        ustore((c + 1) & 1, ur);
+        uload(ur, cn);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
 #pragma unroll
@@ -724,15 +691,6 @@ __global__ void __launch_bounds__(256, 2) wino_conv3x3_shared_kernel(
         kstep(c + 1, pa, pb, ur);
     }
     if (nchunks & 1) kstep(c, pb, pa, ur);              // odd chunk count: one more step (its look-ahead work is discarded)
-    if (ABL & 1) {
-        f32x4 t = acc[0][0];
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-#pragma unroll
-            for (int k = 0; k < NBLK; ++k) if (i | k) t += acc[i][k];
-        if (t[0] + t[1] + t[2] + t[3] == 12345.678f) y[tid] = t[0];
-        return;
-    }
     wn_epilogue<POOL, LOAD, NBLK, false, ACT>(acc, nullptr, y, residual, Cout, H, W, act, b, 2 * cb + cs, kq, ty, tx);
 }
 
@@ -743,13 +701,13 @@ extern "C" {
 size_t mfr_wino_filter_bytes(int Cin, int Cout)
 {
     if (Cin <= 0 || Cout <= 0 || (Cin & 3)) return 0;
-    return sizeof(float) * 16 * (size_t)Cin * wn_coutp(Cout, wn_nblk(Cout));
+    return sizeof(float) * 16 * (size_t)Cin * wn_coutp(Cout, WN_NBLK);
 }
 
 int mfr_wino_filter_transform(const float *w, int Cin, int Cout, float *upk, void *stream)
 {
     if (!w || !upk || Cin <= 0 || Cout <= 0 || (Cin & 3)) return MFR_E_ARG;
-    const int nblk = wn_nblk(Cout), CoutP = wn_coutp(Cout, nblk);
+    const int nblk = WN_NBLK, CoutP = wn_coutp(Cout, nblk);
     if (CoutP != Cout && mfr_zero_async(upk, sizeof(float) * 16 * (size_t)Cin * CoutP, (hipStream_t)stream) != hipSuccess) return MFR_E_LAUNCH;
     hipLaunchKernelGGL(wino_filter_kernel, dim3((Cin * Cout + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, Cin, Cout, CoutP, nblk, upk);
     CHECK_LAUNCH();
@@ -765,7 +723,7 @@ int mfr_conv3x3_wino_variant(const float *x, const float *upk, const float *bias
 {
     if (!x || !upk || !y || B <= 0 || Cin <= 0 || Cout <= 0 || (Cin & 3) || H <= 0 || W <= 0 || act < 0 || act > 2) return MFR_E_ARG;
     if (pool && (H < 2 || W < 2 || residual)) return MFR_E_ARG;
-    if (variant < 0 || (variant > 4 && (variant < 10 || variant > 33)) ) return MFR_E_ARG;
+    if (variant < 0 || variant > 4) return MFR_E_ARG;
     if ((size_t)4 * Cin * H * W >= 0x7fffffffull) return MFR_E_ARG;    // one image must fit a 2 GB buffer descriptor
     const int nblk = WN_NBLK;
     int nbx = ((W + 1) / 2 + WN_TX - 1) / WN_TX;
@@ -783,7 +741,7 @@ int mfr_conv3x3_wino_variant(const float *x, const float *upk, const float *bias
     hipStream_t st = (hipStream_t)stream;
 #define WN_ARGS x, upk, bias, y, residual, Cin, Cout, H, W, nbx, nby, (int)S, (int)Sx, ncb, act
 #define WN_GO(K) hipLaunchKernelGGL(K, dim3((unsigned)grid), dim3(256), 0, st, WN_ARGS)
-    if (variant == 4 || variant >= 26) {                   // 27..33: timing ablations of the shared kernel                   // shared-transform kernel: workgroup = 2 tile rows x 64 couts
+    if (variant == 4) {                                    // shared-transform kernel: workgroup = 2 tile rows x 64 couts
         const int ncb32 = wn_coutp(Cout, nblk) / 32, ncb64 = (ncb32 + 1) / 2;
         // even W: blocks of 2 tile rows x 16 tile columns; odd W: linear tiling, nbx = tiles per row, nby2 = 32-tile groups per image
         const int txn = (W + 1) / 2, tyn = (H + 1) / 2;
@@ -792,31 +750,15 @@ int mfr_conv3x3_wino_variant(const float *x, const float *upk, const float *bias
         const long long S2 = odd ? (long long)nby2 * B : (long long)nbx * nby2 * B, Sx2 = (S2 + 7) / 8, grid2 = Sx2 * 8 * ncb64;
         if (grid2 > 0x7fffffffll) return MFR_E_ARG;
 #define WN_GO2(K) hipLaunchKernelGGL(K, dim3((unsigned)grid2), dim3(256), 0, st, x, upk, bias, y, residual, Cin, Cout, H, W, nbx, nby2, (int)S2, (int)Sx2, ncb64, ncb32, act)
-        if (variant == 4) {
-#define WN_GO2_ACT(P, L) do { if (act == 1) WN_GO2((wino_conv3x3_shared_kernel<P, L, 0, 1>)); else if (act == 2) WN_GO2((wino_conv3x3_shared_kernel<P, L, 0, 2>)); \
-                              else WN_GO2((wino_conv3x3_shared_kernel<P, L, 0, 0>)); } while (0)
-            if (pool) { if (odd) WN_GO2_ACT(true, 2); else WN_GO2_ACT(true, 1); }
-            else { if (odd) WN_GO2_ACT(false, 2); else WN_GO2_ACT(false, 1); }
+#define WN_GO2_ACT(P, L) do { if (act == 1) WN_GO2((wino_conv3x3_shared_kernel<P, L, 1>)); else if (act == 2) WN_GO2((wino_conv3x3_shared_kernel<P, L, 2>)); \
+                          else WN_GO2((wino_conv3x3_shared_kernel<P, L, 0>)); } while (0)
+        if (pool) { if (odd) WN_GO2_ACT(true, 2); else WN_GO2_ACT(true, 1); }
+        else { if (odd) WN_GO2_ACT(false, 2); else WN_GO2_ACT(false, 1); }
 #undef WN_GO2_ACT
-        } else if (variant == 27) { if (pool) WN_GO2((wino_conv3x3_shared_kernel<true, 1, 1>)); else WN_GO2((wino_conv3x3_shared_kernel<false, 1, 1>)); }
-        else if (variant == 28) { if (pool) WN_GO2((wino_conv3x3_shared_kernel<true, 1, 4>)); else WN_GO2((wino_conv3x3_shared_kernel<false, 1, 4>)); }
-        else if (variant == 29) { if (pool) WN_GO2((wino_conv3x3_shared_kernel<true, 1, 5>)); else WN_GO2((wino_conv3x3_shared_kernel<false, 1, 5>)); }
-        else if (variant == 30) { if (pool) WN_GO2((wino_conv3x3_shared_kernel<true, 1, 8>)); else WN_GO2((wino_conv3x3_shared_kernel<false, 1, 8>)); }
-        else if (variant == 31) { if (pool) WN_GO2((wino_conv3x3_shared_kernel<true, 1, 16>)); else WN_GO2((wino_conv3x3_shared_kernel<false, 1, 16>)); }
-        else if (variant == 32) { if (pool) WN_GO2((wino_conv3x3_shared_kernel<true, 1, 29>)); else WN_GO2((wino_conv3x3_shared_kernel<false, 1, 29>)); }
-        else if (variant == 33) { if (pool) WN_GO2((wino_conv3x3_shared_kernel<true, 1, 13>)); else WN_GO2((wino_conv3x3_shared_kernel<false, 1, 13>)); }
-        else return MFR_E_ARG;
 #undef WN_GO2
     } else if (variant == 2) {
         if (pool) { if (odd) WN_GO((wino_conv3x3_pipe_kernel<true, 2, 0>)); else WN_GO((wino_conv3x3_pipe_kernel<true, 1, 0>)); }
         else { if (odd) WN_GO((wino_conv3x3_pipe_kernel<false, 2, 0>)); else WN_GO((wino_conv3x3_pipe_kernel<false, 1, 0>)); }
-    } else if (variant >= 10) {                            // timing ablations of the pipelined kernel (even W, as launched by the tool)
-        switch (variant - 10) {
-#define WN_ABL(A) case A: if (pool) WN_GO((wino_conv3x3_pipe_kernel<true, 1, 0, A>)); else WN_GO((wino_conv3x3_pipe_kernel<false, 1, 0, A>)); break;
-        WN_ABL(1) WN_ABL(2) WN_ABL(3) WN_ABL(4) WN_ABL(8) WN_ABL(12) WN_ABL(15)
-#undef WN_ABL
-        default: return MFR_E_ARG;
-        }
     } else if (variant == 3) {
         if (pool) { if (odd) WN_GO((wino_conv3x3_pipe_kernel<true, 2, 1>)); else WN_GO((wino_conv3x3_pipe_kernel<true, 1, 1>)); }
         else { if (odd) WN_GO((wino_conv3x3_pipe_kernel<false, 2, 1>)); else WN_GO((wino_conv3x3_pipe_kernel<false, 1, 1>)); }

@@ -131,6 +131,228 @@ __device__ unsigned long long wb_prof[8][32];
 #define WB_STAMP(k) do { } while (0)
 #endif
 
+// ---- what the two kernels below share, ONE definition each ------------------------------------------------------------------------------------
+// wino_split_c1_kernel is wino_split_p8_kernel<true, true> behind its own patch production, and the two are held to the same bits
+// (tests/test_gpu_winograd_split.py): from the row combinations to the pooled store both run the text below.  Functions where hipcc emits the
+// same instructions for them (the V split, the products); macros, i.e. the token stream of the hand-written code, for the rest: the accumulator
+// zeroing as a function -- even one inlined at once -- changes the schedule of all five kernels, and the patch reads and fragment loads as
+// member functions of a struct of the lane's state swap two registers and two address adds in p8's K loop (gemm_split.hip found the same).
+// The macros use the kernel's own names: lds, w, wi, jp, lane, col, tysub, kg, bx, by, H, W, upk, bias, oscale, guard, gchk, and F16 (p8's
+// template parameter, a constexpr in c1).
+#define WB_VMCNT(n) __builtin_amdgcn_s_waitcnt(0x0F70 | ((n) & 15) | (((n) >> 4) << 14))      /* vmcnt(n) only; the builtin (not inline asm) so that hipcc's own wait bookkeeping sees it */
+// wavefront w owns Winograd row wi and column pair jp; in the MFMA operands a lane is (tile column col, tile row tysub of the pair, k group kg)
+#define WB_WAVE_GEOMETRY(tid) \
+    const int w = __builtin_amdgcn_readfirstlane((tid) >> 6); \
+    const int wi = w >> 1, jp = w & 1
+#define WB_LANE_GEOMETRY(lane) \
+    const int col = (lane) & 15, tysub = ((lane) >> 4) & 1, kg = (lane) >> 5
+
+// ---- row combination of Winograd row wi for the three patch columns of column pair jp: wread(stage, tile block) -> wX, wY, wZ.
+// row i of B^T d:  i = 0: d0 - d2;  1: d1 + d2;  2: d2 - d1;  3: d1 - d3.  ofa, ofb: the two rows; tile block nb: + 4 nb WB_RS
+#define WB_ROW_COMBINATION() \
+    const int ra = (wi == 0) ? 0 : (wi == 2) ? 2 : 1; \
+    const int rb = (wi == 0) ? 2 : (wi == 2) ? 1 : (wi == 1) ? 2 : 3; \
+    const float sg = (wi == 1) ? 1.0f : -1.0f; \
+    const float beta = jp ? -1.0f : 1.0f; \
+    const int cX = jp ? 2 : 0, cZ = jp ? 1 : 2; \
+    const int ofa = (2 * tysub + ra) * WB_RS + 2 * col, ofb = (2 * tysub + rb) * WB_RS + 2 * col; \
+    float wX[8], wY[8], wZ[8]; \
+    auto wread = [&](int buf, int nb) { \
+        const wb_lds_f32 *st = (const wb_lds_f32 *)lds + buf * WB_STAGE + (8 * kg) * WB_CH + 4 * nb * WB_RS; \
+        _Pragma("unroll") for (int e0 = 0; e0 < 8; e0 += 4) { \
+            wb_f32x2 a2[4], b2[4]; \
+            float a1[4], b1[4]; \
+            _Pragma("unroll") for (int e = 0; e < 4; ++e) { \
+                const wb_lds_f32 *ch = st + (e0 + e) * WB_CH; \
+                /* volatile: keeps hipcc from fusing the reads of a row into ds_read2_b64, which the LDS serves at a quarter of the rate of two */ \
+                /* ds_read_b64 (MI355X_MICROARCH.md, LDS table: 16 vs 2 + 2 cycles per wavefront) */ \
+                a2[e] = *(const volatile wb_lds_f32x2 *)(ch + ofa + cX); a1[e] = *(const volatile wb_lds_f32 *)(ch + ofa + cZ); \
+                b2[e] = *(const volatile wb_lds_f32x2 *)(ch + ofb + cX); b1[e] = *(const volatile wb_lds_f32 *)(ch + ofb + cZ); \
+            } \
+            _Pragma("unroll") for (int e = 0; e < 4; ++e) { \
+                wX[e0 + e] = __builtin_fmaf(sg, b2[e].x, a2[e].x); wY[e0 + e] = __builtin_fmaf(sg, b2[e].y, a2[e].y); \
+                wZ[e0 + e] = __builtin_fmaf(sg, b1[e], a1[e]); \
+            } \
+            /* pin the combinations here (otherwise they sink below the next batch's reads and the raw values pile up) */ \
+            asm volatile("" : "+v"(wX[e0]), "+v"(wY[e0]), "+v"(wZ[e0]), "+v"(wX[e0 + 1]), "+v"(wY[e0 + 1]), "+v"(wZ[e0 + 1]), \
+                              "+v"(wX[e0 + 2]), "+v"(wY[e0 + 2]), "+v"(wZ[e0 + 2]), "+v"(wX[e0 + 3]), "+v"(wY[e0 + 3]), "+v"(wZ[e0 + 3]) :: "memory"); \
+        } \
+    }
+// V(wi, 2 jp + jj) of the tile block from its row combinations, split and packed two input channels at a time: vf[term].u[k] = channels 2 k, 2 k + 1
+template <bool F16>
+__device__ __forceinline__ void wb_vmake(WbFrag (&vf)[3], int jj, float beta, const float (&wX)[8], const float (&wY)[8], const float (&wZ)[8])
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float v[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int q = 2 * k + e;
+            v[e] = jj ? __builtin_fmaf(beta, wY[q], wZ[q]) : wX[q] - wZ[q];
+        }
+        if (F16) sf_split2(v[0], v[1], SF_LOW_SCALE, vf[0].u[k], vf[1].u[k]);
+        else {
+            unsigned h[2], m[2], l[2];
+            bf_split3(v[0], h[0], m[0], l[0]); bf_split3(v[1], h[1], m[1], l[1]);
+            vf[0].u[k] = bf_pack_hi16(h[0], h[1]);
+            vf[1].u[k] = bf_pack_hi16(m[0], m[1]);
+            vf[2].u[k] = bf_pack_hi16(l[0], l[1]);
+        }
+    }
+}
+#define WB_VMAKE(vf, jj) wb_vmake<F16>(vf, jj, beta, wX, wY, wZ)
+
+// ---- filter fragments of positions (wi, 2 jp), (wi, 2 jp + 1): F[jj][mb][term], 12 consecutive fragments of the packed layout.
+// Buffer loads: the fragment index is wave-uniform (scalar offset), the only vector address is lane * 16.
+// KSTEPS: K steps of the whole packed blob, KSTEP0: the first of this workgroup's output group
+#define WB_FRAGMENTS(KSTEPS, KSTEP0) \
+    const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void *)upk, 0, (int)((KSTEPS) * WB_FRAGS_PER_KSTEP * 1024), MFR_RSRC_FLAGS); \
+    const unsigned fbase = (unsigned)(((KSTEP0) * WB_FRAGS_PER_KSTEP + wi * 24 + jp * 12) * 1024); \
+    const unsigned lane16 = (unsigned)lane * 16u; \
+    WbFrag F[2][2][3]; \
+    auto aload = [&](int c, int jj) { \
+        const unsigned so = fbase + (unsigned)((c * WB_FRAGS_PER_KSTEP + jj * 6) * 1024); \
+        _Pragma("unroll") for (int mb = 0; mb < 2; ++mb) \
+            _Pragma("unroll") for (int t = 0; t < 3; ++t) \
+                F[jj][mb][t].q = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsF, lane16, so + (unsigned)((mb * 3 + t) * 1024), 0)); \
+    }
+
+// accumulators acc[jj][mb][nb]: position 2 jp + jj, channel block mb, tile block nb
+#define WB_ZERO_ACC() \
+    f32x16 acc[2][2][2]; \
+    _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) \
+        _Pragma("unroll") for (int mb = 0; mb < 2; ++mb) \
+            _Pragma("unroll") for (int nb = 0; nb < 2; ++nb) \
+                _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[jj][mb][nb][r] = 0.f
+
+// the partial products of position jj and tile block nb, small terms first (ta: filter term, tb: V term); the two channel blocks alternate
+template <bool F16>
+__device__ __forceinline__ void wb_products(f32x16 (&acc)[2][2][2], const WbFrag (&F)[2][2][3], const WbFrag (&vf)[3], int jj, int nb)
+{
+#define WB_PROD(ta, tb) do { \
+        if (F16) { acc[jj][0][nb] = SF_MFMA(F[jj][0][ta].q, vf[tb].q, acc[jj][0][nb]); acc[jj][1][nb] = SF_MFMA(F[jj][1][ta].q, vf[tb].q, acc[jj][1][nb]); } \
+        else     { acc[jj][0][nb] = WB_MFMA_BF(F[jj][0][ta].v, vf[tb].v, acc[jj][0][nb]); acc[jj][1][nb] = WB_MFMA_BF(F[jj][1][ta].v, vf[tb].v, acc[jj][1][nb]); } } while (0)
+    if (F16) { WB_PROD(2, 1); WB_PROD(1, 0); WB_PROD(0, 0); }      // uq vl, ul vh, uh vh
+    else     { WB_PROD(1, 1); WB_PROD(0, 2); WB_PROD(2, 0); WB_PROD(0, 1); WB_PROD(1, 0); WB_PROD(0, 0); }
+#undef WB_PROD
+}
+#define WB_PHASE(jj, nb, vf) wb_products<F16>(acc, F, vf, jj, nb)
+
+// ---- K loop, software-pipelined.  A wavefront that alternates "produce V" and "its MFMAs" is blocked at the MFMA issue while the
+// matrix pipe drains -- and with the barrier its SIMD partner is in the same phase at the same time, so nothing overlaps.
+// tools/ubench/mfma_valu_bf16.hip: five VALU instructions per MFMA are free when they sit BETWEEN the MFMAs in program order.  So V is
+// double-buffered (vfA / vfB) and every block of MFMAs is written together with the production of the NEXT block's V:
+//     S1  products (jj 0, nb 0; vfA)   +  V(jj 1, nb 0) -> vfB
+//     S2  products (jj 1, nb 0; vfB)   +  row combinations of tile block 1, V(jj 0, nb 1) -> vfA
+//     S3  products (jj 0, nb 1; vfA)   +  V(jj 1, nb 1) -> vfB;   fragments (jj 0) of the next step requested
+//     -- BETWEEN (p8: vmcnt, the next step's patches are in; border fix-up; barrier.  c1: nothing, all stages are in LDS) --
+//     S4  products (jj 1, nb 1; vfB)   +  row combinations of tile block 0 of the NEXT step, V(jj 0, nb 0) -> vfA;
+//         fragments (jj 1) of the next step requested
+// Top of a step: vmcnt(0) (the step's fragments are in; hipcc would otherwise wait vmcnt(0) at their first use, i.e. for
+// the DMAs it cannot see), then TOP (p8: the patch DMAs of the step after go out: three blocks of time to land).
+// cur, nxt: where this step's and the next step's 16 channels are staged (p8: two stages, c & 1; c1: four stages in place, c).  The last step
+// (WB_KTAIL) has no successor.
+#define WB_FIRST_V() \
+    WbFrag vfA[3], vfB[3]; \
+    wread(0, 0); \
+    WB_VMAKE(vfA, 0)
+#define WB_S123(cur, TOP) \
+    WB_VMCNT(0); \
+    TOP; \
+    WB_VMAKE(vfB, 1); \
+    WB_PHASE(0, 0, vfA); \
+    wread(cur, 1); \
+    WB_VMAKE(vfA, 0); \
+    WB_PHASE(1, 0, vfB); \
+    WB_VMAKE(vfB, 1); \
+    WB_PHASE(0, 1, vfA)
+#define WB_KSTEP(c, cur, nxt, TOP, BETWEEN) do { \
+        WB_S123(cur, TOP); \
+        aload((c) + 1, 0); \
+        WB_STAMP(4 + 3 * ((c) & 3)); \
+        BETWEEN; \
+        wread(nxt, 0); \
+        WB_VMAKE(vfA, 0); \
+        WB_PHASE(1, 1, vfB); \
+        aload((c) + 1, 1); } while (0)
+#define WB_KTAIL(cur) do { \
+        WB_STAMP(16); \
+        WB_S123(cur, (void)0); \
+        WB_PHASE(1, 1, vfB); \
+        WB_STAMP(17); } while (0)
+
+// ---- output transform.  Row partials over j: pa = M0 + M1 + M2, pb = M1 - M2 - M3; wavefront (wi, 0) contributes (M0 + M1, M1),
+// wavefront (wi, 1) contributes (M2, -(M2 + M3)).  Round mb: part[row][jp][ab][nb][r4][lane] (float4 = registers 4 r4 .. 4 r4 + 3),
+// 8 x 16 KB; wavefront q then finishes tile block q & 1, register group q >> 1 (four channels) of the round.
+#define WB_OUT_GEOMETRY(POOL) \
+    const int qnb = w & 1, qr4 = w >> 1; \
+    const int tr = 2 * qnb + tysub; \
+    const int ty = 4 * by + tr, tx = 16 * bx + col; \
+    const int Ho = (POOL) ? (H >> 1) : H, Wo = (POOL) ? (W >> 1) : W; \
+    const size_t cstride = (size_t)Ho * Wo; \
+    float4 *part = (float4 *)lds
+// one round mb of output group cg, up to the 2 x 2 outputs Y[k][.] of the lane's four channels co0 + k (scaled, + bias; range guard accumulated
+// into gchk) and their maximum m[k], which a pooled layer stores (formed here, next to Y[k]: in a loop of its own behind this one hipcc orders
+// c1's fmas and maxima the other way round).  CH(co): the channel whose bias is read (p8: clamped to Cout - 1, the last group may be partial;
+// oscale is padded to ncg * 64 entries)
+#define WB_CH_CLAMPED(co) min(co, Cout - 1)
+#define WB_CH_ALL(co) (co)
+#define WB_OUT_ROUND(mb, cg, CH) \
+    __syncthreads();                                    /* patch stages (mb = 0) / the previous round's partials (mb = 1) are dead */ \
+    WB_STAMP(18 + 4 * mb); \
+    _Pragma("unroll") for (int nb = 0; nb < 2; ++nb) \
+        _Pragma("unroll") for (int r4 = 0; r4 < 4; ++r4) { \
+            float pa[4], pb[4]; \
+            _Pragma("unroll") for (int k = 0; k < 4; ++k) { \
+                const int r = 4 * r4 + k; \
+                const float sum = acc[0][mb][nb][r] + acc[1][mb][nb][r]; \
+                pa[k] = jp ? acc[0][mb][nb][r] : sum; \
+                pb[k] = jp ? -sum : acc[1][mb][nb][r]; \
+            } \
+            part[((((wi * 2 + jp) * 2 + 0) * 2 + nb) * 4 + r4) * 64 + lane] = make_float4(pa[0], pa[1], pa[2], pa[3]); \
+            part[((((wi * 2 + jp) * 2 + 1) * 2 + nb) * 4 + r4) * 64 + lane] = make_float4(pb[0], pb[1], pb[2], pb[3]); \
+        } \
+    const int co0 = (cg) * 64 + mb * 32 + 4 * kg + 8 * qr4; \
+    float bv[4], os[4]; \
+    _Pragma("unroll") for (int k = 0; k < 4; ++k) { \
+        bv[k] = bias ? bias[CH(co0 + k)] : 0.f; \
+        os[k] = F16 ? oscale[co0 + k] : 1.0f; \
+    } \
+    WB_STAMP(19 + 4 * mb); \
+    __syncthreads(); \
+    WB_STAMP(20 + 4 * mb); \
+    const float4 *pq = part + (qnb * 4 + qr4) * 64 + lane;      /* + ((row * 2 + jp) * 2 + ab) * 8 * 64 */ \
+    float4 P[4][2]; \
+    _Pragma("unroll") for (int row = 0; row < 4; ++row) \
+        _Pragma("unroll") for (int ab = 0; ab < 2; ++ab) { \
+            const float4 u = pq[(((row * 2 + 0) * 2 + ab) * 8) * 64], v = pq[(((row * 2 + 1) * 2 + ab) * 8) * 64]; \
+            P[row][ab] = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w); \
+        } \
+    float Y[4][4], m[4]; \
+    _Pragma("unroll") for (int k = 0; k < 4; ++k) { \
+        /* A^T applied along i:  Y[0][.] = P0 + P1 + P2,  Y[1][.] = P1 - P2 - P3 */ \
+        const float y0 = (WB_EL(P[0][0]) + WB_EL(P[1][0])) + WB_EL(P[2][0]), y1 = (WB_EL(P[0][1]) + WB_EL(P[1][1])) + WB_EL(P[2][1]); \
+        const float y2 = (WB_EL(P[1][0]) - WB_EL(P[2][0])) - WB_EL(P[3][0]), y3 = (WB_EL(P[1][1]) - WB_EL(P[2][1])) - WB_EL(P[3][1]); \
+        /* range guard (guard.h), before bias / residual / activation */ \
+        if (F16 && guard) { MFR_GUARD_ACC(gchk, y0); MFR_GUARD_ACC(gchk, y1); MFR_GUARD_ACC(gchk, y2); MFR_GUARD_ACC(gchk, y3); } \
+        if (F16) { Y[k][0] = __builtin_fmaf(y0, os[k], bv[k]); Y[k][1] = __builtin_fmaf(y1, os[k], bv[k]); Y[k][2] = __builtin_fmaf(y2, os[k], bv[k]); Y[k][3] = __builtin_fmaf(y3, os[k], bv[k]); } \
+        else     { Y[k][0] = y0 + bv[k]; Y[k][1] = y1 + bv[k]; Y[k][2] = y2 + bv[k]; Y[k][3] = y3 + bv[k]; } \
+        m[k] = fmaxf(fmaxf(Y[k][0], Y[k][1]), fmaxf(Y[k][2], Y[k][3])); \
+    }
+#define WB_EL(v) (k == 0 ? (v).x : k == 1 ? (v).y : k == 2 ? (v).z : (v).w)
+// pooled store: activation of the 2 x 2 maximum (the activations are monotone: act(max) = max(act)); yb: channel co0's plane, allco: no channel
+// of the round lies beyond Cout
+#define WB_STORE_POOLED(yb, allco, act) do { \
+        _Pragma("unroll") for (int k = 0; k < 4; ++k) { \
+            if ((act) == 1) m[k] = fmaxf(m[k], 0.f); \
+            else if ((act) == 2) m[k] = m[k] > 0.f ? m[k] : 0.01f * m[k]; \
+        } \
+        if (ty < Ho && tx < Wo) { \
+            float *yo = (yb) + (size_t)ty * Wo + tx; \
+            _Pragma("unroll") for (int k = 0; k < 4; ++k) \
+                if ((allco) || co0 + k < Cout) yo[(size_t)k * cstride] = m[k]; \
+        } } while (0)
+
 // What bounds this kernel (profiles/r05_pmc_conv1b.json, r05_conv1b_timeline.json): not memory (traffic 1.01 x algorithmic) and not the matrix pipe
 // (20 % busy with f16x2) but the SIMD's issue port -- a VALU / LDS / VMEM instruction costs ~4 cycles of the SIMD whichever wavefront issues it
 // and does NOT overlap an MFMA's 32: a K step costs a wavefront 24 x 32 + ~300 x 4 cycles, two wavefronts per SIMD, 3.7 - 4.6 k cycles measured
@@ -166,9 +388,8 @@ __global__ void __launch_bounds__(512, 2) wino_split_p8_kernel(
     if (sl >= Sx || s >= S) return;
     const int bx = s % nbx, by = (s / nbx) % nby, b = s / (nbx * nby);
     const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wi = w >> 1, jp = w & 1;
-    const int col = lane & 15, tysub = (lane >> 4) & 1, kg = lane >> 5;
+    WB_WAVE_GEOMETRY(tid);
+    WB_LANE_GEOMETRY(lane);
     const int HW = H * W;
 
     // ---- patch staging by LDS-DMA: per K step and channel a 10-row x 48-column window (columns 32 bx - 1 + cx, rows 8 by - 1 + r; 34 x 10
@@ -224,235 +445,39 @@ __global__ void __launch_bounds__(512, 2) wino_split_p8_kernel(
         }
     };
 
-    // ---- row combination of Winograd row wi for the three patch columns of column pair jp.
-    // row i of B^T d:  i = 0: d0 - d2;  1: d1 + d2;  2: d2 - d1;  3: d1 - d3
-    const int ra = (wi == 0) ? 0 : (wi == 2) ? 2 : 1;
-    const int rb = (wi == 0) ? 2 : (wi == 2) ? 1 : (wi == 1) ? 2 : 3;
-    const float sg = (wi == 1) ? 1.0f : -1.0f;
-    const float beta = jp ? -1.0f : 1.0f;
-    const int cX = jp ? 2 : 0, cZ = jp ? 1 : 2;
-    const int ofa = (2 * tysub + ra) * WB_RS + 2 * col, ofb = (2 * tysub + rb) * WB_RS + 2 * col;    // tile block nb: + 4 nb WB_RS
-    float wX[8], wY[8], wZ[8];
-    auto wread = [&](int buf, int nb) {
-        const wb_lds_f32 *st = (const wb_lds_f32 *)lds + buf * WB_STAGE + (8 * kg) * WB_CH + 4 * nb * WB_RS;
-#pragma unroll
-        for (int e0 = 0; e0 < 8; e0 += 4) {
-            wb_f32x2 a2[4], b2[4];
-            float a1[4], b1[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const wb_lds_f32 *ch = st + (e0 + e) * WB_CH;
-                // volatile: keeps hipcc from fusing the reads of a row into ds_read2_b64, which the LDS serves at a quarter of the rate of two
-                // ds_read_b64 (MI355X_MICROARCH.md, LDS table: 16 vs 2 + 2 cycles per wavefront)
-                a2[e] = *(const volatile wb_lds_f32x2 *)(ch + ofa + cX); a1[e] = *(const volatile wb_lds_f32 *)(ch + ofa + cZ);
-                b2[e] = *(const volatile wb_lds_f32x2 *)(ch + ofb + cX); b1[e] = *(const volatile wb_lds_f32 *)(ch + ofb + cZ);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                wX[e0 + e] = __builtin_fmaf(sg, b2[e].x, a2[e].x); wY[e0 + e] = __builtin_fmaf(sg, b2[e].y, a2[e].y);
-                wZ[e0 + e] = __builtin_fmaf(sg, b1[e], a1[e]);
-            }
-            // pin the combinations here (otherwise they sink below the next batch's reads and the raw values pile up)
-            asm volatile("" : "+v"(wX[e0]), "+v"(wY[e0]), "+v"(wZ[e0]), "+v"(wX[e0 + 1]), "+v"(wY[e0 + 1]), "+v"(wZ[e0 + 1]),
-                              "+v"(wX[e0 + 2]), "+v"(wY[e0 + 2]), "+v"(wZ[e0 + 2]), "+v"(wX[e0 + 3]), "+v"(wY[e0 + 3]), "+v"(wZ[e0 + 3]) :: "memory");
-        }
-    };
-    // V(wi, 2 jp + jj) of the tile block, split and packed two input channels at a time: vf[term].u[k] = channels 2 k, 2 k + 1
-    auto vmake = [&](WbFrag (&vf)[3], int jj) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float v[2];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const int q = 2 * k + e;
-                v[e] = jj ? __builtin_fmaf(beta, wY[q], wZ[q]) : wX[q] - wZ[q];
-            }
-            if (F16) sf_split2(v[0], v[1], SF_LOW_SCALE, vf[0].u[k], vf[1].u[k]);
-            else {
-                unsigned h[2], m[2], l[2];
-                bf_split3(v[0], h[0], m[0], l[0]); bf_split3(v[1], h[1], m[1], l[1]);
-                vf[0].u[k] = bf_pack_hi16(h[0], h[1]);
-                vf[1].u[k] = bf_pack_hi16(m[0], m[1]);
-                vf[2].u[k] = bf_pack_hi16(l[0], l[1]);
-            }
-        }
-    };
-
-    // ---- filter fragments of positions (wi, 2 jp), (wi, 2 jp + 1): [jj][mb][term], 12 consecutive fragments of the packed layout.
-    // Buffer loads: the fragment index is wave-uniform (scalar offset), the only vector address is lane * 16.
-    const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void *)upk, 0, (int)(ncg * nks * WB_FRAGS_PER_KSTEP * 1024), MFR_RSRC_FLAGS);
-    const unsigned fbase = (unsigned)((cg * nks * WB_FRAGS_PER_KSTEP + wi * 24 + jp * 12) * 1024);
-    const unsigned lane16 = (unsigned)lane * 16u;
-    WbFrag F[2][2][3];
-    auto aload = [&](int c, int jj) {
-        const unsigned so = fbase + (unsigned)((c * WB_FRAGS_PER_KSTEP + jj * 6) * 1024);
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int t = 0; t < 3; ++t)
-                F[jj][mb][t].q = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsF, lane16, so + (unsigned)((mb * 3 + t) * 1024), 0));
-    };
-    // partial products, small terms first (ta: filter term, tb: V term); the two channel blocks alternate
-#define WB8_PROD(jj, nb, vf, ta, tb) do { \
-        if (F16) { acc[jj][0][nb] = SF_MFMA(F[jj][0][ta].q, vf[tb].q, acc[jj][0][nb]); acc[jj][1][nb] = SF_MFMA(F[jj][1][ta].q, vf[tb].q, acc[jj][1][nb]); } \
-        else     { acc[jj][0][nb] = WB_MFMA_BF(F[jj][0][ta].v, vf[tb].v, acc[jj][0][nb]); acc[jj][1][nb] = WB_MFMA_BF(F[jj][1][ta].v, vf[tb].v, acc[jj][1][nb]); } } while (0)
-#define WB8_PHASE(jj, nb, vf) do { \
-        if (F16) { WB8_PROD(jj, nb, vf, 2, 1); WB8_PROD(jj, nb, vf, 1, 0); WB8_PROD(jj, nb, vf, 0, 0); }      /* uq vl, ul vh, uh vh */ \
-        else     { WB8_PROD(jj, nb, vf, 1, 1); WB8_PROD(jj, nb, vf, 0, 2); WB8_PROD(jj, nb, vf, 2, 0); \
-                   WB8_PROD(jj, nb, vf, 0, 1); WB8_PROD(jj, nb, vf, 1, 0); WB8_PROD(jj, nb, vf, 0, 0); } } while (0)
-#define WB8_VMCNT(n) __builtin_amdgcn_s_waitcnt(0x0F70 | ((n) & 15) | (((n) >> 4) << 14))      /* vmcnt(n) only; the builtin (not inline asm) so that hipcc's own wait bookkeeping sees it */
+    WB_ROW_COMBINATION();
+    WB_FRAGMENTS(ncg * nks, cg * nks);
 
     // ---- prologue
     WB_STAMP(0);
     aload(0, 0); aload(0, 1);
     pdma(0, 0);
-    WB8_VMCNT(0);
+    WB_VMCNT(0);
     WB_STAMP(1);
     pfix(0);
     __syncthreads();
     WB_STAMP(2);
-    f32x16 acc[2][2][2];
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[jj][mb][nb][r] = 0.f;
-
-    // ---- K loop, software-pipelined.  A wavefront that alternates "produce V" and "its MFMAs" is blocked at the MFMA issue while the
-    // matrix pipe drains -- and with the barrier its SIMD partner is in the same phase at the same time, so nothing overlaps.
-    // tools/ubench/mfma_valu_bf16.hip: five VALU instructions per MFMA are free when they sit BETWEEN the MFMAs in program order.  So V is
-    // double-buffered (vfA / vfB) and every block of MFMAs is written together with the production of the NEXT block's V:
-    //     S1  products (jj 0, nb 0; vfA)   +  V(jj 1, nb 0) -> vfB
-    //     S2  products (jj 1, nb 0; vfB)   +  row combinations of tile block 1, V(jj 0, nb 1) -> vfA
-    //     S3  products (jj 0, nb 1; vfA)   +  V(jj 1, nb 1) -> vfB;   fragments (jj 0) of the next step requested
-    //     -- vmcnt: the next step's patches are in; border fix-up; barrier --
-    //     S4  products (jj 1, nb 1; vfB)   +  row combinations of tile block 0 of the NEXT step, V(jj 0, nb 0) -> vfA;
-    //         fragments (jj 1) of the next step requested
-    // Top of a step: vmcnt(0) (the step's fragments are in; hipcc would otherwise wait vmcnt(0) at their first use, i.e. for
-    // the DMAs it cannot see), then the patch DMAs of the step after go out: three blocks of time to land.
-    WbFrag vfA[3], vfB[3];
-    wread(0, 0);
-    vmake(vfA, 0);
-    int c = 0;
+    WB_ZERO_ACC();
+    WB_FIRST_V();
     WB_STAMP(3);
-    for (; c + 1 < nks; ++c) {
-        WB8_VMCNT(0);
-        pdma(c + 1, (c + 1) & 1);
-        vmake(vfB, 1);
-        WB8_PHASE(0, 0, vfA);
-        wread(c & 1, 1);
-        vmake(vfA, 0);
-        WB8_PHASE(1, 0, vfB);
-        vmake(vfB, 1);
-        WB8_PHASE(0, 1, vfA);
-        aload(c + 1, 0);
-        WB_STAMP(4 + 3 * (c & 3));
-        WB8_VMCNT(6);                                                     // the four DMAs are older than the six fragment loads
-        pfix((c + 1) & 1);
-        WB_STAMP(5 + 3 * (c & 3));
-        __syncthreads();
-        WB_STAMP(6 + 3 * (c & 3));
-        wread((c + 1) & 1, 0);
-        vmake(vfA, 0);
-        WB8_PHASE(1, 1, vfB);
-        aload(c + 1, 1);
-    }
-    WB_STAMP(16);
-    WB8_VMCNT(0);
-    vmake(vfB, 1);
-    WB8_PHASE(0, 0, vfA);
-    wread(c & 1, 1);
-    vmake(vfA, 0);
-    WB8_PHASE(1, 0, vfB);
-    vmake(vfB, 1);
-    WB8_PHASE(0, 1, vfA);
-    WB8_PHASE(1, 1, vfB);
-    WB_STAMP(17);
-#undef WB8_PHASE
-#undef WB8_PROD
-#undef WB8_VMCNT
+    int c = 0;
+    for (; c + 1 < nks; ++c)
+        WB_KSTEP(c, c & 1, (c + 1) & 1,
+                 pdma(c + 1, (c + 1) & 1),
+                 WB_VMCNT(6);                                             // the four DMAs are older than the six fragment loads
+                 pfix((c + 1) & 1); WB_STAMP(5 + 3 * (c & 3)); __syncthreads(); WB_STAMP(6 + 3 * (c & 3)));
+    WB_KTAIL(c & 1);
 
-    // ---- output transform.  Row partials over j: pa = M0 + M1 + M2, pb = M1 - M2 - M3; wavefront (wi, 0) contributes (M0 + M1, M1),
-    // wavefront (wi, 1) contributes (M2, -(M2 + M3)).  Round mb: part[row][jp][ab][nb][r4][lane] (float4 = registers 4 r4 .. 4 r4 + 3),
-    // 8 x 16 KB; wavefront q then finishes tile block q & 1, register group q >> 1 (four channels) of the round.
-    const int qnb = w & 1, qr4 = w >> 1;
-    const int tr = 2 * qnb + tysub;
-    const int ty = 4 * by + tr, tx = 16 * bx + col;
-    const int Ho = POOL ? (H >> 1) : H, Wo = POOL ? (W >> 1) : W;
-    const size_t cstride = (size_t)Ho * Wo;
-    float4 *part = (float4 *)lds;
+    WB_OUT_GEOMETRY(POOL);
     float gchk = 0.f;
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb) {
-        __syncthreads();                                    // patch stages (mb = 0) / the previous round's partials (mb = 1) are dead
-        WB_STAMP(18 + 4 * mb);
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                float pa[4], pb[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int r = 4 * r4 + k;
-                    const float sum = acc[0][mb][nb][r] + acc[1][mb][nb][r];
-                    pa[k] = jp ? acc[0][mb][nb][r] : sum;
-                    pb[k] = jp ? -sum : acc[1][mb][nb][r];
-                }
-                part[((((wi * 2 + jp) * 2 + 0) * 2 + nb) * 4 + r4) * 64 + lane] = make_float4(pa[0], pa[1], pa[2], pa[3]);
-                part[((((wi * 2 + jp) * 2 + 1) * 2 + nb) * 4 + r4) * 64 + lane] = make_float4(pb[0], pb[1], pb[2], pb[3]);
-            }
-        const int co0 = cg * 64 + mb * 32 + 4 * kg + 8 * qr4;       // this lane's four channels of the round: co0 + k
-        float bv[4], os[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            bv[k] = bias ? bias[min(co0 + k, Cout - 1)] : 0.f;
-            os[k] = F16 ? oscale[co0 + k] : 1.0f;                   // (padded to ncg * 64 entries)
-        }
-        WB_STAMP(19 + 4 * mb);
-        __syncthreads();
-        WB_STAMP(20 + 4 * mb);
-        const float4 *pq = part + (qnb * 4 + qr4) * 64 + lane;      // + ((row * 2 + jp) * 2 + ab) * 8 * 64
-        float4 P[4][2];
-#pragma unroll
-        for (int row = 0; row < 4; ++row)
-#pragma unroll
-            for (int ab = 0; ab < 2; ++ab) {
-                const float4 u = pq[(((row * 2 + 0) * 2 + ab) * 8) * 64], v = pq[(((row * 2 + 1) * 2 + ab) * 8) * 64];
-                P[row][ab] = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
-            }
-        float Y[4][4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-#define WB_EL(v) (k == 0 ? (v).x : k == 1 ? (v).y : k == 2 ? (v).z : (v).w)
-            // A^T applied along i:  Y[0][.] = P0 + P1 + P2,  Y[1][.] = P1 - P2 - P3
-            const float y0 = (WB_EL(P[0][0]) + WB_EL(P[1][0])) + WB_EL(P[2][0]), y1 = (WB_EL(P[0][1]) + WB_EL(P[1][1])) + WB_EL(P[2][1]);
-            const float y2 = (WB_EL(P[1][0]) - WB_EL(P[2][0])) - WB_EL(P[3][0]), y3 = (WB_EL(P[1][1]) - WB_EL(P[2][1])) - WB_EL(P[3][1]);
-#undef WB_EL
-            if (F16 && guard) { MFR_GUARD_ACC(gchk, y0); MFR_GUARD_ACC(gchk, y1); MFR_GUARD_ACC(gchk, y2); MFR_GUARD_ACC(gchk, y3); }   // range guard (guard.h), before bias / residual / activation
-            if (F16) { Y[k][0] = __builtin_fmaf(y0, os[k], bv[k]); Y[k][1] = __builtin_fmaf(y1, os[k], bv[k]); Y[k][2] = __builtin_fmaf(y2, os[k], bv[k]); Y[k][3] = __builtin_fmaf(y3, os[k], bv[k]); }
-            else     { Y[k][0] = y0 + bv[k]; Y[k][1] = y1 + bv[k]; Y[k][2] = y2 + bv[k]; Y[k][3] = y3 + bv[k]; }
-        }
+        WB_OUT_ROUND(mb, cg, WB_CH_CLAMPED);
         WB_STAMP(21 + 4 * mb);
         float *yb = y + ((size_t)b * Cout + co0) * cstride;
         const bool allco = cg * 64 + mb * 32 + 32 <= Cout;
-        if (POOL) {
-            float m[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                m[k] = fmaxf(fmaxf(Y[k][0], Y[k][1]), fmaxf(Y[k][2], Y[k][3]));     // the activations are monotone: act(max) = max(act)
-                if (act == 1) m[k] = fmaxf(m[k], 0.f);
-                else if (act == 2) m[k] = m[k] > 0.f ? m[k] : 0.01f * m[k];
-            }
-            if (ty < Ho && tx < Wo) {
-                float *yo = yb + (size_t)ty * Wo + tx;
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (allco || co0 + k < Cout) yo[(size_t)k * cstride] = m[k];
-            }
-        } else {
+        if (POOL) WB_STORE_POOLED(yb, allco, act);
+        else {
             const int oy = 2 * ty, ox = 2 * tx;
             const bool c0 = ox < W, c1 = ox + 1 < W, r0 = oy < H, r1 = oy + 1 < H;
             if (residual) {
@@ -515,11 +540,13 @@ __global__ void __launch_bounds__(512, 2) wino_split_p8_kernel(
 // columns, its 3 x 8 gray taps in registers for all eight channels) -- the SAME nine fused multiply-adds in the same order, + bias, max 0, as
 // conv3x3_c1_relu_kernel (elementwise.hip), so the patch is that kernel's output bit for bit; positions outside the image are conv1b's zero padding
 // -- and all four K steps' patches (120 KB) sit in LDS before the first MFMA.  The K loop then has no DMA, no border fix-up and no barrier: the
-// wavefronts run free.  Everything from the row combinations to the output transform is the kernel's above (Cin = Cout = 64, pooled, ReLU).
+// wavefronts run free.  From the row combinations to the pooled store it runs the shared pieces above as p8<true, true> does (Cin = Cout = 64, ReLU).
 __global__ void __launch_bounds__(512, 2) wino_split_c1_kernel(
     const float *__restrict__ gray, const float *__restrict__ w1a, const float *__restrict__ b1a, const uint4 *__restrict__ upk, const float *__restrict__ oscale,
     const float *__restrict__ bias, float *__restrict__ y, int H, int W, int nbx, int nby, int S, int Sx, int *guard)
 {
+    constexpr bool F16 = true;                              // what the shared pieces take from p8's template and arguments: f16x2, one full output group
+    constexpr int Cout = 64;
     float gchk = 0.f;                                       // range guard (guard.h), over all blocks of this persistent workgroup
     constexpr int GS = 40;                                  // gray window row stride (38 columns used)
     __shared__ __attribute__((aligned(16))) float lds[32768 + 12 * GS];
@@ -530,8 +557,7 @@ __global__ void __launch_bounds__(512, 2) wino_split_c1_kernel(
     const int id = blockIdx.x;
     const int xcd = id & 7, slot = id >> 3, per_xcd = gridDim.x >> 3;
     const int tid = threadIdx.x;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wi = w >> 1, jp = w & 1;
+    WB_WAVE_GEOMETRY(tid);
     auto gray_of = [&](int sl_) -> float {                  // this thread's element (tid < 456) of the 12 x 38 gray window: rows 8 by - 2 .. 8 by + 9, columns 32 bx - 2 .. 32 bx + 35; outside the image: 0 (conv1a's zero padding)
         const int s_ = xcd * Sx + sl_;
         if (tid >= 12 * 38 || sl_ >= Sx || s_ >= S) return 0.f;
@@ -554,21 +580,10 @@ __global__ void __launch_bounds__(512, 2) wino_split_c1_kernel(
     int tid_ = tid;
     asm volatile("" : "+v"(tid_));
     const int lane = tid_ & 63;
-    const int col = lane & 15, tysub = (lane >> 4) & 1, kg = lane >> 5;
+    WB_LANE_GEOMETRY(lane);
 
     // ---- filter fragments (requested below, once the gray window is in LDS: they land while the patch is computed)
-    const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void *)upk, 0, (int)(4 * WB_FRAGS_PER_KSTEP * 1024), MFR_RSRC_FLAGS);
-    const unsigned fbase = (unsigned)((wi * 24 + jp * 12) * 1024);
-    const unsigned lane16 = (unsigned)lane * 16u;
-    WbFrag F[2][2][3];
-    auto aload = [&](int c, int jj) {
-        const unsigned so = fbase + (unsigned)((c * WB_FRAGS_PER_KSTEP + jj * 6) * 1024);
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int t = 0; t < 3; ++t)
-                F[jj][mb][t].q = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsF, lane16, so + (unsigned)((mb * 3 + t) * 1024), 0));
-    };
+    WB_FRAGMENTS(4, 0);
     WB_STAMP(0);
 
     // ---- this block's gray window is in LDS (written during the previous block); the patch stages are free once every wavefront is past
@@ -637,153 +652,20 @@ __global__ void __launch_bounds__(512, 2) wino_split_c1_kernel(
     if (tid < 12 * 38) gwin[(tid / 38) * GS + (tid - 38 * (tid / 38))] = gnext;
     gnext = gray_of(sl + 2 * per_xcd);
 
-    // ---- from here on: wino_split_p8_kernel<true, true> with the K step's stage = its 16 channels in place (no DMA, no fix-up, no barrier)
-    const int ra = (wi == 0) ? 0 : (wi == 2) ? 2 : 1;
-    const int rb = (wi == 0) ? 2 : (wi == 2) ? 1 : (wi == 1) ? 2 : 3;
-    const float sg = (wi == 1) ? 1.0f : -1.0f;
-    const float beta = jp ? -1.0f : 1.0f;
-    const int cX = jp ? 2 : 0, cZ = jp ? 1 : 2;
-    const int ofa = (2 * tysub + ra) * WB_RS + 2 * col, ofb = (2 * tysub + rb) * WB_RS + 2 * col;
-    float wX[8], wY[8], wZ[8];
-    auto wread = [&](int buf, int nb) {
-        const wb_lds_f32 *st = (const wb_lds_f32 *)lds + buf * WB_STAGE + (8 * kg) * WB_CH + 4 * nb * WB_RS;
-#pragma unroll
-        for (int e0 = 0; e0 < 8; e0 += 4) {
-            wb_f32x2 a2[4], b2[4];
-            float a1[4], b1[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const wb_lds_f32 *ch = st + (e0 + e) * WB_CH;
-                a2[e] = *(const volatile wb_lds_f32x2 *)(ch + ofa + cX); a1[e] = *(const volatile wb_lds_f32 *)(ch + ofa + cZ);
-                b2[e] = *(const volatile wb_lds_f32x2 *)(ch + ofb + cX); b1[e] = *(const volatile wb_lds_f32 *)(ch + ofb + cZ);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                wX[e0 + e] = __builtin_fmaf(sg, b2[e].x, a2[e].x); wY[e0 + e] = __builtin_fmaf(sg, b2[e].y, a2[e].y);
-                wZ[e0 + e] = __builtin_fmaf(sg, b1[e], a1[e]);
-            }
-            asm volatile("" : "+v"(wX[e0]), "+v"(wY[e0]), "+v"(wZ[e0]), "+v"(wX[e0 + 1]), "+v"(wY[e0 + 1]), "+v"(wZ[e0 + 1]),
-                              "+v"(wX[e0 + 2]), "+v"(wY[e0 + 2]), "+v"(wZ[e0 + 2]), "+v"(wX[e0 + 3]), "+v"(wY[e0 + 3]), "+v"(wZ[e0 + 3]) :: "memory");
-        }
-    };
-    auto vmake = [&](WbFrag (&vf)[3], int jj) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float v[2];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const int q = 2 * k + e;
-                v[e] = jj ? __builtin_fmaf(beta, wY[q], wZ[q]) : wX[q] - wZ[q];
-            }
-            sf_split2(v[0], v[1], SF_LOW_SCALE, vf[0].u[k], vf[1].u[k]);
-        }
-    };
-    f32x16 acc[2][2][2];
-#define WC1_PROD(jj, nb, vf, ta, tb) do { \
-        acc[jj][0][nb] = SF_MFMA(F[jj][0][ta].q, vf[tb].q, acc[jj][0][nb]); acc[jj][1][nb] = SF_MFMA(F[jj][1][ta].q, vf[tb].q, acc[jj][1][nb]); } while (0)
-#define WC1_PHASE(jj, nb, vf) do { WC1_PROD(jj, nb, vf, 2, 1); WC1_PROD(jj, nb, vf, 1, 0); WC1_PROD(jj, nb, vf, 0, 0); } while (0)
-#define WC1_VMCNT0() __builtin_amdgcn_s_waitcnt(0x0F70)
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[jj][mb][nb][r] = 0.f;
-    WbFrag vfA[3], vfB[3];
-    wread(0, 0);
-    vmake(vfA, 0);
+    // ---- the shared K loop on stages 0 .. 3 = the 16 channels of a step in place: no DMA, no fix-up, no barrier
+    WB_ROW_COMBINATION();
+    WB_ZERO_ACC();
+    WB_FIRST_V();
 #pragma unroll 1
-    for (int c = 0; c < 3; ++c) {
-        WC1_VMCNT0();
-        vmake(vfB, 1);
-        WC1_PHASE(0, 0, vfA);
-        wread(c, 1);
-        vmake(vfA, 0);
-        WC1_PHASE(1, 0, vfB);
-        vmake(vfB, 1);
-        WC1_PHASE(0, 1, vfA);
-        aload(c + 1, 0);
-        WB_STAMP(4 + 3 * c);
-        wread(c + 1, 0);
-        vmake(vfA, 0);
-        WC1_PHASE(1, 1, vfB);
-        aload(c + 1, 1);
-    }
-    WB_STAMP(16);
-    WC1_VMCNT0();
-    vmake(vfB, 1);
-    WC1_PHASE(0, 0, vfA);
-    wread(3, 1);
-    vmake(vfA, 0);
-    WC1_PHASE(1, 0, vfB);
-    vmake(vfB, 1);
-    WC1_PHASE(0, 1, vfA);
-    WC1_PHASE(1, 1, vfB);
-    WB_STAMP(17);
-#undef WC1_VMCNT0
-#undef WC1_PHASE
-#undef WC1_PROD
+    for (int c = 0; c < 3; ++c) WB_KSTEP(c, c, c + 1, (void)0, (void)0);
+    WB_KTAIL(3);
 
-    // ---- output transform, pooled + ReLU (as above)
-    const int qnb = w & 1, qr4 = w >> 1;
-    const int tr = 2 * qnb + tysub;
-    const int ty = 4 * by + tr, tx = 16 * bx + col;
-    const int Ho = H >> 1, Wo = W >> 1;
-    const size_t cstride = (size_t)Ho * Wo;
-    float4 *part = (float4 *)lds;
+    // ---- the shared output transform, all 64 channels, pooled + ReLU
+    WB_OUT_GEOMETRY(true);
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb) {
-        __syncthreads();
-        WB_STAMP(18 + 4 * mb);
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                float pa[4], pb[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int r = 4 * r4 + k;
-                    const float sum = acc[0][mb][nb][r] + acc[1][mb][nb][r];
-                    pa[k] = jp ? acc[0][mb][nb][r] : sum;
-                    pb[k] = jp ? -sum : acc[1][mb][nb][r];
-                }
-                part[((((wi * 2 + jp) * 2 + 0) * 2 + nb) * 4 + r4) * 64 + lane] = make_float4(pa[0], pa[1], pa[2], pa[3]);
-                part[((((wi * 2 + jp) * 2 + 1) * 2 + nb) * 4 + r4) * 64 + lane] = make_float4(pb[0], pb[1], pb[2], pb[3]);
-            }
-        const int co0 = mb * 32 + 4 * kg + 8 * qr4;
-        float bv[4], os[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { bv[k] = bias ? bias[co0 + k] : 0.f; os[k] = oscale[co0 + k]; }
-        WB_STAMP(19 + 4 * mb);
-        __syncthreads();
-        WB_STAMP(20 + 4 * mb);
-        const float4 *pq = part + (qnb * 4 + qr4) * 64 + lane;
-        float4 P[4][2];
-#pragma unroll
-        for (int row = 0; row < 4; ++row)
-#pragma unroll
-            for (int ab = 0; ab < 2; ++ab) {
-                const float4 u = pq[(((row * 2 + 0) * 2 + ab) * 8) * 64], v = pq[(((row * 2 + 1) * 2 + ab) * 8) * 64];
-                P[row][ab] = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
-            }
-        float m[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-#define WB_EL(v) (k == 0 ? (v).x : k == 1 ? (v).y : k == 2 ? (v).z : (v).w)
-            const float y0 = (WB_EL(P[0][0]) + WB_EL(P[1][0])) + WB_EL(P[2][0]), y1 = (WB_EL(P[0][1]) + WB_EL(P[1][1])) + WB_EL(P[2][1]);
-            const float y2 = (WB_EL(P[1][0]) - WB_EL(P[2][0])) - WB_EL(P[3][0]), y3 = (WB_EL(P[1][1]) - WB_EL(P[2][1])) - WB_EL(P[3][1]);
-#undef WB_EL
-            if (guard) { MFR_GUARD_ACC(gchk, y0); MFR_GUARD_ACC(gchk, y1); MFR_GUARD_ACC(gchk, y2); MFR_GUARD_ACC(gchk, y3); }
-            const float Y0 = __builtin_fmaf(y0, os[k], bv[k]), Y1 = __builtin_fmaf(y1, os[k], bv[k]), Y2 = __builtin_fmaf(y2, os[k], bv[k]), Y3 = __builtin_fmaf(y3, os[k], bv[k]);
-            m[k] = fmaxf(fmaxf(fmaxf(Y0, Y1), fmaxf(Y2, Y3)), 0.f);
-        }
-        if (ty < Ho && tx < Wo) {
-            float *yo = y + ((size_t)b * 64 + co0) * cstride + (size_t)ty * Wo + tx;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) yo[(size_t)k * cstride] = m[k];
-        }
+        WB_OUT_ROUND(mb, 0, WB_CH_ALL);
+        WB_STORE_POOLED(y + ((size_t)b * Cout + co0) * cstride, true, 1);
         WB_STAMP(21 + 4 * mb);
     }
     WB_STAMP(26);

@@ -586,3 +586,13 @@ def test_round6_entry_points_reject_bad_arguments_before_touching_a_device():
     assert lib.mfr_conv3x3_direct_f16x2_rows(p, p, None, 1, 4, 8, 8, 8, 0, p, 4, None) == E_ARG                           # row stride < Cout
     assert lib.mfr_conv3x3_direct_f16x2_rows(p, p, None, 1, 4, 8, 8, 8, 0, p, 10, None) == E_ARG                          # row stride % 4
     assert lib.mfr_mlp_ln_f16x2(None, 256, 256, None, None, None, None, None, None, 1e-5, None, 128, 16, 0, None) == E_ARG
+
+
+def test_wino_variant_entry_takes_only_the_kernels_that_compute_the_convolution():
+    """mfr_conv3x3_wino_variant names kernel variants 0-4; the former timing-ablation numbers (10-16, 27-33: wrong results by design) are
+    rejected like any other value, before any launch"""
+    import ctypes as C
+    lib = mfr._lib.load()
+    p = C.cast(C.create_string_buffer(64), C.c_void_p)
+    for v in [-1, 5, 9] + list(range(10, 17)) + [26] + list(range(27, 35)):
+        assert lib.mfr_conv3x3_wino_variant(p, p, None, None, 1, 4, 32, 8, 8, 1, 0, v, p, None) == -1, v
