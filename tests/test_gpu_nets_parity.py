@@ -131,6 +131,56 @@ def test_attention_vs_fp64_reference(sg_pair, cross, variant):
         assert (got[b, nq:] == 0).all()
 
 
+# (B2, K, n_tok): A -- no key tile, one partial tile, the exact tile edge, one key into the second / third tile, K no multiple of 32 (cross pairs
+# (0, 1), (31, 32), (33, 64), (65, 70));  B -- a second query block (256 queries per workgroup; 128 for variant 1) that is partly filled, empty
+# (n_tok = 256), one row long, or wholly beyond n_tok
+_TILE_CASES = {"A": (8, 70, [0, 1, 31, 32, 33, 64, 65, 70]), "B": (4, 300, [300, 256, 257, 10])}
+_tile_refs = {}
+
+
+def _tile_boundary_case(case, cross):
+    """inputs and the float64 softmax reference (per image: [nq, 256], zeros where the key image is empty) of one case; computed once, shared by
+    the three variants and never modified"""
+    if (case, cross) not in _tile_refs:
+        B2, K, n = _TILE_CASES[case]
+        g = torch.Generator().manual_seed(44)
+        qkv = torch.randn(B2, K, 768, generator=g) * 1.5
+        q, k, v = [t.double().view(B2, K, 4, 64) for t in qkv.split(256, -1)]
+        want = []
+        for b in range(B2):
+            bk = b ^ 1 if cross else b
+            nq, nk = n[b], n[bk]
+            if nk == 0:
+                want.append(torch.zeros(nq, 256))
+                continue
+            s = torch.einsum("nhd,mhd->hnm", q[b, :nq], k[bk, :nk]) / 8.0
+            want.append(torch.einsum("hnm,mhd->nhd", s.softmax(-1), v[bk, :nk]).reshape(nq, 256).float())
+        _tile_refs[case, cross] = (qkv, torch.tensor(n, dtype=torch.int32), want)
+    return _tile_refs[case, cross]
+
+
+@pytest.mark.parametrize("variant", [0, 1, 2])
+@pytest.mark.parametrize("cross", [False, True])
+@pytest.mark.parametrize("case", ["A", "B"])
+def test_attention_tile_boundaries(sg_pair, case, cross, variant):
+    """all three kernels where a tile loop can go wrong: 0 keys, 1, 31, 32, 33, 64, 65 keys, N = 70 / 300 (no multiple of 32), query blocks partly or
+    wholly beyond n_tok.  Same float64 reference and tolerance as test_attention_vs_fp64_reference; rows >= n_tok and every row of an image whose key
+    image is empty are exactly zero (ntiles = 0 leaves l_run = 0, hence inv = 0); the output buffer starts as NaN, so every row must be written."""
+    ref, hip = sg_pair
+    qkv, n, want = _tile_boundary_case(case, cross)
+    B2, K, _ = qkv.shape
+    out = torch.full((B2, K, 256), float("nan"), device=DEV)
+    got = hip.attention(qkv.to(DEV), n.to(DEV), cross, out=out, variant=variant).cpu()
+    assert torch.isfinite(got).all()
+    for b in range(B2):
+        nq, nk = int(n[b]), int(n[b ^ 1 if cross else b])
+        if nk == 0:
+            assert (got[b] == 0).all()
+        else:
+            np.testing.assert_allclose(got[b, :nq].numpy(), want[b].numpy(), rtol=1e-4, atol=2e-5)
+        assert (got[b, nq:] == 0).all()
+
+
 @pytest.mark.parametrize("cross", [False, True])
 def test_attention_split_kernels_ragged_counts(sg_pair, cross):
     """both split kernels on ragged key / query counts (1, 33, 257 ...): finite, zero rows beyond n, and within the fp32-class tolerance of each
