@@ -431,6 +431,12 @@ int mfr_conv1x1_nchw(const float *x, const float *w, const float *bias, int B, i
  *                          (floats): the token-major operand of the linear layers, written in place of torch's permute().contiguous();
  *                          deinterleave != 0: image 2 k + s of a pair-interleaved batch goes to slot s * (B / 2) + k. */
 int mfr_nchw_to_rows(const float *x, const float *add, int B, int C, int HW, int deinterleave, float *out, long long out_img_stride, int ldo, void *stream);
+/*   mfr_nchw_to_rows_gather  the same transposition with the source image of every output slot taken from a table: out[j][p][c] = x[idx[j]][c][p]
+ *                          (+ add[c][p]), j < n_out, x [n_src, C, HW].  `idx` is a HOST array; it travels to the device as a kernel argument (64 slots per
+ *                          launch, more slots = more launches), so the call adds no copy and no synchronisation.  Every index must lie in [0, n_src):
+ *                          otherwise MFR_E_ARG and nothing is launched.  (LoFTR's side-major token buffer filled from cached reference views.) */
+int mfr_nchw_to_rows_gather(const float *x, const float *add, int n_src, int C, int HW, const int32_t *idx, int n_out, float *out, long long out_img_stride,
+                            int ldo, void *stream);
 int mfr_bias_pool2_relu_nchw(const float *x, const float *bias, int B, int C, int H, int W, float *y, void *stream);
 
 /* ------------------------------------------------------------------------------------------

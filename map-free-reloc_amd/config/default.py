@@ -11,8 +11,10 @@ keys this implementation adds (declared here because unknown keys are rejected o
                      EMAT_SCORE: model quality of the E-matrix RANSAC -- 'magsac' (MAGSAC++ loss + sigma-consensus++, the method the
                      reference asks OpenCV for: cv.USAC_MAGSAC, pose_solver.py:46-48) | 'count' (inlier count + LM polish, rounds 1-3);
                      MAGSAC_MAX_THR_RATIO: k * sigma_max of MAGSAC++ as a multiple of EMAT_RANSAC.PIX_THRESHOLD (>= 1);
-                     REF_FEATURE_CACHE: the fused pipeline runs SuperPoint once per distinct reference view of a batch (and keeps the
-                     last few across batches) instead of once per pair -- same bits, fewer images (pipeline.py);
+                     REF_FEATURE_CACHE: the fused pipeline runs the per-image network -- SuperPoint ('SuperGlue'), LoFTR's ResNet-FPN
+                     backbone ('LoFTR', both LOFTR.MATCH_TYPEs) -- once per distinct reference view of a batch (and keeps the last few
+                     across batches) instead of once per pair -- same bits, fewer images (pipeline._RefCachedSuperGlue / _RefCachedLoFTR);
+                     not the per-pair plugin, not GRAPH_FUSED;
                      LOADER_WORKERS: decode workers per rank, 0 = the CPUs the container grants divided by the node's ranks (datasets.usable_cpus);
                      LOADER_DECODE: 'process' | 'thread' -- who decodes the JPEG / PNG files of predict_fused's batches: forked worker
                      processes writing into pinned shared-memory batch slots (default; 820 vs 437 pairs/s on the 16-CPU GPU box,

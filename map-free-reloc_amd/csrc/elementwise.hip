@@ -159,13 +159,11 @@ __global__ void __launch_bounds__(256) conv1x1_nchw_kernel(const float *__restri
 // pixel-contiguous reads and the channel-contiguous writes are conflict-free and 256-byte coalesced).  Replaces torch's strided copy
 // (permute().contiguous(): 0.50 ms for SuperPoint's 64 x 256 x 90 x 67 descriptor map, 1.6 TB/s) in front of the linear layers that
 // consume rows.  deinterleave: image 2 k + s of a pair-interleaved batch lands at s * (B / 2) + k (LoFTR's side-major token buffer).
-__global__ void __launch_bounds__(256) nchw_to_rows_kernel(const float *__restrict__ x, const float *__restrict__ add, int C, int HW, int B, int deinterleave,
-                                                           float *__restrict__ out, long long out_img_stride, int ldo)
+__device__ __forceinline__ void nchw_tile_to_rows(const float *__restrict__ xi, const float *__restrict__ add, int C, int HW, float *__restrict__ oi, int ldo)
 {
     __shared__ float t[64][65];
-    const int img = blockIdx.z, c0 = blockIdx.y * 64, p0 = blockIdx.x * 64;
+    const int c0 = blockIdx.y * 64, p0 = blockIdx.x * 64;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const float *xi = x + (size_t)img * C * HW;
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
         const int c = c0 + ty + 4 * k, pp = p0 + tx;
@@ -174,13 +172,31 @@ __global__ void __launch_bounds__(256) nchw_to_rows_kernel(const float *__restri
         t[ty + 4 * k][tx] = v;
     }
     __syncthreads();
-    const int oimg = deinterleave ? (img & 1) * (B >> 1) + (img >> 1) : img;
-    float *oi = out + (size_t)oimg * out_img_stride;
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
         const int pp = p0 + ty + 4 * k, c = c0 + tx;
         if (pp < HW && c < C) oi[(size_t)pp * ldo + c] = t[tx][ty + 4 * k];
     }
+}
+
+__global__ void __launch_bounds__(256) nchw_to_rows_kernel(const float *__restrict__ x, const float *__restrict__ add, int C, int HW, int B, int deinterleave,
+                                                           float *__restrict__ out, long long out_img_stride, int ldo)
+{
+    const int img = blockIdx.z;
+    const int oimg = deinterleave ? (img & 1) * (B >> 1) + (img >> 1) : img;
+    nchw_tile_to_rows(x + (size_t)img * C * HW, add, C, HW, out + (size_t)oimg * out_img_stride, ldo);
+}
+
+// The same tile with the source image of every output slot looked up in a table: out[j] = rows of x[idx[j]].  The table is a kernel ARGUMENT (by value,
+// ROWS_GATHER_MAX entries per launch), so a caller that knows the indices on the host (LoFTR's token buffer filled from cached reference views,
+// nets/loftr.py match_features) needs no index tensor -- no host-to-device copy, no synchronisation.
+#define ROWS_GATHER_MAX 64
+struct RowsGatherIdx { int v[ROWS_GATHER_MAX]; };
+
+__global__ void __launch_bounds__(256) nchw_to_rows_gather_kernel(const float *__restrict__ x, const float *__restrict__ add, int C, int HW, RowsGatherIdx idx,
+                                                                  float *__restrict__ out, long long out_img_stride, int ldo)
+{
+    nchw_tile_to_rows(x + (size_t)idx.v[blockIdx.z] * C * HW, add, C, HW, out + (size_t)blockIdx.z * out_img_stride, ldo);
 }
 
 #include "guard.h"
@@ -223,6 +239,23 @@ int mfr_nchw_to_rows(const float *x, const float *add, int B, int C, int HW, int
     hipLaunchKernelGGL(nchw_to_rows_kernel, dim3((HW + 63) / 64, (C + 63) / 64, B), dim3(256), 0, (hipStream_t)stream, x, add, C, HW, B, deinterleave, out,
                        out_img_stride, ldo);
     CHECK_LAUNCH();
+    return 0;
+}
+
+int mfr_nchw_to_rows_gather(const float *x, const float *add, int n_src, int C, int HW, const int32_t *idx, int n_out, float *out, long long out_img_stride,
+                            int ldo, void *stream)
+{
+    if (!x || !out || !idx || n_src <= 0 || C <= 0 || HW <= 0 || n_out <= 0 || ldo < C) return MFR_E_ARG;
+    for (int j = 0; j < n_out; ++j)
+        if (idx[j] < 0 || idx[j] >= n_src) return MFR_E_ARG;                  // every index is checked before the first launch
+    for (int j0 = 0; j0 < n_out; j0 += ROWS_GATHER_MAX) {
+        const int n = n_out - j0 < ROWS_GATHER_MAX ? n_out - j0 : ROWS_GATHER_MAX;
+        RowsGatherIdx tab = {};
+        for (int j = 0; j < n; ++j) tab.v[j] = idx[j0 + j];
+        hipLaunchKernelGGL(nchw_to_rows_gather_kernel, dim3((HW + 63) / 64, (C + 63) / 64, n), dim3(256), 0, (hipStream_t)stream, x, add, C, HW, tab,
+                           out + (size_t)j0 * out_img_stride, out_img_stride, ldo);
+        CHECK_LAUNCH();
+    }
     return 0;
 }
 

@@ -11,10 +11,16 @@ restated per SURVEY.md Appendix A.4 with upstream parameter names (`backbone.*`,
 `fine_preprocess.*`, `loftr_fine.*`) so the real checkpoints load through the same path.
 BatchNorm (eval) is folded into the preceding bias-free convolutions at load time.
 
+The network is split at the backbone: `features` (per image) and `match_features` (per pair, each side given as feature set + image index), so
+that a view shared by many pairs -- Map-free's reference image -- runs the ResNet-FPN once (pipeline._RefCachedLoFTR); `__call__` is the two with
+the interleaved indexing (2p, 2p + 1).
+
 The fine-level transformer (2M sequences of 25 tokens, d 128) and the 5x5 expectation are tiny and
 stay on torch ops; everything that touches the 6120-token coarse level is a HIP kernel.
 """
+import ctypes
 import math
+import typing
 
 import torch
 import torch.nn.functional as F
@@ -39,6 +45,13 @@ def position_encoding_sine(d_model, H, W, device):
 
 
 MATCH_TYPES = ("dual_softmax", "sinkhorn")
+
+
+class LoFTRFeatures(typing.NamedTuple):
+    """what the backbone hands to the rest of the network, for n images: everything after it reads images only through these two maps, so a view's rows
+    can be computed once and matched against many partners (LoFTRHIP.features / match_features)"""
+    coarse: torch.Tensor            # [n, 256, hc, wc]   1/8-resolution map (NCHW)
+    fine: torch.Tensor              # [n, Hf, Wf, 128]   1/2-resolution map, token-major (NHWC memory)
 
 
 class LoFTRHIP:
@@ -206,8 +219,9 @@ class LoFTRHIP:
         need = lib.mfr_loftr_coarse_match_workspace_bytes(B, L0, L1)
         if self._ws_cm is None or self._ws_cm.numel() < need:
             self._ws_cm = torch.empty(need, dtype=torch.uint8, device=S.device)
-        i_ids = torch.empty(B, L0, dtype=torch.int32, device=S.device); j_ids = torch.empty_like(i_ids)
-        mconf = torch.empty(B, L0, dtype=torch.float32, device=S.device)
+        # zeros: the kernel writes the first n slots of a pair only, and what is handed out must not depend on what the allocator held before
+        i_ids = torch.zeros(B, L0, dtype=torch.int32, device=S.device); j_ids = torch.zeros_like(i_ids)
+        mconf = torch.zeros(B, L0, dtype=torch.float32, device=S.device)
         n = torch.empty(B, dtype=torch.int32, device=S.device)
         _lib.check(lib.mfr_loftr_coarse_match_variant(_lib.ptr(S.contiguous()), B, hw0[0], hw0[1], hw1[0], hw1[1], self.temp, self.thr,
                                                       self.border, _lib.ptr(self._ws_cm), self._ws_cm.numel(), _lib.ptr(i_ids),
@@ -224,8 +238,9 @@ class LoFTRHIP:
         need = lib.mfr_loftr_ot_match_workspace_bytes(B, L0, L1)
         if self._ws_ot is None or self._ws_ot.numel() < need:
             self._ws_ot = torch.empty(need, dtype=torch.uint8, device=S.device)
-        i_ids = torch.empty(B, L0, dtype=torch.int32, device=S.device); j_ids = torch.empty_like(i_ids)
-        mconf = torch.empty(B, L0, dtype=torch.float32, device=S.device)
+        # zeros: the kernel writes the first n slots of a pair only, and what is handed out must not depend on what the allocator held before
+        i_ids = torch.zeros(B, L0, dtype=torch.int32, device=S.device); j_ids = torch.zeros_like(i_ids)
+        mconf = torch.zeros(B, L0, dtype=torch.float32, device=S.device)
         n = torch.empty(B, dtype=torch.int32, device=S.device)
         u = torch.empty(B, L0 + 1, dtype=torch.float32, device=S.device) if return_potentials else None
         v = torch.empty(B, L1 + 1, dtype=torch.float32, device=S.device) if return_potentials else None
@@ -356,7 +371,36 @@ class LoFTRHIP:
     def __call__(self, images):
         """images [2B,1,H,W] (interleaved pairs; H, W multiples of 8) -> dict(pts0, pts1 [B,L0,2],
         n_corr [B], mconf [B,L0]) in the matcher's pixel frame (mkpts0_f / mkpts1_f)."""
-        return self.fine_stage(self.coarse_stage(images))
+        f, n = self.features(images), images.shape[0]
+        return self.match_features(f, range(0, n, 2), f, range(1, n, 2), images.shape[2])
+
+    @torch.no_grad()
+    def features(self, images):
+        """images [n,1,H,W] (H, W multiples of 8; padding is the caller's job) -> LoFTRFeatures.  Every backbone kernel tiles per image and sums in a
+        fixed order, so an image's rows do not depend on what else is in the batch (tests/test_gpu_loftr_ref_cache.py)."""
+        fc, ff = self.backbone(images)
+        return LoFTRFeatures(fc.contiguous(), self._fine_nhwc(ff))
+
+    @torch.no_grad()
+    def match_features(self, src0, idx0, src1, idx1, H):
+        """everything after the backbone for B = len(idx0) pairs: side s of pair p is image idx_s[p] of the feature set src_s (LoFTRFeatures; the two
+        sides may be different sets, e.g. a pool of cached reference views and this batch's backbone output).  idx_s: host sequences of ints.
+        H: the (padded) image height the features were computed at.  Returns the same dict as __call__."""
+        B = len(idx0)
+        C, hc, wc = src0.coarse.shape[1:]
+        assert len(idx1) == B and B > 0 and src1.coarse.shape[1:] == (C, hc, wc) and src1.fine.shape[1:] == src0.fine.shape[1:]
+        L0 = hc * wc
+        xm = torch.empty(2, B * L0, 2 * C, dtype=torch.float32, device=src0.coarse.device)
+        pe = self._pos_encoding(C, hc, wc, xm.device)
+        for s, (src, idx) in enumerate(((src0, idx0), (src1, idx1))):
+            # the index table is a kernel argument: no index tensor, no interleaved [2B,256,hc,wc] copy of the coarse maps
+            tab = (ctypes.c_int32 * B)(*idx)
+            _lib.check(_lib.load().mfr_nchw_to_rows_gather(_lib.ptr(src.coarse), _lib.ptr(pe), src.coarse.shape[0], C, L0, tab, B, _lib.ptr(xm[s]), L0 * 2 * C,
+                                                           2 * C, _lib.stream_ptr()), "mfr_nchw_to_rows_gather")
+        self._transformer(self.coarse, xm, self.linear_attention, B, L0)
+        c = self._coarse_matches(xm, (hc, wc), H)
+        c["sides"] = ((src0.fine, idx0), (src1.fine, idx1))
+        return self.fine_stage(c)
 
     def coarse_stage(self, images):
         """backbone -> coarse transformer -> dual-softmax matching: everything BEFORE the match count is known.  Fixed shapes and
@@ -371,21 +415,27 @@ class LoFTRHIP:
         """coarse map [2B,256,hc,wc] (+ positional encoding) -> xm [2, B * L0, 512]: NCHW -> token-major, pairs de-interleaved
         (side-major), one strided copy into the left half"""
         B2, C, hc, wc = fc.shape
-        key = (hc, wc)
-        if key not in self._pe:
-            self._pe[key] = position_encoding_sine(C, hc, wc, fc.device)
+        pe = self._pos_encoding(C, hc, wc, fc.device)
         L0 = hc * wc
         xm = torch.empty(2, (B2 // 2) * L0, 2 * C, dtype=torch.float32, device=fc.device)
-        _lib.check(_lib.load().mfr_nchw_to_rows(_lib.ptr(fc.contiguous()), _lib.ptr(self._pe[key].contiguous()), B2, C, L0, 1, _lib.ptr(xm), L0 * 2 * C, 2 * C,
+        _lib.check(_lib.load().mfr_nchw_to_rows(_lib.ptr(fc.contiguous()), _lib.ptr(pe), B2, C, L0, 1, _lib.ptr(xm), L0 * 2 * C, 2 * C,
                                                 _lib.stream_ptr()), "mfr_nchw_to_rows")
         return xm
 
+    def _pos_encoding(self, C, hc, wc, device):
+        if (hc, wc) not in self._pe:
+            self._pe[(hc, wc)] = position_encoding_sine(C, hc, wc, device).contiguous()
+        return self._pe[(hc, wc)]
+
     def coarse_tail(self, xm, ff, hw, H):
         """transformed tokens xm + fine map ff [2B,128,Hf,Wf] -> dual-softmax matches, coarse keypoints, the fine map in NHWC"""
+        return dict(self._coarse_matches(xm, hw, H), ff_nhwc=self._fine_nhwc(ff))
+
+    def _coarse_matches(self, xm, hw, H):
+        """transformed tokens xm -> dual-softmax / optimal-transport matches and the coarse keypoints"""
         hc, wc = hw
         L0 = hc * wc
         B = xm.shape[1] // L0
-        B2 = 2 * B
         f0, f1 = xm[0].view(B, L0, 512)[..., :256], xm[1].view(B, L0, 512)[..., :256]     # row-strided views
         i_ids, j_ids, mconf, n = self.coarse_match_features(f0, f1, (hc, wc))
         scale = H // hc
@@ -394,31 +444,34 @@ class LoFTRHIP:
         valid = torch.arange(L0, device=xm.device)[None] < n[:, None]
         k0 = torch.stack([ii % wc, ii // wc], -1).float() * scale
         k1 = torch.stack([jj % wc, jj // wc], -1).float() * scale
-        Cf, Hf, Wf = ff.shape[1:]
+        return dict(xm=xm, i_ids=i_ids, j_ids=j_ids, ii=ii, jj=jj, mconf=mconf, n=n, valid=valid, k0=k0, k1=k1, hc=hc, wc=wc, H=H)
+
+    def _fine_nhwc(self, ff):
+        """the backbone's fine map [n,128,Hf,Wf] as [n,Hf,Wf,128] memory"""
         if ff.permute(0, 2, 3, 1).is_contiguous() and not ff.is_contiguous():             # already NHWC memory (backbone, round 6)
-            ff_nhwc = ff.permute(0, 2, 3, 1)
-        else:
-            ff_nhwc = torch.empty(B2, Hf, Wf, Cf, dtype=torch.float32, device=ff.device)    # [2B, Hf, Wf, 128]: LDS-tiled transpose (csrc/elementwise.hip)
-            _lib.check(_lib.load().mfr_nchw_to_rows(_lib.ptr(ff.contiguous()), None, B2, Cf, Hf * Wf, 0, _lib.ptr(ff_nhwc), Hf * Wf * Cf, Cf, _lib.stream_ptr()),
-                       "mfr_nchw_to_rows")
-        return dict(xm=xm, ff_nhwc=ff_nhwc, i_ids=i_ids, j_ids=j_ids, ii=ii, jj=jj, mconf=mconf, n=n, valid=valid, k0=k0, k1=k1,
-                    hc=hc, wc=wc, H=H)
+            return ff.permute(0, 2, 3, 1)
+        n, Cf, Hf, Wf = ff.shape
+        ff_nhwc = torch.empty(n, Hf, Wf, Cf, dtype=torch.float32, device=ff.device)        # LDS-tiled transpose (csrc/elementwise.hip)
+        _lib.check(_lib.load().mfr_nchw_to_rows(_lib.ptr(ff.contiguous()), None, n, Cf, Hf * Wf, 0, _lib.ptr(ff_nhwc), Hf * Wf * Cf, Cf, _lib.stream_ptr()),
+                   "mfr_nchw_to_rows")
+        return ff_nhwc
 
     def fine_stage(self, c):
         """the matched cells' 5x5 windows -> fine transformer -> sub-pixel expectation (data-dependent sizes: one host
         synchronisation for the match count)"""
-        xm, ff_nhwc, i_ids, j_ids, ii, jj, mconf, n, valid, k0, k1 = (c[k] for k in ("xm", "ff_nhwc", "i_ids", "j_ids", "ii", "jj", "mconf",
-                                                                                     "n", "valid", "k0", "k1"))
+        xm, i_ids, j_ids, ii, jj, mconf, n, valid, k0, k1 = (c[k] for k in ("xm", "i_ids", "j_ids", "ii", "jj", "mconf", "n", "valid", "k0", "k1"))
         hc, wc, H = c["hc"], c["wc"], c["H"]
         B, L0 = valid.shape
         dev = valid.device
+        # per side (fine map [n,Hf,Wf,128], image of every pair): match_features' feature sets, or the interleaved map of coarse_tail
+        sides = c["sides"] if "sides" in c else ((c["ff_nhwc"], range(0, 2 * B, 2)), (c["ff_nhwc"], range(1, 2 * B, 2)))
         f0, f1 = xm[0].view(B, L0, 512)[..., :256], xm[1].view(B, L0, 512)[..., :256]
         b_ids, slot = torch.where(valid)                                            # (host sync: match count)
         M = b_ids.numel()
         pts1 = k1.clone()
         if M > 0:
             mi, mj = ii[b_ids, slot], jj[b_ids, slot]
-            Hf = ff_nhwc.shape[1]
+            Hf = sides[0][0].shape[1]
             stride = Hf // hc
             WW = self.W * self.W
             # down_proj on the matched coarse features, merge_feat(cat[window, coarse]) = window Wa^T + (coarse Wb^T + b): the coarse half is
@@ -434,8 +487,12 @@ class LoFTRHIP:
             xf = torch.empty(2, M * WW, 256, dtype=torch.float32, device=dev)
             # round 6: the windows' tokens are read from the NHWC fine map inside the product and cw is added per window in its epilogue -- no gather
             # kernel, no [2 M, 25, 128] window tensor, no broadcast add (upstream FinePreprocess: unfold -> gather -> merge_feat)
-            lin_win.windows(ff_nhwc, torch.cat([2 * b_ids, 2 * b_ids + 1]).int(), torch.cat([mi, mj]).int(), wc, stride, self.W,
-                            out=xf.view(2 * M * WW, 256)[:, :128], window_bias=cw)
+            # One launch per side, each on its own map with the pairs' image ids looked up on the device: the maps of the two sides are never copied
+            # into one.  An explicit index list is uploaded HERE, after the match-count read above has drained the stream anyway.
+            for s, ((ff, idx), cells) in enumerate(zip(sides, (mi, mj))):
+                tab = (torch.arange(idx.start, idx.stop, idx.step, dtype=torch.int32, device=dev) if isinstance(idx, range)
+                       else torch.tensor(list(idx), dtype=torch.int32, device=dev))
+                lin_win.windows(ff, tab[b_ids], cells.int(), wc, stride, self.W, out=xf[s][:, :128], window_bias=cw[s * M:(s + 1) * M])
             self._transformer(self.fine, xf, self.fine_attention if self.W == 5 else self._torch_linear_attention(8), M, WW)
             # FineMatching: centre-feature correlation, softmax, spatial expectation and the sub-pixel update in one kernel
             self.fine_match(xf, M, (b_ids * L0 + slot).int(), k1, pts1, float((self.W // 2) * (H // Hf)))

@@ -212,24 +212,22 @@ class LoFTREmatPipeline:
         self.guard = RangeGuard(self.device, lambda: LoFTREmatPipeline(device, loftr_state, pix_thr, scale_thr, conf, seed, pad_to, emat_score,
                                                                         match_type=match_type, skh_iters=skh_iters))
         self._ov = SolverOverlap(self.device) if overlap_solver else None      # E-mat + scale stage under the next call's matcher; join() before reading
+        self._ref = _RefCachedLoFTR(self.loftr, self.guard, pad_to)
 
     def join(self):
         if self._ov is not None:
             self._ov.join()
 
     @torch.no_grad()
-    def match(self, images):
-        H, W = images.shape[-2:]
-        # LoFTR needs multiples of 8; the reference right-pads W 540 -> 544 (matchers.py:41-46, quirk Q3)
-        ph, pw = (-H) % self.pad_to, (-W) % self.pad_to
-        if ph or pw:
-            images = torch.nn.functional.pad(images, (0, pw, 0, ph))
-        return self.loftr(images)
+    def match(self, images, ref_keys=None):
+        """ref_keys (one per pair, as PairBatchLoader's `ref_keys`; None = no sharing): the backbone runs once per distinct reference view
+        (_RefCachedLoFTR), same bits"""
+        return self._ref.plain(images) if ref_keys is None else self._ref(dict(images=images, ref_keys=ref_keys))
 
     @torch.no_grad()
-    def __call__(self, images, depth0, depth1, K0, K1, pair_ids):
+    def __call__(self, images, depth0, depth1, K0, K1, pair_ids, ref_keys=None):
         with self.guard:
-            m = self.match(images)
+            m = self.match(images, ref_keys)
         bad = self.guard.snapshot() if self._ov is not None else None
 
         def solve():
@@ -318,6 +316,109 @@ class _RefCachedSuperGlue:
         return self.net(sp2, tuple(im.shape[-2:]), maxN=self.K)
 
 
+def _pad_to_multiple(images, m):
+    """LoFTR needs multiples of 8; the reference right-pads W 540 -> 544 (matchers.py:41-46, quirk Q3)"""
+    H, W = images.shape[-2:]
+    ph, pw = (-H) % m, (-W) % m
+    return torch.nn.functional.pad(images, (0, pw, 0, ph)) if ph or pw else images
+
+
+class _RefView:
+    """One cached reference view of _RefCachedLoFTR.
+    slot: its row in the pool's coarse and fine maps.
+    flag: a device copy [1] int32 of the f16x2 range-guard flag, taken right after the backbone pass that computed the view (None while the guard is
+          inactive).  The view's maps were computed under THAT batch's guard window, and a flagged accumulator can leave finite wrong values behind
+          (relu(-inf) = 0), so every later batch that reuses the view ORs `flag` into its own live flag."""
+    __slots__ = ("slot", "flag")
+
+    def __init__(self, slot, flag):
+        self.slot, self.flag = slot, flag
+
+
+class _RefCachedLoFTR:
+    """LoFTR over a batch of pairs with ONE backbone pass per distinct reference view: the twin of _RefCachedSuperGlue, same contract.
+
+    The batch's pairs are grouped by `ref_keys` (None: a view nobody shares -- run, not retained); the ResNet-FPN runs on [the reference views not
+    cached yet | all query views] (after the pad-to-8 of the plain path); new reference rows are copied once, device to device, into a small pool of
+    coarse / fine maps (an LRU of `keep` views, or the batch's distinct views if more), and everything after the backbone reads side 0 from the pool
+    and side 1 from this batch's output by index (LoFTRHIP.match_features): no interleaved copy of either map is made.  A batch in which every
+    reference view is new reads side 0 from its own backbone output.  The backbone's kernels tile per image with a fixed summation order, so the
+    result is the SAME BITS as the plain path (tests/test_gpu_loftr_ref_cache.py).  A batch without usable `ref_keys` takes the plain path.
+
+    Not covered: the per-pair plugin and its batch-1 graph replay, the reference side's first self-attention layer (it could be cached the same
+    way), query-side keys (7Scenes / ScanNet would enter through the same (feature set, index) interface) and HIP.GRAPH_FUSED."""
+
+    def __init__(self, net, guard=None, pad_to=8, keep=4):
+        import collections
+        self.net, self.guard, self.pad_to, self.keep = net, guard, pad_to, keep
+        self.cache = collections.OrderedDict()                                    # key -> _RefView, least recently used first
+        self.pool, self._hw = None, None                                          # LoFTRFeatures [slots, ...] of images of size _hw
+        self.stats = dict(reference_views_run=0, reference_views_reused=0)
+
+    def plain(self, images):
+        return self.net(_pad_to_multiple(images, self.pad_to))
+
+    def _free_slots(self, n_new, first, like):
+        """room for n_new more views: evict least recently used views the batch does not use, grow the pool to the batch's distinct views if needed"""
+        cap = max(self.keep, len(first))
+        while len(self.cache) + n_new > cap:
+            del self.cache[next(k for k in self.cache if k not in first)]
+        if self.pool is None or self.pool[0].shape[0] < cap:
+            grown = type(like)(*(t.new_empty((cap,) + tuple(t.shape[1:])) for t in like))
+            if self.pool is not None:
+                for g, t in zip(grown, self.pool):
+                    g[:t.shape[0]].copy_(t)
+            self.pool = grown
+        used = {v.slot for v in self.cache.values()}
+        return [s for s in range(self.pool[0].shape[0]) if s not in used]
+
+    @torch.no_grad()
+    def __call__(self, b):
+        im, keys = b["images"], b.get("ref_keys")
+        if keys is None or len(keys) * 2 != im.shape[0]:
+            return self.plain(im)
+        im = _pad_to_multiple(im, self.pad_to)
+        B = len(keys)
+        solo = {("__pair__", p) for p, k in enumerate(keys) if k is None}         # None: a reference view nobody shares
+        keys = [k if k is not None else ("__pair__", p) for p, k in enumerate(keys)]
+        first = {}
+        for p, k in enumerate(keys):
+            first.setdefault(k, p)
+        if self._hw != tuple(im.shape[-2:]):                                      # another image size: the pooled maps do not fit
+            self.cache.clear()
+            self.pool, self._hw = None, tuple(im.shape[-2:])
+        need = [k for k in first if k not in self.cache]
+        u = len(need)
+        out = self.net.features(torch.cat([im[2 * first[k]][None] for k in need] + [im[1::2]]))
+        guarded = self.guard is not None and self.guard.active
+        flag = self.guard.flag.clone() if guarded else None
+        self.stats["reference_views_run"] += u
+        self.stats["reference_views_reused"] += B - u
+        reused = [k for k in first if k in self.cache]
+        store = need if reused else [k for k in need if k not in solo]            # nothing reused: side 0 is read from `out` itself
+        free = self._free_slots(len(store), first, out) if store else []
+        for k in store:
+            v = self.cache[k] = _RefView(free.pop(0), flag)
+            for pooled, fresh in zip(self.pool, out):
+                pooled[v.slot].copy_(fresh[need.index(k)])
+        if reused:
+            src0, idx0 = self.pool, [self.cache[k].slot for k in keys]
+            if guarded:
+                for k in reused:
+                    self.guard.flag.bitwise_or_(self.cache[k].flag)
+        else:
+            src0, idx0 = out, [need.index(k) for k in keys]
+        m = self.net.match_features(src0, idx0, out, list(range(u, u + B)), im.shape[2])
+        for k in first:                                                           # most recently used last; bounded
+            if k in solo:
+                self.cache.pop(k, None)
+            else:
+                self.cache.move_to_end(k)
+        while len(self.cache) > max(self.keep, len(first)):
+            self.cache.popitem(last=False)
+        return m
+
+
 class FusedPosePipeline:
     """The batched twin of FeatureMatchingModel (lib/models/matching/model.py:7-40): the same two config keys pick the
     stages -- FEATURE_MATCHING in {'Precomputed', 'SuperGlue', 'LoFTR', 'SIFT' (SIFT.DETECTOR 'hip')} x POSE_SOLVER in {'PNP', 'EssentialMatrix',
@@ -368,11 +469,11 @@ class FusedPosePipeline:
         elif fm == "LoFTR":
             lw = cfg.LOFTR.WEIGHTS
             sd = WT.strip_prefix(WT.load_checkpoint(lw), "matcher.") if lw else WT.synthetic_or_raise("LoFTR", cfg, WT.loftr_state_dict)
-            lp = LoFTREmatPipeline.__new__(LoFTREmatPipeline)
             from .nets.loftr import LoFTRHIP
-            lp.loftr = LoFTRHIP(sd, self.device, match_type=cfg.LOFTR.get("MATCH_TYPE", "dual_softmax"), skh_iters=cfg.LOFTR.get("SKH_ITERS", 3))
-            lp.pad_to, lp.device = 8, self.device
-            self.match = lambda b: lp.match(b["images"])
+            net = LoFTRHIP(sd, self.device, match_type=cfg.LOFTR.get("MATCH_TYPE", "dual_softmax"), skh_iters=cfg.LOFTR.get("SKH_ITERS", 3))
+            stage = _RefCachedLoFTR(net, self.guard)
+            # the backbone once per distinct reference view (both MATCH_TYPEs); switched off, every batch takes the stage's plain path
+            self.match = stage if "REF_FEATURE_CACHE" in cfg.HIP and cfg.HIP.REF_FEATURE_CACHE else (lambda b: stage.plain(b["images"]))
         elif fm == "SIFT" and cfg.SIFT.get("DETECTOR", "opencv") == "hip":
             from .sift_ops import SiftDetector, sift_ratio_stage
             self.match = sift_ratio_stage(SiftDetector(cfg.SIFT.NUM_FEATURES, self.device), cfg.SIFT.RATIO_THRESHOLD)
