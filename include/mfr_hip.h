@@ -354,6 +354,41 @@ int mfr_sg_sinkhorn_match_variant(const float *S, int B, int ldS, const int32_t 
                                   int variant, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * LightGlue kernels (csrc/lightglue.hip): the SuperPoint matcher of LightGlue (ICCV 2023) without adaptive depth / width.  The reference has
+ * no LightGlue call site; the stage takes SuperGlue_matcher's place (etc/feature_matching_baselines/matchers.py:62-120) and the network is
+ * restated from the paper with the parameter names of the `transformers` LightGlue module.  Linear layers: mfr_gemm_*; attention:
+ * mfr_sg_attention (scale 1/8, cross = 1 for the flipped pair); similarity S: mfr_gemm_f16x2_batched under SPLIT f16x2, the framework's batched fp32
+ * product (torch.bmm) under bf16x3, as for SuperGlue's scores.  All fp32, kernels only, bit-reproducible.
+ *   mfr_lg_rotary_table   cs [M, 64] = (cos | sin)(Wr p) for M normalised keypoints p [M, 2] and the projector Wr [32, 2]: once per batch
+ *   mfr_lg_rotary_apply   q, k [M, 256] (row stride ld, 4 heads x 64) rotated in place: (x_2i, x_2i+1) <- (x_2i c_i - x_2i+1 s_i, x_2i+1 c_i + x_2i s_i),
+ *                         the same 32 angles for every head (the interleaved pairing; NOT the half-split convention)
+ *   mfr_lg_ln_gelu        x [M, 512] (row stride ld) <- GELU_erf(LayerNorm_512(x) * gamma + beta) in place: the MLP's hidden row between fc1 and fc2 as a
+ *                         pass of its own (the A/B partner of mfr_gemm_*_ln_gelu, which does it in fc1's epilogue)
+ *   mfr_lg_assign         double softmax + matchability + match extraction on S [B, N0, ldS] (ldS >= N1), z0 [B, N0], z1 [B, N1], counts n0, n1 [B]:
+ *                         score_ij = 2 S_ij - lse_j S_i. - lse_i S_.j + logsigmoid(z0_i) + logsigmoid(z1_j) over the valid n0 x n1 block (never
+ *                         written; S is swept twice); matches0 [B, N0] / matches1 [B, N1] i32 (-1 = none): the mutual arg-max (lowest index on a
+ *                         tie) whose exp(score) > threshold; mscores0 / mscores1: exp(score) at the mutual arg-max, 0 elsewhere.  n0 == 0 or
+ *                         n1 == 0: all -1 / 0, S is not read.  Optional (all NULL or none): kpts0, kpts1 [B, K, 2] -> pts0, pts1 [B, maxN, 2], the
+ *                         matched keypoints in ascending i, and n_corr [B] (the layout of mfr_sg_sinkhorn_match).
+ * ------------------------------------------------------------------------------------------ */
+/*   mfr_gemm_f16x2_ln_gelu / mfr_gemm_bf16x3_ln_gelu (csrc/gemm_split.hip): y = GELU_erf(LayerNorm_512(x W^T + bias) * gamma + beta) for N = 512 in ONE launch: fc1 of
+ *                         LightGlue's MLP with the LayerNorm and the GELU in the epilogue.  A workgroup keeps the four 128-feature accumulator blocks of a
+ *                         128-row tile on chip, so the pre-norm hidden row is never written; W packed by mfr_gemm_*_pack, K % 32 == 0.  Two-pass statistics,
+ *                         biased variance, rsqrt(var + eps): the arithmetic of mfr_layernorm.  f16x2: the range guard tests the accumulators. */
+int mfr_gemm_f16x2_ln_gelu(const float *x, int ldx, const void *packed_w, const float *bias, const float *gamma, const float *beta, float eps, float *y, int ldy,
+                           int M, int N, int K, void *stream);
+int mfr_gemm_bf16x3_ln_gelu(const float *x, int ldx, const void *packed_w, const float *bias, const float *gamma, const float *beta, float eps, float *y, int ldy,
+                            int M, int N, int K, void *stream);
+int mfr_lg_rotary_table(const float *kpts_norm, const float *wr, int M, float *cs, void *stream);
+int mfr_lg_rotary_apply(float *q, float *k, int ld, int M, const float *cs, void *stream);
+int mfr_lg_ln_gelu(float *x, int ld, int M, const float *gamma, const float *beta, float eps, void *stream);
+size_t mfr_lg_assign_workspace_bytes(int B, int N0, int N1);
+int mfr_lg_assign(const float *S, int B, int N0, int N1, int ldS, const float *z0, const float *z1, const int32_t *n0, const int32_t *n1,
+                  float threshold, const float *kpts0, const float *kpts1, int K, void *workspace, size_t workspace_bytes,
+                  int32_t *matches0, int32_t *matches1, float *mscores0, float *mscores1, float *pts0, float *pts1, int maxN, int32_t *n_corr,
+                  void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * LoFTR kernels.  Reference call site: LoFTR_matcher.match, etc/feature_matching_baselines/
  * matchers.py:24-59 (LoFTR(default_cfg), *_ot.ckpt strict=False :16-18); network = un-vendored
  * zju3dv/LoFTR submodule (.gitmodules:1-3), restated per SURVEY.md Appendix A.4.

@@ -65,6 +65,14 @@ SIGNATURES = {
                                    _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "mfr_sg_sinkhorn_match_variant": (_i, [_vp, _i, _i, _vp, _vp, C.c_float, _i, C.c_float, _vp, _vp, _i, _vp, _sz,
                                            _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
+    "mfr_gemm_f16x2_ln_gelu": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_float, _vp, _i, _i, _i, _i, _vp]),
+    "mfr_gemm_bf16x3_ln_gelu": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_float, _vp, _i, _i, _i, _i, _vp]),
+    "mfr_lg_rotary_table": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "mfr_lg_rotary_apply": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "mfr_lg_ln_gelu": (_i, [_vp, _i, _i, _vp, _vp, C.c_float, _vp]),
+    "mfr_lg_assign_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mfr_lg_assign": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _i, _vp, _sz,
+                           _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "mfr_loftr_linear_attention_workspace_bytes": (_sz, [_i, _i, _i]),
     "mfr_loftr_linear_attention": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i, _vp]),
     "mfr_loftr_coarse_match_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -13,7 +13,7 @@ keys this implementation adds (declared here because unknown keys are rejected o
                      MAGSAC_MAX_THR_RATIO: k * sigma_max of MAGSAC++ as a multiple of EMAT_RANSAC.PIX_THRESHOLD (>= 1);
                      REF_FEATURE_CACHE: the fused pipeline runs the per-image network -- SuperPoint ('SuperGlue'), LoFTR's ResNet-FPN
                      backbone ('LoFTR', both LOFTR.MATCH_TYPEs) -- once per distinct reference view of a batch (and keeps the last few
-                     across batches) instead of once per pair -- same bits, fewer images (pipeline._RefCachedSuperGlue / _RefCachedLoFTR);
+                     across batches) instead of once per pair -- same bits, fewer images (pipeline._RefCachedKeypointMatcher / _RefCachedLoFTR);
                      not the per-pair plugin, not GRAPH_FUSED;
                      LOADER_WORKERS: decode workers per rank, 0 = the CPUs the container grants divided by the node's ranks (datasets.usable_cpus);
                      LOADER_DECODE: 'process' | 'thread' -- who decodes the JPEG / PNG files of predict_fused's batches: forked worker
@@ -42,6 +42,8 @@ keys this implementation adds (declared here because unknown keys are rejected o
                           buffer, one all-reduce per step instead of DDP's bucket hooks (regression/train.py)
   TRAINING.CHANNELS_LAST  keep weights / activations of the regression model NHWC (MIOpen's implicit-GEMM kernels are NHWC)
   SUPERGLUE.*        matcher hyper-parameters of record (matchers.py:65-71) and weight paths
+  LIGHTGLUE.*        'LightGlue' feature matching: WEIGHTS (a state dict with the `transformers` LightGlue parameter names), FILTER_THRESHOLD,
+                     NUM_LAYERS, SuperPoint's MAX_KEYPOINTS / KEYPOINT_THRESHOLD / NMS_RADIUS; DEPTH_CONFIDENCE / WIDTH_CONFIDENCE must stay -1
 """
 from .node import CfgNode as CN
 
@@ -62,7 +64,7 @@ def get_cfg_defaults():
         c.HEAD[k] = v
     c.BACKPROJECT_ANCHORS = None
     # feature matching options (config/default.py:39-66)
-    c.FEATURE_MATCHING = None      # 'SIFT' | 'Precomputed' | 'SuperGlue' | 'LoFTR' (new: online, on the GPU)
+    c.FEATURE_MATCHING = None      # 'SIFT' | 'Precomputed' | 'SuperGlue' | 'LoFTR' | 'LightGlue' (new: online, on the GPU)
     c.POSE_SOLVER = None           # 'EssentialMatrix' | 'EssentialMatrixMetric' | 'Procrustes' | 'PNP'
     c.SIFT = CN(); c.SIFT.NUM_FEATURES = None; c.SIFT.RATIO_THRESHOLD = None
     c.SIFT.DETECTOR = 'opencv'      # new: 'opencv' (cv.SIFT_create, the reference's) | 'hip' (sift_ops.SiftDetector, on the GPU)
@@ -100,6 +102,12 @@ def get_cfg_defaults():
                      MATCH_THRESHOLD=0.2, SUPERPOINT_WEIGHTS=None, SUPERGLUE_WEIGHTS=None, SYNTHETIC_SEED=1234).items():
         c.SUPERGLUE[k] = v
     c.LOFTR = CN(); c.LOFTR.WEIGHTS = None; c.LOFTR.MATCH_TYPE = 'dual_softmax'; c.LOFTR.SKH_ITERS = 3
+    # LightGlue on SuperPoint features (nets/lightglue.py).  The SuperPoint settings are the SuperGlue stage's (same shapes, same reference-view cache);
+    # SuperPoint's own weights come from SUPERGLUE.SUPERPOINT_WEIGHTS.  DEPTH_CONFIDENCE / WIDTH_CONFIDENCE: only -1 (adaptive depth and width are not built)
+    c.LIGHTGLUE = CN()
+    for k, v in dict(WEIGHTS='', FILTER_THRESHOLD=0.1, NUM_LAYERS=9, MAX_KEYPOINTS=1024, KEYPOINT_THRESHOLD=0.005, NMS_RADIUS=4,
+                     DEPTH_CONFIDENCE=-1, WIDTH_CONFIDENCE=-1).items():
+        c.LIGHTGLUE[k] = v
     c.ALLOW_SYNTHETIC_WEIGHTS = False
     return c
 

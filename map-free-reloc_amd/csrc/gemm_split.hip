@@ -802,6 +802,141 @@ __global__ void __launch_bounds__(256, 2) mlp_ln_kernel(const float *__restrict_
 #undef ML_XLOAD
 }
 
+// ---- LightGlue: fc1 of the MLP block with LayerNorm_512 + exact GELU in the epilogue ------------------------------------------------------------------
+// y = GELU_erf(LayerNorm_512(x W^T + b) gamma + beta) for N = 512 output features: the hidden row of LightGlue's MLP (nets/lightglue.py; the
+// `transformers` LightGlueMLP: fc1 -> layer_norm -> gelu -> fc2).  The LayerNorm spans FOUR 128-feature blocks, so one tile's epilogue cannot hold it:
+// here a workgroup owns a 128-row tile and runs gemm_split_kernel's K loop (register-staged X and W, the shared K step) on the four feature blocks
+// at once -- X is split once per step for all of them --, keeping all four accumulator sets (256 registers per thread: one workgroup per CU) -- the pre-norm hidden row is never written.  Epilogue:
+// scale / bias, the row statistics of GB_STORE_LAYERNORM extended over the four blocks (two-pass: mean, then centred squares; GB_LN_ROW_SUMS), GELU,
+// one store.  Same products in the same order per output element as the plain kernel, both arithmetics from this one template.
+// Measured (65536 rows, K = 512, f16x2): 0.264 ms against 0.105 ms (default kernel) + 0.043 ms (stand-alone LayerNorm + GELU pass): with 256 accumulator
+// registers one workgroup fits a CU and nothing hides the staging between two barriers.  nets/lightglue.py therefore runs the two-launch form by default;
+// this kernel is its tested A/B partner (tools/bench_lightglue.py times both).
+template <bool F16>
+__global__ void __launch_bounds__(256, 1) gemm_ln512_gelu_kernel(const float *__restrict__ X, int ldx, const uint4 *__restrict__ Wp, const float *__restrict__ oscale,
+                                                                 const float *__restrict__ bias, const float *__restrict__ ln_gamma, const float *__restrict__ ln_beta,
+                                                                 float ln_eps, float *__restrict__ Y, int ldy, int M, int K, int *guard)
+{
+    constexpr int XT = GB_XT(F16);
+    constexpr int WT = GB_WT(F16);
+    __shared__ uint4 lds[(XT + 4 * WT) * GB_TERM_UNITS];   // X terms, then the W terms of the four feature blocks (83 KB f16x2, 124 KB bf16x3)
+    __shared__ float lnx[512];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wm = wid >> 1, wn = wid & 1;
+    const int m0 = blockIdx.x * GB_BM;
+    const int nkb = K / GB_BK;
+
+    const float *xrow[2];
+    int xdst[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int u = tid + 256 * i, row = u >> 2, kg = u & 3;
+        const int m = min(m0 + row, M - 1);               // rows beyond M: a valid row is read and its results are never stored
+        xrow[i] = X + (size_t)m * ldx + 8 * kg;
+        xdst[i] = kg * GB_KG_STRIDE + row;
+    }
+    int wdst[2 * WT];
+#pragma unroll
+    for (int i = 0; i < 2 * WT; ++i) wdst[i] = gb_wdst(tid, i, XT);
+    const int arow = GB_FRAG_ROW(wm, GB_KG_STRIDE);
+    const int brow = GB_FRAG_ROW(wn, GB_KG_STRIDE);
+
+    // one K step stages X ONCE and the W tiles of all four feature blocks: 96 (f16x2) / 192 (bf16x3) matrix instructions between two barriers
+    float4 xa0, xa1, xb0, xb1;
+    // (named registers, not arrays: an array here is demoted to LDS / scratch memory)
+    uint4 w00, w01, w02, w03, w04, w05, w10, w11, w12, w13, w14, w15, w20, w21, w22, w23, w24, w25, w30, w31, w32, w33, w34, w35;
+#define GL_WLOAD(q, kb) do { \
+        const uint4 *wt_ = Wp + ((size_t)(q) * nkb + (kb)) * GB_W_TILE_UNITS(F16) + tid; \
+        w##q##0 = wt_[0]; w##q##1 = wt_[256]; w##q##2 = wt_[512]; w##q##3 = wt_[768]; if (WT == 3) { w##q##4 = wt_[1024]; w##q##5 = wt_[1280]; } } while (0)
+#define GL_WSTORE(q) do { \
+        uint4 *ld_ = lds + (q) * WT * GB_TERM_UNITS; \
+        ld_[wdst[0]] = w##q##0; ld_[wdst[1]] = w##q##1; ld_[wdst[2]] = w##q##2; ld_[wdst[3]] = w##q##3; \
+        if (WT == 3) { ld_[wdst[2 * WT - 2]] = w##q##4; ld_[wdst[2 * WT - 1]] = w##q##5; } } while (0)
+#define GL_GLOAD(kb) do { \
+        xa0 = *(const float4 *)(xrow[0] + (kb) * GB_BK); xa1 = *(const float4 *)(xrow[0] + (kb) * GB_BK + 4); \
+        xb0 = *(const float4 *)(xrow[1] + (kb) * GB_BK); xb1 = *(const float4 *)(xrow[1] + (kb) * GB_BK + 4); \
+        GL_WLOAD(0, kb); GL_WLOAD(1, kb); GL_WLOAD(2, kb); GL_WLOAD(3, kb); } while (0)
+#define GL_WIDX ((XT + WT * q + t) * GB_TERM_UNITS + 2 * ks * GB_KG_STRIDE + brow + 32 * i)
+
+    f32x16 acc[4][2][2];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) GB_ZERO(acc[q]);
+    GL_GLOAD(0);
+    for (int kb = 0; kb < nkb; ++kb) {
+        __syncthreads();                                      // the previous step's fragment reads are done
+        gb_xsplit_store<F16>(lds, xa0, xa1, xdst[0]); gb_xsplit_store<F16>(lds, xb0, xb1, xdst[1]);
+        GL_WSTORE(0); GL_WSTORE(1); GL_WSTORE(2); GL_WSTORE(3);
+        __syncthreads();
+        { const int kn = min(kb + 1, nkb - 1); GL_GLOAD(kn); }   // in flight during the MFMAs below (the last step re-reads its own tiles)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) GB_MMA_KSTEP(acc[q], false, GL_WIDX);
+    }
+#undef GL_WIDX
+#undef GL_GLOAD
+#undef GL_WLOAD
+#undef GL_WSTORE
+
+    if (F16 && guard) { float chk = 0.f; GB_GUARD_ROWS(acc[0], chk); }
+    // scale / bias; this thread's 8 columns: 128 nb + 64 wn + 32 jj + (lane & 31)
+    const int nl = 64 * wn + (lane & 31);
+    float part[2][16];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) part[i][r] = 0.f;
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) {
+            const int n = 128 * nb + nl + 32 * jj;
+            const float bv = bias ? bias[n] : 0.f, os = F16 ? oscale[n] : 1.0f;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    acc[nb][i][jj][r] = F16 ? __builtin_fmaf(acc[nb][i][jj][r], os, bv) : acc[nb][i][jj][r] + bv;
+                    part[i][r] += acc[nb][i][jj][r];
+                }
+        }
+    GB_LN_ROW_SUMS(0);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float mean = (lnx[GB_TILE_ROW(64 * wm, i, r)] + lnx[128 + GB_TILE_ROW(64 * wm, i, r)]) * (1.0f / 512.0f);
+            float sq = 0.f;
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+                for (int jj = 0; jj < 2; ++jj) { acc[nb][i][jj][r] -= mean; sq += acc[nb][i][jj][r] * acc[nb][i][jj][r]; }
+            part[i][r] = sq;
+        }
+    GB_LN_ROW_SUMS(256);
+    float rstd[2][16];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            rstd[i][r] = rsqrtf((lnx[256 + GB_TILE_ROW(64 * wm, i, r)] + lnx[384 + GB_TILE_ROW(64 * wm, i, r)]) * (1.0f / 512.0f) + ln_eps);
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) {
+            const int n = 128 * nb + nl + 32 * jj;
+            const float g = ln_gamma[n], be = ln_beta[n];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int m = GB_TILE_ROW(m0 + 64 * wm, i, r);
+                    if (m >= M) continue;
+                    const float u = acc[nb][i][jj][r] * rstd[i][r] * g + be;
+                    Y[(size_t)m * ldy + n] = 0.5f * u * (1.0f + erff(u * 0.70710678118654752440f));
+                }
+        }
+}
+
 // ---- implicit-GEMM convolution on NCHW images (round 5): what the matcher backbones' strided / 1x1 / 7x7 convolutions run ----------------------
 // Reference call site: LoFTR_matcher (etc/feature_matching_baselines/matchers.py:16-19,50) -> the un-vendored ResNet-FPN backbone: conv1 (7x7, stride 2,
 // 1 -> 128), the first 3x3 convolution and the 1x1 downsample of layer2.0 / layer3.0 (stride 2), the 1x1 lateral / output convolutions of the FPN
@@ -1117,6 +1252,20 @@ static int gb_mlp_ln(const float *x, int ldx, int K1, const void *packed_w1, con
 }
 
 template <bool F16>
+static int gb_ln_gelu(const float *x, int ldx, const void *packed_w, const float *bias, const float *gamma, const float *beta, float eps, float *y, int ldy,
+                      int M, int N, int K, void *stream)
+{
+    // N = 512 (four 128-feature blocks held on chip): the hidden layer of LightGlue's MLP
+    if (!x || !packed_w || !gamma || !beta || !y || M <= 0 || N != 4 * GB_BN || K <= 0 || (K % GB_BK) || (ldx & 3) || ldx < K || ldy < N || !(eps >= 0.f) ||
+        ((uintptr_t)x & 15)) return MFR_E_ARG;
+    const GbOperand<F16> w(packed_w, N, K);
+    hipLaunchKernelGGL((gemm_ln512_gelu_kernel<F16>), dim3((unsigned)((M + GB_BM - 1) / GB_BM)), dim3(256), 0, (hipStream_t)stream, x, ldx, w.wp, w.oscale, bias,
+                       gamma, beta, eps, y, ldy, M, K, w.guard());
+    CHECK_LAUNCH();
+    return 0;
+}
+
+template <bool F16>
 static int gb_windows(const float *feat, int Bimg, int Hf, int Wf, int C, const int32_t *img_ids, const int32_t *cell_ids, int nwin, int wc, int stride, int win,
                       const float *zero_row, const void *packed_w, const float *bias, const float *window_bias, float *y, int ldy, int N, void *stream)
 {
@@ -1232,6 +1381,18 @@ int mfr_gemm_bf16x3_ln(const float *x, int ldx, const void *packed_w, const floa
 {
     if (!gamma || !beta) return MFR_E_ARG;
     return gb_launch<false>(x, ldx, packed_w, bias, y, ldy, M, N, K, accumulate ? 2 : 0, stream, 1, 0, 0, 0, gamma, beta, eps);
+}
+
+int mfr_gemm_f16x2_ln_gelu(const float *x, int ldx, const void *packed_w, const float *bias, const float *gamma, const float *beta, float eps, float *y, int ldy,
+                           int M, int N, int K, void *stream)
+{
+    return gb_ln_gelu<true>(x, ldx, packed_w, bias, gamma, beta, eps, y, ldy, M, N, K, stream);
+}
+
+int mfr_gemm_bf16x3_ln_gelu(const float *x, int ldx, const void *packed_w, const float *bias, const float *gamma, const float *beta, float eps, float *y, int ldy,
+                            int M, int N, int K, void *stream)
+{
+    return gb_ln_gelu<false>(x, ldx, packed_w, bias, gamma, beta, eps, y, ldy, M, N, K, stream);
 }
 
 int mfr_gemm_f16x2_batched(const float *x, int ldx, long long x_batch_stride, const void *packed_w, const float *bias, float *y, int ldy, long long y_batch_stride,

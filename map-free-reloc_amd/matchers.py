@@ -1,7 +1,7 @@
 """Offline matcher plugins with the reference's API (etc/feature_matching_baselines/matchers.py):
 class M(resize: (W, H), outdoor: bool) with match(pair_path: (str, str)) -> ndarray [N,4]
 (x0,y0,x1,y1) in the resized pixel frame, or np.full((1,4), nan) when there is no correspondence
-(:59, :120); registered in MATCHERS and driven by compute.py (-ds Mapfree -m SG|LoFTR).
+(:59, :120); registered in MATCHERS and driven by compute.py (-ds Mapfree -m SG|LoFTR|SIFT|LG).
 
 Image reading: the reference uses SuperGlue's read_image (cv2.imread GRAYSCALE, cv2.resize of the float
 image to (W,H), /255).  cv2 is not available offline: the file is decoded with PIL and the
@@ -65,6 +65,21 @@ class SuperGlue_matcher:
         return self.match_tensors(read_image(pair_path[0], self.resize), read_image(pair_path[1], self.resize))
 
 
+class LightGlue_matcher(SuperGlue_matcher):
+    """SuperPoint + LightGlue (nets/lightglue.py; not in the reference): SuperGlue_matcher with the other matcher network.  weights_dir/lightglue.pth: a
+    state dict with the `transformers` LightGlue parameter names"""
+
+    def __init__(self, resize, outdoor=False, weights_dir="LightGlue/weights", sp_weights_dir="SuperGlue/models/weights"):
+        from .nets.superpoint import SuperPointHIP
+        from .nets.lightglue import LightGlueHIP
+        self.resize = resize
+        self.device = torch.device("cuda")
+        sp = _weights(os.path.join(sp_weights_dir, "superpoint_v1.pth"), WT.superpoint_state_dict, "SuperPoint")
+        lg = _weights(os.path.join(weights_dir, "lightglue.pth"), WT.lightglue_state_dict, "LightGlue")
+        self.sp = SuperPointHIP(sp, self.device, nms_radius=4, keypoint_threshold=0.005, max_keypoints=1024)
+        self.sg = LightGlueHIP(lg, self.device, filter_threshold=0.1)
+
+
 class LoFTR_matcher:
     def __init__(self, resize, outdoor=False, weights_dir="LoFTR/weights", match_type="dual_softmax"):
         """match_type 'dual_softmax': the reference's behaviour (matchers.py:16-18 loads the OT checkpoint strict=False into the dual-softmax
@@ -115,4 +130,4 @@ class SIFT_matcher:
         return self.match_arrays(g[0], g[1])
 
 
-MATCHERS = {'LoFTR': LoFTR_matcher, 'SG': SuperGlue_matcher, 'SIFT': SIFT_matcher}
+MATCHERS = {'LoFTR': LoFTR_matcher, 'SG': SuperGlue_matcher, 'SIFT': SIFT_matcher, 'LG': LightGlue_matcher}

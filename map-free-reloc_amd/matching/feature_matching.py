@@ -7,6 +7,7 @@ pixel frame, N may be 0 (np.array([])).  Mirrors lib/models/matching/feature_mat
   SuperGlueMatching    NEW: online SuperPoint+SuperGlue on the GPU (the reference only has it
                        offline, etc/feature_matching_baselines/matchers.py:62-120)
   LoFTRMatching        NEW: online LoFTR on the GPU (reference: offline only, matchers.py:12-59)
+  LightGlueMatching    NEW: online SuperPoint+LightGlue on the GPU (not in the reference; nets/lightglue.py)
   SIFTMatching         feature_matching.py:53-118: detectAndCompute from OpenCV, the HIP detector (SIFT.DETECTOR 'hip',
                        sift_ops.py) or a caller-supplied detector (raises ImportError when none exists), rootSIFT + exact 2-NN + ratio
                        test on the GPU (csrc/descriptor_match.hip) instead of FLANN
@@ -85,13 +86,18 @@ class SuperGlueMatching:
             WT.synthetic_or_raise("SuperPoint", cfg, lambda: WT.superpoint_state_dict(sg.SYNTHETIC_SEED))
         sg_sd = WT.load_checkpoint(sg.SUPERGLUE_WEIGHTS) if sg.SUPERGLUE_WEIGHTS else WT.synthetic_or_raise("SuperGlue", cfg, WT.superglue_state_dict)
         self.device = torch.device("cuda")
-        self.sp = SuperPointHIP(sp_sd, self.device, sg.NMS_RADIUS, sg.KEYPOINT_THRESHOLD, sg.MAX_KEYPOINTS)
-        self.sg = SuperGlueHIP(sg_sd, self.device, sg.SINKHORN_ITERATIONS, sg.MATCH_THRESHOLD)
-        self.use_graph = bool(cfg.HIP.GRAPH_BATCH1)
+        self._init_common(SuperPointHIP(sp_sd, self.device, sg.NMS_RADIUS, sg.KEYPOINT_THRESHOLD, sg.MAX_KEYPOINTS),
+                          SuperGlueHIP(sg_sd, self.device, sg.SINKHORN_ITERATIONS, sg.MATCH_THRESHOLD), bool(cfg.HIP.GRAPH_BATCH1), lambda: SuperGlueMatching(cfg))
+
+    def _init_common(self, sp, net, use_graph, make_twin):
+        """what every SuperPoint + keypoint-matcher plugin holds: the two networks (`sg`: any net with SuperGlueHIP's call), the batch-1 graph
+        switch, the gray stage and the f16x2 range guard (flag travels with the result, exact twin on demand)"""
+        self.sp, self.sg = sp, net
+        self.use_graph = use_graph
         self._graphs = {}
         self._gray = _GrayPairStage()
         from ..pipeline import RangeGuard
-        self.guard = RangeGuard(self.device, lambda: SuperGlueMatching(cfg))       # f16x2 range guard: flag travels with the result, exact twin on demand
+        self.guard = RangeGuard(self.device, make_twin)
 
     def _forward(self, ims):
         with self.guard:
@@ -128,6 +134,17 @@ class SuperGlueMatching:
             return e, e
         K = (len(flat) - 2) // 4
         return flat[2:2 + 2 * K].reshape(K, 2)[:n].copy(), flat[2 + 2 * K:].reshape(K, 2)[:n].copy()
+
+
+class LightGlueMatching(SuperGlueMatching):
+    """online matcher: SuperPoint + LightGlue (nets/lightglue.py; the reference has no LightGlue).  Same per-pair flow as SuperGlueMatching -- packed
+    result, one D2H copy, range guard with the bf16x3 twin -- but always eager: no graph capture of this stage"""
+
+    def __init__(self, cfg):
+        import torch
+        from ..nets import lightglue as LG
+        self.device = torch.device("cuda")
+        self._init_common(*LG.from_cfg(cfg, self.device), False, lambda: LightGlueMatching(cfg))
 
 
 class LoFTRMatching:

@@ -17,6 +17,7 @@ FEATURE_MATCHERS = {
     'Precomputed': _fm.PrecomputedMatching,
     'SuperGlue': _fm.SuperGlueMatching,      # online, GPU (new)
     'LoFTR': _fm.LoFTRMatching,              # online, GPU (new)
+    'LightGlue': _fm.LightGlueMatching,      # online, GPU (new): SuperPoint + LightGlue
 }
 POSE_SOLVERS = {
     'EssentialMatrix': _ps.EssentialMatrixSolver,

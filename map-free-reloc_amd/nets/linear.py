@@ -43,6 +43,16 @@ class SplitLinear:
                                                                    out.data_ptr(), out.stride(0), self.N, _lib.stream_ptr()), f"mfr_gemm_{self.split}_windows")
         return out
 
+    def ln_gelu(self, x, ln, out, eps=1e-5):
+        """out [M, 512] = GELU(LayerNorm_512(x W^T + b) * gamma + beta) in one launch (mfr_gemm_*_ln_gelu: N = 512 only, LightGlue's fc1)"""
+        assert self.N == 512 and x.dim() == 2 and x.shape[1] == self.K and x.stride(1) == 1 and x.dtype == torch.float32
+        M = x.shape[0]
+        assert out.shape == (M, 512) and out.stride(1) == 1
+        fn = getattr(_lib.load(), f"mfr_gemm_{self.split}_ln_gelu")
+        _lib.check(fn(x.data_ptr(), x.stride(0), _lib.ptr(self.packed), _lib.ptr(self.bias), _lib.ptr(ln[0]), _lib.ptr(ln[1]), float(eps), out.data_ptr(), out.stride(0),
+                      M, self.N, self.K, _lib.stream_ptr()), f"mfr_gemm_{self.split}_ln_gelu")
+        return out
+
     def ln_fusable(self):
         """can the LayerNorm that follows this layer run in its epilogue (mfr_gemm_*_ln: one 128-feature block, the LDS-DMA kernel)?"""
         return self.N == 128 and self.K % 64 == 0

@@ -139,6 +139,40 @@ def loftr_state_dict(seed=2468, feat_gain=20.0, msg_gain=0.1, bin_score=None):
     return sd
 
 
+def lightglue_state_dict(seed=9753, n_layers=9, proj_gain=10.0, match_bias=6.0):
+    """LightGlue (SuperPoint variant: descriptor_dim 256, 4 heads, no input_projection) with the parameter names of the `transformers`
+    module.  Plain initialisation (N(0, 0.02) weights, zero biases, identity LayerNorm) leaves the double softmax flat: the best assignment
+    score on planted twin descriptors is ~2e-3, far below the 0.1 filter threshold, and nothing matches.  So, structured random as for
+    SuperGlue: the transformer stays the mild perturbation of its input that the plain initialisation makes it, and the LAST assignment layer
+    is peaky and confident -- final_projection = proj_gain * I with zero bias, matchability weight x 0.1 with bias match_bias (sigmoid(6) =
+    0.9975).  What this makes TRIVIAL: every bias of the transformer is zero and every LayerNorm is the identity affine map;
+    tests/lightglue_ref.py perturbs them for the parity tests, as tests/trained_like.py does for the other nets."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+
+    def lin(name, ci, co):
+        sd[f"{name}.weight"] = _randn(g, (co, ci), 0.02)
+        sd[f"{name}.bias"] = torch.zeros(co)
+    sd["positional_encoder.projector.weight"] = _randn(g, (32, 2), 0.02)
+    for l in range(n_layers):
+        for kind in ("self", "cross"):
+            for n in "qkvo":
+                lin(f"transformer_layers.{l}.{kind}_attention.{n}_proj", 256, 256)
+            lin(f"transformer_layers.{l}.{kind}_mlp.fc1", 512, 512)
+            lin(f"transformer_layers.{l}.{kind}_mlp.fc2", 512, 256)
+            sd[f"transformer_layers.{l}.{kind}_mlp.layer_norm.weight"] = torch.ones(512)
+            sd[f"transformer_layers.{l}.{kind}_mlp.layer_norm.bias"] = torch.zeros(512)
+        lin(f"match_assignment_layers.{l}.final_projection", 256, 256)
+        lin(f"match_assignment_layers.{l}.matchability", 256, 1)
+        if l < n_layers - 1:
+            lin(f"token_confidence.{l}.token", 256, 1)
+    p = f"match_assignment_layers.{n_layers - 1}"
+    sd[f"{p}.final_projection.weight"] = proj_gain * torch.eye(256)
+    sd[f"{p}.matchability.weight"] = sd[f"{p}.matchability.weight"] * 0.1
+    sd[f"{p}.matchability.bias"] = torch.full((1,), float(match_bias))
+    return sd
+
+
 def load_checkpoint(path):
     """upstream .pth / .ckpt -> flat state dict.  superpoint_v1.pth / superglue_*.pth are plain state dicts;
     LoFTR's *_ot.ckpt are Lightning checkpoints that keep it under 'state_dict' with a `matcher.` prefix

@@ -266,14 +266,15 @@ class _PrecomputedStage:
         return dict(pts0=d(p0), pts1=d(p1), n_corr=d(n))
 
 
-class _RefCachedSuperGlue:
-    """SuperPoint + SuperGlue over a batch of pairs with ONE SuperPoint pass per distinct reference view.
+class _RefCachedKeypointMatcher:
+    """SuperPoint + a keypoint matcher (`net`: SuperGlueHIP or LightGlueHIP, the same call) over a batch of pairs with ONE SuperPoint pass per distinct
+    reference view.
 
     Every val / test pair of a Map-free scene has the same reference image, seq0/frame_00000.jpg
     (etc/feature_matching_baselines/compute.py:72-75, lib/datasets/mapfree.py:148-165); the reference runs the detector on it once per
     pair (116 times per scene).  Here the batch's pairs are grouped by `ref_keys` (PairBatchLoader: (scene_root, reference frame
     name)); SuperPoint runs on [the reference views not seen yet | all query views]; the reference rows of the interleaved
-    [2B] keypoint / score / descriptor tensors SuperGlue consumes are gathered from a small cache (the last few reference views: a
+    [2B] keypoint / score / descriptor tensors the matcher consumes are gathered from a small cache (the last few reference views: a
     scene's pairs span several batches).  Every SuperPoint stage is per image with a fixed summation order (own convolutions, own 1x1
     heads), so the result is the SAME BITS as the plain path -- tests/test_gpu_fused_submission.py checks poses byte for byte."""
 
@@ -336,7 +337,7 @@ class _RefView:
 
 
 class _RefCachedLoFTR:
-    """LoFTR over a batch of pairs with ONE backbone pass per distinct reference view: the twin of _RefCachedSuperGlue, same contract.
+    """LoFTR over a batch of pairs with ONE backbone pass per distinct reference view: the twin of _RefCachedKeypointMatcher, same contract.
 
     The batch's pairs are grouped by `ref_keys` (None: a view nobody shares -- run, not retained); the ResNet-FPN runs on [the reference views not
     cached yet | all query views] (after the pad-to-8 of the plain path); new reference rows are copied once, device to device, into a small pool of
@@ -421,7 +422,7 @@ class _RefCachedLoFTR:
 
 class FusedPosePipeline:
     """The batched twin of FeatureMatchingModel (lib/models/matching/model.py:7-40): the same two config keys pick the
-    stages -- FEATURE_MATCHING in {'Precomputed', 'SuperGlue', 'LoFTR', 'SIFT' (SIFT.DETECTOR 'hip')} x POSE_SOLVER in {'PNP', 'EssentialMatrix',
+    stages -- FEATURE_MATCHING in {'Precomputed', 'SuperGlue', 'LightGlue', 'LoFTR', 'SIFT' (SIFT.DETECTOR 'hip')} x POSE_SOLVER in {'PNP', 'EssentialMatrix',
     'EssentialMatrixMetric', 'Procrustes'} -- but every stage consumes / produces a device-resident batch of pairs.
     __call__(batch) with the dict PairBatchLoader yields -> dict(R [b,3,3] f64, t [b,3] f64, n_inliers, status, n_corr)."""
 
@@ -463,9 +464,15 @@ class FusedPosePipeline:
                     return graphs[key](im)
                 self.match = match
             elif "REF_FEATURE_CACHE" in cfg.HIP and cfg.HIP.REF_FEATURE_CACHE:
-                self.match = _RefCachedSuperGlue(sp, net, sg.MAX_KEYPOINTS, fwd)
+                self.match = _RefCachedKeypointMatcher(sp, net, sg.MAX_KEYPOINTS, fwd)
             else:
                 self.match = lambda b: fwd(b["images"])
+        elif fm == "LightGlue":
+            from .nets import lightglue as LG
+            sp, net = LG.from_cfg(cfg, self.device)
+            K = cfg.LIGHTGLUE.MAX_KEYPOINTS
+            fwd = lambda images: net(sp(images), tuple(images.shape[-2:]), maxN=K)      # eager: this stage is not graph-captured
+            self.match = _RefCachedKeypointMatcher(sp, net, K, fwd) if "REF_FEATURE_CACHE" in cfg.HIP and cfg.HIP.REF_FEATURE_CACHE else (lambda b: fwd(b["images"]))
         elif fm == "LoFTR":
             lw = cfg.LOFTR.WEIGHTS
             sd = WT.strip_prefix(WT.load_checkpoint(lw), "matcher.") if lw else WT.synthetic_or_raise("LoFTR", cfg, WT.loftr_state_dict)
