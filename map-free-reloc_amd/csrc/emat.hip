@@ -3,8 +3,9 @@
 // Replaces EssentialMatrixSolver.estimate_pose (lib/models/matching/pose_solver.py:29-61) for a
 // BATCH of image pairs:
 //   emat_prep_kernel    K-normalise both views in f32 (:39-40), thr = PIX_THRESHOLD / mean f (:43, Q8)
-//   emat_hyp_kernel     cv.findEssentialMat hypotheses: one LANE per 5-point minimal solve (Nister; <= 10 candidate E
-//                       each), working set in LDS (emat_lds.h: 145 KB per 64-lane workgroup)       (:46-48)
+//   emat_hyp_kernel     cv.findEssentialMat hypotheses: one LANE per 5-point minimal solve (Nister), front end up to the
+//                       degree-10 polynomial, working set in LDS (emat_lds.h: 145 KB per 64-lane workgroup)   (:46-48)
+//   emat_roots_kernel   eight lanes per hypothesis: the polynomial's real roots -> <= 10 candidate E each
 //   emat_score_kernel   one WAVEFRONT per hypothesis: lanes stride over the LDS-staged correspondences, squared Sampson
 //                       distance -> MAGSAC++ loss through the LDS-resident table (per-lane sums, wave butterfly per tile of
 //                       1024 points) + tentative inliers r^2 < thr^2 by ballot + popcount; or (score COUNT) the count alone
@@ -70,7 +71,7 @@ __global__ void __launch_bounds__(64) emat_hyp_kernel(
     int max_iters, uint64_t seed, const int64_t *__restrict__ pair_ids, double *__restrict__ Es /*[B,iters,10,9]*/,
     int32_t *__restrict__ nsol /*[B,iters]*/)
 {
-    // the solver's working set (Gauss-Jordan tableaux, monomial tables, derivative stack) in LDS, lane-interleaved: emat_lds.h
+    // the solver's working set (Gauss-Jordan tableaux, monomial tables) in LDS, lane-interleaved: emat_lds.h
     __shared__ double fp_lds[FP_LDS_DOUBLES * 64];
     __shared__ int fp_colp[9 * 64];
     const int b = blockIdx.y, it = blockIdx.x * 64 + threadIdx.x;
@@ -78,7 +79,7 @@ __global__ void __launch_bounds__(64) emat_hyp_kernel(
     int n = n_corr[b];
     if (n > maxN) n = maxN;
     int ns = 0;
-    double *o = Es + ((size_t)b * max_iters + it) * 90;
+    double *o = Es + ((size_t)b * max_iters + it) * FP_SLOT_DOUBLES;
     if (n >= 5 && (n > 5 || it == 0)) {
         int s[5];
         if (n == 5) {
@@ -93,20 +94,20 @@ __global__ void __launch_bounds__(64) emat_hyp_kernel(
             a[2 * k] = p0[2 * s[k]]; a[2 * k + 1] = p0[2 * s[k] + 1];
             c[2 * k] = p1[2 * s[k]]; c[2 * k + 1] = p1[2 * s[k] + 1];
         }
-        ns = fivept_lds(a, c, o, fp_lds + threadIdx.x, fp_colp + threadIdx.x, true);      // -1: front end done, 86 doubles in the slot
+        ns = fivept_front_lds(a, c, o, fp_lds + threadIdx.x, fp_colp + threadIdx.x);      // FP_NSOL_PENDING: the record is in the slot
     }
     nsol[(size_t)b * max_iters + it] = ns;
 }
 
-// root stage: 8 lanes per hypothesis, 32 hypotheses per workgroup (emat_lds.h fp_roots_group); turns the 86-double front-end
-// record of a hypothesis into its <= 10 essential matrices in place
+// root stage: 8 lanes per hypothesis, 32 hypotheses per workgroup (emat_lds.h fp_roots_group); turns the front end's record
+// of a hypothesis into its <= 10 essential matrices in place
 __global__ void __launch_bounds__(256) emat_roots_kernel(double *__restrict__ Es, int32_t *__restrict__ nsol, int total)
 {
     __shared__ FprShared sh[FPR_HYP_PER_WG];
     const int g = threadIdx.x / FPR_GROUP, sub = threadIdx.x % FPR_GROUP;
     const int h = blockIdx.x * FPR_HYP_PER_WG + g;
-    const bool active = h < total && nsol[h < total ? h : 0] == -1;
-    fp_roots_group(Es + (size_t)(h < total ? h : 0) * 90, nsol + (h < total ? h : 0), &sh[g], sub, active);
+    const bool active = h < total && nsol[h < total ? h : 0] == FP_NSOL_PENDING;
+    fp_roots_group(Es + (size_t)(h < total ? h : 0) * FP_SLOT_DOUBLES, nsol + (h < total ? h : 0), &sh[g], sub, active);
 }
 
 #define MAGSAC_LO_START 100      // USAC's max_iters_before_LO
@@ -161,7 +162,7 @@ __global__ void __launch_bounds__(256) emat_score_kernel(
             const int it = it0 + h;
             if (it >= max_iters) break;
             const int ns = nsol[(size_t)b * max_iters + it];
-            const double *Eh = Es + ((size_t)b * max_iters + it) * 90;
+            const double *Eh = Es + ((size_t)b * max_iters + it) * FP_SLOT_DOUBLES;
             for (int m = 0; m < ns; ++m) {
                 double E[9];
 #pragma unroll
@@ -501,7 +502,7 @@ __global__ void __launch_bounds__(EM_SEL_THREADS) emat_select_kernel(
                     bit = itr;
                     best_is_lo = false;
                     if (itr >= MAGSAC_LO_START) {
-                        const double *src = Es + ((size_t)b * max_iters + itr) * 90 + 9 * bestm[(size_t)b * max_iters + itr];
+                        const double *src = Es + ((size_t)b * max_iters + itr) * FP_SLOT_DOUBLES + 9 * bestm[(size_t)b * max_iters + itr];
                         double Ein[9], El[9], ll;
                         int cl;
                         for (int k = 0; k < 9; ++k) Ein[k] = src[k];
@@ -529,7 +530,7 @@ __global__ void __launch_bounds__(EM_SEL_THREADS) emat_select_kernel(
     int m = 0;
     if (st == MFR_ST_OK) {
         if (!(MAGSAC && best_is_lo)) {
-            const double *src = Es + ((size_t)b * max_iters + bit) * 90 + 9 * bestm[(size_t)b * max_iters + bit];
+            const double *src = Es + ((size_t)b * max_iters + bit) * FP_SLOT_DOUBLES + 9 * bestm[(size_t)b * max_iters + bit];
             for (int k = 0; k < 9; ++k) Eb[k] = src[k];
         }
         if (MAGSAC && !best_is_lo && n > 5) {        // the winner never went through the local optimisation
@@ -642,7 +643,7 @@ static EmWs em_ws(void *base, int B, int maxN, int iters)
     w.x0 = c.take<double>(2 * b * maxN);
     w.x1 = c.take<double>(2 * b * maxN);
     w.thr2 = c.take<double>(b);
-    w.Es = c.take<double>(90 * b * iters);
+    w.Es = c.take<double>(FP_SLOT_DOUBLES * b * iters);
     w.nsol = c.take<int32_t>(b * iters);
     w.counts = c.take<int32_t>(b * iters);
     w.bestm = c.take<int32_t>(b * iters);

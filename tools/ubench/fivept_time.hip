@@ -1,19 +1,30 @@
-// times the stages of the LDS 5-point solver (csrc/emat_lds.h): build with -DFP_STAGE_LIMIT=k, k = 0..5, 99
-// hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -I../../include -I../../map-free-reloc_amd/csrc -DFP_STAGE_LIMIT=k -o fivept_k fivept_time.hip
+// times the two stages of the 5-point solver (csrc/emat_lds.h) in the launch shapes of emat_hyp_kernel and emat_roots_kernel
+// hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -I../../include -I../../map-free-reloc_amd/csrc -o fivept_time fivept_time.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
 #include <random>
 #include "emat_lds.h"
 using namespace mfr;
-__global__ void __launch_bounds__(64) k(const double *x0, const double *x1, double *Es, int *nsol)
+#define CHECK(e) do { hipError_t r_ = (e); if (r_ != hipSuccess) { printf("%s: %s\n", #e, hipGetErrorString(r_)); return 1; } } while (0)
+// one lane per solve, as emat_hyp_kernel
+__global__ void __launch_bounds__(64) front(const double *x0, const double *x1, double *Es, int *nsol)
 {
     __shared__ double fp_lds[FP_LDS_DOUBLES * 64];
     __shared__ int fp_colp[9 * 64];
     const int it = blockIdx.x * 64 + threadIdx.x;
     double a[10], c[10];
     for (int q = 0; q < 10; ++q) { a[q] = x0[it * 10 + q]; c[q] = x1[it * 10 + q]; }
-    nsol[it] = fivept_lds(a, c, Es + (size_t)it * 90, fp_lds + threadIdx.x, fp_colp + threadIdx.x);
+    nsol[it] = fivept_front_lds(a, c, Es + (size_t)it * FP_SLOT_DOUBLES, fp_lds + threadIdx.x, fp_colp + threadIdx.x);
+}
+// 8 lanes per solve, 32 solves per workgroup, as emat_roots_kernel
+__global__ void __launch_bounds__(256) roots(double *Es, int *nsol, int total)
+{
+    __shared__ FprShared sh[FPR_HYP_PER_WG];
+    const int g = threadIdx.x / FPR_GROUP, sub = threadIdx.x % FPR_GROUP;
+    const int h = blockIdx.x * FPR_HYP_PER_WG + g;
+    const bool active = h < total && nsol[h < total ? h : 0] == FP_NSOL_PENDING;
+    fp_roots_group(Es + (size_t)(h < total ? h : 0) * FP_SLOT_DOUBLES, nsol + (h < total ? h : 0), &sh[g], sub, active);
 }
 int main()
 {
@@ -25,14 +36,20 @@ int main()
             h1[i * 10 + 2 * q] = (X + 0.3) / (Z + 0.05); h1[i * 10 + 2 * q + 1] = (Y + 0.02) / (Z + 0.05); }
     }
     double *d0, *d1, *Es; int *ns;
-    hipMalloc(&d0, n * 80); hipMalloc(&d1, n * 80); hipMalloc(&Es, (size_t)n * 720); hipMalloc(&ns, n * 4);
-    hipMemcpy(d0, h0.data(), n * 80, hipMemcpyHostToDevice); hipMemcpy(d1, h1.data(), n * 80, hipMemcpyHostToDevice);
-    hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    k<<<n / 64, 64>>>(d0, d1, Es, ns); hipDeviceSynchronize();
-    hipEventRecord(e0); k<<<n / 64, 64>>>(d0, d1, Es, ns); hipEventRecord(e1); hipDeviceSynchronize();
-    float ms; hipEventElapsedTime(&ms, e0, e1);
-    std::vector<int> hn(n); hipMemcpy(hn.data(), ns, n * 4, hipMemcpyDeviceToHost);
+    CHECK(hipMalloc(&d0, n * 80)); CHECK(hipMalloc(&d1, n * 80));
+    CHECK(hipMalloc(&Es, (size_t)n * FP_SLOT_DOUBLES * sizeof(double))); CHECK(hipMalloc(&ns, n * 4));
+    CHECK(hipMemcpy(d0, h0.data(), n * 80, hipMemcpyHostToDevice)); CHECK(hipMemcpy(d1, h1.data(), n * 80, hipMemcpyHostToDevice));
+    const int rgrid = (n + FPR_HYP_PER_WG - 1) / FPR_HYP_PER_WG;
+    hipEvent_t e0, e1, e2; CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1)); CHECK(hipEventCreate(&e2));
+    front<<<n / 64, 64>>>(d0, d1, Es, ns); roots<<<rgrid, 256>>>(Es, ns, n); CHECK(hipDeviceSynchronize());      // warm-up
+    // the root stage consumes the records in place, so each timed root launch follows a front launch that wrote them
+    CHECK(hipEventRecord(e0)); front<<<n / 64, 64>>>(d0, d1, Es, ns);
+    CHECK(hipEventRecord(e1)); roots<<<rgrid, 256>>>(Es, ns, n);
+    CHECK(hipEventRecord(e2)); CHECK(hipDeviceSynchronize());
+    float ms_front, ms_roots; CHECK(hipEventElapsedTime(&ms_front, e0, e1)); CHECK(hipEventElapsedTime(&ms_roots, e1, e2));
+    std::vector<int> hn(n); CHECK(hipMemcpy(hn.data(), ns, n * 4, hipMemcpyDeviceToHost));
     long tot = 0; for (int v : hn) tot += v;
-    printf("FP_STAGE_LIMIT=%d: %.3f ms for %d solves (250 workgroups), mean solutions %.2f\n", FP_STAGE_LIMIT, ms, n, (double)tot / n);
+    printf("%d solves: front end %.3f ms (%d workgroups of 64), root stage %.3f ms (%d workgroups of 256), mean solutions %.2f\n",
+           n, ms_front, n / 64, ms_roots, rgrid, (double)tot / n);
     return 0;
 }
