@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define MFR_ABI_VERSION 6   /* 6 (round 6): mfr_conv3x3_direct_f16x2*, later (additive) the SIFT detector mfr_sift_*, the JPEG decoder mfr_jpeg_*, the depth PNG decoder mfr_png_depth_*, mfr_resize_gray_bilinear (the device image resize), mfr_conv3x3s2_direct_f16x2, mfr_mlp_ln_*, mfr_loftr_ot_match (LoFTR's optimal-transport coarse matching), mfr_abs_pose_fuse (7Scenes: absolute pose from relative poses); 5 (round 6): mfr_f16x2_guard_bind (the f16x2 range guard); 2: intrinsics as (const void *K, int k_dtype) instead of const float *; 3: mfr_emat_solve_batch takes the
+#define MFR_ABI_VERSION 6   /* 6 (round 6): mfr_conv3x3_direct_f16x2*, later (additive) the SIFT detector mfr_sift_*, the JPEG decoder mfr_jpeg_*, the depth PNG decoder mfr_png_depth_*, mfr_resize_gray_bilinear (the device image resize), mfr_conv3x3s2_direct_f16x2, mfr_mlp_ln_*, mfr_loftr_ot_match (LoFTR's optimal-transport coarse matching), mfr_abs_pose_fuse (7Scenes: absolute pose from relative poses), mfr_rig_pnp_* (one pose for a rig of query frames); 5 (round 6): mfr_f16x2_guard_bind (the f16x2 range guard); 2: intrinsics as (const void *K, int k_dtype) instead of const float *; 3: mfr_emat_solve_batch takes the
                              * model-quality method (MAGSAC++ / count) and its table; 4 (round 5): the f16x2 entry points (mfr_gemm_f16x2*,
                              * mfr_wino_f16x2_*, mfr_conv3x3_wino_f16x2, mfr_conv_igemm_f16x2), mfr_sg_attention_variant renumbered (0 f16x2,
                              * 1 exact fp32, 2 bf16x3), the measurement-only entry points (mfr_conv3x3_wino_bf16x3_variant,
@@ -121,6 +121,44 @@ int mfr_pnp_ransac(const double *xyz, const double *obs, const int32_t *n_valid,
                    uint8_t *mask_valid /*[B,maxN] over lifted points, may be NULL*/,
                    int32_t *best_iter /*[B] may be NULL*/, int32_t *iters_run /*[B] may be NULL*/,
                    void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Rig PnP path (additive; csrc/pnp_rig.hip): ONE pose for a window of T query frames, the Map-free multi-frame track
+ * (config/mapfree_multi.yaml, DATASET.QUERY_FRAME_COUNT; lib/datasets/mapfree.py:285 reads the device-tracking poses that make
+ * the window a calibrated rig).  Upstream has no such solver (RegressionMultiFrameModel regresses against the last frame).
+ *   Model: (R, t) reference -> LAST window frame.  Frame j sees a reference point X at R_Aj (R X + t) + t_Aj, projected with K_j;
+ *   rig [B,T,12] f64 = R_Aj row-major then t_Aj (A_j: last frame's camera -> frame j's camera; the last row is the identity).
+ *   Rows: frame j of sample b is row b*T + j of pts0 / pts1 / n_corr / xyz / obs / n_valid / K1 ([B*T,3,3]); depth0 [B,H,W] and
+ *   K0 [B,3,3] belong to the one reference view of a sample.  1 <= T <= 16.
+ *   Hypothesis `it` of sample b: a frame with n_valid >= 5 (the only one, or drawn uniformly: word 0 of Philox4x32-10 at counter
+ *   (it, 0x80000000, lo, hi of pair_id*T), key seed -- sample_distinct uses counter word 1 in {0, 1}), four of its points by
+ *   sample_distinct<4>(seed, pair_id*T + j, it, n_j), P3P with K_j, carried to the last frame; its count is summed over ALL frames.
+ *   Then as the PnP path: replay of the adaptive iteration cap (N = sum of n_valid), pooled inlier list in (frame, index) order,
+ *   LM over the six pose parameters (the same two calls), finite / |t| > 1000 checks.  n_inliers = the pooled RANSAC count.
+ *   Status: no frame with n_corr >= 4 -> MFR_ST_TOO_FEW; else none with n_valid >= 4 -> MFR_ST_BAD_DEPTH; else no frame with
+ *   n_valid >= 5: the one model is the fixed sample {0,1,2,3} of the first frame with n_valid == 4 (those four are inliers, the
+ *   other frames' points are scored; LM only if N > 4).
+ *   With T = 1 and the identity rig every output equals mfr_pnp_ransac / mfr_pnp_solve_batch bit for bit.
+ * mask_valid / inlier_mask are [B*T,maxN] (lifted points / ORIGINAL correspondence index), counts [B,max_iters],
+ * inl_idx [B*T,maxN] workspace.  Bad arguments (T < 1, T > 16, NULL pointers, workspace too small) return MFR_E_* and launch nothing.
+ * ------------------------------------------------------------------------------------------ */
+size_t mfr_rig_pnp_workspace_bytes(int B, int T, int maxN, int max_iters);
+int mfr_rig_pnp_ransac(const double *xyz, const double *obs, const int32_t *n_valid, int B, int T, int maxN,
+                       const void *K1, int k_dtype, const double *rig, int max_iters, double reproj_thr, double confidence,
+                       uint64_t seed, const int64_t *pair_ids,
+                       int32_t *counts /*[B,max_iters] workspace*/, int32_t *inl_idx /*[B*T,maxN] workspace*/,
+                       double *R, double *t, int32_t *n_inliers, int32_t *status,
+                       uint8_t *mask_valid /*[B*T,maxN] over lifted points, may be NULL*/,
+                       int32_t *best_iter /*[B] may be NULL*/, int32_t *iters_run /*[B] may be NULL*/,
+                       void *stream);
+int mfr_rig_pnp_solve_batch(const float *pts0, const float *pts1, const int32_t *n_corr, int B, int T, int maxN,
+                            const float *depth0, int H, int W,
+                            const void *K0, const void *K1, int k_dtype, const double *rig,
+                            int max_iters, double reproj_thr, double confidence,
+                            uint64_t seed, const int64_t *pair_ids,
+                            void *workspace, size_t workspace_bytes,
+                            double *R, double *t, int32_t *n_inliers, int32_t *status, uint8_t *inlier_mask /*may be NULL*/,
+                            void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Metric scale from depth: EssentialMatrixMetricSolver.estimate_pose, pose_solver.py:137-172

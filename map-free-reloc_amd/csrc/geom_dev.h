@@ -208,14 +208,19 @@ MFR_DEV void rot_apply(const double *R, const double *t, const double *X, double
 
 // squared reprojection error in pixels; cv::projectPoints semantics (z == 0 -> 1/z := 1, no
 // cheirality test) as used by PnPRansacCallback::computeError.  Kd = {fx, fy, cx, cy}.
-MFR_DEV double reproj_err2(const double *R, const double *t, const double *X, const double *x, const double *Kd)
+// cam_err2 is the part after the rigid transform: Y is the point in the camera's frame.
+MFR_DEV double cam_err2(const double *Y, const double *x, const double *Kd)
 {
-    double Y[3];
-    rot_apply(R, t, X, Y);
     const double iz = (Y[2] != 0.0) ? 1.0 / Y[2] : 1.0;
     const double du = (Kd[0] * (Y[0] * iz) + Kd[2]) - x[0];
     const double dv = (Kd[1] * (Y[1] * iz) + Kd[3]) - x[1];
     return du * du + dv * dv;
+}
+MFR_DEV double reproj_err2(const double *R, const double *t, const double *X, const double *x, const double *Kd)
+{
+    double Y[3];
+    rot_apply(R, t, X, Y);
+    return cam_err2(Y, x, Kd);
 }
 
 // Intrinsics cross the C-ABI in the dtype the `data` dict holds them (include/mfr_hip.h MFR_K_F32 / MFR_K_F64); pair b's matrix

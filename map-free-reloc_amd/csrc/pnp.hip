@@ -4,7 +4,7 @@
 // image pairs, device-resident end to end:
 //
 //   depth_min_kernel      depth_0.min()                                   (:196, quirk Q6)
-//   pnp_lift_kernel       np.int32(pts0) -> depth gather -> valid -> backproject_3d  (:186-206, :6-17)
+//   pnp_lift_kernel       (pnp_dev.h) np.int32(pts0) -> depth gather -> valid -> backproject_3d  (:186-206, :6-17)
 //   pnp_hyp_score_kernel  cv.solvePnPRansac(P3P) hypotheses + inlier counts (:209-213)
 //   pnp_select_kernel     RANSAC best-model replay (adaptive iteration cap), inlier set,
 //                         non-minimal refit + ITERATIVE refinement (:216-220), |t|>1000 (:223-225)
@@ -24,6 +24,7 @@
 #include "../../include/mfr_hip.h"
 #include "zero_fill.h"
 #include "solver_dev.h"
+#include "pnp_dev.h"
 
 using namespace mfr;
 
@@ -56,40 +57,6 @@ __global__ void __launch_bounds__(256) depth_min_kernel(const float *__restrict_
         for (int w = 1; w < 4; ++w) if (sm[w] < r) r = sm[w];
         partial[b * MFR_NSEG + s] = r;
     }
-}
-
-// ------------------------------------------------------------------------------------------
-// one workgroup per pair; order-preserving compaction of the valid correspondences
-__global__ void __launch_bounds__(256) pnp_lift_kernel(
-    const float *__restrict__ pts0, const float *__restrict__ pts1, const int32_t *__restrict__ n_corr, int maxN,
-    const float *__restrict__ depth0, const float *__restrict__ partial_min, int H, int W,
-    const void *__restrict__ K0, int k_dtype, double *__restrict__ xyz, double *__restrict__ obs,
-    int32_t *__restrict__ src_idx, int32_t *__restrict__ n_valid)
-{
-    const int b = blockIdx.x, tid = threadIdx.x;
-    int n = n_corr[b];
-    if (n > maxN) n = maxN;
-    __shared__ Compact256 cs;
-    const float dmin = depth_min_fold(partial_min, b);
-    double Ki[4];
-    kinv(K0, k_dtype, b, Ki);
-    const float *p0 = pts0 + (size_t)b * maxN * 2, *p1 = pts1 + (size_t)b * maxN * 2;
-    const float *dm = depth0 + (size_t)b * H * W;
-    double *oxyz = xyz + (size_t)b * maxN * 3, *oobs = obs + (size_t)b * maxN * 2;
-    int32_t *osrc = src_idx + (size_t)b * maxN;
-    int total = 0;
-    for (int start = 0; start < n; start += 256) {
-        const int i = start + tid;
-        double X[3];
-        const bool valid = i < n && lift_point(p0[2 * i], p0[2 * i + 1], dm, H, W, dmin, Ki, X);   // :186-206 (Q1, Q6), :6-17
-        const int m = compact256_slot(cs, valid, total);
-        if (valid) {
-            oxyz[3 * m] = X[0]; oxyz[3 * m + 1] = X[1]; oxyz[3 * m + 2] = X[2];
-            oobs[2 * m] = (double)p1[2 * i]; oobs[2 * m + 1] = (double)p1[2 * i + 1];
-            osrc[m] = i;
-        }
-    }
-    if (tid == 0) n_valid[b] = total;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -173,88 +140,7 @@ __global__ void __launch_bounds__(HYP_THREADS) pnp_hyp_score_kernel(
 }
 
 // ------------------------------------------------------------------------------------------
-// LM pieces (wave-parallel, deterministic wave64 reduction order)
-static __device__ __forceinline__ double pnp_cost(const double *X, const double *O, const int32_t *idx, int n,
-                                                  const double *Kd, const double *R, const double *t)
-{
-    double acc = 0.0;
-    for (int i = lane_id(); i < n; i += 64) {
-        const int j = idx[i];
-        acc = acc + reproj_err2(R, t, X + 3 * (size_t)j, O + 2 * (size_t)j, Kd);
-    }
-    return wave_sum(acc);
-}
-
-// Levenberg-Marquardt on the reprojection error over the inlier list; stands in for the EPnP
-// refit inside cv::solvePnPRansac and for cv.solvePnPGeneric(ITERATIVE) (pose_solver.py:216-220).
-static __device__ __noinline__ int pnp_lm(const double *X, const double *O, const int32_t *idx, int n_idx,
-                                          const double *Kd, int max_iter, double *R, double *t)
-{
-    LmDamping lm;
-    double cost = pnp_cost(X, O, idx, n_idx, Kd, R, t);
-    if (!(cost == cost) || !(cost < 1e300)) return -1;
-    for (int it = 0; it < max_iter; ++it) {
-        double acc[27];
-#pragma unroll
-        for (int q = 0; q < 27; ++q) acc[q] = 0.0;
-        for (int i = lane_id(); i < n_idx; i += 64) {
-            const int j = idx[i];
-            const double *P = X + 3 * (size_t)j, *x = O + 2 * (size_t)j;
-            double Y[3];
-            rot_apply(R, t, P, Y);
-            const double iz = (Y[2] != 0.0) ? 1.0 / Y[2] : 1.0;
-            const double xn = Y[0] * iz, yn = Y[1] * iz;
-            const double ru = (Kd[0] * xn + Kd[2]) - x[0];
-            const double rv = (Kd[1] * yn + Kd[3]) - x[1];
-            const double a0[3] = { 0.0, -P[2], P[1] }, a1[3] = { P[2], 0.0, -P[0] }, a2[3] = { -P[1], P[0], 0.0 };
-            double G[3][6];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                G[r][0] = (R[3 * r] * a0[0] + R[3 * r + 1] * a0[1]) + R[3 * r + 2] * a0[2];
-                G[r][1] = (R[3 * r] * a1[0] + R[3 * r + 1] * a1[1]) + R[3 * r + 2] * a1[2];
-                G[r][2] = (R[3 * r] * a2[0] + R[3 * r + 1] * a2[1]) + R[3 * r + 2] * a2[2];
-                G[r][3] = (r == 0) ? 1.0 : 0.0; G[r][4] = (r == 1) ? 1.0 : 0.0; G[r][5] = (r == 2) ? 1.0 : 0.0;
-            }
-            const double pu0 = Kd[0] * iz, pu2 = -(Kd[0] * xn) * iz;
-            const double pv1 = Kd[1] * iz, pv2 = -(Kd[1] * yn) * iz;
-            double Ju[6], Jv[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                Ju[k] = pu0 * G[0][k] + pu2 * G[2][k];
-                Jv[k] = pv1 * G[1][k] + pv2 * G[2][k];
-            }
-            int q = 0;
-#pragma unroll
-            for (int r = 0; r < 6; ++r)
-#pragma unroll
-                for (int c = r; c < 6; ++c, ++q) acc[q] = acc[q] + (Ju[r] * Ju[c] + Jv[r] * Jv[c]);
-#pragma unroll
-            for (int r = 0; r < 6; ++r, ++q) acc[q] = acc[q] + (Ju[r] * ru + Jv[r] * rv);
-        }
-#pragma unroll
-        for (int q = 0; q < 27; ++q) acc[q] = wave_sum(acc[q]);
-        double Hm[36], g[6], dlt[6];
-        lm6_unpack(acc, Hm, g);
-        lm.damp(Hm);
-        if (chol_solve6(Hm, g, dlt)) {
-            if (lm.reject()) break;
-            continue;
-        }
-        double Rn[9], tn[3];
-        quat_right_update(R, dlt, Rn);
-        tn[0] = t[0] + dlt[3]; tn[1] = t[1] + dlt[4]; tn[2] = t[2] + dlt[5];
-        const double cn = pnp_cost(X, O, idx, n_idx, Kd, Rn, tn);
-        if (cn < cost) {
-            for (int k = 0; k < 9; ++k) R[k] = Rn[k];
-            for (int k = 0; k < 3; ++k) t[k] = tn[k];
-            const bool done = lm.accept(cost - cn, 1e-14 * cost);
-            cost = cn;
-            if (done) break;
-        } else if (lm.reject()) break;
-        if (lm6_max_abs(dlt) < 1e-13) break;
-    }
-    return 0;
-}
+// the LM refinement (pnp_lm) lives in pnp_dev.h, shared with pnp_rig.hip; here the model is the camera pose (PnpOneCamera)
 
 // ------------------------------------------------------------------------------------------
 // one wavefront per pair: replay of RANSACPointSetRegistrator::run's best-model / adaptive
@@ -308,9 +194,10 @@ __global__ void __launch_bounds__(64) pnp_select_kernel(
         }
         __threadfence();          // idx[] written by other lanes of this wave is read below
         if (n > 4) {
-            if (pnp_lm(X, O, idx, m, Kd, 20, R, t)) st = MFR_ST_NO_MODEL;
+            const PnpOneCamera cam = { Kd };
+            if (pnp_lm(X, O, idx, m, cam, 20, R, t)) st = MFR_ST_NO_MODEL;
             if (st == MFR_ST_OK && m >= 6)
-                if (pnp_lm(X, O, idx, m, Kd, 20, R, t)) st = MFR_ST_NO_MODEL;   // pose_solver.py:216-220
+                if (pnp_lm(X, O, idx, m, cam, 20, R, t)) st = MFR_ST_NO_MODEL;   // pose_solver.py:216-220
         }
     }
     if (st == MFR_ST_OK) {
@@ -437,7 +324,7 @@ int mfr_pnp_lift(const float *pts0, const float *pts1, const int32_t *n_corr, in
     if (!pts0 || !pts1 || !n_corr || !depth0 || !partial_min || !K0 || !xyz || !obs || !src_idx || !n_valid ||
         B <= 0 || maxN <= 0 || H <= 0 || W <= 0 || !k_dtype_ok(k_dtype)) return MFR_E_ARG;
     hipLaunchKernelGGL(pnp_lift_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, pts0, pts1, n_corr, maxN,
-                       depth0, partial_min, H, W, K0, k_dtype, xyz, obs, src_idx, n_valid);
+                       depth0, partial_min, H, W, K0, k_dtype, 1, xyz, obs, src_idx, n_valid);
     CHECK_LAUNCH();
     return 0;
 }

@@ -453,7 +453,13 @@ class MapFreeSceneMultiFrame(MapFreeScene):
       train (overlaps.npz): every overlap row whose query frame has query_frames - 1 valid predecessors in its sequence and whose
       map frame does not fall inside that window (different sequence, or before the window, or after the query frame) -- the valid
       frame lists are taken BEFORE the overlap window is applied, like upstream.
-    The device-tracking poses (poses_device.txt) only feed upstream's debug plot and are not read."""
+    The device-tracking poses (poses_device.txt, the line format of poses.txt, world-to-camera; mapfree.py:285) are read when the file
+    is there (`poses_device` is None otherwise).  They are metric and locally accurate, so they make the window a calibrated rig, and
+    every sample then carries two more keys (no other key changes):
+      K_color1_multi [T,3,3] f64  the rescaled intrinsics of every window frame (the last row equals K_color1);
+      rig_T          [T,4,4] f64  A_j: coordinates in the LAST frame's camera -> coordinates in frame j's camera, from the device
+                                  poses (R_j, t_j), (R_L, t_L): R_Aj = R_j R_L^T, t_Aj = t_j - R_Aj t_L; the last row is the identity.
+    Upstream only feeds them to a debug plot; here FeatureMatchingMultiFrameModel solves one pose for the rig from them."""
     has_gray_pair = False       # a pair's query is a TUPLE of frames here: the batched loaders take the generic per-sample route (ADVICE r4)
 
     def __init__(self, scene_root, resize, query_frames=9, estimated_depth=None, overlap_limits=None, black_white=False):
@@ -464,6 +470,17 @@ class MapFreeSceneMultiFrame(MapFreeScene):
         super().__init__(scene_root, resize, 1, estimated_depth, None, black_white)
         self.shared_reference = False                           # (the single-frame pair list it was computed from is replaced below)
         self.query_frames, self.sample_factor = T, T + 1
+        self.poses_device = None
+        dev = os.path.join(self.scene_root, "poses_device.txt")
+        if os.path.exists(dev):
+            self.poses_device = {}
+            with open(dev) as f:
+                for line in f:
+                    if "#" in line:
+                        continue
+                    parts = line.strip().split(" ")
+                    qt = np.array(list(map(float, parts[1:])))
+                    self.poses_device[parts[0]] = (qt[:4], qt[4:])
         ov = os.path.join(self.scene_root, "overlaps.npz")
         if os.path.exists(ov):
             f = np.load(ov, allow_pickle=False)
@@ -506,10 +523,27 @@ class MapFreeSceneMultiFrame(MapFreeScene):
         q12 = E.qmult(q2, E.qinverse(q1))
         t12 = t2 - E.rotate_vector(t1, q12)
         T = np.eye(4, dtype=np.float32); T[:3, :3] = E.quat2mat(q12); T[:3, -1] = t12
-        return {"image0": img1, "depth0": d1, "image1": img2, "depth1": d2, "T_0to1": torch.from_numpy(T),
-                "K_color0": torch.from_numpy(self.K[p1].copy()), "K_color1": torch.from_numpy(self.K[p2s[-1]].copy()),
-                "dataset_name": "Mapfree", "scene_id": os.path.basename(self.scene_root.rstrip("/")),
-                "scene_root": self.scene_root, "pair_id": index * self.sample_factor, "pair_names": (p1, p2s)}
+        out = {"image0": img1, "depth0": d1, "image1": img2, "depth1": d2, "T_0to1": torch.from_numpy(T),
+               "K_color0": torch.from_numpy(self.K[p1].copy()), "K_color1": torch.from_numpy(self.K[p2s[-1]].copy()),
+               "dataset_name": "Mapfree", "scene_id": os.path.basename(self.scene_root.rstrip("/")),
+               "scene_root": self.scene_root, "pair_id": index * self.sample_factor, "pair_names": (p1, p2s)}
+        if self.poses_device is not None:
+            out["K_color1_multi"] = torch.from_numpy(np.stack([self.K[p] for p in p2s]).astype(np.float64))
+            out["rig_T"] = torch.from_numpy(self._rig(p2s))
+        return out
+
+    def _rig(self, frames):
+        """[T,4,4] f64: A_j = P_j P_L^-1 of the device poses P = (R, t) (world -> camera), L the last of `frames`"""
+        from . import evaluation as E
+        qL, tL = self.poses_device[frames[-1]]
+        RL, tL = E.quat2mat(np.asarray(qL, np.float64)), np.asarray(tL, np.float64)
+        rig = np.tile(np.eye(4), (len(frames), 1, 1))
+        for j, p in enumerate(frames[:-1]):                     # the last row stays the exact identity
+            qj, tj = self.poses_device[p]
+            RA = E.quat2mat(np.asarray(qj, np.float64)) @ RL.T
+            rig[j, :3, :3] = RA
+            rig[j, :3, 3] = np.asarray(tj, np.float64) - RA @ tL
+        return rig
 
 
 def _luma3(img):

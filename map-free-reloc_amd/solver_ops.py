@@ -145,6 +145,84 @@ class PnPBatchSolver(_Workspace):
         return out
 
 
+RIG_MAX_T = 16      # frames per rig the library takes (include/mfr_hip.h)
+
+
+def rig_rows(rig_T):
+    """[B,T,4,4] rigid transforms (last frame's camera -> frame j's camera) -> the library's [B,T,12] f64 rows: R row-major, then t"""
+    rig_T = _chk(rig_T, torch.float64, "rig_T")
+    if rig_T.dim() != 4 or rig_T.shape[-2:] != (4, 4):
+        raise ValueError(f"rig_T: expected [B,T,4,4], got {tuple(rig_T.shape)}")
+    return torch.cat([rig_T[..., :3, :3].reshape(*rig_T.shape[:2], 9), rig_T[..., :3, 3]], dim=-1).contiguous()
+
+
+def rig_pnp_ransac(xyz, obs, n_valid, K1, rig, pair_ids, max_iters=1000, thr=3.0, conf=0.9999, seed=0):
+    """The rig solver on already lifted rows (csrc/pnp_rig.hip): xyz [B,T,maxN,3], obs [B,T,maxN,2], n_valid [B,T], K1 [B,T,3,3],
+    rig [B,T,12] f64 (rig_rows).  Returns dict(R, t, n_inliers, status, mask [B,T,maxN], best_iter, iters_run, counts)."""
+    lib = _lib.load(require_gpu=True)
+    xyz = _chk(xyz, torch.float64, "xyz"); obs = _chk(obs, torch.float64, "obs")
+    n_valid = _chk(n_valid, torch.int32, "n_valid"); K1, _, kdt = _chk_K(K1)
+    rig = _chk(rig, torch.float64, "rig"); pair_ids = _chk(pair_ids, torch.int64, "pair_ids")
+    B, T, maxN, _ = xyz.shape
+    if tuple(rig.shape) != (B, T, 12) or tuple(K1.shape) != (B, T, 3, 3) or tuple(n_valid.shape) != (B, T):
+        raise ValueError("rig_pnp_ransac: rig [B,T,12], K1 [B,T,3,3] and n_valid [B,T] must match xyz [B,T,maxN,3]")
+    dev = xyz.device
+    max_iters = max(int(max_iters), 1)
+    counts, inl = _i32(dev, B, max_iters), _i32(dev, B, T, maxN)
+    R, t, ni, st = _pose_out(B, dev)
+    mask = torch.empty(B, T, maxN, dtype=torch.uint8, device=dev)
+    bi, ir = _i32(dev, B), _i32(dev, B)
+    _lib.check(lib.mfr_rig_pnp_ransac(_lib.ptr(xyz), _lib.ptr(obs), _lib.ptr(n_valid), B, T, maxN, _lib.ptr(K1), kdt, _lib.ptr(rig),
+                                      max_iters, float(thr), float(conf), int(seed), _lib.ptr(pair_ids), _lib.ptr(counts),
+                                      _lib.ptr(inl), _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(st), _lib.ptr(mask),
+                                      _lib.ptr(bi), _lib.ptr(ir), _lib.stream_ptr()), "mfr_rig_pnp_ransac")
+    return dict(R=R, t=t, n_inliers=ni, status=st, mask=mask, best_iter=bi, iters_run=ir, counts=counts)
+
+
+class RigPnPBatchSolver(_Workspace):
+    """One pose (reference -> LAST window frame) for a rig of T query frames per sample, one C-ABI call (csrc/pnp_rig.hip).
+    pts0 / pts1 [B,T,maxN,2] f32, n_corr [B,T] i32, depth0 [B,H,W], K0 [B,3,3], K1_multi [B,T,3,3], rig_T [B,T,4,4] f64
+    (A_j: last frame's camera -> frame j's camera), pair_ids [B].  The mask is [B,T,maxN] over ORIGINAL correspondence indices."""
+
+    def __init__(self, max_iters=1000, reproj_thr=3.0, confidence=0.9999, seed=0):
+        self.max_iters = max(int(max_iters), 1)
+        self.reproj_thr = float(reproj_thr)
+        self.confidence = float(confidence)
+        self.seed = int(seed)
+
+    def __call__(self, pts0, pts1, n_corr, depth0, K0, K1_multi, rig_T, pair_ids, want_mask=False):
+        lib = _lib.load(require_gpu=True)
+        pts0 = _chk(pts0, torch.float32, "pts0"); pts1 = _chk(pts1, torch.float32, "pts1")
+        n_corr = _chk(n_corr, torch.int32, "n_corr")
+        if pts0.dim() != 4 or pts0.shape != pts1.shape or pts0.shape[-1] != 2:
+            raise ValueError(f"pts0 / pts1: expected [B,T,maxN,2], got {tuple(pts0.shape)} / {tuple(pts1.shape)}")
+        B, T, maxN, _ = pts0.shape
+        if not 1 <= T <= RIG_MAX_T:
+            raise ValueError(f"a rig holds 1..{RIG_MAX_T} frames, got T = {T}")
+        dev = pts0.device
+        depth0 = _chk(depth0, torch.float32, "depth0")
+        K0, K1, kdt = _chk_K(K0, K1_multi)
+        rig = rig_rows(rig_T)
+        pair_ids = _chk(pair_ids, torch.int64, "pair_ids")
+        if (tuple(n_corr.shape) != (B, T) or tuple(K1.shape) != (B, T, 3, 3) or tuple(rig.shape) != (B, T, 12)
+                or depth0.dim() != 3 or depth0.shape[0] != B or tuple(K0.shape) != (B, 3, 3) or tuple(pair_ids.shape) != (B,)):
+            raise ValueError("RigPnPBatchSolver: n_corr [B,T], K1_multi [B,T,3,3], rig_T [B,T,4,4], depth0 [B,H,W], K0 [B,3,3], "
+                             "pair_ids [B] must match pts0 [B,T,maxN,2]")
+        _, H, W = depth0.shape
+        ws = self._ws(lib.mfr_rig_pnp_workspace_bytes(B, T, maxN, self.max_iters), dev)
+        R, t, ni, st = _pose_out(B, dev)
+        mask = torch.empty(B, T, maxN, dtype=torch.uint8, device=dev) if want_mask else None
+        _lib.check(lib.mfr_rig_pnp_solve_batch(
+            _lib.ptr(pts0), _lib.ptr(pts1), _lib.ptr(n_corr), B, T, maxN, _lib.ptr(depth0), H, W, _lib.ptr(K0),
+            _lib.ptr(K1), kdt, _lib.ptr(rig), self.max_iters, self.reproj_thr, self.confidence, self.seed, _lib.ptr(pair_ids),
+            _lib.ptr(ws), ws.numel(), _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(st),
+            _lib.ptr(mask), _lib.stream_ptr()), "mfr_rig_pnp_solve_batch")
+        out = dict(R=R, t=t, n_inliers=ni, status=st)
+        if want_mask:
+            out["mask"] = mask
+        return out
+
+
 EMAT_SCORE = {"magsac": 0, "count": 1}      # MFR_EMAT_SCORE_* of include/mfr_hip.h
 MAGSAC_LUT_M = 2048
 

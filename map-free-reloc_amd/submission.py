@@ -74,7 +74,10 @@ def predict(loader, model):
         R, t = R.detach().cpu().numpy(), t.detach().cpu().numpy().reshape(-1)
         if not _has_pose(R, t):
             continue
-        results[data['scene_id'][0]].append(Pose(data['pair_names'][1][0], mat2quat(R).reshape(-1), t, data['inliers']))
+        name = data['pair_names'][1][0]
+        if isinstance(name, (tuple, list)):                     # a multi-frame sample: the pose is the LAST window frame's (pair_name())
+            name = name[-1]
+        results[data['scene_id'][0]].append(Pose(name, mat2quat(R).reshape(-1), t, data['inliers']))
     return results
 
 
