@@ -337,6 +337,12 @@ int mfr_gemm_f16x2_batched(const float *x, int ldx, long long x_batch_stride, co
 int mfr_conv_igemm_k(int Cin, int KH, int KW);
 int mfr_conv_igemm_f16x2(const float *x, const void *packed_w, const float *bias, float *y, int B, int Cin, int H, int W, int Cout, int KH, int KW,
                          int stride, int pad, int relu, void *stream);
+/*   mfr_conv_igemm_f16x2_pad   the same kernel behind an ASYMMETRIC zero padding: pad_lo rows / columns before the image, pad_hi after it (both axes), Ho =
+ *                          (H + pad_lo + pad_hi - KH) / stride + 1.  TF-"SAME" padding of DPT-Hybrid's BiT stem (`transformers` WeightStandardizedConv2d with
+ *                          padding="same": DynamicPad2d) on even sizes: (2, 3) for the 7x7 / 2 stem, (0, 1) for the 3x3 / 2 bottleneck convolutions.
+ *                          pad_lo == pad_hi is mfr_conv_igemm_f16x2 bit for bit. */
+int mfr_conv_igemm_f16x2_pad(const float *x, const void *packed_w, const float *bias, float *y, int B, int Cin, int H, int W, int Cout, int KH, int KW,
+                             int stride, int pad_lo, int pad_hi, int relu, void *stream);
 /*   mfr_conv_igemm_f16x2_upadd (round 6): the same convolution (no activation) + the FPN merge of LoFTR's backbone in one pass,
  *                          y = conv(x) + bias + F.interpolate(lo, scale_factor=2, mode='bilinear', align_corners=True) with lo [B,Cout,Hl,Wl], Ho = 2 Hl,
  *                          Wo = 2 Wl (upstream ResNetFPN_8_2.forward: x2_out = layer2_outconv(x2) + x3_out_2x, x1_out likewise; call site matchers.py:50);
@@ -776,6 +782,49 @@ int mfr_corr_warp_fwd(const float *q, const float *k, const float *v, const floa
 int mfr_corr_warp_bwd(const float *q, const float *k, const float *v, const float *grid, int B, int Dq, int N,
                       const float *d_warped, const float *d_pos, const float *d_max, const float *delta,
                       const float *row_max, const float *row_sum, float *dq, float *dk, float *dv, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * DPT-Hybrid monocular depth (Ranftl et al., "Vision Transformers for Dense Prediction", ICCV 2021), the kernels BETWEEN its matrix products
+ * (csrc/dpt.hip).  The architecture of record is `transformers.DPTForDepthEstimation` with is_hybrid=True (BiT ResNet-50 stem, ViT-Base,
+ * reassemble / fusion neck, depth head); the products are mfr_gemm_*, mfr_conv_igemm_f16x2, mfr_conv3x3_direct_f16x2 and mfr_sg_attention.
+ * fp32 storage and arithmetic.  Every argument check returns MFR_E_ARG before any launch; all pointers are device memory.
+ *   mfr_dpt_prep          img: dtype 0 = u8 [B,H,W,3] (value / 255), 1 = f32 [B,3,H,W] in [0, 1]  ->  out [B,3,Hn,Wn] =
+ *                         (F.interpolate(img, (Hn, Wn), 'bilinear', align_corners=False) - 0.5) / 0.5 with torch's arithmetic (source index
+ *                         scale (dst + 0.5) - 0.5 clamped at 0, scale = in / out in f32).  Hn, Wn multiples of 32.
+ *   mfr_dpt_groupnorm     y = GroupNorm(G, C)(x) [+ residual] [ReLU] over x [B,C,HW] (NCHW): BiT's BitGroupNormActivation, and with `residual` the
+ *                         bottleneck's tail relu(norm3(.) + shortcut).  Two-pass statistics, biased variance, rsqrt(var + eps).  y may alias x or residual.
+ *   mfr_dpt_maxpool3s2    3x3 / stride 2 max-pool of x [planes,H,W] padded with ZEROS by (pad_top, pad_bottom, pad_left, pad_right), each in 0..2 (BiT pads with
+ *                         0, then pools: the padding takes part in the maximum).  TF-"SAME" is (0, 1) on an even axis and (1, 1) on an odd one.
+ *                         y [planes,(H + pt + pb - 3) / 2 + 1,(W + pl + pr - 3) / 2 + 1].
+ *   mfr_dpt_layernorm     mfr_layernorm for any C that is a multiple of 64 (<= 1024): out[r] = [residual[r] +] LayerNorm(x[r]) gamma + beta, row strides
+ *                         ldx / ldr / ldo >= C; out may alias x or residual.  One wavefront per row, the row kept in registers.
+ *   mfr_dpt_bias_gelu     x [rows,N] (row stride ld; N, ld multiples of 4, 16-byte aligned) <- GELU_erf(x + bias) in place (bias may be NULL)
+ *   mfr_dpt_add_relu      s = a (+ b, may be NULL) over n floats (n % 4 == 0, 16-byte aligned): sum <- s (may be NULL), relu_out <- max(s, 0).  The fusion layer's
+ *                         `hidden + residual_layer1(residual)` together with the pre-activation ReLU of the residual unit that reads the sum (no ReLU pass of its own).
+ *   mfr_dpt_tokens        x [B,C,HW] (the patch projection's NCHW output) -> out [B,1 + HW,C] rows (row stride ldo, images (1 + HW) ldo apart):
+ *                         out[b][0] = cls + pos[0];  out[b][1 + p][c] = x[b][c][p] + pos[1 + p][c]  (pos [1 + HW,C]: resized to this grid by the caller)
+ *   mfr_dpt_tokens_inverse  out [B,C,HW] (NCHW) from rows: out[b][c][p] = act(rows[b img_stride + (skip + p) ld + c] + bias_img[b][c]); bias_img [B,C] or NULL
+ *                         (the readout projection's cls half, W_b cls + b, one vector per image), gelu 0 | 1; skip = 1 drops the cls row
+ *   mfr_dpt_shuffle       ConvTranspose2d(C, C, kernel = stride = s), s in {2, 4}, after its GEMM g [B H W, C s^2] (row stride ld, column (co s + i) s + j):
+ *                         out [B,C,H s,W s], out[b][co][h s + i][w s + j] = g[(b H + h) W + w][(co s + i) s + j] + bias[co]
+ *   mfr_dpt_head_tail     f [B,C,Hh,Wh] (C <= 64: the head's ReLU(conv3x3 . -> 32) output), w [C], bias: p = ReLU(w . f + bias); invert: p <- 1 / max(scale p + shift, 1e-8);
+ *                         metres [B,Ho,Wo] = F.interpolate(p, (Ho, Wo), 'bilinear', align_corners=False); mm (u16 [B,Ho,Wo] or NULL) = the exact product
+ *                         1000 metres rounded half to even, clamped to 0..65535 (NaN -> 0).  One pass over the full-resolution map.
+ * ------------------------------------------------------------------------------------------ */
+int mfr_dpt_prep(const void *img, int dtype, int B, int H, int W, float *out, int Hn, int Wn, void *stream);
+int mfr_dpt_groupnorm(const float *x, const float *gamma, const float *beta, const float *residual, int B, int C, int HW, int G, float eps, int relu,
+                      float *y, void *stream);
+int mfr_dpt_maxpool3s2(const float *x, int planes, int H, int W, int pad_top, int pad_bottom, int pad_left, int pad_right, float *y, void *stream);
+int mfr_dpt_layernorm(const float *x, int ldx, const float *gamma, const float *beta, const float *residual, int ldr, long long rows, int C, float eps,
+                      float *out, int ldo, void *stream);
+int mfr_dpt_bias_gelu(float *x, int ld, long long rows, int N, const float *bias, void *stream);
+int mfr_dpt_add_relu(const float *a, const float *b, long long n, float *sum, float *relu_out, void *stream);
+int mfr_dpt_tokens(const float *x, const float *cls, const float *pos, int B, int C, int HW, float *out, int ldo, void *stream);
+int mfr_dpt_tokens_inverse(const float *rows, int ld, long long img_stride, int skip, const float *bias_img, int gelu, int B, int C, int HW, float *out,
+                           void *stream);
+int mfr_dpt_shuffle(const float *g, int ld, const float *bias, int B, int C, int H, int W, int s, float *out, void *stream);
+int mfr_dpt_head_tail(const float *f, const float *w, float bias, int B, int C, int Hh, int Wh, int invert, float scale, float shift, int Ho, int Wo,
+                      float *metres, uint16_t *mm, void *stream);
 
 #ifdef __cplusplus
 }

@@ -53,6 +53,7 @@ SIGNATURES = {
     "mfr_gemm_f16x2_batched": (_i, [_vp, _i, C.c_longlong, _vp, _vp, _vp, _i, C.c_longlong, _i, _i, _i, _i, _i, _vp]),
     "mfr_conv_igemm_k": (_i, [_i, _i, _i]),
     "mfr_conv_igemm_f16x2": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "mfr_conv_igemm_f16x2_pad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mfr_conv_igemm_f16x2_upadd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mfr_gemm_f16x2_windows": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "mfr_gemm_bf16x3_windows": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
@@ -140,6 +141,16 @@ SIGNATURES = {
     "mfr_abs_pose_workspace_bytes": (_sz, [_i]),
     "mfr_test_abs_pose_subset": (_i, [_u64, _vp, _i, _i, _i, _i, _vp, _vp]),
     "mfr_abs_pose_fuse": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _d, _d, _i, _u64, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "mfr_dpt_prep": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "mfr_dpt_groupnorm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_float, _i, _vp, _vp]),
+    "mfr_dpt_maxpool3s2": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mfr_dpt_layernorm": (_i, [_vp, _i, _vp, _vp, _vp, _i, C.c_longlong, _i, C.c_float, _vp, _i, _vp]),
+    "mfr_dpt_bias_gelu": (_i, [_vp, _i, C.c_longlong, _i, _vp, _vp]),
+    "mfr_dpt_add_relu": (_i, [_vp, _vp, C.c_longlong, _vp, _vp, _vp]),
+    "mfr_dpt_tokens": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
+    "mfr_dpt_tokens_inverse": (_i, [_vp, _i, C.c_longlong, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "mfr_dpt_shuffle": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mfr_dpt_head_tail": (_i, [_vp, _vp, C.c_float, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp, _vp]),
 }
 
 

@@ -44,6 +44,10 @@ keys this implementation adds (declared here because unknown keys are rejected o
   SUPERGLUE.*        matcher hyper-parameters of record (matchers.py:65-71) and weight paths
   LIGHTGLUE.*        'LightGlue' feature matching: WEIGHTS (a state dict with the `transformers` LightGlue parameter names), FILTER_THRESHOLD,
                      NUM_LAYERS, SuperPoint's MAX_KEYPOINTS / KEYPOINT_THRESHOLD / NMS_RADIUS; DEPTH_CONFIDENCE / WIDTH_CONFIDENCE must stay -1
+  DPT.*              DPT-Hybrid monocular depth (nets/dpt.py, compute_depth.py): WEIGHTS (a state dict with the `transformers` DPTForDepthEstimation parameter
+                     names), NET_HEIGHT / NET_WIDTH (multiples of 32), SCALE / SHIFT / INVERT (depth = 1 / (SCALE p + SHIFT): the output convention of the
+                     KITTI / NYU checkpoints), QUANTIZE_MM (hand the solver the millimetre-rounded map, the bits a depth PNG holds),
+                     SOURCE 'file' (depth maps are read from the dataset, the default) | 'online' (FeatureMatchingModel computes them from the pair's images)
 """
 from .node import CfgNode as CN
 
@@ -108,6 +112,14 @@ def get_cfg_defaults():
     for k, v in dict(WEIGHTS='', FILTER_THRESHOLD=0.1, NUM_LAYERS=9, MAX_KEYPOINTS=1024, KEYPOINT_THRESHOLD=0.005, NMS_RADIUS=4,
                      DEPTH_CONFIDENCE=-1, WIDTH_CONFIDENCE=-1).items():
         c.LIGHTGLUE[k] = v
+    # DPT-Hybrid depth (nets/dpt.py).  SCALE / SHIFT / INVERT: dpt_hybrid_kitti's output convention (UPSTREAM-KNOWLEDGE: isl-org/DPT run_monodepth.py; NYU: 0.000305 /
+    # 0.1378 / True); synthetic weights (ALLOW_SYNTHETIC_WEIGHTS) come from nets/weights.dpt_state_dict(SYNTHETIC_SEED) and want INVERT False
+    c.DPT = CN()
+    for k, v in dict(WEIGHTS='', NET_HEIGHT=384, NET_WIDTH=512, SCALE=0.00006016, SHIFT=0.00579, INVERT=True, SOURCE='file', QUANTIZE_MM=True,
+                     SYNTHETIC_SEED=8642).items():
+        c.DPT[k] = v
+    from .dpt_arch import ARCH as _dpt_arch             # the architecture (DPT-Hybrid's values): BiT depths / widths / groups, ViT width / layers / heads, neck, taps
+    c.DPT.ARCH = CN({k: (list(v) if isinstance(v, tuple) else v) for k, v in _dpt_arch.items()})
     c.ALLOW_SYNTHETIC_WEIGHTS = False
     return c
 

@@ -1408,11 +1408,13 @@ int mfr_conv_igemm_k(int Cin, int KH, int KW)
 }
 
 static int gb_conv_igemm(const float *x, const void *packed_w, const float *bias, float *y, int B, int Cin, int H, int W, int Cout, int KH, int KW,
-                         int stride, int pad, int relu, const float *lo, int Hl, int Wl, void *stream)
+                         int stride, int pad, int pad_hi, int relu, const float *lo, int Hl, int Wl, void *stream)
 {
-    if (!x || !packed_w || !y || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0) return MFR_E_ARG;
+    // pad: zeros before the first row / column (what the kernel offsets its taps by); pad_hi: zeros after the last -- it only sets the output size, the
+    // kernel range-checks every tap against the image
+    if (!x || !packed_w || !y || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 || pad_hi < 0) return MFR_E_ARG;
     if ((size_t)4 * ((Cin + 31) / 32 * 32) * H * W >= 0x7fffffffull) return MFR_E_ARG;    // one image (padded channel count) must fit a 2 GB buffer descriptor
-    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
+    const int Ho = (H + pad + pad_hi - KH) / stride + 1, Wo = (W + pad + pad_hi - KW) / stride + 1;
     if (Ho <= 0 || Wo <= 0) return MFR_E_ARG;
     if ((size_t)4 * Cout * Ho * Wo >= 0x40000000ull) return MFR_E_ARG;                   // one output image < 1 GB: the epilogue's out-of-buffer offsets must not wrap
     if (lo && (relu || Cin == 1 || Hl <= 0 || Wl <= 0 || Ho != 2 * Hl || Wo != 2 * Wl)) return MFR_E_ARG;
@@ -1437,14 +1439,21 @@ static int gb_conv_igemm(const float *x, const void *packed_w, const float *bias
 int mfr_conv_igemm_f16x2(const float *x, const void *packed_w, const float *bias, float *y, int B, int Cin, int H, int W, int Cout, int KH, int KW,
                          int stride, int pad, int relu, void *stream)
 {
-    return gb_conv_igemm(x, packed_w, bias, y, B, Cin, H, W, Cout, KH, KW, stride, pad, relu, nullptr, 0, 0, stream);
+    return gb_conv_igemm(x, packed_w, bias, y, B, Cin, H, W, Cout, KH, KW, stride, pad, pad, relu, nullptr, 0, 0, stream);
+}
+
+// the same kernel behind an asymmetric zero padding (pad_lo before, pad_hi after, both axes): TF-"SAME" of DPT's BiT stem, (2, 3) for 7x7 / 2 and (0, 1) for 3x3 / 2
+int mfr_conv_igemm_f16x2_pad(const float *x, const void *packed_w, const float *bias, float *y, int B, int Cin, int H, int W, int Cout, int KH, int KW,
+                             int stride, int pad_lo, int pad_hi, int relu, void *stream)
+{
+    return gb_conv_igemm(x, packed_w, bias, y, B, Cin, H, W, Cout, KH, KW, stride, pad_lo, pad_hi, relu, nullptr, 0, 0, stream);
 }
 
 int mfr_conv_igemm_f16x2_upadd(const float *x, const void *packed_w, const float *bias, const float *lo, int Hl, int Wl, float *y, int B, int Cin, int H, int W,
                                int Cout, int KH, int KW, int stride, int pad, void *stream)
 {
     if (!lo) return MFR_E_ARG;
-    return gb_conv_igemm(x, packed_w, bias, y, B, Cin, H, W, Cout, KH, KW, stride, pad, 0, lo, Hl, Wl, stream);
+    return gb_conv_igemm(x, packed_w, bias, y, B, Cin, H, W, Cout, KH, KW, stride, pad, pad, 0, lo, Hl, Wl, stream);
 }
 
 }  // extern "C"

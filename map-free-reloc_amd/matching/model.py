@@ -52,10 +52,21 @@ class FeatureMatchingModel(torch.nn.Module):
         super().__init__()
         self.feature_matching = _lookup(FEATURE_MATCHERS, cfg.FEATURE_MATCHING, 'feature matching')(cfg)
         self.pose_solver = _lookup(POSE_SOLVERS, cfg.POSE_SOLVER, 'pose solver')(cfg)
+        self.depth = None
+        if 'DPT' in cfg and cfg.DPT.SOURCE != 'file':           # DPT.SOURCE 'online': the solver's depth maps come from the pair's images (nets/dpt.py)
+            from ..nets.dpt import DepthEstimator
+            self.depth = DepthEstimator(cfg)
 
     def forward(self, data):
         if data['depth0'].shape[0] != 1:
             raise AssertionError('Baseline models require batch size of 1')
+        # one batched call for both views, on the loader's images: the file resized to DATASET.WIDTH x HEIGHT.  compute_depth works on the file's own pixels, so the two
+        # routes give the solver the same bits only where that is the file's size (Map-free's frames and default)
+        if self.depth is not None:
+            if data['image0'].shape != data['image1'].shape:
+                raise ValueError('DPT.SOURCE online: the two views of a pair must have one size')
+            d = self.depth.metres(torch.cat([data['image0'], data['image1']]).to(torch.float32)).cpu()
+            data['depth0'], data['depth1'] = d[0:1], d[1:2]
         kpts0, kpts1 = self.feature_matching.get_correspondences(data)
         R, t, confidence = self.pose_solver.estimate_pose(kpts0, kpts1, data)
         data['inliers'] = confidence

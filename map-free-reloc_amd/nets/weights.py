@@ -173,6 +173,78 @@ def lightglue_state_dict(seed=9753, n_layers=9, proj_gain=10.0, match_bias=6.0):
     return sd
 
 
+def dpt_state_dict(seed=8642, arch=None, head_bias=3.0, pos_grid=24):
+    """DPT-Hybrid with the parameter names of `transformers.DPTForDepthEstimation` (is_hybrid=True); `arch`: nets/dpt.ARCH keys (None: DPT-Hybrid).
+    Activations stay O(1) through the whole network: BiT's convolutions are weight-standardised and every one is followed by a GroupNorm, the ViT is the
+    mild perturbation of its input that N(0, 0.02) weights make it, and the neck / head convolutions are He-scaled (the pre-activation residual units at a
+    third of that: sixteen of them add up).  The LAST layer's bias is lifted (the map reads as 1 - 5 metres): with a zero bias a third of the depth map sits at the
+    final ReLU's zero, where errors upstream of it do not show.  What this makes TRIVIAL: every norm is the identity affine map and every other bias (but the last) is zero;
+    tests/dpt_ref.perturbed moves them for the parity tests."""
+    from .dpt import check_arch
+    a = check_arch(arch)
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+
+    def conv(name, ci, co, k, gain=1.0, bias=True, std=None):
+        sd[f"{name}.weight"] = _randn(g, (co, ci, k, k), gain * (2.0 / (ci * k * k)) ** 0.5 if std is None else std)
+        if bias:
+            sd[f"{name}.bias"] = torch.zeros(co)
+
+    def norm(name, c):
+        sd[f"{name}.weight"], sd[f"{name}.bias"] = torch.ones(c), torch.zeros(c)
+
+    def lin(name, ci, co, std=0.02):
+        sd[f"{name}.weight"], sd[f"{name}.bias"] = _randn(g, (co, ci), std), torch.zeros(co)
+
+    h = a["VIT_WIDTH"]
+    sd["dpt.embeddings.cls_token"] = _randn(g, (1, 1, h), 0.02)
+    sd["dpt.embeddings.position_embeddings"] = _randn(g, (1, 1 + pos_grid * pos_grid, h), 0.02)
+    bit = "dpt.embeddings.backbone.bit"
+    conv(f"{bit}.embedder.convolution", 3, a["BIT_EMBEDDING_SIZE"], 7, bias=False)
+    norm(f"{bit}.embedder.norm", a["BIT_EMBEDDING_SIZE"])
+    prev = a["BIT_EMBEDDING_SIZE"]
+    for s, (depth, out) in enumerate(zip(a["BIT_DEPTHS"], a["BIT_HIDDEN_SIZES"])):
+        mid = out // 4
+        for l in range(depth):
+            p = f"{bit}.encoder.stages.{s}.layers.{l}"
+            if l == 0:
+                conv(f"{p}.downsample.conv", prev, out, 1, bias=False)
+                norm(f"{p}.downsample.norm", out)
+            conv(f"{p}.conv1", prev, mid, 1, bias=False); norm(f"{p}.norm1", mid)
+            conv(f"{p}.conv2", mid, mid, 3, bias=False); norm(f"{p}.norm2", mid)
+            conv(f"{p}.conv3", mid, out, 1, bias=False); norm(f"{p}.norm3", out)
+            prev = out
+    conv("dpt.embeddings.projection", prev, h, 1, std=prev ** -0.5)
+    for l in range(a["VIT_LAYERS"]):
+        p = f"dpt.encoder.layer.{l}"
+        for n in ("query", "key", "value"):
+            lin(f"{p}.attention.attention.{n}", h, h)
+        lin(f"{p}.attention.output.dense", h, h)
+        lin(f"{p}.intermediate.dense", h, a["VIT_MLP"])
+        lin(f"{p}.output.dense", a["VIT_MLP"], h)
+        norm(f"{p}.layernorm_before", h); norm(f"{p}.layernorm_after", h)
+    norm("dpt.layernorm", h)
+    ns, f = a["NECK_SIZES"], a["FUSION_WIDTH"]
+    for i in (2, 3):
+        conv(f"neck.reassemble_stage.layers.{i}.projection", h, ns[i], 1, std=h ** -0.5)
+    conv("neck.reassemble_stage.layers.3.resize", ns[3], ns[3], 3, std=(9 * ns[3]) ** -0.5)
+    for i in (2, 3):
+        lin(f"neck.reassemble_stage.readout_projects.{i}.0", 2 * h, h, std=(2 * h) ** -0.5)
+    for i in range(4):
+        conv(f"neck.convs.{i}", ns[i], f, 3, bias=False, std=(9 * ns[i]) ** -0.5)
+    for i in range(4):
+        p = f"neck.fusion_stage.layers.{i}"
+        conv(f"{p}.projection", f, f, 1, std=f ** -0.5)
+        for r in (1, 2):
+            for c in (1, 2):
+                conv(f"{p}.residual_layer{r}.convolution{c}", f, f, 3, gain=1.0 / 3.0)
+    conv("head.head.0", f, f // 2, 3)
+    conv("head.head.2", f // 2, 32, 3)
+    conv("head.head.4", 32, 1, 1, std=0.05)
+    sd["head.head.4.bias"] = torch.full((1,), float(head_bias))
+    return sd
+
+
 def load_checkpoint(path):
     """upstream .pth / .ckpt -> flat state dict.  superpoint_v1.pth / superglue_*.pth are plain state dicts;
     LoFTR's *_ot.ckpt are Lightning checkpoints that keep it under 'state_dict' with a `matcher.` prefix
