@@ -810,6 +810,14 @@ int mfr_corr_warp_bwd(const float *q, const float *k, const float *v, const floa
  *   mfr_dpt_head_tail     f [B,C,Hh,Wh] (C <= 64: the head's ReLU(conv3x3 . -> 32) output), w [C], bias: p = ReLU(w . f + bias); invert: p <- 1 / max(scale p + shift, 1e-8);
  *                         metres [B,Ho,Wo] = F.interpolate(p, (Ho, Wo), 'bilinear', align_corners=False); mm (u16 [B,Ho,Wo] or NULL) = the exact product
  *                         1000 metres rounded half to even, clamped to 0..65535 (NaN -> 0).  One pass over the full-resolution map.
+ * Row-table twins of the two ends, for a consumer whose images are scattered rows of a larger batch (the fused route's interleaved pairs, nets/dpt.py
+ * FusedDepthStage).  Added to ABI v6 without a version bump (purely additive); the tables are DEVICE memory and every entry is range-checked on the device:
+ *   mfr_dpt_prep_rows     img u8 [N,H,W,3], rows i32 [m]: out[j] [3,Hn,Wn] = mfr_dpt_prep(dtype 0) of img[rows[j]], the same bits.  rows[j] outside [0, N): nothing is
+ *                         read, out[j] is zeros and bit 0 of *status is set (an atomic OR; the caller clears the word).
+ *   mfr_dpt_head_tail_rows  f [B,C,Hh,Wh], src / dst i32 [d]: plane dst[k] of metres [D,Ho,Wo] (and of mm, u16 or NULL) = mfr_dpt_head_tail of f[src[k]], the same
+ *                         bits; one feature image may feed several planes, the dst entries must be distinct, planes not listed are not touched.  quantize 1: the
+ *                         metres written are float32(mm / 1000.0) with the division in double (the value a reader of the 16-bit PNG holding mm gets).  dst[k]
+ *                         outside [0, D): nothing is written; src[k] outside [0, B): the plane is zeros; either sets bit 0 of *status.
  * ------------------------------------------------------------------------------------------ */
 int mfr_dpt_prep(const void *img, int dtype, int B, int H, int W, float *out, int Hn, int Wn, void *stream);
 int mfr_dpt_groupnorm(const float *x, const float *gamma, const float *beta, const float *residual, int B, int C, int HW, int G, float eps, int relu,
@@ -825,6 +833,9 @@ int mfr_dpt_tokens_inverse(const float *rows, int ld, long long img_stride, int 
 int mfr_dpt_shuffle(const float *g, int ld, const float *bias, int B, int C, int H, int W, int s, float *out, void *stream);
 int mfr_dpt_head_tail(const float *f, const float *w, float bias, int B, int C, int Hh, int Wh, int invert, float scale, float shift, int Ho, int Wo,
                       float *metres, uint16_t *mm, void *stream);
+int mfr_dpt_prep_rows(const uint8_t *img, int N, const int *rows, int m, int H, int W, float *out, int Hn, int Wn, int *status, void *stream);
+int mfr_dpt_head_tail_rows(const float *f, const float *w, float bias, int B, int C, int Hh, int Wh, int invert, float scale, float shift, int Ho, int Wo,
+                           const int *src, const int *dst, int d, float *metres, uint16_t *mm, int D, int quantize, int *status, void *stream);
 
 #ifdef __cplusplus
 }

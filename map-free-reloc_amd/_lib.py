@@ -151,6 +151,8 @@ SIGNATURES = {
     "mfr_dpt_tokens_inverse": (_i, [_vp, _i, C.c_longlong, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "mfr_dpt_shuffle": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mfr_dpt_head_tail": (_i, [_vp, _vp, C.c_float, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp, _vp]),
+    "mfr_dpt_prep_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "mfr_dpt_head_tail_rows": (_i, [_vp, _vp, C.c_float, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
 }
 
 

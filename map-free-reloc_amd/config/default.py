@@ -47,7 +47,10 @@ keys this implementation adds (declared here because unknown keys are rejected o
   DPT.*              DPT-Hybrid monocular depth (nets/dpt.py, compute_depth.py): WEIGHTS (a state dict with the `transformers` DPTForDepthEstimation parameter
                      names), NET_HEIGHT / NET_WIDTH (multiples of 32), SCALE / SHIFT / INVERT (depth = 1 / (SCALE p + SHIFT): the output convention of the
                      KITTI / NYU checkpoints), QUANTIZE_MM (hand the solver the millimetre-rounded map, the bits a depth PNG holds),
-                     SOURCE 'file' (depth maps are read from the dataset, the default) | 'online' (FeatureMatchingModel computes them from the pair's images)
+                     SOURCE 'file' (depth maps are read from the dataset, the default) | 'online' (computed from the pair's images: by FeatureMatchingModel per
+                     pair, and on the fused route by nets/dpt.FusedDepthStage -- the loaders then carry the colour bytes and read no depth file, only the
+                     views the pose solver reads go through the network, and a scene's shared reference view once), FUSED_CHUNK (views per DPT launch on
+                     the fused route, >= 1; 16 is the batch tools/bench_dpt.py measured)
 """
 from .node import CfgNode as CN
 
@@ -116,7 +119,7 @@ def get_cfg_defaults():
     # 0.1378 / True); synthetic weights (ALLOW_SYNTHETIC_WEIGHTS) come from nets/weights.dpt_state_dict(SYNTHETIC_SEED) and want INVERT False
     c.DPT = CN()
     for k, v in dict(WEIGHTS='', NET_HEIGHT=384, NET_WIDTH=512, SCALE=0.00006016, SHIFT=0.00579, INVERT=True, SOURCE='file', QUANTIZE_MM=True,
-                     SYNTHETIC_SEED=8642).items():
+                     SYNTHETIC_SEED=8642, FUSED_CHUNK=16).items():
         c.DPT[k] = v
     from .dpt_arch import ARCH as _dpt_arch             # the architecture (DPT-Hybrid's values): BiT depths / widths / groups, ViT width / layers / heads, neck, taps
     c.DPT.ARCH = CN({k: (list(v) if isinstance(v, tuple) else v) for k, v in _dpt_arch.items()})

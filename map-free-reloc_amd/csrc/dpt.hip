@@ -31,12 +31,25 @@ MFR_DEV void bilinear_taps(int dst, float scale, int n_in, int &i0, int &i1, flo
 MFR_DEV float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
 
 // ---------------------------------------------------------------- prep
-template <bool U8>
-__global__ __launch_bounds__(256) void prep_kernel(const void *__restrict__ img, int H, int W, int Hn, int Wn, float sy, float sx, float *__restrict__ out)
+// ROWS (mfr_dpt_prep_rows): output image blockIdx.y is made from image rows[blockIdx.y] of the N the caller has; an index outside [0, N) is never
+// dereferenced: that output image is zeros and bit 0 of *status is set.  The arithmetic is this one body for both entries
+template <bool U8, bool ROWS>
+__global__ __launch_bounds__(256) void prep_kernel(const void *__restrict__ img, int H, int W, int Hn, int Wn, float sy, float sx, float *__restrict__ out,
+                                                   const int *__restrict__ rows, int N, int *status)
 {
-    const int b = blockIdx.y;
+    const int j = blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= Hn * Wn) return;
+    int b = j;
+    if (ROWS) {
+        b = rows[j];
+        if (b < 0 || b >= N) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[((size_t)j * 3 + c) * Hn * Wn + i] = 0.f;
+            if (i == 0) atomicOr(status, 1);
+            return;
+        }
+    }
     const int y = i / Wn, x = i - y * Wn;
     int y0, y1, x0, x1;
     float ly0, ly1, lx0, lx1;
@@ -54,8 +67,8 @@ __global__ __launch_bounds__(256) void prep_kernel(const void *__restrict__ img,
             v00 = p[(size_t)y0 * W + x0]; v01 = p[(size_t)y0 * W + x1];
             v10 = p[(size_t)y1 * W + x0]; v11 = p[(size_t)y1 * W + x1];
         }
-        const float v = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
-        out[((size_t)b * 3 + c) * Hn * Wn + i] = (v - 0.5f) / 0.5f;
+        const float v = fmaf(ly0, fmaf(lx0, v00, lx1 * v01), ly1 * fmaf(lx0, v10, lx1 * v11));      // (the fusions written out: see head_tail_kernel)
+        out[((size_t)j * 3 + c) * Hn * Wn + i] = (v - 0.5f) / 0.5f;
     }
 }
 
@@ -280,17 +293,35 @@ MFR_DEV float head_value(const float *__restrict__ f, size_t plane, size_t idx, 
     return a;
 }
 
-// one thread per pixel of the full-resolution map: the four taps' head values are computed where they are needed (the 1 / 32-size input stays in cache)
+// one thread per pixel of the full-resolution map: the four taps' head values are computed where they are needed (the 1 / 32-size input stays in cache).
+// ROWS (mfr_dpt_head_tail_rows): entry k = blockIdx.y of the tables reads feature image src[k] of the B the caller has and writes plane dst[k] of the D
+// it has; a dst outside [0, D) writes nothing, a src outside [0, B) zeroes its plane, and either sets bit 0 of *status.  quantize: the metres written are
+// float32(mm / 1000.0), the division in double -- datasets.read_depth_image's value of the 16-bit PNG that holds mm
+template <bool ROWS>
 __global__ __launch_bounds__(256) void head_tail_kernel(const float *__restrict__ f, const float *__restrict__ w, float bias, int C, int Hh, int Wh, int invert,
                                                         float scale, float shift, int Ho, int Wo, float sy, float sx, float *__restrict__ metres,
-                                                        uint16_t *__restrict__ mm)
+                                                        uint16_t *__restrict__ mm, const int *__restrict__ src, const int *__restrict__ dst, int B, int D,
+                                                        int quantize, int *status)
 {
     __shared__ float ws[HEAD_MAX_C];
     if (threadIdx.x < C) ws[threadIdx.x] = w[threadIdx.x];
     __syncthreads();
-    const int b = blockIdx.y;
+    int b = blockIdx.y, bo = blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= Ho * Wo) return;
+    if (ROWS) {
+        b = src[blockIdx.y];
+        bo = dst[blockIdx.y];
+        const bool bad_src = b < 0 || b >= B, bad_dst = bo < 0 || bo >= D;
+        if (bad_src || bad_dst) {
+            if (i == 0) atomicOr(status, 1);
+            if (!bad_dst) {
+                metres[(size_t)bo * Ho * Wo + i] = 0.f;
+                if (mm) mm[(size_t)bo * Ho * Wo + i] = 0;
+            }
+            return;
+        }
+    }
     const int y = i / Wo, x = i - y * Wo;
     int y0, y1, x0, x1;
     float ly0, ly1, lx0, lx1;
@@ -302,13 +333,17 @@ __global__ __launch_bounds__(256) void head_tail_kernel(const float *__restrict_
     const float v01 = head_value(fb, plane, (size_t)y0 * Wh + x1, ws, C, bias, invert, scale, shift);
     const float v10 = head_value(fb, plane, (size_t)y1 * Wh + x0, ws, C, bias, invert, scale, shift);
     const float v11 = head_value(fb, plane, (size_t)y1 * Wh + x1, ws, C, bias, invert, scale, shift);
-    const float v = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
-    const size_t o = (size_t)b * Ho * Wo + i;
-    metres[o] = v;
-    if (mm) {
+    // ly0 (lx0 v00 + lx1 v01) + ly1 (lx0 v10 + lx1 v11) with its three fused multiply-adds written out: left to -ffp-contract the compiler fused them in
+    // the plain kernel and not in the row-table one (packed multiplies, then an add), and the two entry points promise the same bits
+    const float v = fmaf(ly0, fmaf(lx0, v00, lx1 * v01), ly1 * fmaf(lx0, v10, lx1 * v11));
+    const size_t o = (size_t)bo * Ho * Wo + i;
+    if (!ROWS) metres[o] = v;
+    if (mm || ROWS) {
         // round-half-even of the EXACT product 1000 v (a 24-bit by a 10-bit factor is exact in double), clamped; NaN -> 0
         const double t = rint((double)v * 1000.0);
-        mm[o] = (uint16_t)(t >= 65535.0 ? 65535 : (t > 0.0 ? (int)t : 0));
+        const uint16_t q = (uint16_t)(t >= 65535.0 ? 65535 : (t > 0.0 ? (int)t : 0));
+        if (mm) mm[o] = q;
+        if (ROWS) metres[o] = quantize ? (float)((double)q / 1000.0) : v;
     }
 }
 
@@ -324,8 +359,8 @@ extern "C" int mfr_dpt_prep(const void *img, int dtype, int B, int H, int W, flo
     if ((long long)H * W * 3 > I31 || (long long)Hn * Wn * 3 > I31) return MFR_E_ARG;
     const float sy = (float)H / (float)Hn, sx = (float)W / (float)Wn;
     const dim3 grid(blocks256((long long)Hn * Wn), B);
-    if (dtype == 0) hipLaunchKernelGGL(prep_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, img, H, W, Hn, Wn, sy, sx, out);
-    else hipLaunchKernelGGL(prep_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, img, H, W, Hn, Wn, sy, sx, out);
+    if (dtype == 0) hipLaunchKernelGGL((prep_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, img, H, W, Hn, Wn, sy, sx, out, nullptr, 0, nullptr);
+    else hipLaunchKernelGGL((prep_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, img, H, W, Hn, Wn, sy, sx, out, nullptr, 0, nullptr);
     CHECK_LAUNCH();
     return 0;
 }
@@ -424,8 +459,33 @@ extern "C" int mfr_dpt_head_tail(const float *f, const float *w, float bias, int
     if (!f || !w || !metres || B < 1 || B > 65535 || C < 1 || C > HEAD_MAX_C || Hh < 1 || Wh < 1 || Ho < 1 || Wo < 1 || (invert != 0 && invert != 1)) return MFR_E_ARG;
     if ((long long)Hh * Wh * C > I31 || (long long)Ho * Wo > I31 || (invert && !(scale == scale && shift == shift))) return MFR_E_ARG;
     const float sy = (float)Hh / (float)Ho, sx = (float)Wh / (float)Wo;
-    hipLaunchKernelGGL(head_tail_kernel, dim3(blocks256((long long)Ho * Wo), B), dim3(256), 0, (hipStream_t)stream, f, w, bias, C, Hh, Wh, invert, scale, shift, Ho,
-                       Wo, sy, sx, metres, mm);
+    hipLaunchKernelGGL(head_tail_kernel<false>, dim3(blocks256((long long)Ho * Wo), B), dim3(256), 0, (hipStream_t)stream, f, w, bias, C, Hh, Wh, invert, scale, shift, Ho,
+                       Wo, sy, sx, metres, mm, nullptr, nullptr, B, B, 0, nullptr);
+    CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mfr_dpt_prep_rows(const uint8_t *img, int N, const int *rows, int m, int H, int W, float *out, int Hn, int Wn, int *status, void *stream)
+{
+    if (!img || !rows || !out || !status || N < 1 || m < 1 || m > 65535 || H < 1 || W < 1 || Hn < 32 || Wn < 32 || Hn % 32 || Wn % 32) return MFR_E_ARG;
+    if ((long long)H * W * 3 > I31 || (long long)Hn * Wn * 3 > I31) return MFR_E_ARG;
+    const float sy = (float)H / (float)Hn, sx = (float)W / (float)Wn;
+    hipLaunchKernelGGL((prep_kernel<true, true>), dim3(blocks256((long long)Hn * Wn), m), dim3(256), 0, (hipStream_t)stream, (const void *)img, H, W, Hn, Wn, sy, sx,
+                       out, rows, N, status);
+    CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mfr_dpt_head_tail_rows(const float *f, const float *w, float bias, int B, int C, int Hh, int Wh, int invert, float scale, float shift, int Ho, int Wo,
+                                      const int *src, const int *dst, int d, float *metres, uint16_t *mm, int D, int quantize, int *status, void *stream)
+{
+    if (!f || !w || !metres || !src || !dst || !status || B < 1 || D < 1 || d < 1 || d > 65535 || C < 1 || C > HEAD_MAX_C || Hh < 1 || Wh < 1 || Ho < 1 || Wo < 1)
+        return MFR_E_ARG;
+    if ((invert != 0 && invert != 1) || (quantize != 0 && quantize != 1)) return MFR_E_ARG;
+    if ((long long)Hh * Wh * C > I31 || (long long)Ho * Wo > I31 || (invert && !(scale == scale && shift == shift))) return MFR_E_ARG;
+    const float sy = (float)Hh / (float)Ho, sx = (float)Wh / (float)Wo;
+    hipLaunchKernelGGL(head_tail_kernel<true>, dim3(blocks256((long long)Ho * Wo), d), dim3(256), 0, (hipStream_t)stream, f, w, bias, C, Hh, Wh, invert, scale, shift,
+                       Ho, Wo, sy, sx, metres, mm, src, dst, B, D, quantize, status);
     CHECK_LAUNCH();
     return 0;
 }

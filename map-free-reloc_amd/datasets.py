@@ -234,6 +234,35 @@ def read_gray_plane(path, resize, out=None):
     return out
 
 
+def read_gray_rgb_plane(path, out_g, out_rgb):
+    """one decode of a file for the loaders that also carry the colour bytes (PairBatchLoader(rgb=True)): out_rgb [h, w, 3] u8 <- the decoded RGB bytes,
+    Image.open(path).convert("RGB"), and out_g [h, w] f32 <- read_gray_plane(path, None), the luma of those bytes.  The file must be at the planes' size"""
+    from PIL import Image
+    pim = Image.open(path)
+    if pim.mode != "RGB":
+        pim = pim.convert("RGB")
+    im = np.ascontiguousarray(np.asarray(pim))
+    if im.shape != out_rgb.shape:
+        raise NotImplementedError(f"{path}: a {im.shape[1]} x {im.shape[0]} file in a batch of {out_rgb.shape[1]} x {out_rgb.shape[0]} frames: the colour bytes "
+                                  f"(PairBatchLoader rgb=True, DPT.SOURCE 'online') are carried at the files' own size only")
+    out_rgb[...] = im
+    lib = _host_lib()
+    if lib is None:
+        return gray_plane(im, None, out_g)
+    assert out_g.dtype == np.float32 and out_g.shape == im.shape[:2] and out_g.flags["C_CONTIGUOUS"]
+    lib.mfr_host_gray_from_rgb(im.ctypes.data, im.shape[0] * im.shape[1], _luts()[0].ctypes.data, out_g.ctypes.data)
+    return out_g
+
+
+def rgb_bytes(img):
+    """[3, H, W] float image of the loaders (byte / 255 per channel) -> the bytes [H, W, 3] u8, exactly: rint(x * 255)"""
+    a = img.detach().cpu().numpy() if isinstance(img, torch.Tensor) else np.asarray(img)
+    if a.ndim != 3 or a.shape[0] != 3:
+        raise NotImplementedError(f"colour bytes of an image of shape {tuple(a.shape)}: single [3, H, W] frames only (multi-frame samples are not batched)")
+    u8 = np.clip(np.rint(a.astype(np.float32, copy=False) * np.float32(255)), 0, 255).astype(np.uint8)
+    return np.ascontiguousarray(np.moveaxis(u8, 0, -1))
+
+
 def read_depth_plane(path, out=None):
     """read_depth_image as a numpy array (into `out` when given): float32(v / 1000.0), tabulated once for the 65 536 possible values"""
     from PIL import Image
@@ -428,6 +457,31 @@ class MapFreeScene:
         g0, d0 = self._gray_frame(p1, keep=True, out_g=og0 if want_ref else None, out_d=od0, reader=r0, depth_reader=dr0)
         g1, d1 = self._gray_frame(p2, out_g=og1, out_d=od1, reader=r1, depth_reader=dr1)
         return (g0 if want_ref else None, d0, g1, d1, self.K[p1].copy(), self.K[p2].copy(), index * self.sample_factor, (p1, p2))
+
+    def frame_hw(self, index):
+        """(H, W) of pair `index`'s planes without decoding anything: the configured size, else the reference file's header"""
+        if self.resize is not None:
+            return int(self.resize[1]), int(self.resize[0])
+        from PIL import Image
+        sa, ia, _, _ = self.pairs[index]
+        with Image.open(os.path.join(self.scene_root, f"seq{sa}/frame_{ia:05}.jpg")) as im:
+            return int(im.size[1]), int(im.size[0])
+
+    def gray_rgb_pair(self, index, want_ref=True, out=None, readers=None):
+        """gray_pair for the loaders that carry the colour bytes INSTEAD of depth maps (PairBatchLoader(rgb=True): DPT.SOURCE 'online'): out = (g0, c0, g1, c1),
+        the gray [h, w] f32 and colour [h, w, 3] u8 destinations of the two frames, each file decoded once into both (read_gray_rgb_plane); no depth file is
+        opened.  want_ref False: the reference view is another row's (the caller copies it).  readers = (reader0, reader1): callables (path, out_g, out_rgb)
+        that take the place of read_gray_rgb_plane (the device JPEG route).  -> (K0, K1, pair_id, (name0, name1)), or None where gray_pair gives None"""
+        if self.black_white or not self.resize_is_native():
+            return None
+        sa, ia, sb, ib = self.pairs[index]
+        p1, p2 = f"seq{sa}/frame_{ia:05}.jpg", f"seq{sb}/frame_{ib:05}.jpg"
+        g0, c0, g1, c1 = out
+        r0, r1 = readers if readers is not None else (None, None)
+        if want_ref:
+            (r0 or read_gray_rgb_plane)(os.path.join(self.scene_root, p1), g0, c0)
+        (r1 or read_gray_rgb_plane)(os.path.join(self.scene_root, p2), g1, c1)
+        return (self.K[p1].copy(), self.K[p2].copy(), index * self.sample_factor, (p1, p2))
 
     def __getitem__(self, index):
         from . import evaluation as E
@@ -673,6 +727,33 @@ def _jpeg_reader(hdr, rec, row, info):
     return read
 
 
+def _jpeg_rgb_reader(hdr, rec, row, info):
+    """_jpeg_reader for the loaders that also carry the colour bytes (gray_rgb_pair's reader: (path, out_g, out_rgb)): the device writes both planes
+    of a file it takes; the host fall-back fills both here"""
+    def read(path, out_g, out_rgb):
+        from . import jpeg_ops as J
+        with open(path, "rb") as f:
+            data = f.read()
+        st, nb = J.parse_into(data, hdr[row], rec[row])
+        if st == J.OK:
+            info[row] = (0, nb, path)
+        else:
+            read_gray_rgb_plane(path, out_g, out_rgb)
+            info[row] = (st, 0, path)
+        return out_g
+    return read
+
+
+def _rgb_refusal(sc):
+    """why PairBatchLoader(rgb=True) cannot serve scene `sc` (None: it can): the colour bytes are carried for single-frame pairs at the files' own size"""
+    if getattr(sc, "query_frames", None):
+        return "multi-frame samples are not batched with their colour bytes"
+    native = getattr(sc, "resize_is_native", None)
+    if hasattr(sc, "batch_layout") or (getattr(sc, "resize", None) is not None and not (callable(native) and native())):
+        return "its files are not at the batch's size (a resizing reader)"
+    return None
+
+
 DEPTH_DECODE_MODES = ("host", "device")
 
 
@@ -753,7 +834,13 @@ def _jpeg_views(jflat, n_slots, B, cap):
             for k in range(n_slots)]
 
 
-def _pw_init(scenes, flat, layout, jflat=None, jcap=0, png=False):
+def _rgb_views(cflat, n_slots, B, Hh, Ww):
+    """per slot: the colour bytes u8 [2B, Hh, Ww, 3] of PairBatchLoader(rgb=True), out of one shared byte tensor"""
+    per = 2 * B * Hh * Ww * 3
+    return [cflat[k * per:(k + 1) * per].view(2 * B, Hh, Ww, 3) for k in range(n_slots)]
+
+
+def _pw_init(scenes, flat, layout, jflat=None, jcap=0, png=False, cflat=None):
     # Everything inherited from the parent becomes permanent in this process: a garbage-collection pass of the child must never finalise the
     # PARENT's objects -- a dead multiprocessing.Pool of an earlier loader among them, whose __del__ writes to a queue under a lock that a
     # thread of the parent may have held at fork time (the child then waits for it for ever: round 5's first full CPU test run hung exactly
@@ -764,6 +851,34 @@ def _pw_init(scenes, flat, layout, jflat=None, jcap=0, png=False):
     _PW["scenes"], _PW["slots"] = scenes, _slot_views(flat, *layout)
     _PW["jslots"] = _jpeg_views(jflat, layout[0], layout[1], jcap) if jflat is not None else None
     _PW["png"] = bool(png)
+    _PW["cslots"] = _rgb_views(cflat, *layout[:4]) if cflat is not None else None
+
+
+def _pw_fill_rgb(task):
+    """_pw_fill for a loader that carries the colour bytes instead of depth maps: gray plane and RGB bytes of each frame from ONE decode"""
+    import time as _t
+    t0 = _t.perf_counter()
+    k, p, si, i, want_ref = task
+    sc = _PW["scenes"][si]
+    im, col = _PW["slots"][k]["images"].numpy(), _PW["cslots"][k].numpy()
+    if getattr(sc, "has_gray_pair", False) and hasattr(sc, "gray_rgb_pair"):
+        info, readers = {}, None
+        if _PW["jslots"] is not None:
+            hdr, rec = (t.numpy() for t in _PW["jslots"][k])
+            readers = (_jpeg_rgb_reader(hdr, rec, 2 * p, info), _jpeg_rgb_reader(hdr, rec, 2 * p + 1, info))
+        fast = sc.gray_rgb_pair(i, want_ref, out=(im[2 * p, 0], col[2 * p], im[2 * p + 1, 0], col[2 * p + 1]), readers=readers)
+        if fast is not None:
+            K0, K1, pid, (n0, n1) = fast
+            return (np.asarray(K0), np.asarray(K1), int(pid), n1, n0, _t.perf_counter() - t0, info, {})
+    smp = sc[i]
+    npv = lambda t: t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    col[2 * p + 1] = rgb_bytes(smp["image1"])
+    im[2 * p + 1, 0] = npv(to_gray(smp["image1"]))
+    if want_ref:
+        col[2 * p] = rgb_bytes(smp["image0"])
+        im[2 * p, 0] = npv(to_gray(smp["image0"]))
+    return (np.asarray(smp["K_color0"]), np.asarray(smp["K_color1"]), int(smp["pair_id"]), smp["pair_names"][1], smp["pair_names"][0],
+            _t.perf_counter() - t0, {}, {})
 
 
 def _pw_fill(task):
@@ -807,7 +922,7 @@ class _ProcessDecoder:
     """pool of decode processes + ring of shared-memory batch slots (see above).  A slot is reused only after the H2D copies issued from it
     have completed (DevicePrefetcher stores its event in `events[k]`)."""
 
-    def __init__(self, scenes, B, Hh, Ww, has_depth, workers, n_slots, pin, jpeg_cap=0, png=False):
+    def __init__(self, scenes, B, Hh, Ww, has_depth, workers, n_slots, pin, jpeg_cap=0, png=False, rgb=False):
         import torch.multiprocessing as mp
         layout = (n_slots, B, Hh, Ww, has_depth)
         per = 2 * B * Hh * Ww + (2 * B * Hh * Ww if has_depth else 0)
@@ -818,12 +933,18 @@ class _ProcessDecoder:
             from .jpeg_ops import HEADER_BYTES
             self.jflat = torch.empty(n_slots * 2 * B * (HEADER_BYTES + jpeg_cap), dtype=torch.uint8).share_memory_()
             self.jslots = _jpeg_views(self.jflat, n_slots, B, jpeg_cap)
+        self.cflat, self.cslots = None, None
+        if rgb:                                                # the colour bytes (PairBatchLoader(rgb=True)): a u8 plane per row, one more shared segment
+            self.cflat = torch.empty(n_slots * 2 * B * Hh * Ww * 3, dtype=torch.uint8).share_memory_()
+            self.cslots = _rgb_views(self.cflat, n_slots, B, Hh, Ww)
         self.events = [None] * n_slots
-        self.pinned = self.jpinned = False
+        self.pinned = self.jpinned = self.cpinned = False
         if pin and torch.cuda.is_available():
             self.pinned = int(torch.cuda.cudart().cudaHostRegister(self.flat.data_ptr(), self.flat.numel() * 4, 0)) == 0
             if self.jflat is not None:
                 self.jpinned = int(torch.cuda.cudart().cudaHostRegister(self.jflat.data_ptr(), self.jflat.numel(), 0)) == 0
+            if self.cflat is not None:
+                self.cpinned = int(torch.cuda.cudart().cudaHostRegister(self.cflat.data_ptr(), self.cflat.numel(), 0)) == 0
         # the look-up tables and the C helper are set up BEFORE the fork (inherited, not rebuilt per worker), and cyclic garbage of earlier
         # loaders (their pools) is finalised here, in the parent, not in a child (see _pw_init)
         import gc
@@ -832,7 +953,7 @@ class _ProcessDecoder:
         # FORK, like torch's DataLoader workers: the children inherit the scene objects and the shared segment without re-importing anything
         # (spawned workers each re-imported torch: 36 s to start 32 of them under a 16-CPU container quota, tools/bench_fused_split.py) and
         # never touch the HIP runtime -- they run PIL / zlib / numpy only
-        self.pool = mp.get_context("fork").Pool(workers, initializer=_pw_init, initargs=(scenes, self.flat, layout, self.jflat, jpeg_cap, png))
+        self.pool = mp.get_context("fork").Pool(workers, initializer=_pw_init, initargs=(scenes, self.flat, layout, self.jflat, jpeg_cap, png, self.cflat))
         self.next = 0
 
     def acquire(self):
@@ -855,6 +976,9 @@ class _ProcessDecoder:
         if self.jpinned:
             torch.cuda.cudart().cudaHostUnregister(self.jflat.data_ptr())
             self.jpinned = False
+        if self.cpinned:
+            torch.cuda.cudart().cudaHostUnregister(self.cflat.data_ptr())
+            self.cpinned = False
 
 
 class PairBatchLoader:
@@ -870,7 +994,7 @@ class PairBatchLoader:
     this batch), scene_id / scene_root / last_of_scene (of the batch's last pair, kept for single-scene consumers))."""
 
     def __init__(self, scenes, batch_pairs=32, prefetch=2, pin=None, global_offsets=None, workers=8, span_scenes=True, decode="thread",
-                 jpeg_decode="host", jpeg_cap=JPEG_RECORD_CAP, depth_decode="host"):
+                 jpeg_decode="host", jpeg_cap=JPEG_RECORD_CAP, depth_decode="host", rgb=False):
         """workers: decode threads per batch (PIL / zlib / numpy release the GIL): a pair is two JPEGs + one or two 16-bit PNGs,
         ~12 ms of decode on one core, so one thread feeds ~80 pairs/s where the fused pipeline consumes ~700.
         jpeg_decode 'device' (HIP.JPEG_DECODE): on the fast route (gray_pair: MapFreeScene files at their own size) the workers only parse
@@ -880,8 +1004,19 @@ class PairBatchLoader:
         IDAT chunks of each 16-bit depth PNG into its record, written into the row's own depth0 / depth1 plane (no larger ring), and the batch
         carries the headers and the row table under "png"; DevicePrefetcher copies the records and decodes them on the GPU (png_ops).  A
         scene's shared reference depth is decoded once per batch and duplicated on the device.  Files the device does not take are decoded
-        on the host into the same row."""
+        on the host into the same row.
+        rgb=True (submission.predict_fused: DPT.SOURCE 'online' with a solver that reads depth): the batch also carries `rgb`, u8 [2b, H, W, 3] interleaved like
+        `images` -- the decoded RGB bytes of each file, Image.open(path).convert("RGB"), from the same decode as its gray plane -- and NO depth: depth0 / depth1
+        are None, no depth file is opened (a tree without them works) and depth_decode is moot.  Every route carries it: thread and process decode, the generic
+        per-sample route (the bytes are recovered from the byte / 255 floats) and the device JPEG route (the decode launch writes both planes).  Single-frame
+        pairs at the files' own size only: a resizing reader or a multi-frame scene raises NotImplementedError here.  rgb=False: the batch is what it was."""
         self.scenes, self.B, self.prefetch = list(scenes), int(batch_pairs), int(prefetch)
+        self.rgb = bool(rgb)
+        if self.rgb:
+            for sc in self.scenes:
+                why = _rgb_refusal(sc)
+                if why:
+                    raise NotImplementedError(f"PairBatchLoader(rgb=True), scene {getattr(sc, 'scene_id', '?')!r}: {why}")
         self.workers = max(1, int(workers))
         self._pool = None
         if decode not in ("thread", "process"):
@@ -939,8 +1074,12 @@ class PairBatchLoader:
         # (a scene that states its planes' layout -- batch_layout() -> (H, W, has depth): scannet.ScanNetScene -- is not asked for a generic
         # sample at all: its generic sample resizes the 8-bit RGB image, a different plane from gray_pair's whenever a resize happens)
         layout = getattr(self.scenes[items[0][0]], "batch_layout", None)
+        if self.rgb and hasattr(self.scenes[items[0][0]], "gray_rgb_pair"):      # no generic sample: it would open the depth files this route does without
+            sc0 = self.scenes[items[0][0]]
+            layout = lambda: (*sc0.frame_hw(items[0][1]), False)
         first = get(items[0]) if layout is None else None
         Hh, Ww, has_depth = layout() if layout is not None else (*first["image0"].shape[-2:], first["depth0"].numel() > 0)
+        has_depth = has_depth and not self.rgb                 # the colour bytes take the depth maps' place
         mk = (lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, pin_memory=True)) if self.pin else \
              (lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype))
         images = mk(2 * b, 1, Hh, Ww)
@@ -957,8 +1096,35 @@ class PairBatchLoader:
         png = self.depth_decode == "device" and has_depth
         first_of, want_ref = self._ref_plan(items)
         pinfos = [{} for _ in range(b)]
+        colour = mk(2 * b, Hh, Ww, 3, dtype=torch.uint8) if self.rgb else None
+        c_np = colour.numpy() if self.rgb else None
+        dups = []                                              # rgb route: pairs whose reference planes are host copies of another row's
+
+        def fill_rgb(p, smp=None):
+            """fill() of a batch that carries the colour bytes: both planes of a frame from one decode, a shared reference view once per batch"""
+            sc_ = self.scenes[items[p][0]]
+            if smp is None and getattr(sc_, "has_gray_pair", False) and hasattr(sc_, "gray_rgb_pair"):
+                readers = None
+                if jp is not None:
+                    h_np, r_np = jp["headers"].numpy(), jp["records"].numpy()
+                    readers = (_jpeg_rgb_reader(h_np, r_np, 2 * p, jp["rows"]), _jpeg_rgb_reader(h_np, r_np, 2 * p + 1, jp["rows"]))
+                fast = sc_.gray_rgb_pair(items[p][1], want_ref[p], out=(im_np[2 * p, 0], c_np[2 * p], im_np[2 * p + 1, 0], c_np[2 * p + 1]), readers=readers)
+                if fast is not None:
+                    if not want_ref[p]:
+                        if jp is not None:
+                            jp["rows"][2 * p] = ("dup", 2 * first_of[p])
+                        else:
+                            dups.append(p)
+                    K0_, K1_, pid, (n0, n1) = fast
+                    return (torch.as_tensor(K0_), torch.as_tensor(K1_), int(pid), n1, n0)
+            smp = get(items[p]) if smp is None else smp
+            c_np[2 * p], c_np[2 * p + 1] = rgb_bytes(smp["image0"]), rgb_bytes(smp["image1"])
+            im_np[2 * p, 0], im_np[2 * p + 1, 0] = npv(to_gray(smp["image0"])), npv(to_gray(smp["image1"]))
+            return (torch.as_tensor(smp["K_color0"]), torch.as_tensor(smp["K_color1"]), int(smp["pair_id"]), smp["pair_names"][1], smp["pair_names"][0])
 
         def fill(p, smp=None):
+            if self.rgb:
+                return fill_rgb(p, smp)
             sc_ = self.scenes[items[p][0]]
             if smp is None and getattr(sc_, "has_gray_pair", False):      # gray planes / depth straight from the files' bytes into the batch buffers
                 want, readers, kw = True, None, {}
@@ -993,6 +1159,8 @@ class PairBatchLoader:
             meta = [fill(0, first)] + [f.result() for f in futs]             # order preserved
         else:
             meta = [fill(0, first)] + [fill(p) for p in range(1, b)]
+        for p in dups:
+            np.copyto(im_np[2 * p, 0], im_np[2 * first_of[p], 0]); np.copyto(c_np[2 * p], c_np[2 * first_of[p]])
         # intrinsics keep the loader's dtype (float64 on Map-free, float32 on resize=None datasets): the solvers evaluate
         # inv(K) / the K-normalisation in that dtype, as the reference does (include/mfr_hip.h k_dtype)
         kdt = torch.float64 if any(m[0].dtype == torch.float64 or m[1].dtype == torch.float64 for m in meta) else torch.float32
@@ -1004,6 +1172,8 @@ class PairBatchLoader:
         extra = {} if jp is None else dict(jpeg=dict(headers=jp["headers"], records=jp["records"], rows=jp["rows"]))
         if png:
             extra["png"] = _png_rows(b, want_ref, first_of, pinfos, mk)
+        if self.rgb:
+            extra["rgb"] = colour
         return dict(images=images, depth0=depth0, depth1=depth1, K0=K0, K1=K1, **extra,
                     seed_ids=torch.tensor([m[2] for m in meta], dtype=torch.int64),
                     global_ids=torch.tensor([self.offsets[si] + i for si, i in items], dtype=torch.int64),
@@ -1063,14 +1233,17 @@ class PairBatchLoader:
         if self._proc is None:
             t0 = _t.perf_counter()
             layout = getattr(self.scenes[items[0][0]], "batch_layout", None)
+            if self.rgb and hasattr(self.scenes[items[0][0]], "gray_rgb_pair"):
+                sc0 = self.scenes[items[0][0]]
+                layout = lambda: (*sc0.frame_hw(items[0][1]), False)
             if layout is not None:
                 Hh, Ww, has_depth = layout()
             else:
                 first = self.scenes[items[0][0]][items[0][1]]
                 (Hh, Ww), has_depth = first["image0"].shape[-2:], first["depth0"].numel() > 0
-            self._proc = _ProcessDecoder(self.scenes, self.B, Hh, Ww, has_depth, self.workers, max(self.prefetch, 0) + 4, self.pin,
+            self._proc = _ProcessDecoder(self.scenes, self.B, Hh, Ww, has_depth and not self.rgb, self.workers, max(self.prefetch, 0) + 4, self.pin,
                                          jpeg_cap=self.jpeg_cap if self.jpeg_decode == "device" else 0,
-                                         png=self.depth_decode == "device")
+                                         png=self.depth_decode == "device", rgb=self.rgb)
             self._pool_map(_pw_ping, range(self.workers * 2))                          # every worker has started and imported its modules
             st["process_pool_start_s"] = _t.perf_counter() - t0
         pr = self._proc
@@ -1085,7 +1258,7 @@ class PairBatchLoader:
             key = si if getattr(self.scenes[si], "shared_reference", False) else ("pair", p)
             want.append(key not in first_of)
             first_of.setdefault(key, p)
-        meta = self._pool_map(_pw_fill, [(k, p, si, i, want[p]) for p, (si, i) in enumerate(items)])
+        meta = self._pool_map(_pw_fill_rgb if self.rgb else _pw_fill, [(k, p, si, i, want[p]) for p, (si, i) in enumerate(items)])
         jp = None
         if pr.jslots is not None:
             jp = self._jpeg_batch(items, slot=pr.jslots[k])
@@ -1103,6 +1276,8 @@ class PairBatchLoader:
             if not want[p] and (jp is None or jp["rows"][2 * p] is None):
                 q = first_of[si]
                 np.copyto(im[2 * p, 0], im[2 * q, 0])
+                if self.rgb:
+                    np.copyto(pr.cslots[k].numpy()[2 * p], pr.cslots[k].numpy()[2 * q])
         st["ref_copy_s"] = st.get("ref_copy_s", 0.0) + _t.perf_counter() - t0
         K0 = torch.stack([torch.as_tensor(m[0]) for m in meta]); K1 = torch.stack([torch.as_tensor(m[1]) for m in meta])
         sc = self.scenes[items[-1][0]]
@@ -1112,6 +1287,8 @@ class PairBatchLoader:
         if self.depth_decode == "device" and has_depth:
             mk = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, pin_memory=bool(self.pin and torch.cuda.is_available()))
             extra["png"] = _png_rows(b, want, [first_of[items[p][0]] if not want[p] else p for p in range(b)], [m[7] for m in meta], mk)
+        if self.rgb:
+            extra["rgb"] = pr.cslots[k][:2 * b]
         return dict(images=sl["images"][:2 * b], depth0=sl["depth0"][:b] if has_depth else None, depth1=sl["depth1"][:b] if has_depth else None,
                     K0=K0, K1=K1, **extra, seed_ids=torch.tensor([m[2] for m in meta], dtype=torch.int64),
                     global_ids=torch.tensor([self.offsets[si] + i for si, i in items], dtype=torch.int64),
@@ -1180,7 +1357,7 @@ class DevicePrefetcher:
                 raise MfrLibraryError(f"the device {'JPEG' if 'jpeg' in hb else 'depth PNG'} route needs a HIP device (there is no CPU fallback)")
             return dict(hb), None, None
         with torch.cuda.stream(self.stream):
-            skip = ("_slot",) + (("jpeg", "images") if "jpeg" in hb else ()) + (("png", "depth0", "depth1") if "png" in hb else ())
+            skip = ("_slot",) + (("jpeg", "images", "rgb") if "jpeg" in hb else ()) + (("png", "depth0", "depth1") if "png" in hb else ())
             db = {k: (v.to(self.device, non_blocking=True) if isinstance(v, torch.Tensor) else v) for k, v in hb.items() if k not in skip}
             check = [c for c in (self._put_jpeg(hb, db) if "jpeg" in hb else None, self._put_png(hb, db) if "png" in hb else None) if c is not None]
             ev = torch.cuda.Event(); ev.record(self.stream)
@@ -1200,10 +1377,14 @@ class DevicePrefetcher:
         n2, (H, W) = images.shape[0], images.shape[-2:]
         rows = jp["rows"]
         d_img = torch.empty((n2, 1, H, W), dtype=torch.float32, device=self.device)
+        colour = hb.get("rgb")                                  # PairBatchLoader(rgb=True): the decode launch writes the RGB bytes next to the gray planes
+        d_rgb = torch.empty((n2, H, W, 3), dtype=torch.uint8, device=self.device) if colour is not None else None
         dev_rows = [r for r in range(n2) if rows[r] is not None and rows[r][0] == 0]
         for r in range(n2):
             if rows[r] is None or (rows[r][0] not in ("dup", 0)):
                 d_img[r].copy_(images[r], non_blocking=True)
+                if d_rgb is not None:
+                    d_rgb[r].copy_(colour[r], non_blocking=True)
         h_status = None
         if dev_rows:
             if self._jdec is None:
@@ -1222,7 +1403,9 @@ class DevicePrefetcher:
             d_st = torch.zeros(n2, dtype=torch.int32, device=self.device)
             fH, fW = (int(v) for v in hdr.numpy()[dev_rows[0], 4:12].view(np.int32)[::-1])     # mfr_jpeg_header: status, width, height
             if (fH, fW) == (H, W):
-                self._jdec.decode_device(d_hdr, d_rec, d_off, n2, H, W, cap, d_img, d_st)
+                self._jdec.decode_device(d_hdr, d_rec, d_off, n2, H, W, cap, d_img, d_st, d_rgb)
+            elif d_rgb is not None:
+                raise NotImplementedError(f"{rows[dev_rows[0]][2]}: a {fW} x {fH} file in a batch of {W} x {H} frames: the colour bytes are carried at the files' own size only")
             else:                                                   # (a row of yet another size reports E_SIZE, as on the plain route)
                 scratch = torch.empty((n2, fH, fW, 3), dtype=torch.uint8, device=self.device)
                 self._jdec.decode_device(d_hdr, d_rec, d_off, n2, fH, fW, cap, None, d_st, scratch)
@@ -1235,7 +1418,11 @@ class DevicePrefetcher:
         for r in range(n2):
             if rows[r] is not None and rows[r][0] == "dup":
                 d_img[r].copy_(d_img[rows[r][1]], non_blocking=True)
+                if d_rgb is not None:
+                    d_rgb[r].copy_(d_rgb[rows[r][1]], non_blocking=True)
         db["images"] = d_img
+        if d_rgb is not None:
+            db["rgb"] = d_rgb
         return (h_status, [(r, rows[r][2]) for r in dev_rows], "JPEG") if dev_rows else None
 
     def _put_png(self, hb, db):

@@ -82,7 +82,8 @@ class FeatureMatchingMultiFrameModel(torch.nn.Module):
     gray planes with T equal `ref_keys`, so SuperPoint / LoFTR's backbone runs once on the reference view (HIP.REF_FEATURE_CACHE, forced on
     here).  'Precomputed' reads the ordinary single-frame correspondences_*.npz: the row of a window frame is its position among the seq1
     frames of poses.txt, as wire.py writes it.  Then solver_ops.RigPnPBatchSolver.  A sample without `rig_T` (no poses_device.txt in the
-    scene) is an error: there is no silent fall-back to the last frame alone."""
+    scene) is an error: there is no silent fall-back to the last frame alone.  With DPT.SOURCE 'online' the reference view's depth map is computed by the
+    fused route's depth stage (nets/dpt.FusedDepthStage), once per distinct reference view."""
     MATCHERS = ('SuperGlue', 'LightGlue', 'LoFTR', 'SIFT', 'Precomputed')
 
     def __init__(self, cfg):
@@ -99,6 +100,7 @@ class FeatureMatchingMultiFrameModel(torch.nn.Module):
         self.cfg.HIP.GRAPH_FUSED = False                        # the captured stage takes no ref_keys
         pipe = FusedPosePipeline(self.cfg)
         self.match, self.guard, self.device = pipe.match, pipe.guard, pipe.device
+        self.depth = pipe.depth                                 # DPT.SOURCE 'online': the reference map comes from the fused route's stage (PNP reads depth0 only)
         seed = int(cfg.RANSAC.SEED) if 'RANSAC' in cfg else 0
         self.solver = ops.RigPnPBatchSolver(cfg.PNP.RANSAC_ITER, cfg.PNP.REPROJECTION_INLIER_THRESHOLD, cfg.PNP.CONFIDENCE, seed)
         self.precomputed = fm == 'Precomputed'
@@ -139,6 +141,9 @@ class FeatureMatchingMultiFrameModel(torch.nn.Module):
             batch['ref_keys'] = [(batch['scene_root'], data['pair_names'][0][0])] * T
         with self.guard:
             m = self.match(batch)
+            if self.depth is not None:                          # the colour bytes of the reference view (image0 is byte / 255), once per distinct reference view
+                ref = (data['image0'][0].to(dev, torch.float32) * 255.0).round().clamp_(0, 255).to(torch.uint8).permute(1, 2, 0)[None].contiguous()
+                data['depth0'] = self.depth.maps(ref, [0], [(batch['scene_root'], data['pair_names'][0][0])])
         out = self.solver(m['pts0'][None], m['pts1'][None], m['n_corr'][None].to(torch.int32), data['depth0'].to(dev, torch.float32),
                           data['K_color0'].to(dev), data['K_color1_multi'].to(dev), data['rig_T'].to(dev, torch.float64),
                           data['pair_id'].to(dev, torch.int64).reshape(1))

@@ -13,7 +13,10 @@ What is here:
   * DPTHIP                 the network, inference only: fp32 storage; linear layers in the `HIP.SPLIT` arithmetic (nets/linear.SplitLinear), attention in
                            mfr_sg_attention's matching variant, 3x3 / stride 1 / pad 1 layers through nets/conv.WinoConv3x3 (the direct kernel under f16x2), every
                            other convolution through the implicit-GEMM kernel (f16x2, mfr_conv_igemm_f16x2_pad: BiT's TF-"SAME" padding is asymmetric).  Each stage
-                           is a method, which is what the stage-level tests call."""
+                           is a method, which is what the stage-level tests call.
+  * DepthEstimator         the config's stage (DPT.*) for compute_depth and the per-pair plugin: images in, maps out, the range guard's re-run taken here;
+  * FusedDepthStage        DPT.SOURCE 'online' on the batched route (pipeline.FusedPosePipeline): the maps the pose solver reads, from the batch's colour bytes --
+                           only the views it reads, a shared reference view once, through the row-table ends prep_rows / head_tail_rows."""
 import torch
 
 from .. import _lib, options
@@ -286,6 +289,44 @@ def head_tail(f, w, bias, out_h, out_w, invert=False, scale=1.0, shift=0.0, mill
     return metres, mm
 
 
+def _i32_table(t, n=None):
+    assert t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and (n is None or t.numel() == n), "row tables are int32 [n] on the GPU"
+    return t
+
+
+def prep_rows(img, rows, net_h, net_w, status):
+    """img u8 [N, H, W, 3], rows i32 [m] on the GPU -> [m, 3, net_h, net_w] = prep(img[rows]) without the gather (mfr_dpt_prep_rows).  status: i32 [1] on the GPU,
+    bit 0 is set when a row index is outside [0, N) (that image is zeros); the caller clears it"""
+    lib = _lib.load(require_gpu=True)
+    assert img.is_cuda and img.dtype == torch.uint8 and img.dim() == 4 and img.shape[3] == 3 and img.is_contiguous()
+    assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= 1
+    N, H, W = img.shape[:3]
+    m = _i32_table(rows).numel()
+    out = torch.empty(m, 3, net_h, net_w, dtype=torch.float32, device=img.device)
+    _lib.check(lib.mfr_dpt_prep_rows(img.data_ptr(), N, rows.data_ptr(), m, H, W, out.data_ptr(), int(net_h), int(net_w), status.data_ptr(), _lib.stream_ptr()),
+               "mfr_dpt_prep_rows")
+    return out
+
+
+def head_tail_rows(f, w, bias, src, dst, metres, status, mm=None, invert=False, scale=1.0, shift=0.0, quantize=False):
+    """plane dst[k] of metres [D, Ho, Wo] f32 (and of mm, u16 [D, Ho, Wo] or None) <- head_tail(f[src[k]]), for every entry of the i32 tables src / dst [d] on the
+    GPU (mfr_dpt_head_tail_rows): one feature image may feed several planes, planes not listed keep their contents.  quantize: the metres written are
+    millimetres_to_metres(mm).  status as in prep_rows"""
+    lib = _lib.load(require_gpu=True)
+    f = _f32(f)
+    B, C, Hh, Wh = f.shape
+    assert metres.is_cuda and metres.dtype == torch.float32 and metres.dim() == 3 and metres.is_contiguous()
+    D, Ho, Wo = metres.shape
+    assert mm is None or (mm.is_cuda and mm.dtype == torch.uint16 and mm.shape == metres.shape and mm.is_contiguous())
+    assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= 1
+    d = _i32_table(src).numel()
+    _i32_table(dst, d)
+    _lib.check(lib.mfr_dpt_head_tail_rows(f.data_ptr(), _lib.ptr(_f32(w).reshape(C)), float(bias), B, C, Hh, Wh, 1 if invert else 0, float(scale), float(shift), Ho, Wo,
+                                          src.data_ptr(), dst.data_ptr(), d, metres.data_ptr(), _lib.ptr(mm), D, 1 if quantize else 0, status.data_ptr(),
+                                          _lib.stream_ptr()), "mfr_dpt_head_tail_rows")
+    return metres
+
+
 def add_relu(a, b=None, want_sum=True):
     """-> (a + b, relu(a + b)) in one pass (b None: (a, relu(a)))"""
     lib = _lib.load(require_gpu=True)
@@ -522,8 +563,31 @@ def check_cfg(cfg):
         raise ValueError(f"DPT.NET_HEIGHT x NET_WIDTH = {node.NET_HEIGHT} x {node.NET_WIDTH}: both must be multiples of 32")
     if node.SOURCE not in ("file", "online"):
         raise ValueError(f"DPT.SOURCE = {node.SOURCE!r}: 'file' (depth maps come with the dataset) or 'online' (computed per pair)")
+    chunk = node.get("FUSED_CHUNK", 16)
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+        raise ValueError(f"DPT.FUSED_CHUNK = {chunk!r}: the views per DPT launch on the fused route, an integer >= 1")
     check_arch(dict(node.ARCH))
     return node
+
+
+def state_dict_from_cfg(cfg):
+    """(state dict, architecture dict) of a config's DPT node: DPT.WEIGHTS, or the synthetic weights when the config allows them"""
+    from . import weights as WT
+    node = check_cfg(cfg)
+    arch = dict(node.ARCH)
+    if node.WEIGHTS:
+        return WT.load_checkpoint(node.WEIGHTS), arch
+    return WT.synthetic_or_raise("DPT", cfg, lambda: WT.dpt_state_dict(int(node.SYNTHETIC_SEED), arch=arch)), arch
+
+
+FUSED_DEPTH_VIEWS = {"PNP": "ref", "EssentialMatrixMetric": "both", "Procrustes": "both"}     # the depth maps each pose solver reads; EssentialMatrix: none
+
+
+def fused_depth_views(cfg):
+    """what the batched route has to compute itself: None (DPT.SOURCE 'file', or a solver that reads no depth), 'ref' (depth0 only) or 'both'"""
+    if "DPT" not in cfg or cfg.DPT.SOURCE != "online":
+        return None
+    return FUSED_DEPTH_VIEWS.get(cfg.POSE_SOLVER)
 
 
 def millimetres_to_metres(mm):
@@ -537,13 +601,8 @@ class DepthEstimator:
     the millimetre-rounded map -- the bits the 16-bit PNG of compute_depth holds, read back as datasets.read_depth_image does -- else the float32 map."""
 
     def __init__(self, cfg, device="cuda"):
-        from . import weights as WT
         node = check_cfg(cfg)
-        arch = dict(node.ARCH)
-        if node.WEIGHTS:
-            sd = WT.load_checkpoint(node.WEIGHTS)
-        else:
-            sd = WT.synthetic_or_raise("DPT", cfg, lambda: WT.dpt_state_dict(int(node.SYNTHETIC_SEED), arch=arch))
+        sd, arch = state_dict_from_cfg(cfg)
         from ..pipeline import RangeGuard
         self.net = DPTHIP(sd, device, arch=arch)
         self.device = self.net.device
@@ -569,3 +628,113 @@ class DepthEstimator:
     def metres(self, images, out_hw=None):
         m, mm = self(images, out_hw)
         return millimetres_to_metres(mm) if self.quantize else m
+
+
+class _RefMap:
+    """One cached reference map of FusedDepthStage.
+    metres: the map [H, W] the solver reads.
+    flag:   a device copy [1] int32 of the f16x2 range-guard flag, taken right after the launches that computed the map (None while the guard is inactive): a
+            flagged accumulator can leave finite wrong values behind, so every later batch that reuses the map ORs `flag` into its own live flag
+            (cf. pipeline._RefView)."""
+    __slots__ = ("metres", "flag")
+
+    def __init__(self, metres, flag):
+        self.metres, self.flag = metres, flag
+
+
+class FusedDepthStage:
+    """DPT.SOURCE 'online' on the batched route (pipeline.FusedPosePipeline): fills batch['depth0'] (views 'ref') or batch['depth0'] and batch['depth1'] (views
+    'both') [b, H, W] f32 from batch['rgb'], the u8 [2b, H, W, 3] colour bytes PairBatchLoader(rgb=True) carries (row 2p = pair p's reference view).
+
+    Only the views the solver reads go through the network, and a reference view once: the batch's pairs are grouped by `ref_keys` (the semantics of
+    pipeline._RefCachedKeypointMatcher: None = a view nobody shares, never retained; the last `keep` maps are kept, `cache=False`: none across batches).  The
+    selected rows are read in place (mfr_dpt_prep_rows: no gather copy of the images), pass DPTHIP in chunks of DPT.FUSED_CHUNK views, and the tail writes
+    each map straight into every plane that wants it (mfr_dpt_head_tail_rows: a shared reference map lands in the depth0 row of each of its pairs).  With
+    DPT.QUANTIZE_MM the planes hold millimetres_to_metres of the rounded map: the bits the per-pair plugin's DepthEstimator.metres hands its solver.
+
+    Runs INSIDE the caller's RangeGuard window and never reads the flag on the host: a flagged launch marks the batch's rows ST_RANGE through the caller's
+    fold, and the scene is recomputed through the bf16x3 twin (submission._rerun_out_of_range_scenes)."""
+
+    def __init__(self, cfg, device, guard=None, views="both", cache=True, keep=4):
+        import collections
+        assert views in ("ref", "both")
+        node = check_cfg(cfg)
+        sd, arch = state_dict_from_cfg(cfg)
+        self.net = DPTHIP(sd, device, arch=arch)
+        self.device, self.guard, self.views, self.use_cache, self.keep = self.net.device, guard, views, bool(cache), int(keep)
+        self.net_hw = (int(node.NET_HEIGHT), int(node.NET_WIDTH))
+        self.invert, self.scale, self.shift, self.quantize = bool(node.INVERT), float(node.SCALE), float(node.SHIFT), bool(node.QUANTIZE_MM)
+        self.chunk = int(node.get("FUSED_CHUNK", 16))
+        self.cache = collections.OrderedDict()                                    # key -> _RefMap, least recently used first
+        self.stats = dict(depth_views_run=0, depth_views_reused=0)
+        self.table_status = torch.zeros(1, dtype=torch.int32, device=self.device)  # bit 0: a row table of this class left its range (a bug here, never data)
+
+    def _table(self, values):
+        """int32 table on the device through pinned memory: an asynchronous copy, the stream is not drained"""
+        return torch.tensor(values, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
+
+    @torch.no_grad()
+    def maps(self, rgb, ref_rows, ref_keys, query_rows=()):
+        """rgb u8 [N, H, W, 3] on the device; ref_rows[p] / ref_keys[p]: pair p's reference row of `rgb` and its identity (None: not shared); query_rows: rows
+        that always run -> planes [len(ref_rows) + len(query_rows), H, W] f32: the reference maps in pair order, then the query maps"""
+        assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 4 and rgb.shape[3] == 3
+        rgb = rgb.contiguous()
+        H, W = rgb.shape[1:3]
+        b, nq = len(ref_rows), len(query_rows)
+        keys = [k if k is not None else ("__pair__", p) for p, k in enumerate(ref_keys)]
+        first, pairs_of = {}, {}
+        for p, k in enumerate(keys):
+            first.setdefault(k, p)
+            pairs_of.setdefault(k, []).append(p)
+        need = [k for k in first if k not in self.cache]
+        reused = [k for k in first if k in self.cache]
+        rows = [int(ref_rows[first[k]]) for k in need] + [int(r) for r in query_rows]
+        dsts = [pairs_of[k] for k in need] + [[b + q] for q in range(nq)]
+        planes = torch.empty(b + nq, H, W, dtype=torch.float32, device=self.device)
+        guarded = self.guard is not None and self.guard.active
+        flags = {}
+        for c0 in range(0, len(rows), self.chunk):
+            c1 = min(c0 + self.chunk, len(rows))
+            src = [j - c0 for j in range(c0, c1) for _ in dsts[j]]
+            dst = [t for j in range(c0, c1) for t in dsts[j]]
+            m, d = c1 - c0, len(src)
+            tab = self._table(rows[c0:c1] + src + dst)
+            f = self.net.features(prep_rows(rgb, tab[:m], self.net_hw[0], self.net_hw[1], self.table_status))
+            head_tail_rows(f, self.net.head4_w, self.net.head4_b, tab[m:m + d], tab[m + d:], planes, self.table_status, invert=self.invert, scale=self.scale,
+                           shift=self.shift, quantize=self.quantize)
+            if guarded and c0 < len(need):
+                flag = self.guard.flag.clone()
+                flags.update({k: flag for k in need[c0:c1]})
+        self.stats["depth_views_run"] += len(rows)
+        self.stats["depth_views_reused"] += len(reused)
+        for k in reused:
+            hit = self.cache[k]
+            for p in pairs_of[k]:
+                planes[p].copy_(hit.metres)
+            if guarded and hit.flag is not None:
+                self.guard.flag.bitwise_or_(hit.flag)
+        if self.use_cache:
+            for k in need:
+                if k[0] != "__pair__":
+                    self.cache[k] = _RefMap(planes[first[k]].clone(), flags.get(k))
+            for k in first:                                                       # most recently used last; bounded
+                if k in self.cache:
+                    self.cache.move_to_end(k)
+            while len(self.cache) > self.keep:
+                self.cache.popitem(last=False)
+        return planes
+
+    def __call__(self, batch):
+        rgb = batch.get("rgb")
+        if rgb is None:
+            raise ValueError("DPT.SOURCE 'online' on the fused route needs the batch's colour bytes: build the loader with PairBatchLoader(..., rgb=True)")
+        b = rgb.shape[0] // 2
+        keys = batch.get("ref_keys")
+        if keys is None or len(keys) != b:
+            keys = [None] * b
+        both = self.views == "both"
+        planes = self.maps(rgb, [2 * p for p in range(b)], keys, [2 * p + 1 for p in range(b)] if both else ())
+        batch["depth0"] = planes[:b]
+        if both:
+            batch["depth1"] = planes[b:]
+        return batch

@@ -424,7 +424,9 @@ class FusedPosePipeline:
     """The batched twin of FeatureMatchingModel (lib/models/matching/model.py:7-40): the same two config keys pick the
     stages -- FEATURE_MATCHING in {'Precomputed', 'SuperGlue', 'LightGlue', 'LoFTR', 'SIFT' (SIFT.DETECTOR 'hip')} x POSE_SOLVER in {'PNP', 'EssentialMatrix',
     'EssentialMatrixMetric', 'Procrustes'} -- but every stage consumes / produces a device-resident batch of pairs.
-    __call__(batch) with the dict PairBatchLoader yields -> dict(R [b,3,3] f64, t [b,3] f64, n_inliers, status, n_corr)."""
+    __call__(batch) with the dict PairBatchLoader yields -> dict(R [b,3,3] f64, t [b,3] f64, n_inliers, status, n_corr).
+    With DPT.SOURCE 'online' the batch carries `rgb` instead of depth maps (PairBatchLoader(rgb=True)) and the maps are computed here; the result then also
+    holds depth0 (and depth1 when the solver reads it), the planes the solver was given."""
 
     def __init__(self, cfg, device="cuda"):
         from . import solver_ops as ops
@@ -514,11 +516,26 @@ class FusedPosePipeline:
             self.solve = solve_pr
         else:
             raise NotImplementedError(f"POSE_SOLVER={ps!r}")
+        # DPT.SOURCE 'online': the depth maps the solver reads are computed here from batch['rgb'] (nets/dpt.FusedDepthStage), a reference view once per scene.
+        # A solver that reads no depth (EssentialMatrix) builds no stage, needs no DPT weights and asks the loader for no colour bytes (`needs_rgb`)
+        from .nets import dpt as DPT
+        views = DPT.fused_depth_views(cfg)
+        self.depth = None
+        if views is not None:
+            self.depth = DPT.FusedDepthStage(cfg, self.device, self.guard, views, cache="REF_FEATURE_CACHE" in cfg.HIP and bool(cfg.HIP.REF_FEATURE_CACHE))
+        self.needs_rgb = self.depth is not None
+
+    @property
+    def stats(self):
+        """the counters of the stages that keep some: the matcher's reference_views_run / _reused, the depth stage's depth_views_run / _reused"""
+        return dict(getattr(self.match, "stats", {}), **(self.depth.stats if self.depth is not None else {}))
 
     @torch.no_grad()
     def __call__(self, batch):
         with self.guard:
             m = self.match(batch)
+            if self.depth is not None:                          # inside the guard's window: a flagged DPT launch marks the rows ST_RANGE like a matcher's
+                batch = self.depth(dict(batch))
         out = self.solve(m, batch)
         out["status"] = self.guard.fold(out["status"])
         ok = (out["status"] == 0)
@@ -526,4 +543,4 @@ class FusedPosePipeline:
         return dict(R=torch.where(ok[:, None, None], out["R"], torch.full_like(out["R"], nan)),
                     t=torch.where(ok[:, None], out["t"], torch.full_like(out["t"], nan)),
                     n_inliers=torch.where(ok, out["n_inliers"], torch.zeros_like(out["n_inliers"])), status=out["status"],
-                    n_corr=m["n_corr"])
+                    n_corr=m["n_corr"], **({k: batch[k] for k in ("depth0", "depth1") if batch.get(k) is not None} if self.depth is not None else {}))

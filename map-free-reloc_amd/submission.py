@@ -130,7 +130,15 @@ def _run_signature(cfg, split):
     return hashlib.sha256(json.dumps({'cfg': plain(cfg), 'split': str(split)}, sort_keys=True).encode()).hexdigest()
 
 
-def _rerun_out_of_range_scenes(pipeline, recs, names, scenes, todo, offsets, B, device, out_dir):
+def wants_rgb(cfg, pipeline=None):
+    """does the fused route's loader carry the colour bytes (PairBatchLoader(rgb=True)) instead of depth maps?  With DPT.SOURCE 'online' and a pose solver that
+    reads depth: the pipeline says so itself (FusedPosePipeline.needs_rgb); one that does not is answered for from the config"""
+    from .nets.dpt import fused_depth_views
+    needs = getattr(pipeline, 'needs_rgb', None)
+    return bool(needs) if needs is not None else fused_depth_views(cfg) is not None
+
+
+def _rerun_out_of_range_scenes(pipeline, recs, names, scenes, todo, offsets, B, device, out_dir, rgb=False):
     """Second pass of predict_fused for the f16x2 range guard (pipeline.RangeGuard, include/mfr_hip.h mfr_f16x2_guard_bind): the hot loop never
     waits for the guard's flag -- a batch whose activations left the f16x2 range comes back with status ST_RANGE and NaN poses.  Here, after the loop,
     every scene that holds such a pair is computed AGAIN through the exact (bf16x3) twin of the pipeline, its rows replace the first pass's and its
@@ -149,7 +157,8 @@ def _rerun_out_of_range_scenes(pipeline, recs, names, scenes, todo, offsets, B, 
     from .datasets import PairBatchLoader, DevicePrefetcher
     keep = rows[np.array([names[int(g)][0] not in bad for g in rows[:, 0]], bool)]
     new_rows = []
-    loader = PairBatchLoader([scenes[i] for i in idx], B, prefetch=1, pin=device.type == 'cuda', global_offsets=[int(offsets[i]) for i in idx], workers=2, decode='thread')
+    loader = PairBatchLoader([scenes[i] for i in idx], B, prefetch=1, pin=device.type == 'cuda', global_offsets=[int(offsets[i]) for i in idx], workers=2, decode='thread',
+                             rgb=rgb)
     try:
         with options.override(SPLIT='bf16x3'):
             twin = guard.twin()
@@ -173,6 +182,7 @@ def predict_fused(cfg, split, output_root, pipeline=None, batch_pairs=None, resu
     Every rank: its contiguous scene block -> for each scene not yet on disk, batches of <= batch_pairs pairs through
     `pipeline` (default: FusedPosePipeline(cfg) on this rank's GPU; anything with `.device` and __call__(batch) -> dict(R, t,
     n_inliers, status) works) -> `pose_{scene}.txt` written atomically into output_root/poses (= the resume marker).
+    With DPT.SOURCE 'online' and a solver that reads depth the loader carries the frames' colour bytes instead of depth maps (wants_rgb): no depth file is read.
     Then ONE all_gather of the pose records of the pairs solved in this run; rank 0 assembles the zip in global scene
     order from those records (scenes finished in an earlier run: from their files)."""
     from . import options
@@ -226,7 +236,7 @@ def predict_fused(cfg, split, output_root, pipeline=None, batch_pairs=None, resu
     depth_decode = str(cfg.HIP.DEPTH_DECODE) if 'DEPTH_DECODE' in cfg.HIP else 'host'
     loader = PairBatchLoader([scenes[i] for i in todo], B, prefetch=prefetch, pin=device.type == 'cuda',
                              global_offsets=[int(offsets[i]) for i in todo], workers=workers, decode=decode, jpeg_decode=jpeg_decode,
-                             depth_decode=depth_decode)
+                             depth_decode=depth_decode, rgb=wants_rgb(cfg, pipeline))
     recs, names, acc = [], {}, []
     stats = dict(pairs=0, batches=0, loader_wait_s=0.0, issue_s=0.0, gpu_busy_s=0.0, t0=time.perf_counter())
     it = iter(DevicePrefetcher(loader, device))
@@ -340,7 +350,7 @@ def predict_fused(cfg, split, output_root, pipeline=None, batch_pairs=None, resu
             f.write(json.dumps(line, default=float) + '\n')
     except (OSError, TypeError, ValueError):
         pass
-    recs = _rerun_out_of_range_scenes(pipeline, recs, names, scenes, todo, offsets, B, device, out_dir)
+    recs = _rerun_out_of_range_scenes(pipeline, recs, names, scenes, todo, offsets, B, device, out_dir, rgb=wants_rgb(cfg, pipeline))
     mine = torch.from_numpy(np.concatenate(recs) if recs else np.zeros((0, parallel.REC_W))).to(device)
     allrec = parallel.gather_records(mine, world).cpu().numpy()
     if rank != 0:

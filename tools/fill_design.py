@@ -45,6 +45,21 @@ sub = {
     "LOFTR_DCONV": f2(lo("conv_direct")), "LOFTR_GEMM": f2(lo("gemm_split_d")), "LOFTR_MLPLN": f2(lo("mlp_ln")), "LOFTR_FATT": f2(lo("fine_attention")),
     "LOFTR_IGEMM": f2(lo("conv_igemm")), "LOFTR_LA": f2(lo("la_kv", "la_out", "la_fold")), "LOFTR_DSM": f2(lo("dsm_")), "LOFTR_EMAT": f2(lo("emat_", "scale_")),
 }
+df = json.load(open(P("profiles", "dpt_fused.json")))           # DPT on the fused route (tools/bench_dpt_fused.py)
+for key, tag in (("sg_pnp", "PNP"), ("sg_emat_metric", "EM")):
+    a1, b, a2 = (df[key][k] for k in ("a1_depth_from_files", "b_online", "a2_depth_from_files"))
+    sub.update({f"DPTF_{tag}_ON": f2(b["gpu_ms_per_step_median"]), f"DPTF_{tag}_FILE": f2((a1["gpu_ms_per_step_median"] + a2["gpu_ms_per_step_median"]) / 2),
+                f"DPTF_{tag}_SPREAD": f2(abs(a1["gpu_ms_per_step_median"] - a2["gpu_ms_per_step_median"])), f"DPTF_{tag}_RUN": str(b["depth_views_run"]),
+                f"DPTF_{tag}_REUSED": str(b["depth_views_reused"]), f"DPTF_{tag}_STAGE": f2(b["depth_stage_ms_per_step_median"]),
+                f"DPTF_{tag}_PPS_ON": f"{b['pairs_per_s']:.0f}", f"DPTF_{tag}_PPS_A1": f"{a1['pairs_per_s']:.0f}", f"DPTF_{tag}_PPS_A2": f"{a2['pairs_per_s']:.0f}",
+                f"DPTF_{tag}_FIRST": f2(b["depth_stage_ms_first_step"]), f"DPTF_{tag}_TOTAL": f"{b['depth_stage_ms_total']:.0f}"})
+sub.update({"DPTF_STEPS": str(df["sg_pnp"]["b_online"]["steps"]), "DPTF_PAIRS": str(df["tree"]["pairs"]), "DPTF_FRAMES": str(df["compute_depth_over_the_tree"]["frames"]), "DPTF_B": str(df["sg_pnp"]["b_online"]["batch_pairs"]),
+            "DPTF_CD_S": f"{df['compute_depth_over_the_tree']['seconds']:.1f}", "DPTF_CD_MB": f"{df['compute_depth_over_the_tree']['png_MB_written']:.0f}",
+            "DPTF_PNP_S": f"{df['sg_pnp']['b_online']['seconds']:.1f}", "DPTF_EM_S": f"{df['sg_emat_metric']['b_online']['seconds']:.1f}"})
+pr = df["loader_probe"]
+sub.update({"DPTF_PR_FILE0": f"{pr['loaders_alone']['files_process_decode']:.0f}", "DPTF_PR_RGB0": f"{pr['loaders_alone']['rgb_process_decode']:.0f}",
+            "DPTF_PR_FILE1": f"{pr['after_dpt_is_built']['files_process_decode']:.0f}", "DPTF_PR_RGB1": f"{pr['after_dpt_is_built']['rgb_process_decode']:.0f}",
+            "DPTF_PR_THREAD": f"{pr['after_dpt_is_built']['files_thread_decode']:.0f}", "DPTF_PR_FIRST": f"{pr['pool_forked_before_dpt']['rgb_process_decode']:.0f}"})
 census = subprocess.check_output([sys.executable, P("tools", "census_table.py")], text=True).rstrip("\n")
 out = open(P("docs", "DESIGN.template.md")).read()
 parts = {"CENSUS_TABLE_PLACEHOLDER": census, "KERNEL_TABLE_PLACEHOLDER": rd("_design_kernel_table.md"), "SECTION44_PLACEHOLDER": rd("_design_44.md"),
@@ -56,5 +71,5 @@ for k, v in parts.items():
 for k in sorted(sub, key=len, reverse=True):
     out = out.replace(k, sub[k])
 open(P("DESIGN.md"), "w").write(out)
-left = [w for w in ("PLACEHOLDER", "SG_", "LOFTR_", "C1_", "RPR_", "CPU_", "HOSTFED") if w in out]
+left = [w for w in ("PLACEHOLDER", "SG_", "LOFTR_", "C1_", "RPR_", "CPU_", "HOSTFED", "DPTF_") if w in out]
 print("DESIGN.md written,", len(out), "bytes; unresolved markers:", left, "; longest line", max(len(l) for l in out.splitlines()))
