@@ -439,20 +439,31 @@ class MapFreeScene:
         route, so the batched loaders, the reference-view cache and the per-pair plugin see ONE plane."""
         return self.resize is None or all(sz == (int(self.resize[0]), int(self.resize[1])) for sz in self._file_sizes)
 
-    def gray_pair(self, index, want_ref=True, out=None, readers=None, depth_readers=None):
+    has_colour_planes = True    # gray_pair takes `colour` destinations and frame_hw() states the planes' size (PairBatchLoader(rgb=True)'s fast route)
+
+    def gray_pair(self, index, want_ref=True, out=None, readers=None, depth_readers=None, colour=None):
         """what the batched loaders need of sample `index`: (gray0 or None, depth0, gray1, depth1, K0, K1, pair_id, (name0, name1)), numpy arrays
         with the values of to_gray(self[index]['image0' / 'image1']) and its depth maps -- bit for bit AT THE FILES' OWN SIZE, the only case this
         route serves (resize_is_native(); otherwise None).  out = (g0, d0, g1, d1) destination arrays (entries
         may be None): the planes are then decoded / copied straight into them.  Returns None when this scene's images are not plain RGB reads
         (black_white training transform): the caller takes the generic sample then.  readers = (reader0, reader1): callables (path, out_g)
         that take the place of read_gray_plane for the two frames (the device JPEG route, _jpeg_reader); depth_readers = (reader0, reader1):
-        callables (path, out_d) that take the place of read_depth_plane (the device depth route, _png_reader; d0 / d1 are then None)."""
+        callables (path, out_d) that take the place of read_depth_plane (the device depth route, _png_reader; d0 / d1 are then None).
+        colour = (c0, c1), [h, w, 3] u8 destinations (PairBatchLoader(rgb=True): DPT.SOURCE 'online'): the colour bytes INSTEAD of depth maps --
+        each file is decoded once into its gray and colour planes (read_gray_rgb_plane, or its reader, whose host fall-back fills both), no
+        depth file is opened (d0 / d1 are None) and a reference view that is not wanted is not read at all (the caller copies another row's)."""
         if self.black_white or not self.resize_is_native():
             return None
         sa, ia, sb, ib = self.pairs[index]
         p1, p2 = f"seq{sa}/frame_{ia:05}.jpg", f"seq{sb}/frame_{ib:05}.jpg"
         og0, od0, og1, od1 = out if out is not None else (None, None, None, None)
         r0, r1 = readers if readers is not None else (None, None)
+        if colour is not None:
+            for want, rel, og, oc, r in ((want_ref, p1, og0, colour[0], r0), (True, p2, og1, colour[1], r1)):
+                if want:
+                    path = os.path.join(self.scene_root, rel)
+                    r(path, og) if r is not None else read_gray_rgb_plane(path, og, oc)
+            return (og0 if want_ref else None, None, og1, None, self.K[p1].copy(), self.K[p2].copy(), index * self.sample_factor, (p1, p2))
         dr0, dr1 = depth_readers if depth_readers is not None else (None, None)
         g0, d0 = self._gray_frame(p1, keep=True, out_g=og0 if want_ref else None, out_d=od0, reader=r0, depth_reader=dr0)
         g1, d1 = self._gray_frame(p2, out_g=og1, out_d=od1, reader=r1, depth_reader=dr1)
@@ -466,22 +477,6 @@ class MapFreeScene:
         sa, ia, _, _ = self.pairs[index]
         with Image.open(os.path.join(self.scene_root, f"seq{sa}/frame_{ia:05}.jpg")) as im:
             return int(im.size[1]), int(im.size[0])
-
-    def gray_rgb_pair(self, index, want_ref=True, out=None, readers=None):
-        """gray_pair for the loaders that carry the colour bytes INSTEAD of depth maps (PairBatchLoader(rgb=True): DPT.SOURCE 'online'): out = (g0, c0, g1, c1),
-        the gray [h, w] f32 and colour [h, w, 3] u8 destinations of the two frames, each file decoded once into both (read_gray_rgb_plane); no depth file is
-        opened.  want_ref False: the reference view is another row's (the caller copies it).  readers = (reader0, reader1): callables (path, out_g, out_rgb)
-        that take the place of read_gray_rgb_plane (the device JPEG route).  -> (K0, K1, pair_id, (name0, name1)), or None where gray_pair gives None"""
-        if self.black_white or not self.resize_is_native():
-            return None
-        sa, ia, sb, ib = self.pairs[index]
-        p1, p2 = f"seq{sa}/frame_{ia:05}.jpg", f"seq{sb}/frame_{ib:05}.jpg"
-        g0, c0, g1, c1 = out
-        r0, r1 = readers if readers is not None else (None, None)
-        if want_ref:
-            (r0 or read_gray_rgb_plane)(os.path.join(self.scene_root, p1), g0, c0)
-        (r1 or read_gray_rgb_plane)(os.path.join(self.scene_root, p2), g1, c1)
-        return (self.K[p1].copy(), self.K[p2].copy(), index * self.sample_factor, (p1, p2))
 
     def __getitem__(self, index):
         from . import evaluation as E
@@ -707,39 +702,23 @@ def check_jpeg_decode(mode):
     return mode
 
 
-def _jpeg_reader(hdr, rec, row, info):
-    """gray_pair reader of the device JPEG route for batch row `row`: the file's header + record go to hdr[row] / rec[row] and
-    info[row] = (0, record bytes, path); a file the device does not take (unsupported, invalid, above the slot's cap) is decoded here as on the
-    host route, into the row's plane, and info[row] = (parse status, 0, path).  resize = (w, h): the size of `out_g` when it is not the
+def _jpeg_reader(hdr_row, rec_row, key, info, host=read_gray_plane):
+    """gray_pair reader of the device JPEG route for one batch row: the file's header + record go to hdr_row / rec_row and
+    info[key] = (0, record bytes, path); a file the device does not take (unsupported, invalid, above the slot's cap) is decoded here as on the
+    host route, into the row's plane, and info[key] = (parse status, 0, path).  resize = (w, h): the size of `out_g` when it is not the
     file's (scenes whose files are larger than the network input, scannet.ScanNetScene): the device resizes what it decodes
-    (DevicePrefetcher._put_jpeg), the host fallback is read_gray_plane(path, resize)"""
+    (DevicePrefetcher._put_jpeg).  host(path, resize, out_g): the host fall-back -- read_gray_plane, or one that also fills the row's colour
+    bytes (the device writes both planes of a file it takes)"""
     def read(path, out_g, resize=None):
         from . import jpeg_ops as J
         with open(path, "rb") as f:
             data = f.read()
-        st, nb = J.parse_into(data, hdr[row], rec[row])
+        st, nb = J.parse_into(data, hdr_row, rec_row)
         if st == J.OK:
-            info[row] = (0, nb, path)
+            info[key] = (0, nb, path)
         else:
-            read_gray_plane(path, resize, out_g)
-            info[row] = (st, 0, path)
-        return out_g
-    return read
-
-
-def _jpeg_rgb_reader(hdr, rec, row, info):
-    """_jpeg_reader for the loaders that also carry the colour bytes (gray_rgb_pair's reader: (path, out_g, out_rgb)): the device writes both planes
-    of a file it takes; the host fall-back fills both here"""
-    def read(path, out_g, out_rgb):
-        from . import jpeg_ops as J
-        with open(path, "rb") as f:
-            data = f.read()
-        st, nb = J.parse_into(data, hdr[row], rec[row])
-        if st == J.OK:
-            info[row] = (0, nb, path)
-        else:
-            read_gray_rgb_plane(path, out_g, out_rgb)
-            info[row] = (st, 0, path)
+            host(path, resize, out_g)
+            info[key] = (st, 0, path)
         return out_g
     return read
 
@@ -765,11 +744,11 @@ def check_depth_decode(mode):
     return mode
 
 
-def _png_reader(row, info):
-    """gray_pair depth reader of the device depth route for row `row` = (0 | 1: depth0 / depth1, pair position): the file's record (its zlib
-    stream) goes into the row's own float plane -- H W 4 bytes always hold the stream of an H x W 16-bit image -- and info[row] = (0, record
+def _png_reader(which, info):
+    """gray_pair depth reader of the device depth route for a pair's depth0 (which = 0) or depth1 (1) row: the file's record (its zlib
+    stream) goes into the row's own float plane -- H W 4 bytes always hold the stream of an H x W 16-bit image -- and info[which] = (0, record
     bytes, path, header bytes); a file the device does not take (unsupported, invalid, a record above the plane's size) is decoded here as
-    on the host route, into the plane, and info[row] = (parse status, 0, path, None)"""
+    on the host route, into the plane, and info[which] = (parse status, 0, path, None)"""
     def read(path, out_d):
         from . import png_ops as P
         with open(path, "rb") as f:
@@ -779,10 +758,10 @@ def _png_reader(row, info):
         hdr = np.zeros(P.HEADER_BYTES, dtype=np.uint8)
         st, nb = P.parse_into(data, hdr, slot[:slot.size // 16 * 16])
         if st == P.OK:
-            info[row] = (0, nb, path, hdr.tobytes())
+            info[which] = (0, nb, path, hdr.tobytes())
         else:
             read_depth_plane(path, out_d)
-            info[row] = (st, 0, path, None)
+            info[which] = (st, 0, path, None)
         return out_d
     return read
 
@@ -792,55 +771,160 @@ def _png_skip(path, out_d):
     return out_d
 
 
-def _png_rows(b, want, first_of_p, infos, mk):
+_BatchPlan = _collections.namedtuple("_BatchPlan", "items first_of want_ref")
+_PairDest = _collections.namedtuple("_PairDest", "gray depth colour jpeg png")
+_PairMeta = _collections.namedtuple("_PairMeta", "K0 K1 pair_id name1 name0 jpeg png has_ref")
+
+
+def _batch_plan(scenes, items):
+    """what is decided about a batch before anything is decoded, by pair position: items[p] = (scene index, pair index), want_ref[p] = pair p
+    is the first of the batch with its reference view (one per distinct scene that shares its reference; every pair of other scenes) and so
+    the one that decodes it, first_of[p] = the position of that first pair.  Every route and both device row tables follow THIS plan"""
+    seen, first_of, want = {}, [], []
+    for p, (si, i) in enumerate(items):
+        k = si if getattr(scenes[si], "shared_reference", False) else ("pair", p)
+        want.append(k not in seen)
+        first_of.append(seen.setdefault(k, p))
+    return _BatchPlan(list(items), first_of, want)
+
+
+def _batch_layout(sc, index, rgb):
+    """(H, W, has depth, first sample or None) of the batches that start with pair `index` of scene `sc`: what the scene states (batch_layout():
+    scannet.ScanNetScene -- its generic sample resizes the 8-bit RGB image, a different plane from gray_pair's whenever a resize happens), else,
+    for a batch that carries the colour bytes, the frames' size (a generic sample would open the depth files that route does without), else what
+    a generic first sample shows; the sample is handed back so that nobody decodes it twice.  The colour bytes take the depth maps' place"""
+    first = None
+    if hasattr(sc, "batch_layout"):
+        Hh, Ww, has_depth = sc.batch_layout()
+    elif rgb and getattr(sc, "has_colour_planes", False):
+        (Hh, Ww), has_depth = sc.frame_hw(index), False
+    else:
+        first = sc[index]
+        (Hh, Ww), has_depth = first["image0"].shape[-2:], first["depth0"].numel() > 0
+    return int(Hh), int(Ww), bool(has_depth) and not rgb, first
+
+
+def _pair_dest(p, images, depth0, depth1, colour, jpeg, png):
+    """pair p's rows of a batch's buffers (numpy views; depth0 / depth1 / colour / jpeg = (headers, records) may be None) as _fill_pair's
+    destination.  png: the device depth route is on (the records then go into the depth rows themselves)"""
+    return _PairDest(gray=(images[2 * p, 0], images[2 * p + 1, 0]), depth=(depth0[p], depth1[p]) if depth0 is not None else None,
+                     colour=(colour[2 * p], colour[2 * p + 1]) if colour is not None else None,
+                     jpeg=(jpeg[0][2 * p:2 * p + 2], jpeg[1][2 * p:2 * p + 2]) if jpeg is not None else None, png=bool(png))
+
+
+def _fill_pair(sc, index, want_ref, dest, smp=None, ref_gray=None):
+    """decode pair `index` of scene `sc` into `dest` (a _PairDest) -- THE per-pair code of every route: thread decode calls it with views of the
+    batch's own buffers, a decode process with views of its shared-memory slot.  -> _PairMeta: the intrinsics, data['pair_id'], the two names,
+    jpeg / png = what the device readers recorded ({0 | 1: _jpeg_reader / _png_reader entry}; empty: nothing of this pair is for the device)
+    and has_ref = the pair's reference gray (and colour) row was filled or recorded (else the caller duplicates the row of the pair that has it).
+    The fast route (scenes with has_gray_pair: planes straight from the files' bytes, device readers where `dest` has room for their records)
+    when the scene serves it, else the generic sample sc[index].  want_ref False: the reference view is another pair's.
+    smp: the generic sample when the caller holds it already.  ref_gray(image0) -> gray plane: given by a caller that wants the reference row
+    of every HOST-decoded pair written here, not copied afterwards (thread decode: through the frame cache on the fast route, through this
+    callable -- its memo of one conversion per keyframe tensor -- on the generic one)"""
+    if smp is None and getattr(sc, "has_gray_pair", False) and (dest.colour is None or getattr(sc, "has_colour_planes", False)):
+        jinfo, pinfo, kw = {}, {}, {}
+        if dest.jpeg is not None:                              # device JPEG route: headers + records into the packed buffers
+            host = [read_gray_plane] * 2 if dest.colour is None else \
+                   [lambda path, resize, out_g, c=c: read_gray_rgb_plane(path, out_g, c) for c in dest.colour]
+            kw["readers"] = tuple(_jpeg_reader(dest.jpeg[0][j], dest.jpeg[1][j], j, jinfo, host[j]) for j in (0, 1))
+        if dest.png and dest.depth is not None and getattr(sc, "has_depth_readers", False):    # device depth route: the records into the depth planes
+            kw["depth_readers"] = (_png_reader(0, pinfo) if want_ref else _png_skip, _png_reader(1, pinfo))
+        if dest.colour is not None:
+            kw["colour"] = dest.colour
+        gray_ref = want_ref or (ref_gray is not None and dest.jpeg is None and dest.colour is None)
+        d0, d1 = dest.depth if dest.depth is not None else (None, None)
+        fast = sc.gray_pair(index, gray_ref, out=(dest.gray[0], d0, dest.gray[1], d1), **kw)
+        if fast is not None:
+            K0, K1, pid, (n0, n1) = fast[4:]
+            return _PairMeta(np.asarray(K0), np.asarray(K1), int(pid), n1, n0, jinfo, pinfo, gray_ref)
+    smp = sc[index] if smp is None else smp
+    npv = lambda t: t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    has_ref = want_ref or ref_gray is not None
+    if has_ref:
+        dest.gray[0][...] = ref_gray(smp["image0"]) if ref_gray is not None else npv(to_gray(smp["image0"]))
+    dest.gray[1][...] = npv(to_gray(smp["image1"]))
+    if dest.colour is not None:
+        if has_ref:
+            dest.colour[0][...] = rgb_bytes(smp["image0"])
+        dest.colour[1][...] = rgb_bytes(smp["image1"])
+    if dest.depth is not None and smp["depth0"].numel() > 0:
+        dest.depth[0][...] = npv(smp["depth0"]); dest.depth[1][...] = npv(smp["depth1"])
+    return _PairMeta(np.asarray(smp["K_color0"]), np.asarray(smp["K_color1"]), int(smp["pair_id"]), smp["pair_names"][1], smp["pair_names"][0],
+                     {}, {}, has_ref)
+
+
+def _jpeg_rows(plan, meta):
+    """the device JPEG route's row table of a batch (rows 2p / 2p + 1 = pair p's reference / query view): None = a host plane in `images`,
+    (status, record bytes, path) from _jpeg_reader, ("dup", row) = the device copies that row (a reference view another pair decodes)"""
+    rows = [None] * (2 * len(meta))
+    for p, m in enumerate(meta):
+        for j, v in m.jpeg.items():
+            rows[2 * p + j] = v
+        if m.jpeg and not plan.want_ref[p]:
+            rows[2 * p] = ("dup", 2 * plan.first_of[p])
+    return rows
+
+
+def _png_rows(plan, meta, mk):
     """the device depth route's part of a batch of b pairs: rows 0..b-1 are depth0's, b..2b-1 depth1's.  rows[r] = None (the plane holds
     host-decoded depth), (0, record bytes, path) (it holds the file's record) or ("dup", source row); headers u8 [2b, HEADER_BYTES], rows
-    the device must not touch marked unsupported.  infos[p]: pair p's _png_reader entries (empty: the pair took the generic route)"""
+    the device must not touch marked unsupported.  meta[p].png: pair p's _png_reader entries (empty: the pair took the generic route)"""
     from . import png_ops as P
+    b = len(meta)
     headers = mk(2 * b, P.HEADER_BYTES, dtype=torch.uint8)
     h_np = headers.numpy()
     h_np[...] = 0
     h_np[:, :4].view(np.int32)[:, 0] = P.UNSUPPORTED
     rows = [None] * (2 * b)
-    for p, info in enumerate(infos):
-        for (which, _), v in info.items():
+    for p, m in enumerate(meta):
+        for which, v in m.png.items():
             if v[0] == 0:
                 r = which * b + p
                 rows[r] = v[:3]
                 h_np[r] = np.frombuffer(v[3], dtype=np.uint8)
-        if info and not want[p]:
-            rows[p] = ("dup", first_of_p[p])
+        if m.png and not plan.want_ref[p]:
+            rows[p] = ("dup", plan.first_of[p])
     return dict(headers=headers, rows=rows)
 
 
-def _slot_views(flat, n_slots, B, Hh, Ww, has_depth):
-    """carve the ring's batch slots out of ONE shared tensor (one shared-memory segment = one descriptor per worker)"""
-    per = 2 * B * Hh * Ww + (2 * B * Hh * Ww if has_depth else 0)
-    out = []
-    for k in range(n_slots):
-        o = k * per
-        im = flat[o:o + 2 * B * Hh * Ww].view(2 * B, 1, Hh, Ww)
-        d0 = flat[o + 2 * B * Hh * Ww:o + 3 * B * Hh * Ww].view(B, Hh, Ww) if has_depth else None
-        d1 = flat[o + 3 * B * Hh * Ww:o + 4 * B * Hh * Ww].view(B, Hh, Ww) if has_depth else None
-        out.append(dict(images=im, depth0=d0, depth1=d1))
-    return out
+def _ring_spec(B, Hh, Ww, has_depth, jpeg_cap, rgb):
+    """the shared segments of the process decoder's ring as (name, dtype, elements per slot, carve): carve(a slot's part of the segment) ->
+    the slot's views.  "planes": (images [2B,1,Hh,Ww], depth0, depth1 [B,Hh,Ww] or None) f32; "jpeg": the device JPEG route's packed (headers u8
+    [2B, HEADER_BYTES], records u8 [2B, cap]); "rgb": the colour bytes u8 [2B,Hh,Ww,3] of PairBatchLoader(rgb=True)"""
+    n = B * Hh * Ww
+
+    def planes(c):
+        return (c[:2 * n].view(2 * B, 1, Hh, Ww), c[2 * n:3 * n].view(B, Hh, Ww) if has_depth else None,
+                c[3 * n:4 * n].view(B, Hh, Ww) if has_depth else None)
+    spec = [("planes", torch.float32, (4 if has_depth else 2) * n, planes)]
+    if jpeg_cap:
+        from .jpeg_ops import HEADER_BYTES as hb
+        spec.append(("jpeg", torch.uint8, 2 * B * (hb + jpeg_cap), lambda c: (c[:2 * B * hb].view(2 * B, hb), c[2 * B * hb:].view(2 * B, jpeg_cap))))
+    if rgb:
+        spec.append(("rgb", torch.uint8, 6 * n, lambda c: c.view(2 * B, Hh, Ww, 3)))
+    return spec
 
 
-def _jpeg_views(jflat, n_slots, B, cap):
-    """per slot: (headers u8 [2B, HEADER_BYTES], records u8 [2B, cap]) of the device JPEG route, out of one shared byte tensor"""
-    from .jpeg_ops import HEADER_BYTES
-    per = 2 * B * (HEADER_BYTES + cap)
-    return [(jflat[k * per:k * per + 2 * B * HEADER_BYTES].view(2 * B, HEADER_BYTES), jflat[k * per + 2 * B * HEADER_BYTES:(k + 1) * per].view(2 * B, cap))
-            for k in range(n_slots)]
+def _ring_slots(spec, flats, n_slots):
+    """carve the ring's batch slots out of the shared tensors (one shared-memory segment each = one descriptor per worker): per slot
+    {segment name: its views}"""
+    return [{name: carve(flat[k * per:(k + 1) * per]) for (name, _, per, carve), flat in zip(spec, flats)} for k in range(n_slots)]
 
 
-def _rgb_views(cflat, n_slots, B, Hh, Ww):
-    """per slot: the colour bytes u8 [2B, Hh, Ww, 3] of PairBatchLoader(rgb=True), out of one shared byte tensor"""
-    per = 2 * B * Hh * Ww * 3
-    return [cflat[k * per:(k + 1) * per].view(2 * B, Hh, Ww, 3) for k in range(n_slots)]
+def _slot_buffers(slot):
+    """(images, depth0, depth1, colour, (jpeg headers, jpeg records)) of a ring slot, None where the ring carries none"""
+    return (*slot["planes"], slot.get("rgb"), slot.get("jpeg"))
 
 
-def _pw_init(scenes, flat, layout, jflat=None, jcap=0, png=False, cflat=None):
+def _np_views(images, depth0, depth1, colour, jpeg):
+    """a batch's buffers as numpy views, in _pair_dest's order.  The pairs are packed through them: plain memcpy on the worker's own thread (a
+    torch copy_ of a 1.5 MB plane is dispatched to the intra-op thread pool)"""
+    npv = lambda t: t.numpy() if t is not None else None
+    return npv(images), npv(depth0), npv(depth1), npv(colour), tuple(t.numpy() for t in jpeg) if jpeg is not None else None
+
+
+def _pw_init(scenes, flats, n_slots, layout, png):
     # Everything inherited from the parent becomes permanent in this process: a garbage-collection pass of the child must never finalise the
     # PARENT's objects -- a dead multiprocessing.Pool of an earlier loader among them, whose __del__ writes to a queue under a lock that a
     # thread of the parent may have held at fork time (the child then waits for it for ever: round 5's first full CPU test run hung exactly
@@ -848,70 +932,18 @@ def _pw_init(scenes, flat, layout, jflat=None, jcap=0, png=False, cflat=None):
     import gc
     gc.freeze()
     torch.set_num_threads(1)
-    _PW["scenes"], _PW["slots"] = scenes, _slot_views(flat, *layout)
-    _PW["jslots"] = _jpeg_views(jflat, layout[0], layout[1], jcap) if jflat is not None else None
-    _PW["png"] = bool(png)
-    _PW["cslots"] = _rgb_views(cflat, *layout[:4]) if cflat is not None else None
-
-
-def _pw_fill_rgb(task):
-    """_pw_fill for a loader that carries the colour bytes instead of depth maps: gray plane and RGB bytes of each frame from ONE decode"""
-    import time as _t
-    t0 = _t.perf_counter()
-    k, p, si, i, want_ref = task
-    sc = _PW["scenes"][si]
-    im, col = _PW["slots"][k]["images"].numpy(), _PW["cslots"][k].numpy()
-    if getattr(sc, "has_gray_pair", False) and hasattr(sc, "gray_rgb_pair"):
-        info, readers = {}, None
-        if _PW["jslots"] is not None:
-            hdr, rec = (t.numpy() for t in _PW["jslots"][k])
-            readers = (_jpeg_rgb_reader(hdr, rec, 2 * p, info), _jpeg_rgb_reader(hdr, rec, 2 * p + 1, info))
-        fast = sc.gray_rgb_pair(i, want_ref, out=(im[2 * p, 0], col[2 * p], im[2 * p + 1, 0], col[2 * p + 1]), readers=readers)
-        if fast is not None:
-            K0, K1, pid, (n0, n1) = fast
-            return (np.asarray(K0), np.asarray(K1), int(pid), n1, n0, _t.perf_counter() - t0, info, {})
-    smp = sc[i]
-    npv = lambda t: t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-    col[2 * p + 1] = rgb_bytes(smp["image1"])
-    im[2 * p + 1, 0] = npv(to_gray(smp["image1"]))
-    if want_ref:
-        col[2 * p] = rgb_bytes(smp["image0"])
-        im[2 * p, 0] = npv(to_gray(smp["image0"]))
-    return (np.asarray(smp["K_color0"]), np.asarray(smp["K_color1"]), int(smp["pair_id"]), smp["pair_names"][1], smp["pair_names"][0],
-            _t.perf_counter() - t0, {}, {})
+    _PW["scenes"], _PW["png"] = scenes, bool(png)
+    _PW["slots"] = [_np_views(*_slot_buffers(sl)) for sl in _ring_slots(_ring_spec(*layout), flats, n_slots)]
 
 
 def _pw_fill(task):
-    """decode one pair into slot `k`, position `p`; `want_ref` False: the reference plane is a duplicate the parent copies"""
+    """decode one pair into slot `k`, position `p`; `want_ref` False: the reference plane is a duplicate the parent copies.
+    -> (_PairMeta, seconds spent)"""
     import time as _t
     t0 = _t.perf_counter()
     k, p, si, i, want_ref = task
-    sc = _PW["scenes"][si]
-    sl = _PW["slots"][k]
-    im = sl["images"].numpy()
-    if getattr(sc, "has_gray_pair", False):                 # gray planes / depth straight from the files' bytes into the slot (MapFreeScene)
-        has_d = sl["depth0"] is not None
-        info, readers = {}, None
-        if _PW["jslots"] is not None:                        # device JPEG route: headers + records into the slot's packed buffers
-            hdr, rec = (t.numpy() for t in _PW["jslots"][k])
-            readers = (_jpeg_reader(hdr, rec, 2 * p, info), _jpeg_reader(hdr, rec, 2 * p + 1, info))
-        pinfo, kw = {}, {}
-        if _PW["png"] and has_d and getattr(sc, "has_depth_readers", False):     # device depth route: the records into the depth planes
-            kw = dict(depth_readers=(_png_reader((0, p), pinfo) if want_ref else _png_skip, _png_reader((1, p), pinfo)))
-        fast = sc.gray_pair(i, want_ref, out=(im[2 * p, 0], sl["depth0"].numpy()[p] if has_d else None, im[2 * p + 1, 0],
-                                              sl["depth1"].numpy()[p] if has_d else None), readers=readers, **kw)
-        if fast is not None:
-            _, _, _, _, K0, K1, pid, (n0, n1) = fast
-            return (np.asarray(K0), np.asarray(K1), int(pid), n1, n0, _t.perf_counter() - t0, info, pinfo)
-    smp = sc[i]
-    npv = lambda t: t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-    if want_ref:
-        im[2 * p, 0] = npv(to_gray(smp["image0"]))
-    im[2 * p + 1, 0] = npv(to_gray(smp["image1"]))
-    if sl["depth0"] is not None and smp["depth0"].numel() > 0:
-        sl["depth0"].numpy()[p] = npv(smp["depth0"]); sl["depth1"].numpy()[p] = npv(smp["depth1"])
-    return (np.asarray(smp["K_color0"]), np.asarray(smp["K_color1"]), int(smp["pair_id"]), smp["pair_names"][1], smp["pair_names"][0],
-            _t.perf_counter() - t0, {}, {})
+    meta = _fill_pair(_PW["scenes"][si], i, want_ref, _pair_dest(p, *_PW["slots"][k], _PW["png"]))
+    return meta, _t.perf_counter() - t0
 
 
 def _pw_ping(i):
@@ -924,27 +956,14 @@ class _ProcessDecoder:
 
     def __init__(self, scenes, B, Hh, Ww, has_depth, workers, n_slots, pin, jpeg_cap=0, png=False, rgb=False):
         import torch.multiprocessing as mp
-        layout = (n_slots, B, Hh, Ww, has_depth)
-        per = 2 * B * Hh * Ww + (2 * B * Hh * Ww if has_depth else 0)
-        self.flat = torch.empty(n_slots * per, dtype=torch.float32).share_memory_()
-        self.slots = _slot_views(self.flat, *layout)
-        self.jflat, self.jslots = None, None
-        if jpeg_cap:                                           # the device JPEG route's packed headers + records, one more shared segment
-            from .jpeg_ops import HEADER_BYTES
-            self.jflat = torch.empty(n_slots * 2 * B * (HEADER_BYTES + jpeg_cap), dtype=torch.uint8).share_memory_()
-            self.jslots = _jpeg_views(self.jflat, n_slots, B, jpeg_cap)
-        self.cflat, self.cslots = None, None
-        if rgb:                                                # the colour bytes (PairBatchLoader(rgb=True)): a u8 plane per row, one more shared segment
-            self.cflat = torch.empty(n_slots * 2 * B * Hh * Ww * 3, dtype=torch.uint8).share_memory_()
-            self.cslots = _rgb_views(self.cflat, n_slots, B, Hh, Ww)
+        layout = (B, Hh, Ww, has_depth, jpeg_cap, rgb)
+        spec = _ring_spec(*layout)
+        self.flats = [torch.empty(n_slots * per, dtype=dtype).share_memory_() for _, dtype, per, _ in spec]
+        self.slots = _ring_slots(spec, self.flats, n_slots)
         self.events = [None] * n_slots
-        self.pinned = self.jpinned = self.cpinned = False
+        self.registered = []                                   # the segments registered as pinned host memory
         if pin and torch.cuda.is_available():
-            self.pinned = int(torch.cuda.cudart().cudaHostRegister(self.flat.data_ptr(), self.flat.numel() * 4, 0)) == 0
-            if self.jflat is not None:
-                self.jpinned = int(torch.cuda.cudart().cudaHostRegister(self.jflat.data_ptr(), self.jflat.numel(), 0)) == 0
-            if self.cflat is not None:
-                self.cpinned = int(torch.cuda.cudart().cudaHostRegister(self.cflat.data_ptr(), self.cflat.numel(), 0)) == 0
+            self.registered = [f for f in self.flats if int(torch.cuda.cudart().cudaHostRegister(f.data_ptr(), f.numel() * f.element_size(), 0)) == 0]
         # the look-up tables and the C helper are set up BEFORE the fork (inherited, not rebuilt per worker), and cyclic garbage of earlier
         # loaders (their pools) is finalised here, in the parent, not in a child (see _pw_init)
         import gc
@@ -953,7 +972,7 @@ class _ProcessDecoder:
         # FORK, like torch's DataLoader workers: the children inherit the scene objects and the shared segment without re-importing anything
         # (spawned workers each re-imported torch: 36 s to start 32 of them under a 16-CPU container quota, tools/bench_fused_split.py) and
         # never touch the HIP runtime -- they run PIL / zlib / numpy only
-        self.pool = mp.get_context("fork").Pool(workers, initializer=_pw_init, initargs=(scenes, self.flat, layout, self.jflat, jpeg_cap, png, self.cflat))
+        self.pool = mp.get_context("fork").Pool(workers, initializer=_pw_init, initargs=(scenes, self.flats, n_slots, layout, png))
         self.next = 0
 
     def acquire(self):
@@ -970,15 +989,8 @@ class _ProcessDecoder:
             self.pool.terminate(); self.pool.join(); self.pool = None
             import gc
             gc.collect()                                       # the pool's cycles die in THIS process, now
-        if self.pinned:
-            torch.cuda.cudart().cudaHostUnregister(self.flat.data_ptr())
-            self.pinned = False
-        if self.jpinned:
-            torch.cuda.cudart().cudaHostUnregister(self.jflat.data_ptr())
-            self.jpinned = False
-        if self.cpinned:
-            torch.cuda.cudart().cudaHostUnregister(self.cflat.data_ptr())
-            self.cpinned = False
+        while self.registered:
+            torch.cuda.cudart().cudaHostUnregister(self.registered.pop().data_ptr())
 
 
 class PairBatchLoader:
@@ -991,7 +1003,10 @@ class PairBatchLoader:
     side stream).  Yields dict(images [2b,1,H,W] f32 gray interleaved (2p = reference view), depth0/depth1 [b,H,W],
     K0/K1 [b,3,3] in the loader's dtype (float64 on Map-free), seed_ids [b] i64 (= data['pair_id'], the RANSAC stream id the per-pair plugin uses),
     global_ids [b] i64, names [b], scene_ids [b] / scene_roots [b] (per pair), scenes_done (ids of the scenes whose LAST pair is in
-    this batch), scene_id / scene_root / last_of_scene (of the batch's last pair, kept for single-scene consumers))."""
+    this batch), scene_id / scene_root / last_of_scene (of the batch's last pair, kept for single-scene consumers)).
+    Thread and process decode differ in where the pairs are decoded and into which buffers, nothing else: one plan per batch (_batch_plan),
+    one layout discovery (_batch_layout), one per-pair decode (_fill_pair), one pass over the reference rows nobody filled (_share_refs) and
+    one batch dictionary (_batch)."""
 
     def __init__(self, scenes, batch_pairs=32, prefetch=2, pin=None, global_offsets=None, workers=8, span_scenes=True, decode="thread",
                  jpeg_decode="host", jpeg_cap=JPEG_RECORD_CAP, depth_decode="host", rgb=False):
@@ -1060,97 +1075,43 @@ class PairBatchLoader:
             self._ref_ident[k] = ident
         return (root, frame) + ident
 
+    def _mk(self, *shape, dtype=torch.float32):
+        """a host buffer of a batch: pinned when the loader pins"""
+        return torch.empty(*shape, dtype=dtype, pin_memory=True) if self.pin else torch.empty(*shape, dtype=dtype)
+
     def _load(self, items):
         """decode the pairs of one batch STRAIGHT INTO the batch's (pinned) buffers: every worker thread decodes its pair, converts to
-        gray and writes its slots itself; the loader thread only allocates and collects the small fields (a serial gray conversion +
-        copy of 64 images per batch on this thread capped the loader at ~300 pairs/s)"""
+        gray and writes its slots itself (_fill_pair); the loader thread only allocates and collects the small fields (a serial gray
+        conversion + copy of 64 images per batch on this thread capped the loader at ~300 pairs/s)"""
         if self.decode == "process" and self.workers > 1:
             return self._load_process(items)
-        get = lambda it: self.scenes[it[0]][it[1]]
-        b = len(items)
-        # shapes / dtypes of the batch buffers come from the first pair; it is decoded on this thread before the pool gets the others (an
-        # attempt to overlap the two -- pool tasks that decode, then pool tasks that wait for them and fill -- halved the loader's rate:
-        # workers parked in .result() while the next batches' decodes queued behind them; tools/bench_fused_split.py, round 4)
-        # (a scene that states its planes' layout -- batch_layout() -> (H, W, has depth): scannet.ScanNetScene -- is not asked for a generic
-        # sample at all: its generic sample resizes the 8-bit RGB image, a different plane from gray_pair's whenever a resize happens)
-        layout = getattr(self.scenes[items[0][0]], "batch_layout", None)
-        if self.rgb and hasattr(self.scenes[items[0][0]], "gray_rgb_pair"):      # no generic sample: it would open the depth files this route does without
-            sc0 = self.scenes[items[0][0]]
-            layout = lambda: (*sc0.frame_hw(items[0][1]), False)
-        first = get(items[0]) if layout is None else None
-        Hh, Ww, has_depth = layout() if layout is not None else (*first["image0"].shape[-2:], first["depth0"].numel() > 0)
-        has_depth = has_depth and not self.rgb                 # the colour bytes take the depth maps' place
-        mk = (lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, pin_memory=True)) if self.pin else \
-             (lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype))
-        images = mk(2 * b, 1, Hh, Ww)
-        depth0 = mk(b, Hh, Ww) if has_depth else None
-        depth1 = mk(b, Hh, Ww) if has_depth else None
-        # packing through the buffers' numpy views: plain memcpy on the worker's own thread (a torch copy_ of a 1.5 MB plane is
-        # dispatched to the intra-op thread pool)
-        npv = lambda t: t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-        im_np = images.numpy()
-        d0_np, d1_np = (depth0.numpy(), depth1.numpy()) if has_depth else (None, None)
+        b, mk = len(items), self._mk
+        plan = _batch_plan(self.scenes, items)
+        # shapes / dtypes of the batch buffers come from the first pair when the scene does not state them; it is then decoded on this thread
+        # before the pool gets the others (an attempt to overlap the two -- pool tasks that decode, then pool tasks that wait for them and
+        # fill -- halved the loader's rate: workers parked in .result() while the next batches' decodes queued behind them;
+        # tools/bench_fused_split.py, round 4) and takes the generic route
+        Hh, Ww, has_depth, first = _batch_layout(self.scenes[items[0][0]], items[0][1], self.rgb)
+        bufs = (mk(2 * b, 1, Hh, Ww), mk(b, Hh, Ww) if has_depth else None, mk(b, Hh, Ww) if has_depth else None,
+                mk(2 * b, Hh, Ww, 3, dtype=torch.uint8) if self.rgb else None)
+        jpeg = None
+        if self.jpeg_decode == "device":
+            from .jpeg_ops import HEADER_BYTES
+            jpeg = (mk(2 * b, HEADER_BYTES, dtype=torch.uint8), mk(2 * b, self.jpeg_cap, dtype=torch.uint8))
+        png = self.depth_decode == "device" and has_depth
+        views = _np_views(*bufs, jpeg)
         gray_of = {}                                           # id(map-frame tensor) -> (the tensor, its gray plane): one conversion per scene
                                                                # keyframe; the tensor is held so that its id cannot be reused inside the batch
-        jp = self._jpeg_batch(items, mk) if self.jpeg_decode == "device" else None
-        png = self.depth_decode == "device" and has_depth
-        first_of, want_ref = self._ref_plan(items)
-        pinfos = [{} for _ in range(b)]
-        colour = mk(2 * b, Hh, Ww, 3, dtype=torch.uint8) if self.rgb else None
-        c_np = colour.numpy() if self.rgb else None
-        dups = []                                              # rgb route: pairs whose reference planes are host copies of another row's
 
-        def fill_rgb(p, smp=None):
-            """fill() of a batch that carries the colour bytes: both planes of a frame from one decode, a shared reference view once per batch"""
-            sc_ = self.scenes[items[p][0]]
-            if smp is None and getattr(sc_, "has_gray_pair", False) and hasattr(sc_, "gray_rgb_pair"):
-                readers = None
-                if jp is not None:
-                    h_np, r_np = jp["headers"].numpy(), jp["records"].numpy()
-                    readers = (_jpeg_rgb_reader(h_np, r_np, 2 * p, jp["rows"]), _jpeg_rgb_reader(h_np, r_np, 2 * p + 1, jp["rows"]))
-                fast = sc_.gray_rgb_pair(items[p][1], want_ref[p], out=(im_np[2 * p, 0], c_np[2 * p], im_np[2 * p + 1, 0], c_np[2 * p + 1]), readers=readers)
-                if fast is not None:
-                    if not want_ref[p]:
-                        if jp is not None:
-                            jp["rows"][2 * p] = ("dup", 2 * first_of[p])
-                        else:
-                            dups.append(p)
-                    K0_, K1_, pid, (n0, n1) = fast
-                    return (torch.as_tensor(K0_), torch.as_tensor(K1_), int(pid), n1, n0)
-            smp = get(items[p]) if smp is None else smp
-            c_np[2 * p], c_np[2 * p + 1] = rgb_bytes(smp["image0"]), rgb_bytes(smp["image1"])
-            im_np[2 * p, 0], im_np[2 * p + 1, 0] = npv(to_gray(smp["image0"])), npv(to_gray(smp["image1"]))
-            return (torch.as_tensor(smp["K_color0"]), torch.as_tensor(smp["K_color1"]), int(smp["pair_id"]), smp["pair_names"][1], smp["pair_names"][0])
+        def ref_gray(img):
+            hit = gray_of.get(id(img))
+            if hit is None or hit[0] is not img:
+                g = to_gray(img)
+                hit = gray_of[id(img)] = (img, g.numpy() if isinstance(g, torch.Tensor) else np.asarray(g))
+            return hit[1]
 
         def fill(p, smp=None):
-            if self.rgb:
-                return fill_rgb(p, smp)
-            sc_ = self.scenes[items[p][0]]
-            if smp is None and getattr(sc_, "has_gray_pair", False):      # gray planes / depth straight from the files' bytes into the batch buffers
-                want, readers, kw = True, None, {}
-                if jp is not None:
-                    want = jp["want"][p]
-                    h_np, r_np = jp["headers"].numpy(), jp["records"].numpy()
-                    readers = (_jpeg_reader(h_np, r_np, 2 * p, jp["rows"]), _jpeg_reader(h_np, r_np, 2 * p + 1, jp["rows"]))
-                if png and getattr(sc_, "has_depth_readers", False):
-                    kw = dict(depth_readers=(_png_reader((0, p), pinfos[p]) if want_ref[p] else _png_skip, _png_reader((1, p), pinfos[p])))
-                fast = sc_.gray_pair(items[p][1], want, out=(im_np[2 * p, 0], d0_np[p] if has_depth else None, im_np[2 * p + 1, 0],
-                                                             d1_np[p] if has_depth else None), readers=readers, **kw)
-                if fast is not None:
-                    if not want:
-                        jp["rows"][2 * p] = ("dup", 2 * jp["first_of"][jp["key"][p]])
-                    _, _, _, _, K0_, K1_, pid, (n0, n1) = fast
-                    return (torch.as_tensor(K0_), torch.as_tensor(K1_), int(pid), n1, n0)
-            smp = get(items[p]) if smp is None else smp
-            k0 = id(smp["image0"])
-            hit = gray_of.get(k0)
-            if hit is None or hit[0] is not smp["image0"]:
-                hit = gray_of[k0] = (smp["image0"], npv(to_gray(smp["image0"])))
-            im_np[2 * p, 0] = hit[1]
-            im_np[2 * p + 1, 0] = npv(to_gray(smp["image1"]))
-            if has_depth:
-                d0_np[p] = npv(smp["depth0"]); d1_np[p] = npv(smp["depth1"])
-            return (torch.as_tensor(smp["K_color0"]), torch.as_tensor(smp["K_color1"]), int(smp["pair_id"]), smp["pair_names"][1], smp["pair_names"][0])
+            return _fill_pair(self.scenes[items[p][0]], items[p][1], plan.want_ref[p], _pair_dest(p, *views, png), smp=smp, ref_gray=ref_gray)
         if self.workers > 1 and b > 1:
             if self._pool is None:
                 import concurrent.futures
@@ -1159,60 +1120,49 @@ class PairBatchLoader:
             meta = [fill(0, first)] + [f.result() for f in futs]             # order preserved
         else:
             meta = [fill(0, first)] + [fill(p) for p in range(1, b)]
-        for p in dups:
-            np.copyto(im_np[2 * p, 0], im_np[2 * first_of[p], 0]); np.copyto(c_np[2 * p], c_np[2 * first_of[p]])
+        return self._batch(plan, meta, *bufs, jpeg, self._share_refs(plan, meta, *bufs, jpeg), png)
+
+    def _share_refs(self, plan, meta, images, depth0, depth1, colour, jpeg):
+        """the reference gray (and colour) rows that no pair filled: the device JPEG route's row table says which the device duplicates, the
+        others are host copies of the row of the pair that decoded the view.  -> the row table (None off the device JPEG route)"""
+        rows = _jpeg_rows(plan, meta) if jpeg is not None else None
+        for p, m in enumerate(meta):
+            if not m.has_ref and (rows is None or rows[2 * p] is None):
+                q = plan.first_of[p]
+                np.copyto(images.numpy()[2 * p, 0], images.numpy()[2 * q, 0])
+                if colour is not None:
+                    np.copyto(colour.numpy()[2 * p], colour.numpy()[2 * q])
+        return rows
+
+    def _batch(self, plan, meta, images, depth0, depth1, colour, jpeg, jpeg_rows, png, **extra):
+        """the batch dictionary of both decoders, from the plan, the pairs' _PairMeta and the filled buffers (b pairs' rows each; jpeg =
+        (headers, records) with its row table, png = the device depth route is on)"""
+        items, b, mk = plan.items, len(plan.items), self._mk
         # intrinsics keep the loader's dtype (float64 on Map-free, float32 on resize=None datasets): the solvers evaluate
         # inv(K) / the K-normalisation in that dtype, as the reference does (include/mfr_hip.h k_dtype)
-        kdt = torch.float64 if any(m[0].dtype == torch.float64 or m[1].dtype == torch.float64 for m in meta) else torch.float32
+        kdt = torch.float64 if any(m.K0.dtype == np.float64 or m.K1.dtype == np.float64 for m in meta) else torch.float32
         K0 = mk(b, 3, 3, dtype=kdt); K1 = mk(b, 3, 3, dtype=kdt)
         for p, m in enumerate(meta):
-            K0[p] = m[0]; K1[p] = m[1]
+            K0[p] = torch.as_tensor(m.K0); K1[p] = torch.as_tensor(m.K1)
         sc = self.scenes[items[-1][0]]
         done = [self.scenes[si].scene_id for si, i in items if i == len(self.scenes[si]) - 1]
-        extra = {} if jp is None else dict(jpeg=dict(headers=jp["headers"], records=jp["records"], rows=jp["rows"]))
+        device = {} if jpeg is None else dict(jpeg=dict(headers=jpeg[0], records=jpeg[1], rows=jpeg_rows))
         if png:
-            extra["png"] = _png_rows(b, want_ref, first_of, pinfos, mk)
-        if self.rgb:
-            extra["rgb"] = colour
-        return dict(images=images, depth0=depth0, depth1=depth1, K0=K0, K1=K1, **extra,
-                    seed_ids=torch.tensor([m[2] for m in meta], dtype=torch.int64),
+            device["png"] = _png_rows(plan, meta, mk)
+        if colour is not None:
+            device["rgb"] = colour
+        return dict(images=images, depth0=depth0, depth1=depth1, K0=K0, K1=K1, **device,
+                    seed_ids=torch.tensor([m.pair_id for m in meta], dtype=torch.int64),
                     global_ids=torch.tensor([self.offsets[si] + i for si, i in items], dtype=torch.int64),
-                    names=[m[3] for m in meta], scene_ids=[self.scenes[si].scene_id for si, _ in items],
+                    names=[m.name1 for m in meta], scene_ids=[self.scenes[si].scene_id for si, _ in items],
                     scene_roots=[self.scenes[si].scene_root for si, _ in items], scenes_done=done,
                     # identity of every pair's REFERENCE view (a val / test scene pairs one keyframe with all its queries, mapfree.py:148-165):
                     # what FusedPosePipeline keys its reference-view feature cache on
                     # -- only for scenes that DECLARE the sharing (`shared_reference`: MapFreeScene val / test); None = do not cache
-                    ref_keys=[self._ref_key(si, m[4]) if getattr(self.scenes[si], "shared_reference", False) else None
+                    ref_keys=[self._ref_key(si, m.name0) if getattr(self.scenes[si], "shared_reference", False) else None
                               for (si, _), m in zip(items, meta)],
-                    scene_id=sc.scene_id, scene_root=sc.scene_root, scene_index=items[-1][0], last_of_scene=bool(done and done[-1] == sc.scene_id))
-
-    def _ref_plan(self, items):
-        """(first_of [b], want [b]): want[p] = pair p is the first of the batch with its reference view (one per distinct scene that shares
-        its reference; every pair of other scenes), first_of[p] = the position of that first pair"""
-        seen, first_of, want = {}, [], []
-        for p, (si, i) in enumerate(items):
-            k = si if getattr(self.scenes[si], "shared_reference", False) else ("pair", p)
-            want.append(k not in seen)
-            first_of.append(seen.setdefault(k, p))
-        return first_of, want
-
-    def _jpeg_batch(self, items, mk=None, slot=None):
-        """device JPEG route of one batch: packed buffers (fresh pinned ones, or a process slot's), the row table (None = host plane in
-        `images`; (status, record bytes, path) from _jpeg_reader; ("dup", row) = device copy of that row) and the reference views to decode:
-        one per distinct (scene, shared reference), as the process decoder's want_ref"""
-        from .jpeg_ops import HEADER_BYTES
-        b = len(items)
-        if slot is None:
-            headers, records = mk(2 * b, HEADER_BYTES, dtype=torch.uint8), mk(2 * b, self.jpeg_cap, dtype=torch.uint8)
-        else:
-            headers, records = slot
-        first_of, want, key = {}, [], []
-        for p, (si, i) in enumerate(items):
-            k = si if getattr(self.scenes[si], "shared_reference", False) else ("pair", p)
-            key.append(k)
-            want.append(k not in first_of)
-            first_of.setdefault(k, p)
-        return dict(headers=headers, records=records, rows=[None] * (2 * b), want=want, key=key, first_of=first_of)
+                    scene_id=sc.scene_id, scene_root=sc.scene_root, scene_index=items[-1][0], last_of_scene=bool(done and done[-1] == sc.scene_id),
+                    **extra)
 
     POOL_ANSWER_S = 600.0            # a batch is < 1 s of decode; a pool that stays silent this long is dead (never wait for it for ever)
 
@@ -1225,23 +1175,15 @@ class PairBatchLoader:
             raise RuntimeError(f"PairBatchLoader: the decode workers did not answer within {self.POOL_ANSWER_S:.0f} s (pool closed)") from None
 
     def _load_process(self, items):
-        """the same batch through the process pool: workers write into a shared-memory slot; the first pair of the loader's life is
-        decoded here once to learn the shapes"""
+        """the same batch through the process pool: workers write into a shared-memory slot (_pw_fill); the layout is learnt once, when the
+        pool starts"""
         import time as _t
         b = len(items)
         st = self.stats
         if self._proc is None:
             t0 = _t.perf_counter()
-            layout = getattr(self.scenes[items[0][0]], "batch_layout", None)
-            if self.rgb and hasattr(self.scenes[items[0][0]], "gray_rgb_pair"):
-                sc0 = self.scenes[items[0][0]]
-                layout = lambda: (*sc0.frame_hw(items[0][1]), False)
-            if layout is not None:
-                Hh, Ww, has_depth = layout()
-            else:
-                first = self.scenes[items[0][0]][items[0][1]]
-                (Hh, Ww), has_depth = first["image0"].shape[-2:], first["depth0"].numel() > 0
-            self._proc = _ProcessDecoder(self.scenes, self.B, Hh, Ww, has_depth and not self.rgb, self.workers, max(self.prefetch, 0) + 4, self.pin,
+            Hh, Ww, has_depth, _ = _batch_layout(self.scenes[items[0][0]], items[0][1], self.rgb)
+            self._proc = _ProcessDecoder(self.scenes, self.B, Hh, Ww, has_depth, self.workers, max(self.prefetch, 0) + 4, self.pin,
                                          jpeg_cap=self.jpeg_cap if self.jpeg_decode == "device" else 0,
                                          png=self.depth_decode == "device", rgb=self.rgb)
             self._pool_map(_pw_ping, range(self.workers * 2))                          # every worker has started and imported its modules
@@ -1251,53 +1193,20 @@ class PairBatchLoader:
         k = pr.acquire()
         st["slot_wait_s"] = st.get("slot_wait_s", 0.0) + _t.perf_counter() - t0
         t0 = _t.perf_counter()
-        sl = pr.slots[k]
         # reference views: decoded once per distinct (scene, shared reference) of the batch, duplicates copied below
-        first_of, want = {}, []
-        for p, (si, i) in enumerate(items):
-            key = si if getattr(self.scenes[si], "shared_reference", False) else ("pair", p)
-            want.append(key not in first_of)
-            first_of.setdefault(key, p)
-        meta = self._pool_map(_pw_fill_rgb if self.rgb else _pw_fill, [(k, p, si, i, want[p]) for p, (si, i) in enumerate(items)])
-        jp = None
-        if pr.jslots is not None:
-            jp = self._jpeg_batch(items, slot=pr.jslots[k])
-            for p, m in enumerate(meta):
-                for r, v in m[6].items():
-                    jp["rows"][r] = v
-                if not want[p] and jp["rows"][2 * p + 1] is not None:     # a device-route pair whose reference is decoded in another row
-                    jp["rows"][2 * p] = ("dup", 2 * first_of[items[p][0]])
+        plan = _batch_plan(self.scenes, items)
+        done = self._pool_map(_pw_fill, [(k, p, si, i, plan.want_ref[p]) for p, (si, i) in enumerate(items)])
+        meta = [m for m, _ in done]
         st["decode_map_s"] = st.get("decode_map_s", 0.0) + _t.perf_counter() - t0
-        st["worker_task_s"] = st.get("worker_task_s", 0.0) + sum(m[5] for m in meta)
+        st["worker_task_s"] = st.get("worker_task_s", 0.0) + sum(dt for _, dt in done)
         st["batches"] = st.get("batches", 0) + 1
         t0 = _t.perf_counter()
-        im = sl["images"].numpy()
-        for p, (si, i) in enumerate(items):
-            if not want[p] and (jp is None or jp["rows"][2 * p] is None):
-                q = first_of[si]
-                np.copyto(im[2 * p, 0], im[2 * q, 0])
-                if self.rgb:
-                    np.copyto(pr.cslots[k].numpy()[2 * p], pr.cslots[k].numpy()[2 * q])
+        images, depth0, depth1, colour, jpeg = _slot_buffers(pr.slots[k])
+        bufs = (images[:2 * b], depth0[:b] if depth0 is not None else None, depth1[:b] if depth0 is not None else None,
+                colour[:2 * b] if colour is not None else None, jpeg)
+        rows = self._share_refs(plan, meta, *bufs)
         st["ref_copy_s"] = st.get("ref_copy_s", 0.0) + _t.perf_counter() - t0
-        K0 = torch.stack([torch.as_tensor(m[0]) for m in meta]); K1 = torch.stack([torch.as_tensor(m[1]) for m in meta])
-        sc = self.scenes[items[-1][0]]
-        done = [self.scenes[si].scene_id for si, i in items if i == len(self.scenes[si]) - 1]
-        has_depth = sl["depth0"] is not None
-        extra = {} if jp is None else dict(jpeg=dict(headers=jp["headers"], records=jp["records"], rows=jp["rows"]))
-        if self.depth_decode == "device" and has_depth:
-            mk = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, pin_memory=bool(self.pin and torch.cuda.is_available()))
-            extra["png"] = _png_rows(b, want, [first_of[items[p][0]] if not want[p] else p for p in range(b)], [m[7] for m in meta], mk)
-        if self.rgb:
-            extra["rgb"] = pr.cslots[k][:2 * b]
-        return dict(images=sl["images"][:2 * b], depth0=sl["depth0"][:b] if has_depth else None, depth1=sl["depth1"][:b] if has_depth else None,
-                    K0=K0, K1=K1, **extra, seed_ids=torch.tensor([m[2] for m in meta], dtype=torch.int64),
-                    global_ids=torch.tensor([self.offsets[si] + i for si, i in items], dtype=torch.int64),
-                    names=[m[3] for m in meta], scene_ids=[self.scenes[si].scene_id for si, _ in items],
-                    scene_roots=[self.scenes[si].scene_root for si, _ in items], scenes_done=done,
-                    ref_keys=[self._ref_key(si, m[4]) if getattr(self.scenes[si], "shared_reference", False) else None
-                              for (si, _), m in zip(items, meta)],
-                    scene_id=sc.scene_id, scene_root=sc.scene_root, scene_index=items[-1][0], last_of_scene=bool(done and done[-1] == sc.scene_id),
-                    _slot=(pr, k))
+        return self._batch(plan, meta, *bufs, rows, self.depth_decode == "device" and depth0 is not None, _slot=(pr, k))
 
     def close(self):
         if self._proc is not None:
@@ -1366,10 +1275,32 @@ class DevicePrefetcher:
                 pr.events[k] = ev
         return db, ev, check
 
+    def _decode_rows(self, rows, dev_rows, cap, record, decode, outs, what):
+        """what the two device decode routes share (on the side stream): the records of `dev_rows` packed at r * cap (record(r) = the host bytes
+        that hold row r's record), their offsets and status words, decode(d_rec, d_off, d_st) -- the route's launch --, the status copy into a
+        pinned word array that _ready checks when the batch is handed out, then the ("dup", source) rows duplicated in every tensor of `outs`.
+        -> the check tuple (None when the device decoded nothing)"""
+        n2, h_status = len(rows), None
+        if dev_rows:
+            d_rec = torch.empty(n2 * cap + 16, dtype=torch.uint8, device=self.device)
+            for r in dev_rows:
+                nb = rows[r][1]
+                d_rec[r * cap:r * cap + nb].copy_(record(r)[:nb], non_blocking=True)
+            d_off = torch.arange(n2 + 1, dtype=torch.int64, device=self.device) * cap
+            d_st = torch.zeros(n2, dtype=torch.int32, device=self.device)
+            decode(d_rec, d_off, d_st)
+            h_status = torch.empty(n2, dtype=torch.int32, pin_memory=True)
+            h_status.copy_(d_st, non_blocking=True)
+        for r in range(n2):
+            if rows[r] is not None and rows[r][0] == "dup":
+                for t in outs:
+                    t[r].copy_(t[rows[r][1]], non_blocking=True)
+        return (h_status, [(r, rows[r][2]) for r in dev_rows], what) if dev_rows else None
+
     def _put_jpeg(self, hb, db):
         """device JPEG route (on the side stream): host planes of the rows the host decoded, then the packed headers / records of the others
-        and the decode kernels straight into the batch's device images, then the duplicated reference rows.  The per-image status goes to a
-        pinned word array that _ready checks when the batch is handed out.  When the files are not at the batch's size (the headers say so:
+        and the decode kernels straight into the batch's device images, then the duplicated reference rows (_decode_rows).  When the files are
+        not at the batch's size (the headers say so:
         ScanNet's 1296 x 968 frames for a 640 x 480 batch) they are decoded at their own size into RGB scratch and resized into the batch's
         rows on the device (jpeg_ops.GrayResizer: the plane read_gray_plane(path, (W, H)) gives on the host route, bit for bit)."""
         from . import jpeg_ops as J
@@ -1385,22 +1316,18 @@ class DevicePrefetcher:
                 d_img[r].copy_(images[r], non_blocking=True)
                 if d_rgb is not None:
                     d_rgb[r].copy_(colour[r], non_blocking=True)
-        h_status = None
+        hdr, rec = jp["headers"][:n2], jp["records"][:n2]
+        cap, d_hdr = rec.shape[1], None
         if dev_rows:
             if self._jdec is None:
                 self._jdec = J.JpegDecoder(self.device)
-            hdr, rec = jp["headers"][:n2], jp["records"][:n2]
             st_field = hdr.numpy()[:, :4].view(np.int32)            # rows the device must not touch are marked unsupported
             for r in range(n2):
                 if r not in dev_rows:
                     st_field[r, 0] = J.UNSUPPORTED
-            cap = rec.shape[1]
             d_hdr = hdr.to(self.device, non_blocking=True)
-            d_rec = torch.empty(n2 * cap + 16, dtype=torch.uint8, device=self.device)
-            for r in dev_rows:
-                d_rec[r * cap:r * cap + rows[r][1]].copy_(rec[r, :rows[r][1]], non_blocking=True)
-            d_off = torch.arange(n2 + 1, dtype=torch.int64, device=self.device) * cap
-            d_st = torch.zeros(n2, dtype=torch.int32, device=self.device)
+
+        def decode(d_rec, d_off, d_st):
             fH, fW = (int(v) for v in hdr.numpy()[dev_rows[0], 4:12].view(np.int32)[::-1])     # mfr_jpeg_header: status, width, height
             if (fH, fW) == (H, W):
                 self._jdec.decode_device(d_hdr, d_rec, d_off, n2, H, W, cap, d_img, d_st, d_rgb)
@@ -1413,22 +1340,16 @@ class DevicePrefetcher:
                     self._jres = J.GrayResizer(self.device)
                 self._jres(scratch, d_img, d_st)
                 scratch.record_stream(torch.cuda.current_stream(self.device))
-            h_status = torch.empty(n2, dtype=torch.int32, pin_memory=True)
-            h_status.copy_(d_st, non_blocking=True)
-        for r in range(n2):
-            if rows[r] is not None and rows[r][0] == "dup":
-                d_img[r].copy_(d_img[rows[r][1]], non_blocking=True)
-                if d_rgb is not None:
-                    d_rgb[r].copy_(d_rgb[rows[r][1]], non_blocking=True)
+        check = self._decode_rows(rows, dev_rows, cap, lambda r: rec[r], decode, [d_img] + ([d_rgb] if d_rgb is not None else []), "JPEG")
         db["images"] = d_img
         if d_rgb is not None:
             db["rgb"] = d_rgb
-        return (h_status, [(r, rows[r][2]) for r in dev_rows], "JPEG") if dev_rows else None
+        return check
 
     def _put_png(self, hb, db):
         """device depth route (on the side stream): the planes of the rows the host decoded, then the records of the others (each lies at the
         start of its own pinned depth plane; only its bytes are copied) with the headers, the decode kernel straight into the batch's device
-        depth maps, then the duplicated reference rows.  The per-image status goes to a pinned word array that _ready checks."""
+        depth maps, then the duplicated reference rows (_decode_rows)."""
         from . import png_ops as P
         pg, d0, d1 = hb["png"], hb["depth0"], hb["depth1"]
         b, (H, W) = d0.shape[0], d0.shape[-2:]
@@ -1439,26 +1360,17 @@ class DevicePrefetcher:
         for r in range(n2):
             if rows[r] is None:
                 d_depth[r].copy_(plane(r), non_blocking=True)
-        h_status = None
+        cap = d_hdr = None
         if dev_rows:
             if self._pdec is None:
                 self._pdec = P.DepthPngDecoder(self.device)
             cap = max(rows[r][1] for r in dev_rows)                 # record sizes are multiples of 16
             d_hdr = pg["headers"].to(self.device, non_blocking=True)
-            d_rec = torch.empty(n2 * cap + 16, dtype=torch.uint8, device=self.device)
-            for r in dev_rows:
-                nb = rows[r][1]
-                d_rec[r * cap:r * cap + nb].copy_(plane(r).reshape(-1).view(torch.uint8)[:nb], non_blocking=True)
-            d_off = torch.arange(n2 + 1, dtype=torch.int64, device=self.device) * cap
-            d_st = torch.zeros(n2, dtype=torch.int32, device=self.device)
-            self._pdec.decode_device(d_hdr, d_rec, d_off, n2, H, W, cap, d_depth, d_st)
-            h_status = torch.empty(n2, dtype=torch.int32, pin_memory=True)
-            h_status.copy_(d_st, non_blocking=True)
-        for r in range(n2):
-            if rows[r] is not None and rows[r][0] == "dup":
-                d_depth[r].copy_(d_depth[rows[r][1]], non_blocking=True)
+        check = self._decode_rows(rows, dev_rows, cap, lambda r: plane(r).reshape(-1).view(torch.uint8),
+                                  lambda d_rec, d_off, d_st: self._pdec.decode_device(d_hdr, d_rec, d_off, n2, H, W, cap, d_depth, d_st), [d_depth], "depth PNG")
         db["depth0"], db["depth1"] = d_depth[:b], d_depth[b:]
-        return (h_status, [(r, rows[r][2]) for r in dev_rows], "depth PNG") if dev_rows else None
+        return check
+
 
     def __iter__(self):
         nxt = None
