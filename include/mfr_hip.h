@@ -837,6 +837,59 @@ int mfr_dpt_prep_rows(const uint8_t *img, int N, const int *rows, int m, int H, 
 int mfr_dpt_head_tail_rows(const float *f, const float *w, float bias, int B, int C, int Hh, int Wh, int invert, float scale, float shift, int Ho, int Wo,
                            const int *src, const int *dst, int d, float *metres, uint16_t *mm, int D, int quantize, int *status, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * EfficientLoFTR (Wang et al., "Efficient LoFTR: Semi-Dense Local Feature Matching with Sparse-Like Speed", CVPR 2024), the kernels the
+ * convolution / GEMM / coarse-matching entry points above do not cover (csrc/eloftr.hip; network: nets/eloftr.py).  The architecture of record is
+ * `transformers.EfficientLoFTRForKeypointMatching` with the default configuration: hidden size 256, 8 heads x 32, 4 x 4 aggregation, 8 x 8 / 10 x 10
+ * fine windows of 64 channels split 56 | 8.  fp32 storage and arithmetic.  Every argument check returns MFR_E_ARG before any launch; all pointers
+ * are device memory.
+ *   mfr_eloftr_stem_s2        y [B,Cout,H/2,W/2] = relu(conv3x3(x [B,1,H,W], w [Cout,1,3,3], stride 2, pad 1) + bias): the folded first RepVGG block
+ *                             (mfr_conv3x3_c1_relu is stride 1).  H, W even, Cout <= 64.
+ *   mfr_eloftr_aggregate      token rows x (token p of image i at x + i img_stride + p ldx, 256 channels, grid hc x wc, both multiples of 4) ->
+ *                             q_out [nimg, hc/4 * wc/4, 256] = LayerNorm(depthwise 4x4 / stride 4 convolution, wq [256,1,4,4], no bias) and
+ *                             kv_out (same shape) = LayerNorm(4x4 / stride 4 max-pool): ONE LayerNorm (gamma, beta, eps) for both, the 16 tokens of a
+ *                             cell read once.  Either output may be NULL (cross attention takes q and k / v from different images).
+ *   mfr_eloftr_rotary         rotary encoding in place on rows of q (and k, may be NULL) [rows, 256], row stride ld, row r at position r % La:
+ *                             cos_sin [La, 256] = cos [128] | sin [128]; the pair (2 i, 2 i + 1) turns by angle i (the module's interleaved
+ *                             rotate_half on the whole vector, before the split into heads).
+ *   mfr_eloftr_attention      out = softmax(q k^T / sqrt(32)) v per head, heads x 32 contiguous channels, q [nb, Lq, .] (row stride ldq), k, v
+ *                             [nb, Lk, .] (row stride ldkv), out row stride ldo: the short-sequence kernel (a wavefront owns 64 queries, key tiles of
+ *                             a head in LDS); strides multiples of 4, pointers 16-byte aligned.
+ *   mfr_eloftr_upsample4_rows dst rows of the 4 ha x 4 wa token grid (row stride ldx, image stride img_stride) = F.interpolate(msg [nimg, ha wa, 256]
+ *                             as a map, scale_factor=4, bilinear, align_corners=False): the right half of the MLP's [x | message] operand.
+ *   mfr_eloftr_upsample2x     out [planes,2H,2W] = (add, may be NULL) + F.interpolate(in [planes,H,W], scale_factor=2, bilinear, align_corners=False)
+ *   mfr_eloftr_leaky_relu     x [rows, N] (row stride ld; N, ld multiples of 4) <- leaky_relu(x, slope) in place
+ *   mfr_eloftr_rows_to_nchw   out [nimg, C, HW] = scale * token rows x (as for _aggregate), C % 32 == 0: the transformer's output as the map the fine
+ *                             pyramid convolves, with the module's 1 / sqrt(hidden) in the same pass.
+ *   mfr_eloftr_gather_windows out [B maxN, win^2, 64]: slot b maxN + s (s < min(n[b], maxN); other slots untouched) = the win x win window of image
+ *                             img_ids[b] whose origin is the corner of cell cell_ids[b ld_cells + s] (grid width wc, cell_px pixels) minus pad, in the
+ *                             FULL-resolution frame 2 Hh x 2 Wh, zeros outside it (unfold's padding).  feat_half [nimg, Hh, Wh, 64] is the HALF
+ *                             resolution NHWC map: the pyramid's last x2 bilinear up-sampling is evaluated per window pixel, the full-resolution map
+ *                             is never written.  (win, pad) = (8, 0) for image 0, (10, 1) for image 1.
+ *   mfr_eloftr_fine_match     the two-stage refinement per slot, one wavefront each: stage 1 = correlation of the first 56 channels (both / sqrt 56),
+ *                             softmax over rows x softmax over columns of the 64 x 100 matrix, interior 8 x 8, arg-max (lowest index on ties),
+ *                             offsets grid - 4 + 0.5; stage 2 = last 8 channels (window 1 / sqrt 8), the 3 x 3 values of the padded 10 x 10 grid at
+ *                             the UNPADDED winner index + {-1, 0, 1} (-1 wraps to 9, as in the module), softmax(. / 10), expectation added to pts1.
+ *                             pts0 / pts1 [B maxN, 2] pixels of the padded frame; stage1_arg [B maxN] (may be NULL) the flat arg-max index.
+ *   mfr_eloftr_compact        per pair, the first min(n[b], maxN) slots in order with both end points inside the unpadded frame (x < W, y < H) ->
+ *                             out0 / out1 [B, maxN, 2], out_conf [B, maxN] (from conf [B, ld_conf]) zero-filled behind n_out[b].
+ * ------------------------------------------------------------------------------------------ */
+int mfr_eloftr_stem_s2(const float *x, const float *w, const float *bias, int B, int H, int W, int out_channels, float *y, void *stream);
+int mfr_eloftr_aggregate(const float *x, int ldx, long long img_stride, int nimg, int hc, int wc, const float *wq, const float *gamma, const float *beta, float eps,
+                         float *q_out, float *kv_out, void *stream);
+int mfr_eloftr_rotary(float *q, float *k, int ld, const float *cos_sin, long long rows, int La, void *stream);
+int mfr_eloftr_attention(const float *q, int ldq, const float *k, const float *v, int ldkv, int nb, int Lq, int Lk, int heads, float *out, int ldo, void *stream);
+int mfr_eloftr_upsample4_rows(const float *msg, int ldm, int nimg, int ha, int wa, float *dst, int ldx, long long img_stride, void *stream);
+int mfr_eloftr_upsample2x(const float *in, const float *add, float *out, int planes, int H, int W, void *stream);
+int mfr_eloftr_leaky_relu(float *x, int ld, long long rows, int N, float slope, void *stream);
+int mfr_eloftr_rows_to_nchw(const float *x, int ldx, long long img_stride, int nimg, int C, int HW, float scale, float *out, void *stream);
+int mfr_eloftr_gather_windows(const float *feat_half, int nimg, int Hh, int Wh, int C, const int32_t *img_ids, const int32_t *cell_ids, long long ld_cells,
+                              const int32_t *n, int B, int maxN, int wc, int cell_px, int win, int pad, float *out, void *stream);
+int mfr_eloftr_fine_match(const float *win0, const float *win1, const int32_t *cell_i, const int32_t *cell_j, long long ld_cells, const int32_t *n, int B, int maxN,
+                          int wc, int cell_px, float *pts0, float *pts1, int32_t *stage1_arg, void *stream);
+int mfr_eloftr_compact(const float *pts0, const float *pts1, const float *conf, long long ld_conf, const int32_t *n, int B, int maxN, int W, int H, float *out0,
+                       float *out1, float *out_conf, int32_t *n_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,17 @@ SIGNATURES = {
     "mfr_dpt_head_tail": (_i, [_vp, _vp, C.c_float, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp, _vp]),
     "mfr_dpt_prep_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "mfr_dpt_head_tail_rows": (_i, [_vp, _vp, C.c_float, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "mfr_eloftr_stem_s2": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "mfr_eloftr_aggregate": (_i, [_vp, _i, C.c_longlong, _i, _i, _i, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp]),
+    "mfr_eloftr_rotary": (_i, [_vp, _vp, _i, _vp, C.c_longlong, _i, _vp]),
+    "mfr_eloftr_attention": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "mfr_eloftr_upsample4_rows": (_i, [_vp, _i, _i, _i, _i, _vp, _i, C.c_longlong, _vp]),
+    "mfr_eloftr_upsample2x": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mfr_eloftr_leaky_relu": (_i, [_vp, _i, C.c_longlong, _i, C.c_float, _vp]),
+    "mfr_eloftr_rows_to_nchw": (_i, [_vp, _i, C.c_longlong, _i, _i, _i, C.c_float, _vp, _vp]),
+    "mfr_eloftr_gather_windows": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, C.c_longlong, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mfr_eloftr_fine_match": (_i, [_vp, _vp, _vp, _vp, C.c_longlong, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "mfr_eloftr_compact": (_i, [_vp, _vp, _vp, C.c_longlong, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

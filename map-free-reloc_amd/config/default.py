@@ -44,6 +44,8 @@ keys this implementation adds (declared here because unknown keys are rejected o
   SUPERGLUE.*        matcher hyper-parameters of record (matchers.py:65-71) and weight paths
   LIGHTGLUE.*        'LightGlue' feature matching: WEIGHTS (a state dict with the `transformers` LightGlue parameter names), FILTER_THRESHOLD,
                      NUM_LAYERS, SuperPoint's MAX_KEYPOINTS / KEYPOINT_THRESHOLD / NMS_RADIUS; DEPTH_CONFIDENCE / WIDTH_CONFIDENCE must stay -1
+  ELOFTR.*           'EfficientLoFTR' feature matching (nets/eloftr.py): WEIGHTS (a state dict with the `transformers` EfficientLoFTRForKeypointMatching
+                     parameter names), MATCH_THRESHOLD / BORDER_RM / TEMPERATURE of the dual-softmax coarse matcher, MAX_MATCHES (0: every cell), SYNTHETIC_SEED
   DPT.*              DPT-Hybrid monocular depth (nets/dpt.py, compute_depth.py): WEIGHTS (a state dict with the `transformers` DPTForDepthEstimation parameter
                      names), NET_HEIGHT / NET_WIDTH (multiples of 32), SCALE / SHIFT / INVERT (depth = 1 / (SCALE p + SHIFT): the output convention of the
                      KITTI / NYU checkpoints), QUANTIZE_MM (hand the solver the millimetre-rounded map, the bits a depth PNG holds),
@@ -115,6 +117,10 @@ def get_cfg_defaults():
     for k, v in dict(WEIGHTS='', FILTER_THRESHOLD=0.1, NUM_LAYERS=9, MAX_KEYPOINTS=1024, KEYPOINT_THRESHOLD=0.005, NMS_RADIUS=4,
                      DEPTH_CONFIDENCE=-1, WIDTH_CONFIDENCE=-1).items():
         c.LIGHTGLUE[k] = v
+    # EfficientLoFTR (nets/eloftr.py): the module's defaults (coarse_matching_threshold / _border_removal / _temperature)
+    c.ELOFTR = CN()
+    for k, v in dict(WEIGHTS='', MATCH_THRESHOLD=0.2, BORDER_RM=2, TEMPERATURE=0.1, MAX_MATCHES=0, SYNTHETIC_SEED=1357).items():
+        c.ELOFTR[k] = v
     # DPT-Hybrid depth (nets/dpt.py).  SCALE / SHIFT / INVERT: dpt_hybrid_kitti's output convention (UPSTREAM-KNOWLEDGE: isl-org/DPT run_monodepth.py; NYU: 0.000305 /
     # 0.1378 / True); synthetic weights (ALLOW_SYNTHETIC_WEIGHTS) come from nets/weights.dpt_state_dict(SYNTHETIC_SEED) and want INVERT False
     c.DPT = CN()

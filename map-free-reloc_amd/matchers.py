@@ -1,7 +1,7 @@
 """Offline matcher plugins with the reference's API (etc/feature_matching_baselines/matchers.py):
 class M(resize: (W, H), outdoor: bool) with match(pair_path: (str, str)) -> ndarray [N,4]
 (x0,y0,x1,y1) in the resized pixel frame, or np.full((1,4), nan) when there is no correspondence
-(:59, :120); registered in MATCHERS and driven by compute.py (-ds Mapfree -m SG|LoFTR|SIFT|LG).
+(:59, :120); registered in MATCHERS and driven by compute.py (-ds Mapfree -m SG|LoFTR|SIFT|LG|ELoFTR).
 
 Image reading: the reference uses SuperGlue's read_image (cv2.imread GRAYSCALE, cv2.resize of the float
 image to (W,H), /255).  cv2 is not available offline: the file is decoded with PIL and the
@@ -103,6 +103,28 @@ class LoFTR_matcher:
         return self.match_tensors(read_image(pair_path[0], self.resize), read_image(pair_path[1], self.resize))
 
 
+class ELoFTR_matcher:
+    """EfficientLoFTR (nets/eloftr.py; not in the reference).  weights_dir/efficientloftr.pth: a state dict with the `transformers`
+    EfficientLoFTRForKeypointMatching parameter names.  The stage pads to multiples of 32 itself and drops what lies outside the frame."""
+
+    def __init__(self, resize, outdoor=False, weights_dir="EfficientLoFTR/weights"):
+        from .nets.eloftr import EfficientLoFTRHIP
+        self.resize = resize
+        self.device = torch.device("cuda")
+        self.net = EfficientLoFTRHIP(_weights(os.path.join(weights_dir, "efficientloftr.pth"), WT.eloftr_state_dict, "EfficientLoFTR"), self.device)
+
+    def match_tensors(self, im0, im1):
+        out = self.net(torch.from_numpy(np.stack([im0, im1]))[:, None].to(self.device))
+        n = int(out["n_corr"][0])
+        if n > 0:
+            return torch.cat([out["pts0"][0, :n], out["pts1"][0, :n]], 1).cpu().numpy()
+        print("no correspondences")
+        return np.full((1, 4), np.nan)
+
+    def match(self, pair_path):
+        return self.match_tensors(read_image(pair_path[0], self.resize), read_image(pair_path[1], self.resize))
+
+
 class SIFT_matcher:
     """matchers.py:123-188: 2048 SIFT features, rootSIFT, 2-NN, ratio 0.8.  Detection is OpenCV's (or the
     `detector` callable's); the descriptor leg runs in csrc/descriptor_match.hip."""
@@ -130,4 +152,4 @@ class SIFT_matcher:
         return self.match_arrays(g[0], g[1])
 
 
-MATCHERS = {'LoFTR': LoFTR_matcher, 'SG': SuperGlue_matcher, 'SIFT': SIFT_matcher, 'LG': LightGlue_matcher}
+MATCHERS = {'LoFTR': LoFTR_matcher, 'SG': SuperGlue_matcher, 'SIFT': SIFT_matcher, 'LG': LightGlue_matcher, 'ELoFTR': ELoFTR_matcher}

@@ -8,6 +8,7 @@ pixel frame, N may be 0 (np.array([])).  Mirrors lib/models/matching/feature_mat
                        offline, etc/feature_matching_baselines/matchers.py:62-120)
   LoFTRMatching        NEW: online LoFTR on the GPU (reference: offline only, matchers.py:12-59)
   LightGlueMatching    NEW: online SuperPoint+LightGlue on the GPU (not in the reference; nets/lightglue.py)
+  EfficientLoFTRMatching  NEW: online EfficientLoFTR on the GPU (not in the reference; nets/eloftr.py)
   SIFTMatching         feature_matching.py:53-118: detectAndCompute from OpenCV, the HIP detector (SIFT.DETECTOR 'hip',
                        sift_ops.py) or a caller-supplied detector (raises ImportError when none exists), rootSIFT + exact 2-NN + ratio
                        test on the GPU (csrc/descriptor_match.hip) instead of FLANN
@@ -194,6 +195,40 @@ class LoFTRMatching:
                 out = self.net.fine_stage(c)                   # reads the graph's static buffers before the next replay
             n_t = out["n_corr"][:1].to(torch.float32)
             flat = torch.cat([n_t, self.guard.flag.to(torch.float32), out["pts0"][0].reshape(-1), out["pts1"][0].reshape(-1)]).cpu().numpy()      # one D2H copy
+        if flat[1] != 0:                                       # f16x2 range guard fired: the exact (bf16x3) twin
+            from .. import options
+            self.guard.reruns += 1
+            with options.override(SPLIT="bf16x3"):
+                return self.guard.twin().get_correspondences(data)
+        n = int(flat[0])
+        if n == 0:
+            e = np.array([])
+            return e, e
+        L = (len(flat) - 2) // 4
+        return flat[2:2 + 2 * L].reshape(L, 2)[:n].copy(), flat[2 + 2 * L:].reshape(L, 2)[:n].copy()
+
+
+class EfficientLoFTRMatching:
+    """online matcher: EfficientLoFTR (nets/eloftr.py; the reference has none).  The per-pair flow of LoFTRMatching -- gray stage, one packed D2H copy, range
+    guard with the bf16x3 twin -- but always eager: the stage has no host synchronisation to cut a graph at, and is not graph-captured"""
+
+    def __init__(self, cfg):
+        import torch
+        from ..nets import eloftr as EL
+        self.device = torch.device("cuda")
+        self.net = EL.from_cfg(cfg, self.device)
+        self._gray = _GrayPairStage()
+        from ..pipeline import RangeGuard
+        self.guard = RangeGuard(self.device, lambda: EfficientLoFTRMatching(cfg))
+
+    def get_correspondences(self, data):
+        import torch
+        ims = self._gray(data).to(self.device)
+        with torch.no_grad():
+            with self.guard:
+                out = self.net(ims)                            # pads to multiples of 32 itself, drops what lies outside the frame
+            flat = torch.cat([out["n_corr"][:1].to(torch.float32), self.guard.flag.to(torch.float32), out["pts0"][0].reshape(-1),
+                              out["pts1"][0].reshape(-1)]).cpu().numpy()                   # one D2H copy
         if flat[1] != 0:                                       # f16x2 range guard fired: the exact (bf16x3) twin
             from .. import options
             self.guard.reruns += 1

@@ -24,6 +24,7 @@ FEATURE_MATCHERS = {
     'SuperGlue': _fm.SuperGlueMatching,      # online, GPU (new)
     'LoFTR': _fm.LoFTRMatching,              # online, GPU (new)
     'LightGlue': _fm.LightGlueMatching,      # online, GPU (new): SuperPoint + LightGlue
+    'EfficientLoFTR': _fm.EfficientLoFTRMatching,    # online, GPU (new): nets/eloftr.py
 }
 POSE_SOLVERS = {
     'EssentialMatrix': _ps.EssentialMatrixSolver,

@@ -245,6 +245,79 @@ def dpt_state_dict(seed=8642, arch=None, head_bias=3.0, pos_grid=24):
     return sd
 
 
+ELOFTR_STAGES = ((1, 64, 2, 1), (64, 64, 1, 2), (64, 128, 2, 4), (128, 256, 2, 14))      # (Cin, Cout, stride of the first block, blocks) of the RepVGG stages
+
+
+def eloftr_state_dict(seed=1357, branch_gain=0.15, feat_gain=4.0, msg_gain=0.5, beta_gain=0.1, calib_hw=(96, 96)):
+    """EfficientLoFTR with the parameter names of `transformers.EfficientLoFTRForKeypointMatching` (default configuration).  The module's own
+    initialisation (BatchNorm gains ~ N(0, 0.02)) finds no match, and fan-in weights with arbitrary BatchNorm statistics grow to 1e5 through the 21
+    RepVGG blocks' three summed branches.  So:
+      * convolution / linear weights N(0, 1 / fan_in);
+      * every BatchNorm's running statistics are those of its input on ONE seeded calibration pair, layer by layer (activations stay O(1));
+      * in the blocks that have an identity branch, the two convolution branches' gains are scaled by `branch_gain`: features stay local, so a cell
+        of one image resembles the same cell of a near-identical image more than its neighbours;
+      * the last block is scaled by `feat_gain` (peaky dual softmax), the MLP LayerNorms by `msg_gain` / `beta_gain` (the transformer perturbs mildly).
+    Every affine term is NON-trivial here (BatchNorm gains x U(0.7, 1.3), biases N(0, 0.05), LayerNorm gains U(0.7, 1.3), biases N(0, 0.3)), so a
+    device module that drops or swaps one disagrees with the oracle on these weights.  Tuned on the CPU module alone (tests/test_eloftr_host.py);
+    parity with the published zju-community/efficientloftr weights is unpinned offline."""
+    import torch.nn.functional as F
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+
+    def conv(name, ci, co, k):
+        sd[f"{name}.weight"] = _randn(g, (co, ci, k, k), (ci * k * k) ** -0.5)
+        return sd[f"{name}.weight"]
+
+    def bn(name, y, gain, bias_gain=1.0):
+        """seeded affine terms, statistics of y: returns the normalised y"""
+        c = y.shape[1]
+        w = gain * (0.7 + 0.6 * torch.rand(c, generator=g))
+        b = 0.05 * bias_gain * torch.randn(c, generator=g)
+        m, v = y.mean((0, 2, 3)), y.var((0, 2, 3), unbiased=False)
+        sd[f"{name}.weight"], sd[f"{name}.bias"], sd[f"{name}.running_mean"], sd[f"{name}.running_var"] = w, b, m, v
+        sd[f"{name}.num_batches_tracked"] = torch.tensor(1)
+        return (y - m[None, :, None, None]) / torch.sqrt(v[None, :, None, None] + 1e-5) * w[None, :, None, None] + b[None, :, None, None]
+
+    x = torch.rand(2, 1, *calib_hw, generator=g)
+    feats = []
+    base = 3 ** -0.5                                                    # three (or two) branches of unit variance sum to ~1
+    for s, (ci, co, stride, blocks) in enumerate(ELOFTR_STAGES):
+        for b in range(blocks):
+            p = f"efficientloftr.backbone.stages.{s}.blocks.{b}"
+            cin, st = (ci, stride) if b == 0 else (co, 1)
+            ident = cin == co and st == 1
+            last = s == len(ELOFTR_STAGES) - 1 and b == blocks - 1
+            fg = feat_gain if last else 1.0
+            gain = base * (branch_gain if ident else 1.0) * fg
+            y = bn(f"{p}.conv1.norm", F.conv2d(x, conv(f"{p}.conv1.conv", cin, co, 3), stride=st, padding=1), gain, fg)
+            y = y + bn(f"{p}.conv2.norm", F.conv2d(x, conv(f"{p}.conv2.conv", cin, co, 1), stride=st), gain, fg)
+            if ident:
+                y = y + bn(f"{p}.identity", x, fg, fg)
+            x = F.relu(y)
+        feats.append(x)
+    for l in range(4):
+        for kind in ("self", "cross"):
+            p = f"efficientloftr.local_feature_transformer.layers.{l}.{kind}_attention"
+            sd[f"{p}.aggregation.q_aggregation.weight"] = _randn(g, (256, 1, 4, 4), 0.25)
+            sd[f"{p}.aggregation.norm.weight"] = 0.7 + 0.6 * torch.rand(256, generator=g)
+            sd[f"{p}.aggregation.norm.bias"] = _randn(g, (256,), 0.3)
+            for n in "qkvo":
+                sd[f"{p}.attention.{n}_proj.weight"] = _randn(g, (256, 256), 256 ** -0.5)
+            sd[f"{p}.mlp.fc1.weight"] = _randn(g, (512, 512), 512 ** -0.5)
+            sd[f"{p}.mlp.fc2.weight"] = _randn(g, (256, 512), 512 ** -0.5)
+            sd[f"{p}.mlp.layer_norm.weight"] = msg_gain * (0.7 + 0.6 * torch.rand(256, generator=g))
+            sd[f"{p}.mlp.layer_norm.bias"] = _randn(g, (256,), 0.3 * beta_gain)
+    # the fine pyramid, calibrated on the backbone's coarse map (the transformer changes it mildly)
+    up = lambda t: F.interpolate(t, scale_factor=2.0, mode="bilinear", align_corners=False)
+    h = up(F.conv2d(feats[3] / 16.0, conv("refinement_layer.out_conv", 256, 256, 1)))
+    for i, (res, hid, mid) in enumerate(((feats[2], 128, 256), (feats[1], 64, 128))):
+        p = f"refinement_layer.out_conv_layers.{i}"
+        r = F.conv2d(res, conv(f"{p}.out_conv1", hid, mid, 1)) + h
+        r = F.leaky_relu(bn(f"{p}.batch_norm", F.conv2d(r, conv(f"{p}.out_conv2", mid, mid, 3), padding=1), 1.0))
+        h = up(F.conv2d(r, conv(f"{p}.out_conv3", mid, hid, 3), padding=1))
+    return sd
+
+
 def load_checkpoint(path):
     """upstream .pth / .ckpt -> flat state dict.  superpoint_v1.pth / superglue_*.pth are plain state dicts;
     LoFTR's *_ot.ckpt are Lightning checkpoints that keep it under 'state_dict' with a `matcher.` prefix

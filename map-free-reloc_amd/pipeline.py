@@ -422,7 +422,7 @@ class _RefCachedLoFTR:
 
 class FusedPosePipeline:
     """The batched twin of FeatureMatchingModel (lib/models/matching/model.py:7-40): the same two config keys pick the
-    stages -- FEATURE_MATCHING in {'Precomputed', 'SuperGlue', 'LightGlue', 'LoFTR', 'SIFT' (SIFT.DETECTOR 'hip')} x POSE_SOLVER in {'PNP', 'EssentialMatrix',
+    stages -- FEATURE_MATCHING in {'Precomputed', 'SuperGlue', 'LightGlue', 'LoFTR', 'EfficientLoFTR', 'SIFT' (SIFT.DETECTOR 'hip')} x POSE_SOLVER in {'PNP', 'EssentialMatrix',
     'EssentialMatrixMetric', 'Procrustes'} -- but every stage consumes / produces a device-resident batch of pairs.
     __call__(batch) with the dict PairBatchLoader yields -> dict(R [b,3,3] f64, t [b,3] f64, n_inliers, status, n_corr).
     With DPT.SOURCE 'online' the batch carries `rgb` instead of depth maps (PairBatchLoader(rgb=True)) and the maps are computed here; the result then also
@@ -483,6 +483,17 @@ class FusedPosePipeline:
             stage = _RefCachedLoFTR(net, self.guard)
             # the backbone once per distinct reference view (both MATCH_TYPEs); switched off, every batch takes the stage's plain path
             self.match = stage if "REF_FEATURE_CACHE" in cfg.HIP and cfg.HIP.REF_FEATURE_CACHE else (lambda b: stage.plain(b["images"]))
+        elif fm == "EfficientLoFTR":
+            from .nets import eloftr as EL
+            net = EL.from_cfg(cfg, self.device)
+            stage = _RefCachedLoFTR(net, self.guard, pad_to=EL.PAD_TO)       # the per-image part is the backbone's three maps: the same pool, the same bits
+            cached = "REF_FEATURE_CACHE" in cfg.HIP and bool(cfg.HIP.REF_FEATURE_CACHE)
+
+            def match_eloftr(b):
+                net.frame_hw = tuple(b["images"].shape[-2:])                # the stage pads; matches outside the unpadded frame are dropped
+                return stage(b) if cached else stage.plain(b["images"])
+            match_eloftr.stats = stage.stats                                  # reference_views_run / _reused, as the LoFTR stage reports them
+            self.match = match_eloftr
         elif fm == "SIFT" and cfg.SIFT.get("DETECTOR", "opencv") == "hip":
             from .sift_ops import SiftDetector, sift_ratio_stage
             self.match = sift_ratio_stage(SiftDetector(cfg.SIFT.NUM_FEATURES, self.device), cfg.SIFT.RATIO_THRESHOLD)
