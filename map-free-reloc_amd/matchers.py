@@ -39,30 +39,43 @@ def _weights(path, synth, what):
     return synth()
 
 
-class SuperGlue_matcher:
-    def __init__(self, resize, outdoor=False, weights_dir="SuperGlue/models/weights"):
-        from .nets.superpoint import SuperPointHIP
-        from .nets.superglue import SuperGlueHIP
-        self.resize = resize
-        self.device = torch.device("cuda")
-        sp = _weights(os.path.join(weights_dir, "superpoint_v1.pth"), WT.superpoint_state_dict, "SuperPoint")
-        sg = _weights(os.path.join(weights_dir, f"superglue_{'outdoor' if outdoor else 'indoor'}.pth"),
-                      WT.superglue_state_dict, "SuperGlue")
-        self.sp = SuperPointHIP(sp, self.device, nms_radius=4, keypoint_threshold=0.005, max_keypoints=1024)   # :65-67
-        self.sg = SuperGlueHIP(sg, self.device, sinkhorn_iterations=20, match_threshold=0.2)                   # :70-71
+def _superpoint(weights_dir, device):
+    from .nets.superpoint import SuperPointHIP
+    sd = _weights(os.path.join(weights_dir, "superpoint_v1.pth"), WT.superpoint_state_dict, "SuperPoint")
+    return SuperPointHIP(sd, device, nms_radius=4, keypoint_threshold=0.005, max_keypoints=1024)                # :65-67
+
+
+def first_pair_rows(out):
+    """the first pair of a batched match dict (pts0, pts1 [B,K,2], n_corr [B]) -> [N,4] rows (x0,y0,x1,y1), or the reference's answer to no
+    correspondence: a print and one NaN row (:59, :120)"""
+    n = int(out["n_corr"][0])
+    if n > 0:
+        return torch.cat([out["pts0"][0, :n], out["pts1"][0, :n]], 1).cpu().numpy()
+    print("no correspondences")
+    return np.full((1, 4), np.nan)
+
+
+class _GrayPairMatcher:
+    """a matcher of two gray planes on the GPU: subclasses set `resize`, `device` and `_net(ims [2,1,H,W]) -> batched match dict`"""
 
     def match_tensors(self, im0, im1):
-        ims = torch.from_numpy(np.stack([im0, im1]))[:, None].to(self.device)
-        out = self.sg(self.sp(ims), tuple(ims.shape[-2:]))
-        n = int(out["n_corr"][0])
-        if n > 0:
-            return torch.cat([out["pts0"][0, :n], out["pts1"][0, :n]], 1).cpu().numpy()
-        print("no correspondences")
-        return np.full((1, 4), np.nan)
+        return first_pair_rows(self._net(torch.from_numpy(np.stack([im0, im1]))[:, None].to(self.device)))
 
     def match(self, pair_path):
         '''return correspondences between images (w/ path pair_path)'''
         return self.match_tensors(read_image(pair_path[0], self.resize), read_image(pair_path[1], self.resize))
+
+
+class SuperGlue_matcher(_GrayPairMatcher):
+    def __init__(self, resize, outdoor=False, weights_dir="SuperGlue/models/weights"):
+        from .nets.superglue import SuperGlueHIP
+        self.resize, self.device = resize, torch.device("cuda")
+        self.sp = _superpoint(weights_dir, self.device)
+        sg = _weights(os.path.join(weights_dir, f"superglue_{'outdoor' if outdoor else 'indoor'}.pth"), WT.superglue_state_dict, "SuperGlue")
+        self.sg = SuperGlueHIP(sg, self.device, sinkhorn_iterations=20, match_threshold=0.2)                   # :70-71
+
+    def _net(self, ims):
+        return self.sg(self.sp(ims), tuple(ims.shape[-2:]))
 
 
 class LightGlue_matcher(SuperGlue_matcher):
@@ -70,59 +83,34 @@ class LightGlue_matcher(SuperGlue_matcher):
     state dict with the `transformers` LightGlue parameter names"""
 
     def __init__(self, resize, outdoor=False, weights_dir="LightGlue/weights", sp_weights_dir="SuperGlue/models/weights"):
-        from .nets.superpoint import SuperPointHIP
         from .nets.lightglue import LightGlueHIP
-        self.resize = resize
-        self.device = torch.device("cuda")
-        sp = _weights(os.path.join(sp_weights_dir, "superpoint_v1.pth"), WT.superpoint_state_dict, "SuperPoint")
-        lg = _weights(os.path.join(weights_dir, "lightglue.pth"), WT.lightglue_state_dict, "LightGlue")
-        self.sp = SuperPointHIP(sp, self.device, nms_radius=4, keypoint_threshold=0.005, max_keypoints=1024)
-        self.sg = LightGlueHIP(lg, self.device, filter_threshold=0.1)
+        self.resize, self.device = resize, torch.device("cuda")
+        self.sp = _superpoint(sp_weights_dir, self.device)
+        self.sg = LightGlueHIP(_weights(os.path.join(weights_dir, "lightglue.pth"), WT.lightglue_state_dict, "LightGlue"), self.device, filter_threshold=0.1)
 
 
-class LoFTR_matcher:
+class LoFTR_matcher(_GrayPairMatcher):
     def __init__(self, resize, outdoor=False, weights_dir="LoFTR/weights", match_type="dual_softmax"):
         """match_type 'dual_softmax': the reference's behaviour (matchers.py:16-18 loads the OT checkpoint strict=False into the dual-softmax
         model, dropping coarse_matching.bin_score); 'sinkhorn': the optimal-transport matcher those weights were trained with"""
-        from .pipeline import LoFTREmatPipeline
-        self.resize = resize
+        from .nets.loftr import LoFTRHIP
+        self.resize, self.device = resize, torch.device("cuda")
         sd = _weights(os.path.join(weights_dir, "outdoor_ot.ckpt" if outdoor else "indoor_ot.ckpt"), WT.loftr_state_dict, "LoFTR")
-        sd = {k[len("matcher."):] if k.startswith("matcher.") else k: v for k, v in sd.items()}
-        self._pipe = LoFTREmatPipeline("cuda", loftr_state=sd, match_type=match_type)
+        self.net = LoFTRHIP(WT.strip_prefix(sd, "matcher."), self.device, match_type=match_type)
 
-    def match_tensors(self, im0, im1):
-        ims = torch.from_numpy(np.stack([im0, im1]))[:, None].to(self._pipe.device)
-        out = self._pipe.match(ims)
-        n = int(out["n_corr"][0])
-        if n > 0:
-            return torch.cat([out["pts0"][0, :n], out["pts1"][0, :n]], 1).cpu().numpy()
-        print("no correspondences")
-        return np.full((1, 4), np.nan)
-
-    def match(self, pair_path):
-        return self.match_tensors(read_image(pair_path[0], self.resize), read_image(pair_path[1], self.resize))
+    def _net(self, ims):
+        from .nets.loftr import pad_to_multiple
+        return self.net(pad_to_multiple(ims, 8))
 
 
-class ELoFTR_matcher:
+class ELoFTR_matcher(_GrayPairMatcher):
     """EfficientLoFTR (nets/eloftr.py; not in the reference).  weights_dir/efficientloftr.pth: a state dict with the `transformers`
     EfficientLoFTRForKeypointMatching parameter names.  The stage pads to multiples of 32 itself and drops what lies outside the frame."""
 
     def __init__(self, resize, outdoor=False, weights_dir="EfficientLoFTR/weights"):
         from .nets.eloftr import EfficientLoFTRHIP
-        self.resize = resize
-        self.device = torch.device("cuda")
-        self.net = EfficientLoFTRHIP(_weights(os.path.join(weights_dir, "efficientloftr.pth"), WT.eloftr_state_dict, "EfficientLoFTR"), self.device)
-
-    def match_tensors(self, im0, im1):
-        out = self.net(torch.from_numpy(np.stack([im0, im1]))[:, None].to(self.device))
-        n = int(out["n_corr"][0])
-        if n > 0:
-            return torch.cat([out["pts0"][0, :n], out["pts1"][0, :n]], 1).cpu().numpy()
-        print("no correspondences")
-        return np.full((1, 4), np.nan)
-
-    def match(self, pair_path):
-        return self.match_tensors(read_image(pair_path[0], self.resize), read_image(pair_path[1], self.resize))
+        self.resize, self.device = resize, torch.device("cuda")
+        self.net = self._net = EfficientLoFTRHIP(_weights(os.path.join(weights_dir, "efficientloftr.pth"), WT.eloftr_state_dict, "EfficientLoFTR"), self.device)
 
 
 class SIFT_matcher:
@@ -140,12 +128,7 @@ class SIFT_matcher:
         self.matcher = DescriptorRatioMatcher(0.8)                                          # :145
 
     def match_arrays(self, img0, img1):
-        out = self.matcher([self.detector(img0)], [self.detector(img1)])
-        n = int(out["n_corr"][0])
-        if n > 0:
-            return torch.cat([out["pts0"][0, :n], out["pts1"][0, :n]], 1).cpu().numpy()
-        print("no correspondences")
-        return np.full((1, 4), np.nan)
+        return first_pair_rows(self.matcher([self.detector(img0)], [self.detector(img1)]))
 
     def match(self, pair_path):
         g = [np.round(read_image(p, self.resize) * 255.0).astype(np.uint8) for p in pair_path]

@@ -14,6 +14,7 @@ pixel frame, N may be 0 (np.array([])).  Mirrors lib/models/matching/feature_mat
                        test on the GPU (csrc/descriptor_match.hip) instead of FLANN
 """
 import numpy as np
+import torch
 
 from .. import wire
 
@@ -55,7 +56,6 @@ class _GrayPairStage:
         self.buf = self.np = None
 
     def __call__(self, data):
-        import torch
         ims = [data['image0'][0], data['image1'][0]]
         if any(isinstance(im, torch.Tensor) and im.is_cuda for im in ims):      # device-resident inputs: torch ops on the device
             return torch.stack([_to_gray(im) for im in ims])[:, None].to(torch.float32)
@@ -74,57 +74,38 @@ class _GrayPairStage:
         return self.buf
 
 
-class SuperGlueMatching:
-    """online matcher: data['image0'], data['image1'] ([1,3,H,W] in [0,1]) -> correspondences"""
+class _OnlineMatching:
+    """What every online GPU plugin holds -- the device, the gray stage, the f16x2 range guard (its flag travels with the result, the exact twin is built on
+    demand) and the batch-1 graph switch around `_stage`, the part of the forward without host synchronisation -- and the one result tail."""
 
-    def __init__(self, cfg):
-        import torch
-        from ..nets import weights as WT
-        from ..nets.superpoint import SuperPointHIP
-        from ..nets.superglue import SuperGlueHIP
-        sg = cfg.SUPERGLUE
-        sp_sd = WT.load_checkpoint(sg.SUPERPOINT_WEIGHTS) if sg.SUPERPOINT_WEIGHTS else \
-            WT.synthetic_or_raise("SuperPoint", cfg, lambda: WT.superpoint_state_dict(sg.SYNTHETIC_SEED))
-        sg_sd = WT.load_checkpoint(sg.SUPERGLUE_WEIGHTS) if sg.SUPERGLUE_WEIGHTS else WT.synthetic_or_raise("SuperGlue", cfg, WT.superglue_state_dict)
-        self.device = torch.device("cuda")
-        self._init_common(SuperPointHIP(sp_sd, self.device, sg.NMS_RADIUS, sg.KEYPOINT_THRESHOLD, sg.MAX_KEYPOINTS),
-                          SuperGlueHIP(sg_sd, self.device, sg.SINKHORN_ITERATIONS, sg.MATCH_THRESHOLD), bool(cfg.HIP.GRAPH_BATCH1), lambda: SuperGlueMatching(cfg))
-
-    def _init_common(self, sp, net, use_graph, make_twin):
-        """what every SuperPoint + keypoint-matcher plugin holds: the two networks (`sg`: any net with SuperGlueHIP's call), the batch-1 graph
-        switch, the gray stage and the f16x2 range guard (flag travels with the result, exact twin on demand)"""
-        self.sp, self.sg = sp, net
-        self.use_graph = use_graph
-        self._graphs = {}
-        self._gray = _GrayPairStage()
+    def __init__(self, cfg, use_graph=False):
+        from ..nets.graph import GraphOrEager
         from ..pipeline import RangeGuard
-        self.guard = RangeGuard(self.device, make_twin)
+        self.device = torch.device("cuda")
+        self._gray = _GrayPairStage()
+        self.guard = RangeGuard(self.device, lambda: type(self)(cfg))
+        # batch 1 is launch-bound: `_stage` replayed from one HIP graph per image shape.  A replay is handed the gray stage's host tensor as it is
+        self._run = GraphOrEager(self._stage, type(self).__name__, enabled=use_graph, device=self.device)
 
-    def _forward(self, ims):
-        with self.guard:
-            out = self.sg(self.sp(ims), tuple(ims.shape[-2:]))
-        # one packed result so that the host needs a single D2H copy: [n | range flag | pts0 (K x 2) | pts1 (K x 2)]
-        import torch
-        return torch.cat([out["n_corr"].to(torch.float32), self.guard.flag.to(torch.float32), out["pts0"].reshape(-1), out["pts1"].reshape(-1)])
+    use_graph = property(lambda self: self._run.enabled)
+    _graphs = property(lambda self: self._run.graphs)
 
     def get_correspondences(self, data):
-        import torch
         ims = self._gray(data)
-        flat = None
-        if self.use_graph:                                   # batch 1 is launch-bound: replay the whole forward from one HIP graph
-            from ..nets.graph import GraphCaptureError, GraphedCall
-            key = tuple(ims.shape)
-            try:
-                if key not in self._graphs:
-                    self._graphs[key] = GraphedCall(self._forward, [ims.to(self.device)])
-                flat = self._graphs[key](ims).cpu().numpy()
-            except GraphCaptureError as e:
-                import warnings
-                warnings.warn(f"SuperGlueMatching: {e}; running eagerly from now on")
-                self.use_graph = False
-        if flat is None:
-            flat = self._forward(ims.to(self.device).contiguous()).cpu().numpy()
-        if flat[1] != 0:                                     # an activation left the f16x2 range: the same pair through the exact (bf16x3) twin
+        return self._unpack(data, self._tail(self._run(tuple(ims.shape), ims)))
+
+    def _tail(self, out):
+        """what follows `_stage`, eagerly: here the packing alone"""
+        with torch.no_grad():
+            return self._pack(out)
+
+    def _pack(self, out):
+        """the first pair of a match dict as ONE tensor, so that the host needs a single D2H copy: [n | range flag | pts0 (K x 2) | pts1 (K x 2)]"""
+        return torch.cat([out["n_corr"][:1].to(torch.float32), self.guard.flag.to(torch.float32), out["pts0"][0].reshape(-1), out["pts1"][0].reshape(-1)])
+
+    def _unpack(self, data, packed):
+        flat = packed.cpu().numpy()                            # the one D2H copy
+        if flat[1] != 0:                                       # an activation left the f16x2 range: the same pair through the exact (bf16x3) twin
             from .. import options
             self.guard.reruns += 1
             with options.override(SPLIT="bf16x3"):
@@ -137,109 +118,68 @@ class SuperGlueMatching:
         return flat[2:2 + 2 * K].reshape(K, 2)[:n].copy(), flat[2 + 2 * K:].reshape(K, 2)[:n].copy()
 
 
-class LightGlueMatching(SuperGlueMatching):
-    """online matcher: SuperPoint + LightGlue (nets/lightglue.py; the reference has no LightGlue).  Same per-pair flow as SuperGlueMatching -- packed
-    result, one D2H copy, range guard with the bf16x3 twin -- but always eager: no graph capture of this stage"""
+class SuperGlueMatching(_OnlineMatching):
+    """online matcher: data['image0'], data['image1'] ([1,3,H,W] in [0,1]) -> correspondences.  The whole forward, packing included, runs inside the guard
+    window and inside the captured graph (HIP.GRAPH_BATCH1)"""
 
     def __init__(self, cfg):
-        import torch
+        from ..nets import superglue as SG
+        super().__init__(cfg, bool(cfg.HIP.GRAPH_BATCH1))
+        self.sp, self.sg = SG.from_cfg(cfg, self.device)
+
+    def _stage(self, ims):
+        with self.guard:
+            out = self.sg(self.sp(ims), tuple(ims.shape[-2:]))
+        return self._pack(out)
+
+    def _tail(self, packed):
+        return packed
+
+
+class LightGlueMatching(SuperGlueMatching):
+    """online matcher: SuperPoint + LightGlue (nets/lightglue.py; the reference has no LightGlue).  Same per-pair flow as SuperGlueMatching, but always
+    eager: no graph capture of this stage"""
+
+    def __init__(self, cfg):
         from ..nets import lightglue as LG
-        self.device = torch.device("cuda")
-        self._init_common(*LG.from_cfg(cfg, self.device), False, lambda: LightGlueMatching(cfg))
+        _OnlineMatching.__init__(self, cfg)
+        self.sp, self.sg = LG.from_cfg(cfg, self.device)
 
 
-class LoFTRMatching:
+class LoFTRMatching(_OnlineMatching):
     """online matcher: LoFTR coarse-to-fine on the GPU (the reference only has it offline,
     etc/feature_matching_baselines/matchers.py:12-59), incl. the right-padding to a multiple of 8 (quirk Q3)"""
 
     def __init__(self, cfg):
-        import torch
-        from ..nets import weights as WT
-        from ..nets.loftr import LoFTRHIP
-        lw = cfg.LOFTR.WEIGHTS
-        sd = WT.strip_prefix(WT.load_checkpoint(lw), "matcher.") if lw else WT.synthetic_or_raise("LoFTR", cfg, WT.loftr_state_dict)
-        self.device = torch.device("cuda")
-        # LOFTR.MATCH_TYPE 'sinkhorn': the optimal-transport matcher with the checkpoint's bin_score (default: dual softmax, as the reference)
-        self.net = LoFTRHIP(sd, self.device, match_type=cfg.LOFTR.get("MATCH_TYPE", "dual_softmax"), skh_iters=cfg.LOFTR.get("SKH_ITERS", 3))
-        self._gray = _GrayPairStage()
-        self.use_graph = bool(cfg.HIP.GRAPH_BATCH1)
-        self._graphs = {}
-        from ..pipeline import RangeGuard
-        self.guard = RangeGuard(self.device, lambda: LoFTRMatching(cfg))
+        from ..nets import loftr as LO
+        super().__init__(cfg, bool(cfg.HIP.GRAPH_BATCH1))
+        self.net = LO.from_cfg(cfg, self.device)
 
-    def _coarse(self, ims):
-        import torch
+    def _stage(self, ims):
+        """everything before the match count is known: ~350 launches, captured"""
         H, W = ims.shape[-2:]
         with torch.no_grad(), self.guard:
             return self.net.coarse_stage(torch.nn.functional.pad(ims, (0, (-W) % 8, 0, (-H) % 8)).contiguous())
 
-    def get_correspondences(self, data):
-        import torch
-        ims = self._gray(data)
-        c = None
-        if self.use_graph:          # everything before the match count is known: ~350 launches replayed as one HIP graph
-            from ..nets.graph import GraphCaptureError, GraphedCall
-            key = tuple(ims.shape)
-            try:
-                if key not in self._graphs:
-                    self._graphs[key] = GraphedCall(self._coarse, [ims.to(self.device)])
-                c = self._graphs[key](ims)
-            except GraphCaptureError as e:
-                import warnings
-                warnings.warn(f"LoFTRMatching: {e}; running eagerly from now on")
-                self.use_graph = False
-        if c is None:
-            c = self._coarse(ims.to(self.device))
+    def _tail(self, c):
         with torch.no_grad():
             with self.guard.keep():
                 out = self.net.fine_stage(c)                   # reads the graph's static buffers before the next replay
-            n_t = out["n_corr"][:1].to(torch.float32)
-            flat = torch.cat([n_t, self.guard.flag.to(torch.float32), out["pts0"][0].reshape(-1), out["pts1"][0].reshape(-1)]).cpu().numpy()      # one D2H copy
-        if flat[1] != 0:                                       # f16x2 range guard fired: the exact (bf16x3) twin
-            from .. import options
-            self.guard.reruns += 1
-            with options.override(SPLIT="bf16x3"):
-                return self.guard.twin().get_correspondences(data)
-        n = int(flat[0])
-        if n == 0:
-            e = np.array([])
-            return e, e
-        L = (len(flat) - 2) // 4
-        return flat[2:2 + 2 * L].reshape(L, 2)[:n].copy(), flat[2 + 2 * L:].reshape(L, 2)[:n].copy()
+            return self._pack(out)
 
 
-class EfficientLoFTRMatching:
-    """online matcher: EfficientLoFTR (nets/eloftr.py; the reference has none).  The per-pair flow of LoFTRMatching -- gray stage, one packed D2H copy, range
-    guard with the bf16x3 twin -- but always eager: the stage has no host synchronisation to cut a graph at, and is not graph-captured"""
+class EfficientLoFTRMatching(_OnlineMatching):
+    """online matcher: EfficientLoFTR (nets/eloftr.py; the reference has none).  Always eager: the stage has no host synchronisation to cut a graph at,
+    and is not graph-captured"""
 
     def __init__(self, cfg):
-        import torch
         from ..nets import eloftr as EL
-        self.device = torch.device("cuda")
+        super().__init__(cfg)
         self.net = EL.from_cfg(cfg, self.device)
-        self._gray = _GrayPairStage()
-        from ..pipeline import RangeGuard
-        self.guard = RangeGuard(self.device, lambda: EfficientLoFTRMatching(cfg))
 
-    def get_correspondences(self, data):
-        import torch
-        ims = self._gray(data).to(self.device)
-        with torch.no_grad():
-            with self.guard:
-                out = self.net(ims)                            # pads to multiples of 32 itself, drops what lies outside the frame
-            flat = torch.cat([out["n_corr"][:1].to(torch.float32), self.guard.flag.to(torch.float32), out["pts0"][0].reshape(-1),
-                              out["pts1"][0].reshape(-1)]).cpu().numpy()                   # one D2H copy
-        if flat[1] != 0:                                       # f16x2 range guard fired: the exact (bf16x3) twin
-            from .. import options
-            self.guard.reruns += 1
-            with options.override(SPLIT="bf16x3"):
-                return self.guard.twin().get_correspondences(data)
-        n = int(flat[0])
-        if n == 0:
-            e = np.array([])
-            return e, e
-        L = (len(flat) - 2) // 4
-        return flat[2:2 + 2 * L].reshape(L, 2)[:n].copy(), flat[2 + 2 * L:].reshape(L, 2)[:n].copy()
+    def _stage(self, ims):
+        with torch.no_grad(), self.guard:
+            return self.net(ims)                               # pads to multiples of 32 itself, drops what lies outside the frame
 
 
 def _cv_sift_detector(num_features):

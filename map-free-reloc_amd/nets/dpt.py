@@ -575,9 +575,7 @@ def state_dict_from_cfg(cfg):
     from . import weights as WT
     node = check_cfg(cfg)
     arch = dict(node.ARCH)
-    if node.WEIGHTS:
-        return WT.load_checkpoint(node.WEIGHTS), arch
-    return WT.synthetic_or_raise("DPT", cfg, lambda: WT.dpt_state_dict(int(node.SYNTHETIC_SEED), arch=arch)), arch
+    return WT.from_cfg("DPT", cfg, node.WEIGHTS, lambda: WT.dpt_state_dict(int(node.SYNTHETIC_SEED), arch=arch)), arch
 
 
 FUSED_DEPTH_VIEWS = {"PNP": "ref", "EssentialMatrixMetric": "both", "Procrustes": "both"}     # the depth maps each pose solver reads; EssentialMatrix: none
@@ -630,24 +628,12 @@ class DepthEstimator:
         return millimetres_to_metres(mm) if self.quantize else m
 
 
-class _RefMap:
-    """One cached reference map of FusedDepthStage.
-    metres: the map [H, W] the solver reads.
-    flag:   a device copy [1] int32 of the f16x2 range-guard flag, taken right after the launches that computed the map (None while the guard is inactive): a
-            flagged accumulator can leave finite wrong values behind, so every later batch that reuses the map ORs `flag` into its own live flag
-            (cf. pipeline._RefView)."""
-    __slots__ = ("metres", "flag")
-
-    def __init__(self, metres, flag):
-        self.metres, self.flag = metres, flag
-
-
 class FusedDepthStage:
     """DPT.SOURCE 'online' on the batched route (pipeline.FusedPosePipeline): fills batch['depth0'] (views 'ref') or batch['depth0'] and batch['depth1'] (views
     'both') [b, H, W] f32 from batch['rgb'], the u8 [2b, H, W, 3] colour bytes PairBatchLoader(rgb=True) carries (row 2p = pair p's reference view).
 
     Only the views the solver reads go through the network, and a reference view once: the batch's pairs are grouped by `ref_keys` (the semantics of
-    pipeline._RefCachedKeypointMatcher: None = a view nobody shares, never retained; the last `keep` maps are kept, `cache=False`: none across batches).  The
+    ref_cache.RefViewCache: None = a view nobody shares, never retained; the last `keep` maps are kept, `cache=False`: none across batches).  The
     selected rows are read in place (mfr_dpt_prep_rows: no gather copy of the images), pass DPTHIP in chunks of DPT.FUSED_CHUNK views, and the tail writes
     each map straight into every plane that wants it (mfr_dpt_head_tail_rows: a shared reference map lands in the depth0 row of each of its pairs).  With
     DPT.QUANTIZE_MM the planes hold millimetres_to_metres of the rounded map: the bits the per-pair plugin's DepthEstimator.metres hands its solver.
@@ -656,7 +642,7 @@ class FusedDepthStage:
     fold, and the scene is recomputed through the bf16x3 twin (submission._rerun_out_of_range_scenes)."""
 
     def __init__(self, cfg, device, guard=None, views="both", cache=True, keep=4):
-        import collections
+        from ..ref_cache import RefViewCache
         assert views in ("ref", "both")
         node = check_cfg(cfg)
         sd, arch = state_dict_from_cfg(cfg)
@@ -665,7 +651,7 @@ class FusedDepthStage:
         self.net_hw = (int(node.NET_HEIGHT), int(node.NET_WIDTH))
         self.invert, self.scale, self.shift, self.quantize = bool(node.INVERT), float(node.SCALE), float(node.SHIFT), bool(node.QUANTIZE_MM)
         self.chunk = int(node.get("FUSED_CHUNK", 16))
-        self.cache = collections.OrderedDict()                                    # key -> _RefMap, least recently used first
+        self.cache = RefViewCache(guard)                                          # key -> RefEntry(flag, metres: the map [H, W] the solver reads)
         self.stats = dict(depth_views_run=0, depth_views_reused=0)
         self.table_status = torch.zeros(1, dtype=torch.int32, device=self.device)  # bit 0: a row table of this class left its range (a bug here, never data)
 
@@ -681,17 +667,11 @@ class FusedDepthStage:
         rgb = rgb.contiguous()
         H, W = rgb.shape[1:3]
         b, nq = len(ref_rows), len(query_rows)
-        keys = [k if k is not None else ("__pair__", p) for p, k in enumerate(ref_keys)]
-        first, pairs_of = {}, {}
-        for p, k in enumerate(keys):
-            first.setdefault(k, p)
-            pairs_of.setdefault(k, []).append(p)
-        need = [k for k in first if k not in self.cache]
-        reused = [k for k in first if k in self.cache]
+        plan = self.cache.plan(ref_keys)
+        first, pairs_of, need = plan.first, plan.pairs_of, plan.need
         rows = [int(ref_rows[first[k]]) for k in need] + [int(r) for r in query_rows]
         dsts = [pairs_of[k] for k in need] + [[b + q] for q in range(nq)]
         planes = torch.empty(b + nq, H, W, dtype=torch.float32, device=self.device)
-        guarded = self.guard is not None and self.guard.active
         flags = {}
         for c0 in range(0, len(rows), self.chunk):
             c1 = min(c0 + self.chunk, len(rows))
@@ -702,26 +682,20 @@ class FusedDepthStage:
             f = self.net.features(prep_rows(rgb, tab[:m], self.net_hw[0], self.net_hw[1], self.table_status))
             head_tail_rows(f, self.net.head4_w, self.net.head4_b, tab[m:m + d], tab[m + d:], planes, self.table_status, invert=self.invert, scale=self.scale,
                            shift=self.shift, quantize=self.quantize)
-            if guarded and c0 < len(need):
-                flag = self.guard.flag.clone()
+            if c0 < len(need):                                                    # one flag copy per chunk that holds reference rows
+                flag = self.cache.take_flag()
                 flags.update({k: flag for k in need[c0:c1]})
         self.stats["depth_views_run"] += len(rows)
-        self.stats["depth_views_reused"] += len(reused)
-        for k in reused:
-            hit = self.cache[k]
+        self.stats["depth_views_reused"] += len(plan.reused)
+        for k in plan.reused:
             for p in pairs_of[k]:
-                planes[p].copy_(hit.metres)
-            if guarded and hit.flag is not None:
-                self.guard.flag.bitwise_or_(hit.flag)
+                planes[p].copy_(self.cache[k].metres)
+        self.cache.carry(plan)
         if self.use_cache:
             for k in need:
-                if k[0] != "__pair__":
-                    self.cache[k] = _RefMap(planes[first[k]].clone(), flags.get(k))
-            for k in first:                                                       # most recently used last; bounded
-                if k in self.cache:
-                    self.cache.move_to_end(k)
-            while len(self.cache) > self.keep:
-                self.cache.popitem(last=False)
+                if k not in plan.solo:
+                    self.cache.put(k, flags[k], metres=planes[first[k]].clone())
+            self.cache.settle(plan, self.keep)
         return planes
 
     def __call__(self, batch):

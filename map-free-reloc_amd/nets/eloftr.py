@@ -134,7 +134,7 @@ def from_cfg(cfg, device):
     """-> EfficientLoFTRHIP of a config (ELOFTR.*)"""
     from . import weights as WT
     el = check_cfg(cfg)
-    sd = WT.load_checkpoint(el.WEIGHTS) if el.WEIGHTS else WT.synthetic_or_raise("EfficientLoFTR", cfg, lambda: WT.eloftr_state_dict(el.SYNTHETIC_SEED))
+    sd = WT.from_cfg("EfficientLoFTR", cfg, el.WEIGHTS, lambda: WT.eloftr_state_dict(el.SYNTHETIC_SEED))
     return EfficientLoFTRHIP(sd, device, el.MATCH_THRESHOLD, el.BORDER_RM, el.TEMPERATURE, el.get("MAX_MATCHES", None))
 
 

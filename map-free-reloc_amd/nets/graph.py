@@ -65,3 +65,29 @@ class GraphedCall:
             s.copy_(t, non_blocking=True)
         self.graph.replay()
         return _clone(self.static_out) if self.clone_outputs else self.static_out
+
+
+class GraphOrEager:
+    """fn(*tensors) replayed from one GraphedCall per `key` (the caller's: the shapes, with the dtypes where they change the arithmetic), or run eagerly:
+    while `enabled` is off, for a new key once `max_keys` are captured (every capture pins its intermediates), and -- with one warning -- for every
+    call after a capture failed.  device: where capture and the eager call want their inputs; a replay is handed the caller's tensors as they are (a
+    host tensor is copied straight into the static buffer)."""
+
+    def __init__(self, fn, who, enabled=True, clone_outputs=False, max_keys=None, device=None):
+        self.fn, self.who, self.enabled, self.clone_outputs, self.max_keys, self.device = fn, who, bool(enabled), clone_outputs, max_keys, device
+        self.graphs = {}
+
+    def __call__(self, key, *args):
+        if self.enabled and key not in self.graphs and (self.max_keys is None or len(self.graphs) < self.max_keys):
+            try:
+                self.graphs[key] = GraphedCall(self.fn, self._placed(args), clone_outputs=self.clone_outputs)
+            except GraphCaptureError as e:
+                import warnings
+                warnings.warn(f"{self.who}: {e}; running eagerly from now on")
+                self.enabled = False
+        if self.enabled and key in self.graphs:
+            return self.graphs[key](*args)
+        return self.fn(*self._placed(args))
+
+    def _placed(self, args):
+        return list(args) if self.device is None else [a.to(self.device) for a in args]

@@ -93,13 +93,10 @@ def check_cfg(cfg):
 def from_cfg(cfg, device):
     """-> (SuperPointHIP, LightGlueHIP) of a config (LIGHTGLUE.*; SuperPoint's weights are the SuperGlue stage's: SUPERGLUE.SUPERPOINT_WEIGHTS)"""
     from . import weights as WT
-    from .superpoint import SuperPointHIP
-    lg, sg = check_cfg(cfg), cfg.SUPERGLUE
-    sp_sd = WT.load_checkpoint(sg.SUPERPOINT_WEIGHTS) if sg.SUPERPOINT_WEIGHTS else \
-        WT.synthetic_or_raise("SuperPoint", cfg, lambda: WT.superpoint_state_dict(sg.SYNTHETIC_SEED))
-    lg_sd = WT.load_checkpoint(lg.WEIGHTS) if lg.WEIGHTS else WT.synthetic_or_raise("LightGlue", cfg, WT.lightglue_state_dict)
-    sp = SuperPointHIP(sp_sd, device, lg.NMS_RADIUS, lg.KEYPOINT_THRESHOLD, lg.MAX_KEYPOINTS)
-    return sp, LightGlueHIP(lg_sd, device, lg.FILTER_THRESHOLD, lg.NUM_LAYERS)
+    from .superglue import superpoint_from_cfg
+    lg = check_cfg(cfg)
+    sp = superpoint_from_cfg(cfg, device, lg)
+    return sp, LightGlueHIP(WT.from_cfg("LightGlue", cfg, lg.WEIGHTS, WT.lightglue_state_dict), device, lg.FILTER_THRESHOLD, lg.NUM_LAYERS)
 
 
 class Assignment:

@@ -54,6 +54,22 @@ class LoFTRFeatures(typing.NamedTuple):
     fine: torch.Tensor              # [n, Hf, Wf, 128]   1/2-resolution map, token-major (NHWC memory)
 
 
+def pad_to_multiple(images, m):
+    """LoFTR needs multiples of 8; the reference right-pads W 540 -> 544 (matchers.py:41-46, quirk Q3)"""
+    H, W = images.shape[-2:]
+    ph, pw = (-H) % m, (-W) % m
+    return F.pad(images, (0, pw, 0, ph)) if ph or pw else images
+
+
+def from_cfg(cfg, device):
+    """-> LoFTRHIP of a config: LOFTR.WEIGHTS (a Lightning checkpoint: `matcher.` prefix), LOFTR.MATCH_TYPE ('sinkhorn': the optimal-transport matcher with
+    the checkpoint's bin_score; default dual softmax, as the reference) and LOFTR.SKH_ITERS"""
+    from . import weights as WT
+    lo = cfg.LOFTR
+    sd = WT.from_cfg("LoFTR", cfg, lo.WEIGHTS, WT.loftr_state_dict, strip="matcher.")
+    return LoFTRHIP(sd, device, match_type=lo.get("MATCH_TYPE", "dual_softmax"), skh_iters=lo.get("SKH_ITERS", 3))
+
+
 class LoFTRHIP:
     def __init__(self, state_dict, device="cuda", thr=0.2, border_rm=2, temperature=0.1, window=5, match_type="dual_softmax", skh_iters=3):
         if match_type not in MATCH_TYPES:

@@ -62,6 +62,24 @@ def fold_weights(state_dict, n_layers=18):
     return dict(kenc=kenc, layers=layers, wf=f32(wf), bf=f32(sd["final_proj.bias"] + wf @ c), bin_score=float(sd["bin_score"]))
 
 
+def superpoint_from_cfg(cfg, device, node):
+    """-> SuperPointHIP with the detector settings of `node` (cfg.SUPERGLUE or cfg.LIGHTGLUE); the weights are SUPERGLUE.SUPERPOINT_WEIGHTS, the synthetic
+    ones seeded with SUPERGLUE.SYNTHETIC_SEED, for every route and both matchers"""
+    from . import weights as WT
+    from .superpoint import SuperPointHIP
+    sg = cfg.SUPERGLUE
+    sd = WT.from_cfg("SuperPoint", cfg, sg.SUPERPOINT_WEIGHTS, lambda: WT.superpoint_state_dict(sg.SYNTHETIC_SEED))
+    return SuperPointHIP(sd, device, node.NMS_RADIUS, node.KEYPOINT_THRESHOLD, node.MAX_KEYPOINTS)
+
+
+def from_cfg(cfg, device):
+    """-> (SuperPointHIP, SuperGlueHIP) of a config (SUPERGLUE.*)"""
+    from . import weights as WT
+    sg = cfg.SUPERGLUE
+    sp = superpoint_from_cfg(cfg, device, sg)
+    return sp, SuperGlueHIP(WT.from_cfg("SuperGlue", cfg, sg.SUPERGLUE_WEIGHTS, WT.superglue_state_dict), device, sg.SINKHORN_ITERATIONS, sg.MATCH_THRESHOLD)
+
+
 class SuperGlueHIP:
     def __init__(self, state_dict, device="cuda", sinkhorn_iterations=20, match_threshold=0.2, n_layers=18):
         _lib.load(require_gpu=True)

@@ -344,3 +344,11 @@ def synthetic_or_raise(what, cfg, maker):
                                 f"requested (ALLOW_SYNTHETIC_WEIGHTS: True or DATASET.SYNTHETIC)")
     warnings.warn(f"{what}: seeded synthetic weights in use (results are NOT meaningful)")
     return maker()
+
+
+def from_cfg(what, cfg, path, maker, strip=None):
+    """the state dict of a config's network: the checkpoint `path` (keys without the prefix `strip`), or -- no path configured -- synthetic_or_raise"""
+    if not path:
+        return synthetic_or_raise(what, cfg, maker)
+    sd = load_checkpoint(path)
+    return strip_prefix(sd, strip) if strip else sd

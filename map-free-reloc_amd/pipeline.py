@@ -12,9 +12,12 @@ plugin API stay available (matching/, wire.py) for drop-in use.
 import torch
 
 from . import _lib, options
+from .nets.graph import GraphOrEager
+from .nets.loftr import pad_to_multiple
 from .nets.superpoint import SuperPointHIP
 from .nets.superglue import SuperGlueHIP
 from .nets import weights as WT
+from .ref_cache import RefViewCache
 from .solver_ops import PnPBatchSolver
 
 
@@ -135,7 +138,7 @@ class SuperGluePnPPipeline:
         per batch shape and replayed as ONE HIP graph; inputs are copied into the graph's static buffers on every call and the
         (small) results are handed out as copies (nets/graph.py)."""
         _lib.load(require_gpu=True)
-        self.graph, self._graphs = bool(graph), {}
+        self.graph, self._graphed = bool(graph), GraphOrEager(self._run, "SuperGluePnPPipeline", clone_outputs=True)
         self.device = torch.device(device)
         self.sp = SuperPointHIP(sp_state or WT.superpoint_state_dict(), self.device, max_keypoints=max_keypoints)
         self.sg = SuperGlueHIP(sg_state or WT.superglue_state_dict(), self.device)
@@ -159,19 +162,10 @@ class SuperGluePnPPipeline:
         return m
 
     def __call__(self, images, depth0, K0, K1, pair_ids, want_mask=False):
-        if self.graph and not want_mask:
-            from .nets.graph import GraphCaptureError, GraphedCall
-            args = [images, depth0, K0, K1, pair_ids]
-            key = tuple((tuple(a.shape), a.dtype) for a in args)      # dtype too: float32 K and float64 K are different arithmetic (k_dtype)
-            try:
-                if key not in self._graphs:
-                    self._graphs[key] = GraphedCall(self._run, args, clone_outputs=True)
-                return self._graphs[key](*args)
-            except GraphCaptureError as e:
-                import warnings
-                warnings.warn(f"SuperGluePnPPipeline: {e}; running eagerly from now on")
-                self.graph = False
-        return self._run(images, depth0, K0, K1, pair_ids, want_mask)
+        if want_mask or not self.graph:                                # the mask is not among the captured outputs
+            return self._run(images, depth0, K0, K1, pair_ids, want_mask)
+        args = [images, depth0, K0, K1, pair_ids]
+        return self._graphed(tuple((tuple(a.shape), a.dtype) for a in args), *args)      # dtype too: float32 K and float64 K are different arithmetic (k_dtype)
 
     @torch.no_grad()
     def _run(self, images, depth0, K0, K1, pair_ids, want_mask=False):
@@ -274,14 +268,15 @@ class _RefCachedKeypointMatcher:
     (etc/feature_matching_baselines/compute.py:72-75, lib/datasets/mapfree.py:148-165); the reference runs the detector on it once per
     pair (116 times per scene).  Here the batch's pairs are grouped by `ref_keys` (PairBatchLoader: (scene_root, reference frame
     name)); SuperPoint runs on [the reference views not seen yet | all query views]; the reference rows of the interleaved
-    [2B] keypoint / score / descriptor tensors the matcher consumes are gathered from a small cache (the last few reference views: a
-    scene's pairs span several batches).  Every SuperPoint stage is per image with a fixed summation order (own convolutions, own 1x1
-    heads), so the result is the SAME BITS as the plain path -- tests/test_gpu_fused_submission.py checks poses byte for byte."""
+    [2B] keypoint / score / descriptor tensors the matcher consumes are gathered from a small cache (ref_cache.RefViewCache, the last few reference
+    views: a scene's pairs span several batches; each view with the range-guard flag of the pass that computed it).  Every SuperPoint stage is per image
+    with a fixed summation order (own convolutions, own 1x1 heads), so the result is the SAME BITS as the plain path --
+    tests/test_gpu_fused_submission.py checks poses byte for byte."""
+    FIELDS = ("kpts", "scores", "desc", "n")
 
-    def __init__(self, sp, net, max_kpts, plain, keep=4):
-        import collections
+    def __init__(self, sp, net, max_kpts, plain, guard=None, keep=4):
         self.sp, self.net, self.K, self.plain, self.keep = sp, net, max_kpts, plain, keep
-        self.cache = collections.OrderedDict()
+        self.cache = RefViewCache(guard)                                          # key -> RefEntry(flag, rows: the view's SuperPoint rows [1, ...])
         self.stats = dict(reference_views_run=0, reference_views_reused=0)
 
     def __call__(self, b):
@@ -289,51 +284,24 @@ class _RefCachedKeypointMatcher:
         if keys is None or len(keys) * 2 != im.shape[0]:
             return self.plain(im)
         B = len(keys)
-        keys = [k if k is not None else ("__pair__", p) for p, k in enumerate(keys)]      # None: a reference view nobody shares
-        first = {}
-        for p, k in enumerate(keys):
-            first.setdefault(k, p)
-        need = [k for k in first if k not in self.cache]
-        parts = [im[2 * first[k]][None] for k in need] + [im[1::2]]
+        plan = self.cache.plan(keys)
+        need = plan.need
+        parts = [im[2 * plan.first[k]][None] for k in need] + [im[1::2]]
         out = self.sp(torch.cat(parts) if need else im[1::2].contiguous())
         u = len(need)
+        flag = self.cache.take_flag() if need else None
         for i, k in enumerate(need):
-            self.cache[k] = {f: out[f][i:i + 1].clone() for f in ("kpts", "scores", "desc", "n")}
+            self.cache.put(k, flag, rows={f: out[f][i:i + 1].clone() for f in self.FIELDS})
+        self.cache.carry(plan)
         self.stats["reference_views_run"] += u
         self.stats["reference_views_reused"] += B - u
-        order = list(first)
         sp2 = {}
-        for f in ("kpts", "scores", "desc", "n"):
-            ref = torch.cat([self.cache[k][f] for k in keys])                      # [B, ...] reference rows (no index tensor: an H2D copy would
+        for f in self.FIELDS:
+            ref = torch.cat([self.cache[k].rows[f] for k in plan.keys])           # [B, ...] reference rows (no index tensor: an H2D copy would
             qry = out[f][u:]                                                       # synchronise the stream once per batch)
             sp2[f] = torch.stack([ref, qry], 1).reshape((2 * B,) + tuple(qry.shape[1:]))
-        for k in order:                                                           # most recently used last; bounded
-            if k[0] == "__pair__":
-                del self.cache[k]
-            else:
-                self.cache.move_to_end(k)
-        while len(self.cache) > max(self.keep, len(order)):
-            self.cache.popitem(last=False)
+        self.cache.settle(plan, max(self.keep, len(plan.first)))
         return self.net(sp2, tuple(im.shape[-2:]), maxN=self.K)
-
-
-def _pad_to_multiple(images, m):
-    """LoFTR needs multiples of 8; the reference right-pads W 540 -> 544 (matchers.py:41-46, quirk Q3)"""
-    H, W = images.shape[-2:]
-    ph, pw = (-H) % m, (-W) % m
-    return torch.nn.functional.pad(images, (0, pw, 0, ph)) if ph or pw else images
-
-
-class _RefView:
-    """One cached reference view of _RefCachedLoFTR.
-    slot: its row in the pool's coarse and fine maps.
-    flag: a device copy [1] int32 of the f16x2 range-guard flag, taken right after the backbone pass that computed the view (None while the guard is
-          inactive).  The view's maps were computed under THAT batch's guard window, and a flagged accumulator can leave finite wrong values behind
-          (relu(-inf) = 0), so every later batch that reuses the view ORs `flag` into its own live flag."""
-    __slots__ = ("slot", "flag")
-
-    def __init__(self, slot, flag):
-        self.slot, self.flag = slot, flag
 
 
 class _RefCachedLoFTR:
@@ -350,14 +318,13 @@ class _RefCachedLoFTR:
     way), query-side keys (7Scenes / ScanNet would enter through the same (feature set, index) interface) and HIP.GRAPH_FUSED."""
 
     def __init__(self, net, guard=None, pad_to=8, keep=4):
-        import collections
         self.net, self.guard, self.pad_to, self.keep = net, guard, pad_to, keep
-        self.cache = collections.OrderedDict()                                    # key -> _RefView, least recently used first
+        self.cache = RefViewCache(guard)                                          # key -> RefEntry(flag, slot: its row in the pool's coarse and fine maps)
         self.pool, self._hw = None, None                                          # LoFTRFeatures [slots, ...] of images of size _hw
         self.stats = dict(reference_views_run=0, reference_views_reused=0)
 
     def plain(self, images):
-        return self.net(_pad_to_multiple(images, self.pad_to))
+        return self.net(pad_to_multiple(images, self.pad_to))
 
     def _free_slots(self, n_new, first, like):
         """room for n_new more views: evict least recently used views the batch does not use, grow the pool to the batch's distinct views if needed"""
@@ -378,46 +345,101 @@ class _RefCachedLoFTR:
         im, keys = b["images"], b.get("ref_keys")
         if keys is None or len(keys) * 2 != im.shape[0]:
             return self.plain(im)
-        im = _pad_to_multiple(im, self.pad_to)
+        im = pad_to_multiple(im, self.pad_to)
         B = len(keys)
-        solo = {("__pair__", p) for p, k in enumerate(keys) if k is None}         # None: a reference view nobody shares
-        keys = [k if k is not None else ("__pair__", p) for p, k in enumerate(keys)]
-        first = {}
-        for p, k in enumerate(keys):
-            first.setdefault(k, p)
         if self._hw != tuple(im.shape[-2:]):                                      # another image size: the pooled maps do not fit
             self.cache.clear()
             self.pool, self._hw = None, tuple(im.shape[-2:])
-        need = [k for k in first if k not in self.cache]
+        plan = self.cache.plan(keys)
+        first, need = plan.first, plan.need
         u = len(need)
         out = self.net.features(torch.cat([im[2 * first[k]][None] for k in need] + [im[1::2]]))
-        guarded = self.guard is not None and self.guard.active
-        flag = self.guard.flag.clone() if guarded else None
+        flag = self.cache.take_flag()                                             # one copy per backbone pass
         self.stats["reference_views_run"] += u
         self.stats["reference_views_reused"] += B - u
-        reused = [k for k in first if k in self.cache]
-        store = need if reused else [k for k in need if k not in solo]            # nothing reused: side 0 is read from `out` itself
+        store = need if plan.reused else [k for k in need if k not in plan.solo]  # nothing reused: side 0 is read from `out` itself
         free = self._free_slots(len(store), first, out) if store else []
         for k in store:
-            v = self.cache[k] = _RefView(free.pop(0), flag)
+            v = self.cache.put(k, flag, slot=free.pop(0))
             for pooled, fresh in zip(self.pool, out):
                 pooled[v.slot].copy_(fresh[need.index(k)])
-        if reused:
-            src0, idx0 = self.pool, [self.cache[k].slot for k in keys]
-            if guarded:
-                for k in reused:
-                    self.guard.flag.bitwise_or_(self.cache[k].flag)
+        if plan.reused:
+            src0, idx0 = self.pool, [self.cache[k].slot for k in plan.keys]
+            self.cache.carry(plan)
         else:
-            src0, idx0 = out, [need.index(k) for k in keys]
+            src0, idx0 = out, [need.index(k) for k in plan.keys]
         m = self.net.match_features(src0, idx0, out, list(range(u, u + B)), im.shape[2])
-        for k in first:                                                           # most recently used last; bounded
-            if k in solo:
-                self.cache.pop(k, None)
-            else:
-                self.cache.move_to_end(k)
-        while len(self.cache) > max(self.keep, len(first)):
-            self.cache.popitem(last=False)
+        self.cache.settle(plan, max(self.keep, len(first)))
         return m
+
+
+def _hip_flag(cfg, name):
+    """an optional boolean of cfg.HIP (REF_FEATURE_CACHE, GRAPH_FUSED): absent = off"""
+    return name in cfg.HIP and bool(cfg.HIP[name])
+
+
+class _EfficientLoFTRStage:
+    """EfficientLoFTR on the fused route.  The per-image part is the backbone's three maps: _RefCachedLoFTR's pool, the same bits.  That stage pads, so the
+    network is told the unpadded frame: matches outside it are dropped"""
+
+    def __init__(self, net, guard, pad_to, cached):
+        self.net, self.cached, self.ref = net, cached, _RefCachedLoFTR(net, guard, pad_to=pad_to)
+        self.stats = self.ref.stats                                            # reference_views_run / _reused, as the LoFTR stage reports them
+
+    def __call__(self, b):
+        self.net.frame_hw = tuple(b["images"].shape[-2:])
+        return self.ref(b) if self.cached else self.ref.plain(b["images"])
+
+
+def _keypoint_stage(cfg, guard, sp, net, K, graphed=False):
+    """SuperPoint + SuperGlue / LightGlue: graph replay (HIP.GRAPH_FUSED, where the matcher can be captured), one SuperPoint pass per reference view
+    (HIP.REF_FEATURE_CACHE), or plain"""
+    fwd = lambda images: net(sp(images), tuple(images.shape[-2:]), maxN=K)
+    if graphed:
+        # the matcher stage (~300 launches) replayed from one HIP graph per batch shape; at most two shapes are captured (the full batch and one
+        # remainder), anything else -- and images that are not on the device -- runs eagerly: every capture pins its intermediates
+        run = GraphOrEager(torch.no_grad()(fwd), "FusedPosePipeline", clone_outputs=True, max_keys=2)
+        return lambda b: run(tuple(b["images"].shape), b["images"]) if b["images"].is_cuda else fwd(b["images"])
+    return _RefCachedKeypointMatcher(sp, net, K, fwd, guard) if _hip_flag(cfg, "REF_FEATURE_CACHE") else (lambda b: fwd(b["images"]))
+
+
+def _superglue_stage(cfg, device, guard):
+    from .nets import superglue as SG
+    return _keypoint_stage(cfg, guard, *SG.from_cfg(cfg, device), cfg.SUPERGLUE.MAX_KEYPOINTS, graphed=_hip_flag(cfg, "GRAPH_FUSED"))
+
+
+def _lightglue_stage(cfg, device, guard):
+    from .nets import lightglue as LG
+    return _keypoint_stage(cfg, guard, *LG.from_cfg(cfg, device), cfg.LIGHTGLUE.MAX_KEYPOINTS)      # eager: this stage is not graph-captured
+
+
+def _loftr_stage(cfg, device, guard):
+    from .nets import loftr as LO
+    stage = _RefCachedLoFTR(LO.from_cfg(cfg, device), guard)
+    # the backbone once per distinct reference view (both MATCH_TYPEs); switched off, every batch takes the stage's plain path
+    return stage if _hip_flag(cfg, "REF_FEATURE_CACHE") else (lambda b: stage.plain(b["images"]))
+
+
+def _eloftr_stage(cfg, device, guard):
+    from .nets import eloftr as EL
+    return _EfficientLoFTRStage(EL.from_cfg(cfg, device), guard, EL.PAD_TO, _hip_flag(cfg, "REF_FEATURE_CACHE"))
+
+
+def _sift_stage(cfg, device, guard):
+    if cfg.SIFT.get("DETECTOR", "opencv") != "hip":
+        raise _no_batched_stage("SIFT")
+    from .sift_ops import SiftDetector, sift_ratio_stage
+    return sift_ratio_stage(SiftDetector(cfg.SIFT.NUM_FEATURES, device), cfg.SIFT.RATIO_THRESHOLD)
+
+
+def _no_batched_stage(fm):
+    return NotImplementedError(f"FEATURE_MATCHING={fm!r} has no batched stage (SIFT with DETECTOR 'opencv' is OpenCV / per pair)")
+
+
+# cfg.FEATURE_MATCHING -> builder(cfg, device, guard) -> stage: a callable on the batch dict, with `.stats` where it keeps counters (the batched twin of
+# matching/model.FEATURE_MATCHERS)
+MATCHER_STAGES = {"Precomputed": lambda cfg, device, guard: _PrecomputedStage(cfg, device), "SuperGlue": _superglue_stage, "LightGlue": _lightglue_stage,
+                  "LoFTR": _loftr_stage, "EfficientLoFTR": _eloftr_stage, "SIFT": _sift_stage}
 
 
 class FusedPosePipeline:
@@ -435,70 +457,9 @@ class FusedPosePipeline:
         self.guard = RangeGuard(self.device, lambda: FusedPosePipeline(cfg, device))
         seed = int(cfg.RANSAC.SEED) if "RANSAC" in cfg else 0
         fm = cfg.FEATURE_MATCHING
-        if fm == "Precomputed":
-            self.match = _PrecomputedStage(cfg, self.device)
-        elif fm == "SuperGlue":
-            sg = cfg.SUPERGLUE
-            sp_sd = WT.load_checkpoint(sg.SUPERPOINT_WEIGHTS) if sg.SUPERPOINT_WEIGHTS else WT.synthetic_or_raise("SuperPoint", cfg, WT.superpoint_state_dict)
-            sg_sd = WT.load_checkpoint(sg.SUPERGLUE_WEIGHTS) if sg.SUPERGLUE_WEIGHTS else WT.synthetic_or_raise("SuperGlue", cfg, WT.superglue_state_dict)
-            sp = SuperPointHIP(sp_sd, self.device, sg.NMS_RADIUS, sg.KEYPOINT_THRESHOLD, sg.MAX_KEYPOINTS)
-            net = SuperGlueHIP(sg_sd, self.device, sg.SINKHORN_ITERATIONS, sg.MATCH_THRESHOLD)
-            fwd = lambda images: net(sp(images), tuple(images.shape[-2:]), maxN=sg.MAX_KEYPOINTS)
-            if "GRAPH_FUSED" in cfg.HIP and cfg.HIP.GRAPH_FUSED:
-                # the matcher stage (~300 launches) replayed from one HIP graph per batch shape; at most two shapes are captured
-                # (the full batch and one remainder), anything else runs eagerly: every capture pins its intermediates
-                from .nets.graph import GraphCaptureError, GraphedCall
-                graphs = {}
-
-                def match(b):
-                    im = b["images"]
-                    key = tuple(im.shape)
-                    if key not in graphs:
-                        if len(graphs) >= 2 or not im.is_cuda or graphs.get("failed"):
-                            return fwd(im)
-                        try:
-                            graphs[key] = GraphedCall(torch.no_grad()(fwd), [im], clone_outputs=True)
-                        except GraphCaptureError as e:
-                            import warnings
-                            warnings.warn(f"FusedPosePipeline: {e}; the matcher stage runs eagerly")
-                            graphs["failed"] = True
-                            return fwd(im)
-                    return graphs[key](im)
-                self.match = match
-            elif "REF_FEATURE_CACHE" in cfg.HIP and cfg.HIP.REF_FEATURE_CACHE:
-                self.match = _RefCachedKeypointMatcher(sp, net, sg.MAX_KEYPOINTS, fwd)
-            else:
-                self.match = lambda b: fwd(b["images"])
-        elif fm == "LightGlue":
-            from .nets import lightglue as LG
-            sp, net = LG.from_cfg(cfg, self.device)
-            K = cfg.LIGHTGLUE.MAX_KEYPOINTS
-            fwd = lambda images: net(sp(images), tuple(images.shape[-2:]), maxN=K)      # eager: this stage is not graph-captured
-            self.match = _RefCachedKeypointMatcher(sp, net, K, fwd) if "REF_FEATURE_CACHE" in cfg.HIP and cfg.HIP.REF_FEATURE_CACHE else (lambda b: fwd(b["images"]))
-        elif fm == "LoFTR":
-            lw = cfg.LOFTR.WEIGHTS
-            sd = WT.strip_prefix(WT.load_checkpoint(lw), "matcher.") if lw else WT.synthetic_or_raise("LoFTR", cfg, WT.loftr_state_dict)
-            from .nets.loftr import LoFTRHIP
-            net = LoFTRHIP(sd, self.device, match_type=cfg.LOFTR.get("MATCH_TYPE", "dual_softmax"), skh_iters=cfg.LOFTR.get("SKH_ITERS", 3))
-            stage = _RefCachedLoFTR(net, self.guard)
-            # the backbone once per distinct reference view (both MATCH_TYPEs); switched off, every batch takes the stage's plain path
-            self.match = stage if "REF_FEATURE_CACHE" in cfg.HIP and cfg.HIP.REF_FEATURE_CACHE else (lambda b: stage.plain(b["images"]))
-        elif fm == "EfficientLoFTR":
-            from .nets import eloftr as EL
-            net = EL.from_cfg(cfg, self.device)
-            stage = _RefCachedLoFTR(net, self.guard, pad_to=EL.PAD_TO)       # the per-image part is the backbone's three maps: the same pool, the same bits
-            cached = "REF_FEATURE_CACHE" in cfg.HIP and bool(cfg.HIP.REF_FEATURE_CACHE)
-
-            def match_eloftr(b):
-                net.frame_hw = tuple(b["images"].shape[-2:])                # the stage pads; matches outside the unpadded frame are dropped
-                return stage(b) if cached else stage.plain(b["images"])
-            match_eloftr.stats = stage.stats                                  # reference_views_run / _reused, as the LoFTR stage reports them
-            self.match = match_eloftr
-        elif fm == "SIFT" and cfg.SIFT.get("DETECTOR", "opencv") == "hip":
-            from .sift_ops import SiftDetector, sift_ratio_stage
-            self.match = sift_ratio_stage(SiftDetector(cfg.SIFT.NUM_FEATURES, self.device), cfg.SIFT.RATIO_THRESHOLD)
-        else:
-            raise NotImplementedError(f"FEATURE_MATCHING={fm!r} has no batched stage (SIFT with DETECTOR 'opencv' is OpenCV / per pair)")
+        if fm not in MATCHER_STAGES:
+            raise _no_batched_stage(fm)
+        self.match = MATCHER_STAGES[fm](cfg, self.device, self.guard)
         ps = cfg.POSE_SOLVER
         if ps == "PNP":
             pnp = ops.PnPBatchSolver(cfg.PNP.RANSAC_ITER, cfg.PNP.REPROJECTION_INLIER_THRESHOLD, cfg.PNP.CONFIDENCE, seed)
@@ -533,7 +494,7 @@ class FusedPosePipeline:
         views = DPT.fused_depth_views(cfg)
         self.depth = None
         if views is not None:
-            self.depth = DPT.FusedDepthStage(cfg, self.device, self.guard, views, cache="REF_FEATURE_CACHE" in cfg.HIP and bool(cfg.HIP.REF_FEATURE_CACHE))
+            self.depth = DPT.FusedDepthStage(cfg, self.device, self.guard, views, cache=_hip_flag(cfg, "REF_FEATURE_CACHE"))
         self.needs_rgb = self.depth is not None
 
     @property

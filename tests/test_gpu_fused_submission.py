@@ -149,3 +149,33 @@ def test_reference_view_feature_cache_is_bitwise_neutral(tmp_path):
     with zipfile.ZipFile(zs[0]) as a:
         lines = a.read("pose_s00000.txt").decode().split("\n")
     assert len(lines) == 3 and all("nan" not in l for l in lines)                  # real poses were compared, not failures
+
+
+def test_stale_guard_flag_of_a_cached_superpoint_view_marks_the_batches_that_reuse_it():
+    """the SuperGlue twin of tests/test_gpu_loftr_ref_cache.py's test: a cached SuperPoint view was computed under an EARLIER batch's guard window, so its
+    flag travels with it.  120 x 160 images, two pairs per batch."""
+    from mapfree_reloc_amd import images as IM
+    from mapfree_reloc_amd.pipeline import ST_RANGE, FusedPosePipeline
+    cfg = _cfg("PNP", "SuperGlue")
+    cfg.HIP.REF_FEATURE_CACHE = True
+    pipe = FusedPosePipeline(cfg)
+    assert pipe.guard.active
+
+    def batch(seed, key):
+        p = IM.synthetic_pair(seed, 120, 160, hard=0)
+        planes = [p["img0"], p["img1"], p["img0"], np.ascontiguousarray(np.roll(p["img1"], 8, axis=0))]
+        two = lambda a, dt: torch.from_numpy(np.stack([a, a])).to(dt).cuda()
+        return dict(images=torch.from_numpy(np.stack(planes))[:, None].float().cuda(), depth0=two(p["depth0"], torch.float32),
+                    K0=two(p["K"], torch.float64), K1=two(p["K"], torch.float64), seed_ids=torch.tensor([0, 5], dtype=torch.int64).cuda(), ref_keys=[key] * 2)
+    ka, kb = ("/synthetic/s00000", "seq0/frame_00000.jpg"), ("/synthetic/s00001", "seq0/frame_00000.jpg")
+    first = pipe(batch(11, ka))
+    assert not bool((first["status"] == ST_RANGE).any())
+    view = pipe.match.cache[ka]
+    assert view.flag.shape == (1,) and view.flag.dtype == torch.int32 and int(view.flag) == 0
+    view.flag.fill_(1)
+    reuse = pipe(batch(11, ka))
+    assert reuse["status"].tolist() == [ST_RANGE, ST_RANGE]
+    assert bool(torch.isnan(reuse["R"]).all())
+    other = pipe(batch(12, kb))                                                       # a batch that does not touch the flagged view
+    assert not bool((other["status"] == ST_RANGE).any())
+    assert pipe.match.stats == {"reference_views_run": 2, "reference_views_reused": 4}

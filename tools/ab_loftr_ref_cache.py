@@ -33,7 +33,8 @@ def main():
     import torch
     import mapfree_reloc_amd  # noqa: F401
     from mapfree_reloc_amd import images as IM
-    from mapfree_reloc_amd.pipeline import LoFTREmatPipeline, _pad_to_multiple
+    from mapfree_reloc_amd.nets.loftr import pad_to_multiple
+    from mapfree_reloc_amd.pipeline import LoFTREmatPipeline
     dev = "cuda:0"
     p = IM.synthetic_pair(100)
     planes = []
@@ -43,7 +44,7 @@ def main():
     keys = [("scene", "seq0/frame_00000.jpg")] * a.pairs
     pipe = LoFTREmatPipeline(dev)
     stage, net = pipe._ref, pipe.loftr
-    padded = _pad_to_multiple(images, pipe.pad_to)
+    padded = pad_to_multiple(images, pipe.pad_to)
     feats = net.features(padded)
     idx0, idx1 = list(range(0, 2 * a.pairs, 2)), list(range(1, 2 * a.pairs, 2))
 
