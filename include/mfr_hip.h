@@ -890,6 +890,36 @@ int mfr_eloftr_fine_match(const float *win0, const float *win1, const int32_t *c
 int mfr_eloftr_compact(const float *pts0, const float *pts1, const float *conf, long long ld_conf, const int32_t *n, int B, int maxN, int W, int H, float *out0,
                        float *out1, float *out_conf, int32_t *n_out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Depth Anything V2 (Yang et al., NeurIPS 2024: a DINOv2 ViT behind a DPT head), the kernels the DPT-Hybrid entry points above do not cover
+ * (csrc/depth_anything.hip; network: nets/depth_anything.py).  The architecture of record is `transformers.DepthAnythingForDepthEstimation` on a
+ * Dinov2 backbone.  Purely additive (no ABI version bump).  fp32 storage and arithmetic.  Every argument check returns MFR_E_ARG before any launch;
+ * all pointers are device memory.
+ *   mfr_da_patch_rows      img: dtype 0 = u8 [B,H,W,3] (value / 255), 1 = f32 [B,3,H,W] in [0, 1]  ->  rows [B gh gw, ldk]: row (b gh + y) gw + x holds the
+ *                          14 x 14 patch (y, x) of (F.interpolate(img, (14 gh, 14 gw), 'bilinear', align_corners=False) - mean[c]) / std[c] (torch's arithmetic,
+ *                          as mfr_dpt_prep) at column (c 14 + i) 14 + j, columns 588 .. ldk - 1 zero: the layout in which the 14 x 14 / stride 14 patch
+ *                          convolution's weight reshaped to [h, 588] is a linear layer's.  ldk >= 588, a multiple of 4; rows 16-byte aligned.  The
+ *                          normalised full-resolution image is never written.
+ *   mfr_da_patch_rows_tab  the row-table twin (semantics of mfr_dpt_prep_rows): img u8 [N,H,W,3], tab i32 [m]: the gh gw rows of output image j = those of
+ *                          mfr_da_patch_rows(dtype 0) on img[tab[j]], the same bits.  tab[j] outside [0, N): nothing is read, the image's rows are zeros
+ *                          and bit 0 of *status is set (an atomic OR; the caller clears the word).
+ *   mfr_da_tokens          x [B HW, ldx] (the embedding product's output) -> out [B,1 + HW,C] rows (row stride ldo, images (1 + HW) ldo apart):
+ *                          out[b][0] = cls + pos[0];  out[b][1 + p] = x[b HW + p] + pos[1 + p]  (pos [1 + HW,C]: resized to this grid by the caller).
+ *                          C, ldx, ldo multiples of 4, pointers 16-byte aligned.
+ *   mfr_da_head_tail       mfr_dpt_head_tail with Depth Anything's last activation: p = max_depth sigmoid(w . f + bias) (metric 1) or ReLU(w . f + bias)
+ *                          (metric 0: the relative checkpoints); the resize, the millimetres and their rounding are mfr_dpt_head_tail's (one device function).
+ *   mfr_da_head_tail_rows  its row-table twin: mfr_dpt_head_tail_rows's src / dst / quantize / status semantics, the same bits as the plain entry.
+ * ------------------------------------------------------------------------------------------ */
+int mfr_da_patch_rows(const void *img, int dtype, int B, int H, int W, int gh, int gw, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                      float *rows, int ldk, void *stream);
+int mfr_da_patch_rows_tab(const uint8_t *img, int N, const int *tab, int m, int H, int W, int gh, int gw, float mean0, float mean1, float mean2, float std0,
+                          float std1, float std2, float *rows, int ldk, int *status, void *stream);
+int mfr_da_tokens(const float *x, int ldx, const float *cls, const float *pos, int B, int C, int HW, float *out, int ldo, void *stream);
+int mfr_da_head_tail(const float *f, const float *w, float bias, int B, int C, int Hh, int Wh, int metric, float max_depth, int Ho, int Wo, float *metres,
+                     uint16_t *mm, void *stream);
+int mfr_da_head_tail_rows(const float *f, const float *w, float bias, int B, int C, int Hh, int Wh, int metric, float max_depth, int Ho, int Wo, const int *src,
+                          const int *dst, int d, float *metres, uint16_t *mm, int D, int quantize, int *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,11 @@ SIGNATURES = {
     "mfr_dpt_head_tail": (_i, [_vp, _vp, C.c_float, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp, _vp]),
     "mfr_dpt_prep_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "mfr_dpt_head_tail_rows": (_i, [_vp, _vp, C.c_float, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "mfr_da_patch_rows": (_i, [_vp, _i, _i, _i, _i, _i, _i] + [C.c_float] * 6 + [_vp, _i, _vp]),
+    "mfr_da_patch_rows_tab": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i] + [C.c_float] * 6 + [_vp, _i, _vp, _vp]),
+    "mfr_da_tokens": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
+    "mfr_da_head_tail": (_i, [_vp, _vp, C.c_float, _i, _i, _i, _i, _i, C.c_float, _i, _i, _vp, _vp, _vp]),
+    "mfr_da_head_tail_rows": (_i, [_vp, _vp, C.c_float, _i, _i, _i, _i, _i, C.c_float, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "mfr_eloftr_stem_s2": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "mfr_eloftr_aggregate": (_i, [_vp, _i, C.c_longlong, _i, _i, _i, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp]),
     "mfr_eloftr_rotary": (_i, [_vp, _vp, _i, _vp, C.c_longlong, _i, _vp]),

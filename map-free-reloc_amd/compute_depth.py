@@ -3,7 +3,7 @@
     python -m mapfree_reloc_amd.compute_depth -ds Mapfree --data_root data/mapfree --name dptkitti [--scenes s00460 ...] [--batch 8]
     python -m mapfree_reloc_amd.compute_depth -ds 7Scenes --data_root data/sevenscenes --name dptnyu
 
-Every frame of a scene goes through DPT-Hybrid (nets/dpt.py, the config's DPT node) in batches, at the frame's own size, and the millimetre plane the device
+Every frame of a scene goes through the configured depth network (DPT.NETWORK: DPT-Hybrid, nets/dpt.py, or Depth Anything V2, nets/depth_anything.py) in batches, at the frame's own size, and the millimetre plane the device
 rounds (csrc/dpt.hip mfr_dpt_head_tail) is written beside the frame as a 16-bit gray PNG, exactly where the readers look:
     Map-free   seqX/frame_00012.jpg        -> seqX/frame_00012.<name>.png            (datasets.MapFreeScene)
     7Scenes    seq-01/frame-000012.color.png -> seq-01/frame-000012.depth.<name>.png (sevenscenes.SevenScenesScene)

@@ -52,7 +52,14 @@ keys this implementation adds (declared here because unknown keys are rejected o
                      SOURCE 'file' (depth maps are read from the dataset, the default) | 'online' (computed from the pair's images: by FeatureMatchingModel per
                      pair, and on the fused route by nets/dpt.FusedDepthStage -- the loaders then carry the colour bytes and read no depth file, only the
                      views the pose solver reads go through the network, and a scene's shared reference view once), FUSED_CHUNK (views per DPT launch on
-                     the fused route, >= 1; 16 is the batch tools/bench_dpt.py measured)
+                     the fused route, >= 1; 16 is the batch tools/bench_dpt.py measured), NETWORK 'hybrid' (DPT-Hybrid, the default: every key above is its) |
+                     'depth_anything' (the DA node: SOURCE, QUANTIZE_MM and FUSED_CHUNK stay here; NET_*, SCALE / SHIFT / INVERT, WEIGHTS and ARCH do not apply)
+  DA.*               Depth Anything V2 monocular depth (nets/depth_anything.py), used when DPT.NETWORK is 'depth_anything': WEIGHTS (a state dict with the
+                     `transformers` DepthAnythingForDepthEstimation parameter names; an authors' checkpoint converts with nets/depth_anything.from_upstream),
+                     ENCODER 'vits' | 'vitb' | 'vitl' (the preset of config/depth_anything_arch.py), ARCH (keys of that table laid over the preset; None:
+                     the preset's value), MAX_DEPTH / METRIC (the head's output: MAX_DEPTH sigmoid -- 20 for the Hypersim checkpoints, 80 for Virtual KITTI -- or, METRIC
+                     False, the relative checkpoints' ReLU), NET_HEIGHT / NET_WIDTH (multiples of 14; the default 686 x 518 is for Map-free's portrait frames,
+                     720 high and 540 wide: swap the two for landscape frames), SYNTHETIC_SEED
 """
 from .node import CfgNode as CN
 
@@ -129,6 +136,12 @@ def get_cfg_defaults():
         c.DPT[k] = v
     from .dpt_arch import ARCH as _dpt_arch             # the architecture (DPT-Hybrid's values): BiT depths / widths / groups, ViT width / layers / heads, neck, taps
     c.DPT.ARCH = CN({k: (list(v) if isinstance(v, tuple) else v) for k, v in _dpt_arch.items()})
+    c.DPT.NETWORK = 'hybrid'                            # 'hybrid' (nets/dpt.DPTHIP) | 'depth_anything' (nets/depth_anything.DepthAnythingHIP, the DA node)
+    c.DA = CN()
+    for k, v in dict(WEIGHTS='', ENCODER='vits', MAX_DEPTH=20.0, METRIC=True, NET_HEIGHT=686, NET_WIDTH=518, SYNTHETIC_SEED=7531).items():
+        c.DA[k] = v
+    from .depth_anything_arch import ARCH as _da_arch   # every key of the table, None = the ENCODER preset's value (DA.MAX_DEPTH / DA.METRIC go over both)
+    c.DA.ARCH = CN({k: None for k in _da_arch})
     c.ALLOW_SYNTHETIC_WEIGHTS = False
     return c
 

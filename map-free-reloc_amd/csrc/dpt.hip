@@ -11,22 +11,11 @@
 //   mfr_dpt_head_tail       1x1 32 -> 1, ReLU, optional 1 / (scale p + shift), bilinear resize to the image, metres f32 (+ u16 millimetres)
 // fp32 storage and fp32 arithmetic throughout; wave64; every store is a vector (VMEM) store.  Every index is bounded by the launch geometry that the
 // entry point derives from its own (checked) arguments: no kernel trusts a table or a size it was not launched with.
-#include "wave_dev.h"
+#include "dpt_tail.h"
 
 using namespace mfr;
 
 namespace {
-
-// torch's source index of upsample_bilinear2d with align_corners=False: scale (dst + 0.5) - 0.5, clamped at 0; the second tap stops at the edge
-MFR_DEV void bilinear_taps(int dst, float scale, int n_in, int &i0, int &i1, float &l0, float &l1)
-{
-    float src = scale * ((float)dst + 0.5f) - 0.5f;
-    src = src < 0.f ? 0.f : src;
-    i0 = min((int)src, n_in - 1);
-    i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-    l1 = src - (float)i0;
-    l0 = 1.f - l1;
-}
 
 MFR_DEV float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
 
@@ -281,70 +270,26 @@ __global__ __launch_bounds__(256) void shuffle_kernel(const float *__restrict__ 
     out[idx] = v;
 }
 
-// ---------------------------------------------------------------- head tail
-constexpr int HEAD_MAX_C = 64;
+// ---------------------------------------------------------------- head tail (the body is dpt_tail.h's depth_tail, shared with csrc/depth_anything.hip)
+// DPT-Hybrid's last activation: ReLU, then the optional 1 / (scale p + shift) of the KITTI / NYU checkpoints
+struct HybridAct {
+    int invert;
+    float scale, shift;
+    __device__ __forceinline__ float operator()(float a) const
+    {
+        a = fmaxf(a, 0.f);
+        if (invert) a = 1.f / fmaxf(fmaf(scale, a, shift), 1e-8f);
+        return a;
+    }
+};
 
-MFR_DEV float head_value(const float *__restrict__ f, size_t plane, size_t idx, const float *__restrict__ w, int C, float bias, int invert, float scale, float shift)
-{
-    float a = bias;
-    for (int c = 0; c < C; ++c) a = fmaf(f[c * plane + idx], w[c], a);
-    a = fmaxf(a, 0.f);
-    if (invert) a = 1.f / fmaxf(fmaf(scale, a, shift), 1e-8f);
-    return a;
-}
-
-// one thread per pixel of the full-resolution map: the four taps' head values are computed where they are needed (the 1 / 32-size input stays in cache).
-// ROWS (mfr_dpt_head_tail_rows): entry k = blockIdx.y of the tables reads feature image src[k] of the B the caller has and writes plane dst[k] of the D
-// it has; a dst outside [0, D) writes nothing, a src outside [0, B) zeroes its plane, and either sets bit 0 of *status.  quantize: the metres written are
-// float32(mm / 1000.0), the division in double -- datasets.read_depth_image's value of the 16-bit PNG that holds mm
 template <bool ROWS>
 __global__ __launch_bounds__(256) void head_tail_kernel(const float *__restrict__ f, const float *__restrict__ w, float bias, int C, int Hh, int Wh, int invert,
                                                         float scale, float shift, int Ho, int Wo, float sy, float sx, float *__restrict__ metres,
                                                         uint16_t *__restrict__ mm, const int *__restrict__ src, const int *__restrict__ dst, int B, int D,
                                                         int quantize, int *status)
 {
-    __shared__ float ws[HEAD_MAX_C];
-    if (threadIdx.x < C) ws[threadIdx.x] = w[threadIdx.x];
-    __syncthreads();
-    int b = blockIdx.y, bo = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= Ho * Wo) return;
-    if (ROWS) {
-        b = src[blockIdx.y];
-        bo = dst[blockIdx.y];
-        const bool bad_src = b < 0 || b >= B, bad_dst = bo < 0 || bo >= D;
-        if (bad_src || bad_dst) {
-            if (i == 0) atomicOr(status, 1);
-            if (!bad_dst) {
-                metres[(size_t)bo * Ho * Wo + i] = 0.f;
-                if (mm) mm[(size_t)bo * Ho * Wo + i] = 0;
-            }
-            return;
-        }
-    }
-    const int y = i / Wo, x = i - y * Wo;
-    int y0, y1, x0, x1;
-    float ly0, ly1, lx0, lx1;
-    bilinear_taps(y, sy, Hh, y0, y1, ly0, ly1);
-    bilinear_taps(x, sx, Wh, x0, x1, lx0, lx1);
-    const size_t plane = (size_t)Hh * Wh;
-    const float *fb = f + (size_t)b * C * plane;
-    const float v00 = head_value(fb, plane, (size_t)y0 * Wh + x0, ws, C, bias, invert, scale, shift);
-    const float v01 = head_value(fb, plane, (size_t)y0 * Wh + x1, ws, C, bias, invert, scale, shift);
-    const float v10 = head_value(fb, plane, (size_t)y1 * Wh + x0, ws, C, bias, invert, scale, shift);
-    const float v11 = head_value(fb, plane, (size_t)y1 * Wh + x1, ws, C, bias, invert, scale, shift);
-    // ly0 (lx0 v00 + lx1 v01) + ly1 (lx0 v10 + lx1 v11) with its three fused multiply-adds written out: left to -ffp-contract the compiler fused them in
-    // the plain kernel and not in the row-table one (packed multiplies, then an add), and the two entry points promise the same bits
-    const float v = fmaf(ly0, fmaf(lx0, v00, lx1 * v01), ly1 * fmaf(lx0, v10, lx1 * v11));
-    const size_t o = (size_t)bo * Ho * Wo + i;
-    if (!ROWS) metres[o] = v;
-    if (mm || ROWS) {
-        // round-half-even of the EXACT product 1000 v (a 24-bit by a 10-bit factor is exact in double), clamped; NaN -> 0
-        const double t = rint((double)v * 1000.0);
-        const uint16_t q = (uint16_t)(t >= 65535.0 ? 65535 : (t > 0.0 ? (int)t : 0));
-        if (mm) mm[o] = q;
-        if (ROWS) metres[o] = quantize ? (float)((double)q / 1000.0) : v;
-    }
+    depth_tail<ROWS>(f, w, bias, C, Hh, Wh, HybridAct{invert, scale, shift}, Ho, Wo, sy, sx, metres, mm, src, dst, B, D, quantize, status);
 }
 
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }

@@ -14,6 +14,9 @@ What is here:
                            mfr_sg_attention's matching variant, 3x3 / stride 1 / pad 1 layers through nets/conv.WinoConv3x3 (the direct kernel under f16x2), every
                            other convolution through the implicit-GEMM kernel (f16x2, mfr_conv_igemm_f16x2_pad: BiT's TF-"SAME" padding is asymmetric).  Each stage
                            is a method, which is what the stage-level tests call.
+  * DepthNetBase           what DPTHIP shares with nets/depth_anything.DepthAnythingHIP (the ViT layer, the fusion layer, the residual unit) and the seam the two
+                           classes below drive either network through: prep / prep_rows, features, tail / tail_rows; build_network builds the configured one
+                           (DPT.NETWORK 'hybrid' | 'depth_anything');
   * DepthEstimator         the config's stage (DPT.*) for compute_depth and the per-pair plugin: images in, maps out, the range guard's re-run taken here;
   * FusedDepthStage        DPT.SOURCE 'online' on the batched route (pipeline.FusedPosePipeline): the maps the pose solver reads, from the batch's colour bytes --
                            only the views it reads, a shared reference view once, through the row-table ends prep_rows / head_tail_rows."""
@@ -25,6 +28,7 @@ from .conv import IgemmConv, WinoConv3x3
 from .linear import SplitLinear
 
 HEAD_DIM = 64                       # mfr_sg_attention's head width
+NETWORKS = ("hybrid", "depth_anything")     # DPT.NETWORK: DPTHIP (this file) | nets/depth_anything.DepthAnythingHIP
 STEM_EPS, BOTTLENECK_EPS = 1e-8, 1e-8   # weight standardisation: BitEmbeddings' conv and the bottlenecks' convs
 GN_EPS, LN_EPS = 1e-5, 1e-12        # BitGroupNormActivation / the ViT's layer_norm_eps
 
@@ -267,11 +271,13 @@ def tokens_inverse(rows, gh, gw, bias_img=None, gelu=False, skip=1):
     return out
 
 
-def shuffle(g, bias, B, C, H, W, s):
-    """g [B H W, C s^2] (the GEMM of fold_conv_transpose) -> ConvTranspose2d's output [B, C, H s, W s]"""
+def shuffle(g, bias, B, C, H, W, s, out=None):
+    """g [B H W, C s^2] (the GEMM of fold_conv_transpose) -> ConvTranspose2d's output [B, C, H s, W s] (`out`: written there, contiguous)"""
     lib = _lib.load(require_gpu=True)
     assert g.is_cuda and g.dtype == torch.float32 and g.shape == (B * H * W, C * s * s) and g.stride(1) == 1
-    out = torch.empty(B, C, H * s, W * s, dtype=torch.float32, device=g.device)
+    if out is None:
+        out = torch.empty(B, C, H * s, W * s, dtype=torch.float32, device=g.device)
+    assert out.shape == (B, C, H * s, W * s) and out.dtype == torch.float32 and out.is_contiguous()
     _lib.check(lib.mfr_dpt_shuffle(g.data_ptr(), g.stride(0), None if bias is None else _lib.ptr(_f32(bias)), B, C, H, W, int(s), out.data_ptr(), _lib.stream_ptr()),
                "mfr_dpt_shuffle")
     return out
@@ -359,16 +365,74 @@ class PadIgemmConv(IgemmConv):
         return y
 
 
-def upsample2x(x):
-    """F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=True) (mfr_upsample_bilinear)"""
+def upsample(x, size):
+    """F.interpolate(x, size=size, mode='bilinear', align_corners=True) (mfr_upsample_bilinear)"""
     x = _f32(x)
     B, C, H, W = x.shape
-    y = torch.empty(B, C, 2 * H, 2 * W, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().mfr_upsample_bilinear(x.data_ptr(), y.data_ptr(), B * C, H, W, 2 * H, 2 * W, 0, _lib.stream_ptr()), "mfr_upsample_bilinear")
+    Ho, Wo = int(size[0]), int(size[1])
+    y = torch.empty(B, C, Ho, Wo, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().mfr_upsample_bilinear(x.data_ptr(), y.data_ptr(), B * C, H, W, Ho, Wo, 0, _lib.stream_ptr()), "mfr_upsample_bilinear")
     return y
 
 
-class DPTHIP:
+def upsample2x(x):
+    """F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=True)"""
+    return upsample(x, (2 * x.shape[2], 2 * x.shape[3]))
+
+
+class DepthNetBase:
+    """What the depth networks share (DPTHIP here, nets/depth_anything.DepthAnythingHIP): the pre-norm ViT layer on SplitLinear and mfr_sg_attention, the
+    fusion neck's layer and its residual unit, and the SEAM through which DepthEstimator and FusedDepthStage drive either network:
+        prep / prep_rows     images (or scattered rows of a u8 batch) -> the network's input
+        features             the network's input -> the head's last feature map
+        tail / tail_rows     that map -> metres (and millimetres) at the output size, with the network's own last-layer weights and output convention
+    A subclass sets arch (VIT_WIDTH, VIT_HEADS), device, att_variant, ln_eps, _n_tok = {} and implements the five."""
+
+    ln_eps = LN_EPS
+
+    def attention(self, qkv, B, T, out):
+        h = self.arch["VIT_WIDTH"]
+        if (B, T) not in self._n_tok:                                  # the token counts of the attention kernel's mask: built once per (B, T)
+            self._n_tok[(B, T)] = torch.full((B,), T, dtype=torch.int32, device=self.device)
+        n_tok = self._n_tok[(B, T)]
+        base = qkv.data_ptr()
+        _lib.check(_lib.load().mfr_sg_attention_variant(base, base + h * 4, base + 2 * h * 4, 3 * h, B, T, self.arch["VIT_HEADS"], n_tok.data_ptr(), 0, out.data_ptr(), h,
+                                                        self.att_variant, _lib.stream_ptr()), "mfr_sg_attention")
+        return out
+
+    def vit_layer(self, L, x, B, T):
+        """one pre-norm layer on x [B T, h], in place (a LayerScale, where the network has one, is folded into L['out'] and L['fc2'])"""
+        y = layernorm(x, *L["ln1"], eps=self.ln_eps)
+        qkv = L["qkv"](y)
+        self.attention(qkv, B, T, y)
+        L["out"](y, out=x, accumulate=True)
+        y = layernorm(x, *L["ln2"], eps=self.ln_eps, out=y)
+        hid = bias_gelu(L["fc1"](y))
+        L["fc2"](hid, out=x, accumulate=True)
+        return x
+
+    def residual_unit(self, convs, x, rx):
+        """the pre-activation residual unit: conv2(relu(conv1(relu(x)))) + x; rx = relu(x) comes from the launch that produced x"""
+        return convs[1](convs[0](rx, act=1), residual=x)
+
+    def fusion_layer(self, F, hidden, residual=None, size=None):
+        """size: the map the layer up-samples to (align_corners=True); None: x2"""
+        if residual is not None:
+            _, rr = add_relu(residual)
+            hidden, rh = add_relu(hidden, self.residual_unit(F["r1"], residual, rr))
+        else:
+            _, rh = add_relu(hidden)
+        y = self.residual_unit(F["r2"], hidden, rh)
+        return F["proj"](upsample(y, (2 * y.shape[2], 2 * y.shape[3]) if size is None else size))
+
+    def depth(self, img, net_hw, out_hw=None, millimetres=False):
+        """img u8 [B, H, W, 3] or f32 [B, 3, H, W] in [0, 1] -> (metres f32 [B, *out_hw], u16 millimetres or None); out_hw None: the image's size"""
+        if out_hw is None:
+            out_hw = tuple(img.shape[1:3]) if img.dtype == torch.uint8 else tuple(img.shape[2:4])
+        return self.tail(self.features(self.prep(img, net_hw)), out_hw, millimetres=millimetres)
+
+
+class DPTHIP(DepthNetBase):
     """DPT-Hybrid depth, inference only.  state_dict: the keys of `transformers.DPTForDepthEstimation`; arch: ARCH keys (None: DPT-Hybrid)."""
 
     def __init__(self, state_dict, device="cuda", arch=None):
@@ -377,6 +441,7 @@ class DPTHIP:
         self.device = torch.device(device)
         self.split = options.get("SPLIT")
         self.att_variant = 0 if self.split == "f16x2" else 2
+        self.convention = dict(invert=False, scale=1.0, shift=0.0)      # the output convention tail / tail_rows apply (build_network: the config's)
         sd = state_dict
         dev = lambda t: t.float().to(self.device).contiguous()
         ws = lambda name, eps: dev(fold_weight_standardisation(sd[name + ".weight"], eps))
@@ -475,27 +540,6 @@ class DPTHIP:
         """stage-3 feature map -> token rows [B, 1 + gh gw, h]: patch projection (1x1), cls row, position embeddings"""
         return tokens(self.patch(feat), self.cls, self.position_embeddings(feat.shape[2], feat.shape[3]))
 
-    def attention(self, qkv, B, T, out):
-        h = self.arch["VIT_WIDTH"]
-        if (B, T) not in self._n_tok:                                  # the token counts of the attention kernel's mask: built once per (B, T)
-            self._n_tok[(B, T)] = torch.full((B,), T, dtype=torch.int32, device=self.device)
-        n_tok = self._n_tok[(B, T)]
-        base = qkv.data_ptr()
-        _lib.check(_lib.load().mfr_sg_attention_variant(base, base + h * 4, base + 2 * h * 4, 3 * h, B, T, self.arch["VIT_HEADS"], n_tok.data_ptr(), 0, out.data_ptr(), h,
-                                                        self.att_variant, _lib.stream_ptr()), "mfr_sg_attention")
-        return out
-
-    def vit_layer(self, L, x, B, T):
-        """one pre-norm layer on x [B T, h], in place"""
-        y = layernorm(x, *L["ln1"])
-        qkv = L["qkv"](y)
-        self.attention(qkv, B, T, y)
-        L["out"](y, out=x, accumulate=True)
-        y = layernorm(x, *L["ln2"], out=y)
-        hid = bias_gelu(L["fc1"](y))
-        L["fc2"](hid, out=x, accumulate=True)
-        return x
-
     def encoder(self, tok):
         """token rows [B, T, h] -> the tapped hidden states (the last two taps: the first two are BiT's feature maps)"""
         B, T, h = tok.shape
@@ -515,18 +559,6 @@ class DPTHIP:
         bias_img = R["cls"](hidden[:, 0])                          # [B, h]: one small product per image set
         y = R["proj"](tokens_inverse(rows, gh, gw, bias_img=bias_img, gelu=True))
         return self.resize3(y) if i == 3 else y
-
-    def residual_unit(self, convs, x, rx):
-        """DPTPreActResidualLayer: conv2(relu(conv1(relu(x)))) + x; rx = relu(x) comes from the launch that produced x"""
-        return convs[1](convs[0](rx, act=1), residual=x)
-
-    def fusion_layer(self, F, hidden, residual=None):
-        if residual is not None:
-            _, rr = add_relu(residual)
-            hidden, rh = add_relu(hidden, self.residual_unit(F["r1"], residual, rr))
-        else:
-            _, rh = add_relu(hidden)
-        return F["proj"](upsample2x(self.residual_unit(F["r2"], hidden, rh)))
 
     def neck(self, feats):
         """four reassembled maps (finest first) -> the last fused map [B, F, Hn / 2, Wn / 2]"""
@@ -554,19 +586,39 @@ class DPTHIP:
         f = self.features(prep(img, int(net_hw[0]), int(net_hw[1])))
         return head_tail(f, self.head4_w, self.head4_b, int(out_hw[0]), int(out_hw[1]), invert=invert, scale=scale, shift=shift, millimetres=millimetres)
 
+    # ---- the seam (DepthNetBase) ----
+    def prep(self, img, net_hw):
+        return prep(img, int(net_hw[0]), int(net_hw[1]))
+
+    def prep_rows(self, img, rows, net_hw, status):
+        return prep_rows(img, rows, int(net_hw[0]), int(net_hw[1]), status)
+
+    def tail(self, f, out_hw, millimetres=False):
+        return head_tail(f, self.head4_w, self.head4_b, int(out_hw[0]), int(out_hw[1]), millimetres=millimetres, **self.convention)
+
+    def tail_rows(self, f, src, dst, metres, status, quantize=False):
+        return head_tail_rows(f, self.head4_w, self.head4_b, src, dst, metres, status, quantize=quantize, **self.convention)
+
 
 # ------------------------------------------------------------------------------------------------ the config's stage
 def check_cfg(cfg):
     """the DPT node of a config, checked: network sizes are multiples of 32, SOURCE is 'file' or 'online', the architecture is one the kernels have"""
     node = cfg.DPT
-    if node.NET_HEIGHT % 32 or node.NET_WIDTH % 32 or node.NET_HEIGHT < 32 or node.NET_WIDTH < 32:
+    network = node.get("NETWORK", "hybrid")
+    if network not in NETWORKS:
+        raise ValueError(f"DPT.NETWORK = {network!r}: one of {NETWORKS}")
+    if network == "depth_anything":                                            # its sizes and architecture live in the DA node
+        from .depth_anything import check_cfg as check_da
+        check_da(cfg)
+    elif node.NET_HEIGHT % 32 or node.NET_WIDTH % 32 or node.NET_HEIGHT < 32 or node.NET_WIDTH < 32:
         raise ValueError(f"DPT.NET_HEIGHT x NET_WIDTH = {node.NET_HEIGHT} x {node.NET_WIDTH}: both must be multiples of 32")
     if node.SOURCE not in ("file", "online"):
         raise ValueError(f"DPT.SOURCE = {node.SOURCE!r}: 'file' (depth maps come with the dataset) or 'online' (computed per pair)")
     chunk = node.get("FUSED_CHUNK", 16)
     if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
         raise ValueError(f"DPT.FUSED_CHUNK = {chunk!r}: the views per DPT launch on the fused route, an integer >= 1")
-    check_arch(dict(node.ARCH))
+    if network == "hybrid":
+        check_arch(dict(node.ARCH))
     return node
 
 
@@ -576,6 +628,24 @@ def state_dict_from_cfg(cfg):
     node = check_cfg(cfg)
     arch = dict(node.ARCH)
     return WT.from_cfg("DPT", cfg, node.WEIGHTS, lambda: WT.dpt_state_dict(int(node.SYNTHETIC_SEED), arch=arch)), arch
+
+
+def build_network(cfg, device="cuda"):
+    """the ONE place where the configured depth network is built -> (maker, net_hw): maker() returns a new network object (DepthNetBase's seam) in the
+    arithmetic `HIP.SPLIT` names at that moment -- the range guard's twin is a second call -- and net_hw is the network's input size.  DPT.NETWORK 'hybrid':
+    DPTHIP with the DPT node's SCALE / SHIFT / INVERT as its output convention; 'depth_anything': nets/depth_anything.DepthAnythingHIP (the DA node)"""
+    node = check_cfg(cfg)
+    if node.get("NETWORK", "hybrid") == "depth_anything":
+        from . import depth_anything as DA
+        return DA.network_from_cfg(cfg, device)
+    sd, arch = state_dict_from_cfg(cfg)
+    convention = dict(invert=bool(node.INVERT), scale=float(node.SCALE), shift=float(node.SHIFT))
+
+    def maker():
+        net = DPTHIP(sd, device, arch=arch)
+        net.convention = dict(convention)
+        return net
+    return maker, (int(node.NET_HEIGHT), int(node.NET_WIDTH))
 
 
 FUSED_DEPTH_VIEWS = {"PNP": "ref", "EssentialMatrixMetric": "both", "Procrustes": "both"}     # the depth maps each pose solver reads; EssentialMatrix: none
@@ -600,27 +670,25 @@ class DepthEstimator:
 
     def __init__(self, cfg, device="cuda"):
         node = check_cfg(cfg)
-        sd, arch = state_dict_from_cfg(cfg)
+        maker, self.net_hw = build_network(cfg, device)
         from ..pipeline import RangeGuard
-        self.net = DPTHIP(sd, device, arch=arch)
+        self.net = maker()
         self.device = self.net.device
         # the f16x2 range guard, as for the matcher networks: a launch whose accumulators left the fp32-finite range (an operand beyond 65504) sets the flag,
         # and the batch runs again through the bf16x3 twin (linear layers, attention and the 3x3 / stride 1 layers; the implicit-GEMM layers exist in f16x2 only)
-        self.guard = RangeGuard(self.device, lambda: DPTHIP(sd, device, arch=arch))
-        self.net_hw = (int(node.NET_HEIGHT), int(node.NET_WIDTH))
-        self.invert, self.scale, self.shift, self.quantize = bool(node.INVERT), float(node.SCALE), float(node.SHIFT), bool(node.QUANTIZE_MM)
+        self.guard = RangeGuard(self.device, maker)
+        self.quantize = bool(node.QUANTIZE_MM)
 
     @torch.no_grad()
     def __call__(self, images, out_hw=None):
         """images u8 [B, H, W, 3] or f32 [B, 3, H, W] in [0, 1] (any device) -> (metres f32, millimetres u16), both [B, *out_hw] on the GPU (out_hw None: the
         images' own size)"""
         images = images.to(self.device)
-        kw = dict(out_hw=out_hw, invert=self.invert, scale=self.scale, shift=self.shift, millimetres=True)
         with self.guard:
-            out = self.net(images, self.net_hw, **kw)
+            out = self.net.depth(images, self.net_hw, out_hw, millimetres=True)
         if self.guard.active and int(self.guard.flag.item()):           # the maps are read on the host next anyway: this is not an extra synchronisation
             self.guard.reruns += 1
-            out = self.guard.twin()(images, self.net_hw, **kw)
+            out = self.guard.twin().depth(images, self.net_hw, out_hw, millimetres=True)
         return out
 
     def metres(self, images, out_hw=None):
@@ -645,11 +713,10 @@ class FusedDepthStage:
         from ..ref_cache import RefViewCache
         assert views in ("ref", "both")
         node = check_cfg(cfg)
-        sd, arch = state_dict_from_cfg(cfg)
-        self.net = DPTHIP(sd, device, arch=arch)
+        maker, self.net_hw = build_network(cfg, device)
+        self.net = maker()
         self.device, self.guard, self.views, self.use_cache, self.keep = self.net.device, guard, views, bool(cache), int(keep)
-        self.net_hw = (int(node.NET_HEIGHT), int(node.NET_WIDTH))
-        self.invert, self.scale, self.shift, self.quantize = bool(node.INVERT), float(node.SCALE), float(node.SHIFT), bool(node.QUANTIZE_MM)
+        self.quantize = bool(node.QUANTIZE_MM)
         self.chunk = int(node.get("FUSED_CHUNK", 16))
         self.cache = RefViewCache(guard)                                          # key -> RefEntry(flag, metres: the map [H, W] the solver reads)
         self.stats = dict(depth_views_run=0, depth_views_reused=0)
@@ -679,9 +746,8 @@ class FusedDepthStage:
             dst = [t for j in range(c0, c1) for t in dsts[j]]
             m, d = c1 - c0, len(src)
             tab = self._table(rows[c0:c1] + src + dst)
-            f = self.net.features(prep_rows(rgb, tab[:m], self.net_hw[0], self.net_hw[1], self.table_status))
-            head_tail_rows(f, self.net.head4_w, self.net.head4_b, tab[m:m + d], tab[m + d:], planes, self.table_status, invert=self.invert, scale=self.scale,
-                           shift=self.shift, quantize=self.quantize)
+            f = self.net.features(self.net.prep_rows(rgb, tab[:m], self.net_hw, self.table_status))
+            self.net.tail_rows(f, tab[m:m + d], tab[m + d:], planes, self.table_status, quantize=self.quantize)
             if c0 < len(need):                                                    # one flag copy per chunk that holds reference rows
                 flag = self.cache.take_flag()
                 flags.update({k: flag for k in need[c0:c1]})

@@ -245,6 +245,121 @@ def dpt_state_dict(seed=8642, arch=None, head_bias=3.0, pos_grid=24):
     return sd
 
 
+def _depth_anything_logit(sd, a, x):
+    """the pre-activation output of head.conv3 of Depth Anything on x [B, 3, 14 gh, 14 gw] (already normalised): plain float32 torch on the host, used by
+    depth_anything_state_dict to calibrate the last layer -- the tests' oracle is the `transformers` module, never this"""
+    import torch.nn.functional as F
+    B, _, H, W = x.shape
+    gh, gw, h, heads = H // 14, W // 14, a["VIT_WIDTH"], a["VIT_HEADS"]
+    e = "backbone.embeddings"
+    tok = F.conv2d(x, sd[f"{e}.patch_embeddings.projection.weight"], sd[f"{e}.patch_embeddings.projection.bias"], stride=14).flatten(2).transpose(1, 2)
+    pos = sd[f"{e}.position_embeddings"]
+    g = a["POS_GRID"]
+    grid = F.interpolate(pos[:, 1:].reshape(1, g, g, h).permute(0, 3, 1, 2), size=(gh, gw), mode="bicubic", align_corners=False)
+    t = torch.cat([sd[f"{e}.cls_token"].expand(B, -1, -1), tok], 1) + torch.cat([pos[:, :1], grid.permute(0, 2, 3, 1).reshape(1, gh * gw, h)], 1)
+    ln = lambda v, n: F.layer_norm(v, (h,), sd[f"{n}.weight"], sd[f"{n}.bias"], 1e-6)
+    lin = lambda v, n: F.linear(v, sd[f"{n}.weight"], sd[f"{n}.bias"])
+    taps = []
+    for l in range(max(a["TAPS"]) + 1):
+        p = f"backbone.encoder.layer.{l}"
+        y = ln(t, f"{p}.norm1")
+        q, k, v = (lin(y, f"{p}.attention.attention.{n}").view(B, -1, heads, 64).transpose(1, 2) for n in ("query", "key", "value"))
+        y = (torch.softmax(q @ k.transpose(-1, -2) / 8.0, -1) @ v).transpose(1, 2).reshape(B, -1, h)
+        t = t + sd[f"{p}.layer_scale1.lambda1"] * lin(y, f"{p}.attention.output.dense")
+        t = t + sd[f"{p}.layer_scale2.lambda1"] * lin(F.gelu(lin(ln(t, f"{p}.norm2"), f"{p}.mlp.fc1")), f"{p}.mlp.fc2")
+        if l in a["TAPS"]:
+            taps.append(ln(t, "backbone.layernorm")[:, 1:].transpose(1, 2).reshape(B, h, gh, gw))
+    rs = "neck.reassemble_stage.layers"
+    feats = []
+    for i, y in enumerate(taps):
+        y = F.conv2d(y, sd[f"{rs}.{i}.projection.weight"], sd[f"{rs}.{i}.projection.bias"])
+        if i < 2:
+            y = F.conv_transpose2d(y, sd[f"{rs}.{i}.resize.weight"], sd[f"{rs}.{i}.resize.bias"], stride=4 >> i)
+        elif i == 3:
+            y = F.conv2d(y, sd[f"{rs}.3.resize.weight"], sd[f"{rs}.3.resize.bias"], stride=2, padding=1)
+        feats.append(F.conv2d(y, sd[f"neck.convs.{i}.weight"], padding=1))
+    c3 = lambda v, n: F.conv2d(v, sd[f"{n}.weight"], sd[f"{n}.bias"], padding=1)
+    unit = lambda v, n: c3(F.relu(c3(F.relu(v), f"{n}.convolution1")), f"{n}.convolution2") + v
+    y = None
+    for i in range(4):
+        p = f"neck.fusion_stage.layers.{i}"
+        y = feats[3 - i] if y is None else y + unit(feats[3 - i], f"{p}.residual_layer1")
+        y = unit(y, f"{p}.residual_layer2")
+        size = feats[2 - i].shape[2:] if i < 3 else (2 * y.shape[2], 2 * y.shape[3])
+        y = F.conv2d(F.interpolate(y, size=tuple(size), mode="bilinear", align_corners=True), sd[f"{p}.projection.weight"], sd[f"{p}.projection.bias"])
+    y = F.interpolate(c3(y, "head.conv1"), size=(H, W), mode="bilinear", align_corners=True)
+    return F.conv2d(F.relu(c3(y, "head.conv2")), sd["head.conv3.weight"], sd["head.conv3.bias"])
+
+
+def depth_anything_state_dict(seed=7531, arch=None, calib_hw=(70, 98)):
+    """Depth Anything V2 with the parameter names of `transformers.DepthAnythingForDepthEstimation` on a Dinov2 backbone; `arch`: the keys of
+    config/depth_anything_arch (None: ViT-S).  Activations stay O(1): the patch projection and the neck / head convolutions are fan-in scaled (the sixteen
+    pre-activation residual units at a third of He: they add up), the ViT is the mild perturbation of its input that N(0, 0.02) weights make it, LayerScale is 1.
+    The LAST layer (head.conv3) is calibrated on one seeded image at `calib_hw`: its weight is scaled and its bias set so that the pre-sigmoid logit has zero
+    mean and unit spread over that image.  Plain initialisation gives a map constant to 1e-4, He scaling everywhere saturates the sigmoid at 0 and MAX_DEPTH:
+    both hide every error upstream of the head.  What this makes TRIVIAL: every norm is the identity affine map, every LayerScale is 1 and every bias (but the
+    last) is zero; tests/depth_anything_ref.perturbed moves them for the parity tests."""
+    from .depth_anything import check_arch
+    a = check_arch(arch)
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+
+    def conv(name, ci, co, k, std, bias=True, transpose=False):
+        sd[f"{name}.weight"] = _randn(g, (ci, co, k, k) if transpose else (co, ci, k, k), std)
+        if bias:
+            sd[f"{name}.bias"] = torch.zeros(co)
+
+    def norm(name, c):
+        sd[f"{name}.weight"], sd[f"{name}.bias"] = torch.ones(c), torch.zeros(c)
+
+    def lin(name, ci, co, std=0.02):
+        sd[f"{name}.weight"], sd[f"{name}.bias"] = _randn(g, (co, ci), std), torch.zeros(co)
+
+    h, e = a["VIT_WIDTH"], "backbone.embeddings"
+    sd[f"{e}.cls_token"] = _randn(g, (1, 1, h), 0.02)
+    sd[f"{e}.mask_token"] = torch.zeros(1, h)                              # part of the module's state dict; inference never reads it
+    sd[f"{e}.position_embeddings"] = _randn(g, (1, 1 + a["POS_GRID"] ** 2, h), 0.02)
+    conv(f"{e}.patch_embeddings.projection", 3, h, 14, std=588 ** -0.5)
+    for l in range(a["VIT_LAYERS"]):
+        p = f"backbone.encoder.layer.{l}"
+        norm(f"{p}.norm1", h); norm(f"{p}.norm2", h)
+        for n in ("query", "key", "value"):
+            lin(f"{p}.attention.attention.{n}", h, h)
+        lin(f"{p}.attention.output.dense", h, h)
+        lin(f"{p}.mlp.fc1", h, a["VIT_MLP"])
+        lin(f"{p}.mlp.fc2", a["VIT_MLP"], h)
+        sd[f"{p}.layer_scale1.lambda1"], sd[f"{p}.layer_scale2.lambda1"] = torch.ones(h), torch.ones(h)
+    norm("backbone.layernorm", h)
+    ns, f, rs = a["NECK_SIZES"], a["FUSION_WIDTH"], "neck.reassemble_stage.layers"
+    for i in range(4):
+        conv(f"{rs}.{i}.projection", a["REASSEMBLE_WIDTH"], ns[i], 1, std=a["REASSEMBLE_WIDTH"] ** -0.5)
+    conv(f"{rs}.0.resize", ns[0], ns[0], 4, std=ns[0] ** -0.5, transpose=True)
+    conv(f"{rs}.1.resize", ns[1], ns[1], 2, std=ns[1] ** -0.5, transpose=True)
+    conv(f"{rs}.3.resize", ns[3], ns[3], 3, std=(9 * ns[3]) ** -0.5)
+    for i in range(4):
+        conv(f"neck.convs.{i}", ns[i], f, 3, std=(9 * ns[i]) ** -0.5, bias=False)
+    for i in range(4):
+        p = f"neck.fusion_stage.layers.{i}"
+        conv(f"{p}.projection", f, f, 1, std=f ** -0.5)
+        for r in (1, 2):
+            for c in (1, 2):
+                conv(f"{p}.residual_layer{r}.convolution{c}", f, f, 3, std=(2.0 / (9 * f)) ** 0.5 / 3.0)
+    conv("head.conv1", f, f // 2, 3, std=(2.0 / (9 * f)) ** 0.5)
+    conv("head.conv2", f // 2, a["HEAD_WIDTH"], 3, std=(2.0 / (9 * (f // 2))) ** 0.5)
+    conv("head.conv3", a["HEAD_WIDTH"], 1, 1, std=1.0)
+    # the calibration image: smooth structure plus a little noise, normalised as the network's input is
+    H, W = calib_hw
+    lo = torch.rand(2, 3, max(H // 8, 2), max(W // 8, 2), generator=g)
+    img = (torch.nn.functional.interpolate(lo, size=(H, W), mode="bicubic", align_corners=False) + 0.05 * torch.randn(2, 3, H, W, generator=g)).clamp(0, 1)
+    x = (img - torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1)) / torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1)
+    with torch.no_grad():
+        logit = _depth_anything_logit(sd, a, x)
+    s = 1.0 / float(logit.std())
+    sd["head.conv3.weight"] = sd["head.conv3.weight"] * s
+    sd["head.conv3.bias"] = torch.full((1,), -float(logit.mean()) * s)
+    return sd
+
+
 ELOFTR_STAGES = ((1, 64, 2, 1), (64, 64, 1, 2), (64, 128, 2, 4), (128, 256, 2, 14))      # (Cin, Cout, stride of the first block, blocks) of the RepVGG stages
 
 

@@ -60,6 +60,22 @@ pr = df["loader_probe"]
 sub.update({"DPTF_PR_FILE0": f"{pr['loaders_alone']['files_process_decode']:.0f}", "DPTF_PR_RGB0": f"{pr['loaders_alone']['rgb_process_decode']:.0f}",
             "DPTF_PR_FILE1": f"{pr['after_dpt_is_built']['files_process_decode']:.0f}", "DPTF_PR_RGB1": f"{pr['after_dpt_is_built']['rgb_process_decode']:.0f}",
             "DPTF_PR_THREAD": f"{pr['after_dpt_is_built']['files_thread_decode']:.0f}", "DPTF_PR_FIRST": f"{pr['pool_forked_before_dpt']['rgb_process_decode']:.0f}"})
+da = json.load(open(P("profiles", "depth_anything_stage.json")))   # Depth Anything's stage record (tools/bench_depth_anything.py)
+f3 = lambda v: f"{v:.3f}"
+enc = {d["encoder"]: d for d in da["depth_anything"] if d["arithmetic"] == "f16x2"}
+S3 = [enc[k] for k in ("vits", "vitb", "vitl")]
+hyb = next(d for d in da["dpt_hybrid"] if d["arithmetic"] == "f16x2")
+for tag, d in (("S", S3[0]), ("B", S3[1]), ("L", S3[2]), ("H", hyb)):
+    w = d["whole_pass"]
+    sub.update({f"DAS_{tag}_WHOLE": f3(w["ms_per_frame"]), f"DAS_{tag}_LO": f3(w["spread_ms_per_frame"][0]), f"DAS_{tag}_HI": f3(w["spread_ms_per_frame"][1])})
+for tag, key in (("PATCH", "patch_rows"), ("EMBED", "embedding_product"), ("TOKENS", "token_assembly"), ("ENCODER", "encoder"), ("REASSEMBLE", "taps_and_reassemble"),
+                 ("NECK", "neck"), ("HEAD", "head_at_14g"), ("TAIL", "tail")):
+    sub[f"DAS_ST_{tag}"] = " / ".join(f3(d["stages"][key]["ms_per_frame"]) for d in S3)
+sub.update({"DAS_ST_SUM": " / ".join(f3(d["stages_sum_ms_per_frame"]) for d in S3),
+            "DAS_ENC_SHARE": " / ".join(f"{100 * d['stages']['encoder']['ms_per_frame'] / d['whole_pass']['ms_per_frame']:.0f}" for d in S3),
+            "DAS_L_TFLOPS": f"{S3[2]['tflops_whole_pass']:.0f}", "DAS_HEAD_MB": " / ".join(f"{d['head_map_bytes_per_frame']['bytes'] / 1e6:.0f}" for d in S3),
+            "DAS_BATCH": str(da["workload"]["batch"]), "DAS_TOKENS": str(S3[0]["tokens"]), "DAS_H_TOKENS": str(hyb["tokens"]), "DAS_REPEATS": str(da["workload"]["repeats"]),
+            "DAS_ITERS": str(da["workload"]["iters"]), "DAS_WINDOW": f"{da['workload']['min_window_ms']:.0f}"})
 census = subprocess.check_output([sys.executable, P("tools", "census_table.py")], text=True).rstrip("\n")
 out = open(P("docs", "DESIGN.template.md")).read()
 parts = {"CENSUS_TABLE_PLACEHOLDER": census, "KERNEL_TABLE_PLACEHOLDER": rd("_design_kernel_table.md"), "SECTION44_PLACEHOLDER": rd("_design_44.md"),
@@ -71,5 +87,5 @@ for k, v in parts.items():
 for k in sorted(sub, key=len, reverse=True):
     out = out.replace(k, sub[k])
 open(P("DESIGN.md"), "w").write(out)
-left = [w for w in ("PLACEHOLDER", "SG_", "LOFTR_", "C1_", "RPR_", "CPU_", "HOSTFED", "DPTF_") if w in out]
+left = [w for w in ("PLACEHOLDER", "SG_", "LOFTR_", "C1_", "RPR_", "CPU_", "HOSTFED", "DPTF_", "DAS_") if w in out]
 print("DESIGN.md written,", len(out), "bytes; unresolved markers:", left, "; longest line", max(len(l) for l in out.splitlines()))
