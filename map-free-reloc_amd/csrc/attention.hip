@@ -1,6 +1,7 @@
 // attention.hip -- SuperGlue multi-head softmax attention (self and cross) on gfx950: the exact-fp32 kernel (rounds 1-2, kept for A/B and parity),
 // and ONE software-pipelined kernel body on the 16-bit matrix cores at fp32 accuracy by operand splitting, instantiated for two arithmetics
-// (AtF16x2: round 5, the default; AtBf16x3: rounds 3-4, what an out-of-range scene is re-run on).
+// (AtF16x2: round 5, the default; AtBf16x3: rounds 3-4, what an out-of-range scene is re-run on).  The split body's online softmax keeps a STALE
+// per-query reference that moves only when a tile's maximum outgrows it by 2^AT_TAU (the exact-fp32 kernel keeps the running maximum).
 //
 // Reference call site: SuperGlue_matcher (etc/feature_matching_baselines/matchers.py:62-120) ->
 // upstream AttentionalGNN / MultiHeadedAttention (un-vendored):
@@ -36,6 +37,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define AT_KT 32            // keys per tile
 #define AT_KS 68            // K tile row stride (floats): 272 B -> conflict-free ds_read_b128
 #define AT_QW 32            // queries per wavefront
+// The split kernels' softmax reference moves only when a tile's maximum exceeds it by more than AT_TAU (in log2 units), so 0 < p <= 2^AT_TAU.
+// Derived, not tuned: f16x2 needs p <= 65504, and its low term is (p - ph) 2^11 <= 2^(AT_TAU - 11) 2^11 = 2^AT_TAU <= 65504, i.e. AT_TAU <= 15 by
+// range; 14 leaves a factor of two for the rounding of exp2 and of the comparison.  bf16x3 has no range limit and shares the body and the constant.
+constexpr float AT_TAU = 14.0f;
 #define AT_WAVES 4
 
 // The two stores every kernel here ends in; lane (q, half) of a wavefront owns query row q.
@@ -257,6 +262,32 @@ struct AtF16x2 {
     static __device__ __forceinline__ float fold(float main, float second) { return __builtin_fmaf(second, 1.0f / SF_LOW_SCALE, main); }
 };
 
+// Measurement build only (tools/attention_rescale_count.py compiles THIS file a second time with -DAT_PROF into tools/ubench/libmfr_hip_att_prof.so; the
+// product library never defines it): per launch (slot = launch number mod AT_PROF_SLOTS) the tiles executed, the tiles whose rescale branch was
+// taken, and the tiles in which the branch of a reference that follows the running maximum (m_true, what the kernel did before AT_TAU) would have
+// been taken; counted per wavefront in scalars, one atomicAdd per counter and wavefront at exit.
+#ifdef AT_PROF
+#define AT_PROF_SLOTS 64
+__device__ unsigned at_prof[AT_PROF_SLOTS][3];
+static int at_prof_launches = 0;
+#define AT_PROF_DECL , int prof_slot
+#define AT_PROF_PASS , prof_slot
+#define AT_PROF_NEXT , (at_prof_launches++ % AT_PROF_SLOTS)
+#define AT_PROF_INIT() float m_true = -INFINITY; unsigned prof_resc = 0, prof_run = 0
+#define AT_PROF_TILE(mx) do { const float mt_ = fmaxf(m_true, (mx)); prof_run += __ballot(mt_ != m_true) != 0ull; m_true = mt_; } while (0)
+#define AT_PROF_RESCALED() (++prof_resc)
+#define AT_PROF_COMMIT(ntiles) do { if (lane == 0) { atomicAdd(&at_prof[prof_slot][0], (unsigned)(ntiles)); atomicAdd(&at_prof[prof_slot][1], prof_resc); \
+        atomicAdd(&at_prof[prof_slot][2], prof_run); } } while (0)
+#else
+#define AT_PROF_DECL
+#define AT_PROF_PASS
+#define AT_PROF_NEXT
+#define AT_PROF_INIT() do { } while (0)
+#define AT_PROF_TILE(mx) do { } while (0)
+#define AT_PROF_RESCALED() do { } while (0)
+#define AT_PROF_COMMIT(ntiles) do { } while (0)
+#endif
+
 // ---- the pipelined kernel: eight wavefronts (256 queries) per workgroup -------------------------------------------------------------------------
 // K / V rows are read through buffer descriptors that end at row nk: the row offset of a tile is a SCALAR (no address VALU), rows beyond nk
 // read as zero in hardware (no clamp, no select); a K / V tile is split once per 256 queries.  (Round 3's 128-query kernel and the
@@ -268,9 +299,18 @@ struct AtF16x2 {
 // iteration ago) -- independent instruction streams that one wavefront overlaps by itself; then O^T += V(t)^T P(t).  K is therefore staged one
 // tile further ahead than V (K(t+2) and V(t+1) are written during iteration t; two LDS stages each).  Per query the same
 // arithmetic in the same order as a non-pipelined loop.  The two __global__ kernels below are this body with an arithmetic.
+// The softmax reference is STALE: flash-style softmax is exact for any per-query reference m_ref (p = exp2(s - m_ref); the final division by l_run
+// cancels it), so m_ref follows the running maximum only when a tile's maximum exceeds it by more than AT_TAU.  Rescaling the accumulator sets and
+// l_run -- one exp2 and 33 (packed) multiplies that no MFMA overlaps -- thereby becomes a cold, wave-uniform branch instead of one taken whenever
+// any of the wavefront's 32 queries saw a new maximum (share of tiles, before -> after: profiles/attention_rescale_ab.json).  Invariants:
+//   m_ref <= the true running maximum <= m_ref + AT_TAU   (m_ref is a tile maximum once set; a tile that exceeds m_ref + AT_TAU moves it)
+//   hence 0 < p <= 2^AT_TAU, inside the f16 operand range with its low term (AT_TAU), and l_run >= 1 from the tile that set m_ref on;
+//   small probabilities are no less precise than with the running maximum as reference: against a stale reference they are LARGER.
+// A NaN tile maximum (an out-of-range q row: every score NaN) never moves the reference (the comparison is false); p = exp2(NaN - m_ref) is NaN all
+// the same, so the accumulators the range guard tests still turn NaN.
 template <class AR>
 __device__ __forceinline__ void sg_attention_split_p(
-    const float *Q, const float *Kp, const float *Vp, int ld, int N, int heads, int B2, const int *n_tok, int cross, float scale_log2e, float *O, int ldo, int *guard)
+    const float *Q, const float *Kp, const float *Vp, int ld, int N, int heads, int B2, const int *n_tok, int cross, float scale_log2e, float *O, int ldo, int *guard AT_PROF_DECL)
 {
     constexpr int NT = AR::NT, NO = AR::NO;
     __shared__ __attribute__((aligned(16))) unsigned short Ks[2][NT][AT_KT][AB_KS];
@@ -306,7 +346,8 @@ __device__ __forceinline__ void sg_attention_split_p(
     f32x16 o0, o1, c0, c1;                                  // O^T of channels 0-31 / 32-63: main and (NO = 2) correction accumulators
 #pragma unroll
     for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; c0[r] = 0.f; c1[r] = 0.f; }
-    float m_run = -INFINITY, l_run = 0.f;
+    float m_ref = -INFINITY, m_thr = -INFINITY, l_run = 0.f;    // m_thr = m_ref + AT_TAU, kept so that the sum is formed where m_ref moves (the cold branch)
+    AT_PROF_INIT();
 
     const int sr = tid >> 4, sc4 = (tid & 15) * 4;
     const unsigned rowb = (unsigned)ld * 4u;
@@ -405,7 +446,9 @@ __device__ __forceinline__ void sg_attention_split_p(
         for (int r = 1; r < 15; r += 2) mx = fmaxf(fmaxf(mx, sc[r]), sc[r + 1]);
         mx = fmaxf(mx, sc[15]);
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
+        const bool need = mx > m_thr;                       // (tile 0: m_thr = -inf, true wherever mx is finite; a NaN mx: false, and p below is NaN)
+        const float m_use = need ? mx : m_ref;
+        AT_PROF_TILE(mx);
         AT_WEAVE(6, 2);
         __builtin_amdgcn_sched_barrier(0);
         // ---- step 1  ||  exponentials of keys 0 .. 7
@@ -413,7 +456,7 @@ __device__ __forceinline__ void sg_attention_split_p(
         AT_KLOAD(kb2, kq, 3);
         float p[16];
         at_f2 rs2; rs2.x = 0.f; rs2.y = 0.f;
-        at_f2 mm; mm.x = m_new; mm.y = m_new;
+        at_f2 mm; mm.x = m_use; mm.y = m_use;
 #pragma unroll
         for (int r = 0; r < 8; r += 2) {
             at_f2 d; d.x = sc[r]; d.y = sc[r + 1];
@@ -438,14 +481,16 @@ __device__ __forceinline__ void sg_attention_split_p(
         rs += __shfl_xor(rs, 32, 64);
         AT_WEAVE(6, 3);
         __builtin_amdgcn_sched_barrier(0);
-        if (__ballot(m_new != m_run) != 0ull) {             // the running maximum moved for some query of this wavefront: rescale
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+        if (__ballot(need) != 0ull) {                       // the reference moved for some query of this wavefront (cold): rescale; alpha = 1 in the other lanes
+            const float alpha = __builtin_amdgcn_exp2f(m_ref - m_use);
+            m_thr = m_use + AT_TAU;
+            AT_PROF_RESCALED();
             l_run *= alpha;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; c0[r] *= alpha; c1[r] *= alpha; }
         }
         l_run += rs;
-        m_run = m_new;
+        m_ref = m_use;
         // ---- step 3  ||  split of P (first 16 keys), staging of K(t+2) / V(t+1)
         AT_QK(kb2, qf[3], s, s2);
         Frag8 va[2 * NT];
@@ -475,6 +520,7 @@ __device__ __forceinline__ void sg_attention_split_p(
 #undef AT_WEAVE
 #undef AT_VLOAD
 #undef AT_KLOAD
+    AT_PROF_COMMIT(ntiles);
 
     if (q < N) {
         const float inv = (l_run > 0.f && q < nq) ? 1.f / l_run : 0.f;
@@ -500,19 +546,32 @@ __device__ __forceinline__ void sg_attention_split_p(
 
 __global__ void __launch_bounds__(512, 1) sg_attention_bf16x3_p_kernel(
     const float *__restrict__ Q, const float *__restrict__ Kp, const float *__restrict__ Vp, int ld,
-    int N, int heads, int B2, const int *__restrict__ n_tok, int cross, float scale_log2e, float *__restrict__ O, int ldo)
+    int N, int heads, int B2, const int *__restrict__ n_tok, int cross, float scale_log2e, float *__restrict__ O, int ldo AT_PROF_DECL)
 {
-    sg_attention_split_p<AtBf16x3>(Q, Kp, Vp, ld, N, heads, B2, n_tok, cross, scale_log2e, O, ldo, nullptr);
+    sg_attention_split_p<AtBf16x3>(Q, Kp, Vp, ld, N, heads, B2, n_tok, cross, scale_log2e, O, ldo, nullptr AT_PROF_PASS);
 }
 
 __global__ void __launch_bounds__(512, 1) sg_attention_f16x2_p_kernel(
     const float *__restrict__ Q, const float *__restrict__ Kp, const float *__restrict__ Vp, int ld,
-    int N, int heads, int B2, const int *__restrict__ n_tok, int cross, float scale_log2e, float *__restrict__ O, int ldo, int *guard)
+    int N, int heads, int B2, const int *__restrict__ n_tok, int cross, float scale_log2e, float *__restrict__ O, int ldo, int *guard AT_PROF_DECL)
 {
-    sg_attention_split_p<AtF16x2>(Q, Kp, Vp, ld, N, heads, B2, n_tok, cross, scale_log2e, O, ldo, guard);
+    sg_attention_split_p<AtF16x2>(Q, Kp, Vp, ld, N, heads, B2, n_tok, cross, scale_log2e, O, ldo, guard AT_PROF_PASS);
 }
 
 extern "C" {
+
+#ifdef AT_PROF
+// the counters of the launches since the last call, [AT_PROF_SLOTS][3] = (tiles, rescaled, rescaled with a running-maximum reference), and their number; clears both
+int mfr_sg_attention_profile(unsigned *out_host, int *launches)
+{
+    static const unsigned zero[AT_PROF_SLOTS][3] = {};
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(out_host, HIP_SYMBOL(at_prof), sizeof(zero), 0, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpyToSymbol(HIP_SYMBOL(at_prof), zero, sizeof(zero), 0, hipMemcpyHostToDevice) != hipSuccess) return MFR_E_LAUNCH;
+    *launches = at_prof_launches;
+    at_prof_launches = 0;
+    return 0;
+}
+#endif
 
 // q,k,v: [B2, N, ld] fp32 (row = keypoint; channels of head h at [h*64, h*64+64) from the given base
 // pointers, so a fused [.., 768] qkv buffer is passed as base, base+256, base+512 with ld = 768).
@@ -532,10 +591,10 @@ int mfr_sg_attention_variant(const float *q, const float *k, const float *v, int
         const int nqb = (N + AT_QW * AB_WAVES - 1) / (AT_QW * AB_WAVES);
         if (variant == 0)
             hipLaunchKernelGGL(sg_attention_f16x2_p_kernel, dim3(nqb * heads * B2), dim3(512), 0, (hipStream_t)stream, q, k, v, ld, N, heads, B2, n_tok, cross,
-                               scale_log2e, out, ldo, mfr_guard_current());
+                               scale_log2e, out, ldo, mfr_guard_current() AT_PROF_NEXT);
         else
             hipLaunchKernelGGL(sg_attention_bf16x3_p_kernel, dim3(nqb * heads * B2), dim3(512), 0, (hipStream_t)stream, q, k, v, ld, N, heads, B2, n_tok, cross,
-                               scale_log2e, out, ldo);
+                               scale_log2e, out, ldo AT_PROF_NEXT);
     } else {
         const int nqb = (N + AT_QW * AT_WAVES - 1) / (AT_QW * AT_WAVES);
         hipLaunchKernelGGL(sg_attention_kernel, dim3(nqb * heads * B2), dim3(256), 0, (hipStream_t)stream, q, k, v, ld, N, heads, B2, n_tok, cross,
