@@ -280,10 +280,20 @@ int mfr_procrustes_solve_batch(const float *pts0, const float *pts1, const int32
 int mfr_sp_scoremap(const float *logits, int B, int Hc, int Wc, float *scores, void *stream);
 int mfr_sp_nms_candidates(const float *scores, int B, int H, int W, int nms_radius, float threshold, int border,
                           float *nms_out, uint64_t *cand, int cand_cap, int32_t *cand_count, void *stream);
+/*   mfr_sp_nms_candidates_variant  0 = the streaming kernel (a wavefront walks down a strip of an image, no workgroup barrier), 1 = the tile kernel
+ *                              (one workgroup per 64 x 32 tile in LDS); the same dense output and the same candidate set, list order arbitrary in both.
+ *   mfr_sp_nms_stream_geometry the streaming kernel's useful columns per strip and output rows per segment (for tests on the seams) */
+int mfr_sp_nms_candidates_variant(const float *scores, int B, int H, int W, int nms_radius, float threshold, int border,
+                                  float *nms_out, uint64_t *cand, int cand_cap, int32_t *cand_count, int variant, void *stream);
+int mfr_sp_nms_stream_geometry(int *useful_cols, int *segment_rows);
 int mfr_sp_select_topk(const uint64_t *cand, int cand_cap, const int32_t *cand_count, int B, int W, int K,
                        float *kpts, float *kscores, int32_t *n_kpts, void *stream);
 int mfr_sp_sample_descriptors(const float *dense_nhwc, int B, int Hc, int Wc, const float *kpts,
                               const int32_t *n_kpts, int K, float *desc, void *stream);
+/*   mfr_sp_sample_descriptors_ld  the same with desc rows `ldd` >= 256 floats apart (a multiple of 4): into a wider buffer, e.g. the left half of
+ *                              SuperGlue's [x | a] rows; the floats beyond a row's 256 are not touched */
+int mfr_sp_sample_descriptors_ld(const float *dense_nhwc, int B, int Hc, int Wc, const float *kpts,
+                                 const int32_t *n_kpts, int K, float *desc, int ldd, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * SuperGlue kernels (same call site; upstream algorithm per SURVEY.md Appendix A.3).
@@ -396,6 +406,19 @@ int mfr_sg_sinkhorn_match_variant(const float *S, int B, int ldS, const int32_t 
                                   void *workspace, size_t workspace_bytes,
                                   int32_t *matches0, float *mscores0, float *pts0, float *pts1, int maxN, int32_t *n_corr,
                                   int variant, void *stream);
+/*   mfr_sg_sinkhorn_match_strided  the same, reading the matcher's interleaved [2B] tensors in place: `n_stride` elements between two pairs' counts
+ *                          in n0 / n1, `kpts_stride` floats between two pairs' [K, 2] keypoints in kpts0 / kpts1 (contiguous: 1 and 2 K).  Like the
+ *                          entry points above it writes zeros to the rows >= n_corr of pts0 / pts1, so the caller need not clear them. */
+int mfr_sg_sinkhorn_match_strided(const float *S, int B, int ldS, const int32_t *n0, const int32_t *n1, long long n_stride,
+                                  float bin_score, int iters, float match_thr,
+                                  const float *kpts0, const float *kpts1, int K, long long kpts_stride,
+                                  void *workspace, size_t workspace_bytes,
+                                  int32_t *matches0, float *mscores0, float *pts0, float *pts1, int maxN, int32_t *n_corr,
+                                  int variant, void *stream);
+/*   mfr_sg_kenc_in         SuperGlue's keypoint-encoder input in one launch: kn = (kpts - (W, H) / 2) * fp32(1 / (0.7 max(W, H))) and layer 0 (w [32, 3], BatchNorm
+ *                          folded), h = relu((kn_x w0 + kn_y w1) + (score w2 + b)), every operation rounded on its own; kpts [rows, 2], scores [rows] ->
+ *                          out [rows, 32] (csrc/elementwise.hip) */
+int mfr_sg_kenc_in(const float *kpts, const float *scores, const float *w, const float *bias, long long rows, int H, int W, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * LightGlue kernels (csrc/lightglue.hip): the SuperPoint matcher of LightGlue (ICCV 2023) without adaptive depth / width.  The reference has

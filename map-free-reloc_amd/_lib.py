@@ -44,8 +44,11 @@ SIGNATURES = {
     "mfr_procrustes_icp_refine": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _d, _d, _d, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mfr_sp_scoremap": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "mfr_sp_nms_candidates": (_i, [_vp, _i, _i, _i, _i, C.c_float, _i, _vp, _vp, _i, _vp, _vp]),
+    "mfr_sp_nms_candidates_variant": (_i, [_vp, _i, _i, _i, _i, C.c_float, _i, _vp, _vp, _i, _vp, _i, _vp]),
+    "mfr_sp_nms_stream_geometry": (_i, [_vp, _vp]),
     "mfr_sp_select_topk": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mfr_sp_sample_descriptors": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "mfr_sp_sample_descriptors_ld": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
     "mfr_gemm_f16x2_pack_bytes": (_sz, [_i, _i]),
     "mfr_gemm_f16x2_pack": (_i, [_vp, _i, _i, _vp, _vp]),
     "mfr_gemm_f16x2": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -71,6 +74,9 @@ SIGNATURES = {
                                    _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "mfr_sg_sinkhorn_match_variant": (_i, [_vp, _i, _i, _vp, _vp, C.c_float, _i, C.c_float, _vp, _vp, _i, _vp, _sz,
                                            _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
+    "mfr_sg_sinkhorn_match_strided": (_i, [_vp, _i, _i, _vp, _vp, C.c_longlong, C.c_float, _i, C.c_float, _vp, _vp, _i, C.c_longlong, _vp, _sz,
+                                           _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
+    "mfr_sg_kenc_in": (_i, [_vp, _vp, _vp, _vp, C.c_longlong, _i, _i, _vp, _vp]),
     "mfr_gemm_f16x2_ln_gelu": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_float, _vp, _i, _i, _i, _i, _vp]),
     "mfr_gemm_bf16x3_ln_gelu": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_float, _vp, _i, _i, _i, _i, _vp]),
     "mfr_lg_rotary_table": (_i, [_vp, _vp, _i, _vp, _vp]),

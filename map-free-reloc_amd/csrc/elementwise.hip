@@ -199,6 +199,31 @@ __global__ void __launch_bounds__(256) nchw_to_rows_gather_kernel(const float *_
     nchw_tile_to_rows(x + (size_t)idx.v[blockIdx.z] * C * HW, add, C, HW, out + (size_t)blockIdx.z * out_img_stride, ldo);
 }
 
+// SuperGlue's keypoint-encoder input in ONE pass: normalize_keypoints + layer 0 (3 -> 32, BatchNorm folded) + ReLU, [rows] keypoints / scores ->
+// out [rows, 32].  It restates, operation by operation, kn = (kpts - size / 2) * fp32(1 / c) (how the framework divides by a host scalar) and
+// h = (kn_x w0 + kn_y w1) + (s w2 + b): every product and sum rounded on its own (this TU allows contraction: kenc_rn pins every intermediate).
+// A thread = 4 output channels of a row.
+// a value the compiler must materialise as it is: no contraction into an fma across it, no packing with a neighbour (vectorised into
+// v_pk_mul_f32 / v_pk_add_f32 the kernel missed the framework's bits in a quarter of the outputs on MI355X; scalar instructions give them)
+static __device__ __forceinline__ float kenc_rn(float x) { asm volatile("" : "+v"(x)); return x; }
+__global__ void __launch_bounds__(256) sg_kenc_in_kernel(const float *__restrict__ kpts, const float *__restrict__ scores, const float *__restrict__ w /*[32,3]*/,
+                                                         const float *__restrict__ bias, float cx, float cy, float inv, long long rows, float *__restrict__ out)
+{
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x, row = t >> 3;
+    const int c0 = (int)(t & 7) * 4;
+    if (row >= rows) return;
+    const float kx = kenc_rn(kenc_rn(kpts[2 * row] - cx) * inv), ky = kenc_rn(kenc_rn(kpts[2 * row + 1] - cy) * inv), sc = scores[row];
+    float o[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = c0 + k;
+        const float p = kenc_rn(kenc_rn(kx * w[3 * c]) + kenc_rn(ky * w[3 * c + 1])), q = kenc_rn(kenc_rn(sc * w[3 * c + 2]) + bias[c]);
+        const float h = kenc_rn(p + q);
+        o[k] = h > 0.f ? h : 0.f;
+    }
+    *(float4 *)(out + row * 32 + c0) = make_float4(o[0], o[1], o[2], o[3]);
+}
+
 #include "guard.h"
 // the f16x2 range guard's flag pointer (guard.h): per host thread, NULL = no test
 static thread_local int *mfr_guard_tls = nullptr;
@@ -279,6 +304,17 @@ int mfr_bias_pool2_relu_nchw(const float *x, const float *bias, int B, int C, in
         int gx = (Ho * Wo + 255) / 256; if (gx > 64) gx = 64;
         hipLaunchKernelGGL(bias_pool_relu_kernel, dim3(gx, B * C), dim3(256), 0, (hipStream_t)stream, x, bias, C, H, W, y);
     }
+    CHECK_LAUNCH();
+    return 0;
+}
+
+int mfr_sg_kenc_in(const float *kpts, const float *scores, const float *w, const float *bias, long long rows, int H, int W, float *out, void *stream)
+{
+    if (!kpts || !scores || !w || !bias || !out || rows <= 0 || rows > 0x7fffffffLL * 32 || H <= 0 || W <= 0 || (((size_t)out) & 15)) return MFR_E_ARG;
+    // normalize_keypoints divides by the host scalar 0.7 max(W, H): the framework multiplies by its reciprocal, taken in fp64 and then rounded to fp32
+    const float inv = (float)(1.0 / ((double)(W > H ? W : H) * 0.7));
+    hipLaunchKernelGGL(sg_kenc_in_kernel, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, kpts, scores, w, bias,
+                       (float)W / 2.f, (float)H / 2.f, inv, rows, out);
     CHECK_LAUNCH();
     return 0;
 }

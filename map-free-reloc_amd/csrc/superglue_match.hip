@@ -97,13 +97,13 @@ static __device__ __forceinline__ int sg_row_of(int g, int r, int nq, int t) { r
 // float4 pieces (16-byte loads of the row and of v, all issued before the first use), reduces them with max-then-sum (no
 // data-dependent branch per element) and the 64 partial (max, sum) pairs merge in a butterfly.
 __global__ void __launch_bounds__(256) sg_row_kernel(const float *__restrict__ S, int ldS, const int *__restrict__ n0,
-                                                     const int *__restrict__ n1, float alpha,
+                                                     const int *__restrict__ n1, int nstr, float alpha,
                                                      const float *__restrict__ v /*[B, SG_LDV]*/,
                                                      float *__restrict__ u /*[B, SG_LDV]*/)
 {
     const int b = blockIdx.y, lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int m = n0[b], n = n1[b];
+    const int m = n0[(size_t)b * nstr], n = n1[(size_t)b * nstr];
     if (i > m || m == 0 || n == 0) return;
     const float *vb = v + (size_t)b * SG_LDV(ldS);
     const float norm = -__logf((float)(m + n));
@@ -144,13 +144,13 @@ __global__ void __launch_bounds__(256) sg_row_kernel(const float *__restrict__ S
 
 // columns 0..n (column n = dustbin column); block = 64 columns x 16 row-groups
 __global__ void __launch_bounds__(1024) sg_col_kernel(const float *__restrict__ S, int ldS, const int *__restrict__ n0,
-                                                      const int *__restrict__ n1, float alpha,
+                                                      const int *__restrict__ n1, int nstr, float alpha,
                                                       const float *__restrict__ u, float *__restrict__ v)
 {
     __shared__ float sm[16][64], ss[16][64];
     const int b = blockIdx.y, lane = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int j = blockIdx.x * 64 + lane;
-    const int m = n0[b], n = n1[b];
+    const int m = n0[(size_t)b * nstr], n = n1[(size_t)b * nstr];
     if (m == 0 || n == 0) return;
     const float *ub = u + (size_t)b * SG_LDV(ldS);
     Lse a = { -INFINITY, 0.f };
@@ -200,7 +200,7 @@ __global__ void __launch_bounds__(1024) sg_col_kernel(const float *__restrict__ 
 // in sg_col_kernel's order (k = 1 .. 15) into v.  The dustbin column is a 17th column of every lane (its entries are all alpha), and the
 // dustbin row's u_m is computed by workgroup 0 before its rows.  Requires the 16-byte fast path of sg_row_kernel (ldS % 4 == 0, ldS <= 1024); other shapes keep
 // the two-pass kernels.
-__global__ void __launch_bounds__(512, 2) sg_sweep_kernel(const float *__restrict__ S, int ldS, const int *__restrict__ n0, const int *__restrict__ n1,
+__global__ void __launch_bounds__(512, 2) sg_sweep_kernel(const float *__restrict__ S, int ldS, const int *__restrict__ n0, const int *__restrict__ n1, int nstr,
                                                        float alpha, const float *__restrict__ v, float *__restrict__ u,
                                                        float *__restrict__ part_m /*[B, 16, SG_LDV]*/, float *__restrict__ part_s)
 {
@@ -217,7 +217,7 @@ __global__ void __launch_bounds__(512, 2) sg_sweep_kernel(const float *__restric
     // SIMD holds four wavefronts of ~110 registers instead of two of 204: their dependent exponential chains and row loads fill each other's gaps
     // (profiles/r05_pmc_sinkhorn.json: the four-wavefront kernel spent 34 % of its wave cycles blocked at issue, 28 % parked on loads)
     const int b = blockIdx.y, g = blockIdx.x, lane = threadIdx.x & 63, w8 = threadIdx.x >> 6, r = w8 & 3, hb = w8 >> 2;
-    const int m = n0[b], n = n1[b];
+    const int m = n0[(size_t)b * nstr], n = n1[(size_t)b * nstr];
     if (m == 0 || n == 0) return;
     const int ldv = SG_LDV(ldS);
     const float *vb = v + (size_t)b * ldv;
@@ -378,11 +378,11 @@ __global__ void __launch_bounds__(512, 2) sg_sweep_kernel(const float *__restric
 }
 
 // v_j = log_nu_j - LSE over the 16 group partials (k = 1 .. 15 folded into group 0's, sg_col_kernel's order), columns 0 .. n (n = dustbin)
-__global__ void __launch_bounds__(64) sg_colmerge_kernel(int ldS, const int *__restrict__ n0, const int *__restrict__ n1,
+__global__ void __launch_bounds__(64) sg_colmerge_kernel(int ldS, const int *__restrict__ n0, const int *__restrict__ n1, int nstr,
                                                          const float *__restrict__ part_m, const float *__restrict__ part_s, float *__restrict__ v)
 {
     const int b = blockIdx.y, j = blockIdx.x * 64 + threadIdx.x;
-    const int m = n0[b], n = n1[b];
+    const int m = n0[(size_t)b * nstr], n = n1[(size_t)b * nstr];
     if (m == 0 || n == 0 || j > n) return;
     const int ldv = SG_LDV(ldS);
     const float norm = -__logf((float)(m + n));
@@ -399,13 +399,13 @@ __global__ void __launch_bounds__(64) sg_colmerge_kernel(int ldS, const int *__r
 
 // per-row argmax over j<n of (S_ij + v_j) and per-column argmax over i<m of (S_ij + u_i)
 __global__ void __launch_bounds__(256) sg_rowmax_kernel(const float *__restrict__ S, int ldS,
-                                                        const int *__restrict__ n0, const int *__restrict__ n1,
+                                                        const int *__restrict__ n0, const int *__restrict__ n1, int nstr,
                                                         const float *__restrict__ v, int *__restrict__ idx0,
                                                         float *__restrict__ val0)
 {
     const int b = blockIdx.y, lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int m = n0[b], n = n1[b];
+    const int m = n0[(size_t)b * nstr], n = n1[(size_t)b * nstr];
     if (i >= m || n == 0) return;
     const float *row = S + ((size_t)b * ldS + i) * ldS;
     const float *vb = v + (size_t)b * SG_LDV(ldS);
@@ -419,14 +419,14 @@ __global__ void __launch_bounds__(256) sg_rowmax_kernel(const float *__restrict_
 }
 
 __global__ void __launch_bounds__(1024) sg_colmax_kernel(const float *__restrict__ S, int ldS,
-                                                         const int *__restrict__ n0, const int *__restrict__ n1,
+                                                         const int *__restrict__ n0, const int *__restrict__ n1, int nstr,
                                                          const float *__restrict__ u, int *__restrict__ idx1)
 {
     __shared__ float sb[16][64];
     __shared__ int si[16][64];
     const int b = blockIdx.y, lane = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int j = blockIdx.x * 64 + lane;
-    const int m = n0[b], n = n1[b];
+    const int m = n0[(size_t)b * nstr], n = n1[(size_t)b * nstr];
     if (m == 0 || n == 0) return;
     const float *ub = u + (size_t)b * SG_LDV(ldS);
     float best = -INFINITY; int bi = 0x7fffffff;
@@ -450,15 +450,15 @@ __global__ void __launch_bounds__(1024) sg_colmax_kernel(const float *__restrict
 
 // one workgroup per pair: mutual check + threshold + ordered compaction (matchers.py:111-116)
 __global__ void __launch_bounds__(256) sg_match_kernel(
-    int ldS, const int *__restrict__ n0, const int *__restrict__ n1, const float *__restrict__ u,
+    int ldS, const int *__restrict__ n0, const int *__restrict__ n1, int nstr, const float *__restrict__ u,
     const int *__restrict__ idx0, const float *__restrict__ val0, const int *__restrict__ idx1, float thr,
-    const float *__restrict__ kpts0, const float *__restrict__ kpts1, int K /*kpts stride*/,
+    const float *__restrict__ kpts0, const float *__restrict__ kpts1, long long kstr /*floats between two pairs' keypoints*/,
     int *__restrict__ matches0, float *__restrict__ mscores0, float *__restrict__ pts0, float *__restrict__ pts1,
     int maxN, int *__restrict__ n_corr)
 {
     __shared__ Compact256 cs;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int m = n0[b], n = n1[b];
+    const int m = n0[(size_t)b * nstr], n = n1[(size_t)b * nstr];
     int total = 0;
     const float norm = (m > 0 && n > 0) ? -__logf((float)(m + n)) : 0.f;
     for (int start = 0; start < ldS; start += 256) {
@@ -481,13 +481,15 @@ __global__ void __launch_bounds__(256) sg_match_kernel(
         const int o = compact256_slot(cs, valid, total);
         if (valid) {
             if (o < maxN) {
-                pts0[((size_t)b * maxN + o) * 2] = kpts0[((size_t)b * K + i) * 2];
-                pts0[((size_t)b * maxN + o) * 2 + 1] = kpts0[((size_t)b * K + i) * 2 + 1];
-                pts1[((size_t)b * maxN + o) * 2] = kpts1[((size_t)b * K + j) * 2];
-                pts1[((size_t)b * maxN + o) * 2 + 1] = kpts1[((size_t)b * K + j) * 2 + 1];
+                pts0[((size_t)b * maxN + o) * 2] = kpts0[(size_t)b * kstr + (size_t)i * 2];
+                pts0[((size_t)b * maxN + o) * 2 + 1] = kpts0[(size_t)b * kstr + (size_t)i * 2 + 1];
+                pts1[((size_t)b * maxN + o) * 2] = kpts1[(size_t)b * kstr + (size_t)j * 2];
+                pts1[((size_t)b * maxN + o) * 2 + 1] = kpts1[(size_t)b * kstr + (size_t)j * 2 + 1];
             }
         }
     }
+    // rows >= n_corr are zero whatever the caller's buffers held
+    for (int o = min(total, maxN) * 2 + tid; o < maxN * 2; o += 256) { pts0[(size_t)b * maxN * 2 + o] = 0.f; pts1[(size_t)b * maxN * 2 + o] = 0.f; }
     if (tid == 0) n_corr[b] = min(total, maxN);
 }
 
@@ -516,15 +518,20 @@ size_t mfr_sg_match_workspace_bytes(int B, int ldS)
 
 // variant: 0 = one sweep over S per iteration (sg_sweep_kernel + sg_colmerge_kernel) when ldS % 4 == 0 and ldS <= 1024, else as 1;
 // 1 = the two-pass kernels (sg_row_kernel + sg_col_kernel).  Both produce the same bits.
-int mfr_sg_sinkhorn_match_variant(const float *S, int B, int ldS, const int32_t *n0, const int32_t *n1,
+// n0 / n1 [B] with `n_stride` elements between two pairs' counts, kpts0 / kpts1 [K, 2] per pair with `kpts_stride` floats between two pairs:
+// the interleaved [2B] tensors of the matcher are read in place (n0 = n, n1 = n + 1, n_stride 2; kpts_stride 4 K)
+int mfr_sg_sinkhorn_match_strided(const float *S, int B, int ldS, const int32_t *n0, const int32_t *n1, long long n_stride,
                                   float bin_score, int iters, float match_thr,
-                                  const float *kpts0, const float *kpts1, int K,
+                                  const float *kpts0, const float *kpts1, int K, long long kpts_stride,
                                   void *workspace, size_t workspace_bytes,
                                   int32_t *matches0, float *mscores0, float *pts0, float *pts1, int maxN, int32_t *n_corr,
                                   int variant, void *stream)
 {
     if (!S || !n0 || !n1 || !kpts0 || !kpts1 || !workspace || !matches0 || !mscores0 || !pts0 || !pts1 || !n_corr ||
-        B <= 0 || ldS <= 0 || K < ldS || maxN <= 0 || iters < 0 || variant < 0 || variant > 1) return MFR_E_ARG;
+        B <= 0 || ldS <= 0 || K < ldS || maxN <= 0 || iters < 0 || variant < 0 || variant > 1 || n_stride < 1 || n_stride > 0x7fffffffLL / B ||
+        kpts_stride < 2LL * K) return MFR_E_ARG;
+    const int nstr = (int)n_stride;
+    const long long kstr = kpts_stride;
     const SgWs w = sg_ws_layout(B, ldS);
     if (workspace_bytes < w.total) return MFR_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
@@ -538,20 +545,31 @@ int mfr_sg_sinkhorn_match_variant(const float *S, int B, int ldS, const int32_t 
     const dim3 rgrid((ldS + 1 + 3) / 4, B), cgrid((ldS + 1 + 63) / 64, B);
     for (int it = 0; it < iters; ++it) {
         if (sweep) {
-            hipLaunchKernelGGL(sg_sweep_kernel, dim3(16, B), dim3(512), 0, s, S, ldS, n0, n1, bin_score, v, u, part_m, part_s);
-            hipLaunchKernelGGL(sg_colmerge_kernel, cgrid, dim3(64), 0, s, ldS, n0, n1, part_m, part_s, v);
+            hipLaunchKernelGGL(sg_sweep_kernel, dim3(16, B), dim3(512), 0, s, S, ldS, n0, n1, nstr, bin_score, v, u, part_m, part_s);
+            hipLaunchKernelGGL(sg_colmerge_kernel, cgrid, dim3(64), 0, s, ldS, n0, n1, nstr, part_m, part_s, v);
         } else {
-            hipLaunchKernelGGL(sg_row_kernel, rgrid, dim3(256), 0, s, S, ldS, n0, n1, bin_score, v, u);
-            hipLaunchKernelGGL(sg_col_kernel, cgrid, dim3(1024), 0, s, S, ldS, n0, n1, bin_score, u, v);
+            hipLaunchKernelGGL(sg_row_kernel, rgrid, dim3(256), 0, s, S, ldS, n0, n1, nstr, bin_score, v, u);
+            hipLaunchKernelGGL(sg_col_kernel, cgrid, dim3(1024), 0, s, S, ldS, n0, n1, nstr, bin_score, u, v);
         }
     }
     CHECK_LAUNCH();
-    hipLaunchKernelGGL(sg_rowmax_kernel, dim3((ldS + 3) / 4, B), dim3(256), 0, s, S, ldS, n0, n1, v, idx0, val0);
-    hipLaunchKernelGGL(sg_colmax_kernel, dim3((ldS + 63) / 64, B), dim3(1024), 0, s, S, ldS, n0, n1, u, idx1);
-    hipLaunchKernelGGL(sg_match_kernel, dim3(B), dim3(256), 0, s, ldS, n0, n1, u, idx0, val0, idx1, match_thr, kpts0,
-                       kpts1, K, matches0, mscores0, pts0, pts1, maxN, n_corr);
+    hipLaunchKernelGGL(sg_rowmax_kernel, dim3((ldS + 3) / 4, B), dim3(256), 0, s, S, ldS, n0, n1, nstr, v, idx0, val0);
+    hipLaunchKernelGGL(sg_colmax_kernel, dim3((ldS + 63) / 64, B), dim3(1024), 0, s, S, ldS, n0, n1, nstr, u, idx1);
+    hipLaunchKernelGGL(sg_match_kernel, dim3(B), dim3(256), 0, s, ldS, n0, n1, nstr, u, idx0, val0, idx1, match_thr, kpts0,
+                       kpts1, kstr, matches0, mscores0, pts0, pts1, maxN, n_corr);
     CHECK_LAUNCH();
     return 0;
+}
+
+int mfr_sg_sinkhorn_match_variant(const float *S, int B, int ldS, const int32_t *n0, const int32_t *n1,
+                                  float bin_score, int iters, float match_thr,
+                                  const float *kpts0, const float *kpts1, int K,
+                                  void *workspace, size_t workspace_bytes,
+                                  int32_t *matches0, float *mscores0, float *pts0, float *pts1, int maxN, int32_t *n_corr,
+                                  int variant, void *stream)
+{
+    return mfr_sg_sinkhorn_match_strided(S, B, ldS, n0, n1, 1, bin_score, iters, match_thr, kpts0, kpts1, K, 2LL * K, workspace, workspace_bytes, matches0,
+                                         mscores0, pts0, pts1, maxN, n_corr, variant, stream);
 }
 
 int mfr_sg_sinkhorn_match(const float *S, int B, int ldS, const int32_t *n0, const int32_t *n1,

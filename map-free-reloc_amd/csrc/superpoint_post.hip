@@ -10,6 +10,8 @@
 //                        (2r+1)^2 max-pools run on an LDS tile with a 5r halo; also applies the
 //                        keypoint threshold + border removal and appends survivors to a per-image
 //                        candidate list (key = score bits | ~raster index)
+//   sp_nms_stream_kernel the same NMS, streaming: a wavefront walks down a strip of an image with the five pools pipelined in
+//                        row lag, no workgroup barrier (what mfr_sp_nms_candidates runs; sp_nms_kernel is its A/B partner)
 //   sp_select_kernel     top-K by (score desc, raster index asc) via 64-bit radix select + bitonic
 //                        sort in LDS (or raster order when there are <= K candidates, like upstream's
 //                        nonzero() order) -> keypoints (x,y), scores, count
@@ -19,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <type_traits>
+#include <utility>
 
 #include "../../include/mfr_hip.h"
 #include "wave_dev.h"
@@ -247,6 +251,173 @@ __global__ void __launch_bounds__(NMS_THREADS, 8) sp_nms_kernel(const float *__r
 }
 
 // ------------------------------------------------------------------------------------------
+// streaming simple_nms: the same five pools, no workgroup barrier.  ONE wavefront owns a strip of NMSS_COLS columns (lane l holds the two
+// ADJACENT columns c0 + 2 l and c0 + 2 l + 1; the outer NMS_HALO columns on each side are halo) and walks down NMSS_G output rows of one
+// image plus a NMS_HALO-row warm-up and run-out.  Per row step (r = the row just read) the pipeline advances in row lag:
+//     lag  4   P1 = pool(scores),               M0 = (scores == P1)
+//     lag  8   D1 = dilate(M0),                 SS1 = where(D1, 0, scores)
+//     lag 12   P2 = pool(SS1),                  M1 = M0 | ((SS1 == P2) & ~D1)
+//     lag 16   D2 = dilate(M1),                 SS2 = where(D2, 0, scores)
+//     lag 20   P3 = pool(SS2),                  M2 = M1 | ((SS2 == P3) & ~D2)  -> output row r - 20
+// Pools are separable: the horizontal 9-max of a row crosses lanes (6 lane shifts for the two columns), the vertical one runs over a
+// register ring of the last 9 horizontally-maxed rows; the scores sit in a ring of 24 rows.  The row loop is unrolled 24 times, so every
+// ring index is a compile-time register; a row is read NMSS_PF steps before its use.  A mask is a per-lane BIT HISTORY (bit k of m0 = M0 of the lane's column k rows ago): the
+// vertical 9-dilation is one AND, the horizontal one a ballot, scalar shifts and ORs.  Whatever the rings hold before the warm-up only
+// reaches rows above the segment (each stage consumes 4 rows / 4 columns of halo), like the tile edges of sp_nms_kernel.
+// Out-of-image cells are -inf (max_pool2d's padding), never turned into 0, and carry no mask bit.
+// what mfr_sp_nms_candidates runs: 0 = the streaming kernel, 1 = the tile kernel (profiles/nms_stream_ab.json)
+#define MFR_SP_NMS_DEFAULT_VARIANT 0
+#define NMSS_COLS 128
+#define NMSS_U (NMSS_COLS - 2 * NMS_HALO)      // 88 useful columns per strip
+#define NMSS_G 136                             // output rows per segment
+#define NMSS_SR 24                             // score ring (21 rows live)
+#define NMSS_HR 12                             // pooled-row rings (9 rows live)
+#define NMSS_PF 3                              // rows read ahead: 21 live + 3 in flight fill the score ring
+#define NMSS_STAGE 256                         // wave-private candidate staging (keys); a row adds at most NMSS_U
+
+// horizontal 9-max for the lane's two columns (a = column 2 l, b = column 2 l + 1 of the strip)
+static __device__ __forceinline__ void nmss_hmax9(float a, float b, float &wa, float &wb)
+{
+    const float p = fmaxf(a, b);
+    const float pm1 = __shfl_up(p, 1, 64), pp1 = __shfl_down(p, 1, 64);
+    const float am2 = __shfl_up(a, 2, 64), bm2 = __shfl_up(b, 2, 64);
+    const float ap2 = __shfl_down(a, 2, 64), bp2 = __shfl_down(b, 2, 64);
+    const float q = fmaxf(fmaxf(pm1, p), pp1);                       // columns 2 l - 2 .. 2 l + 3
+    wa = fmaxf(fmaxf(q, fmaxf(am2, bm2)), ap2);                      // 2 l - 4 .. 2 l + 4
+    wb = fmaxf(fmaxf(q, bm2), fmaxf(ap2, bp2));                      // 2 l - 3 .. 2 l + 5
+}
+// horizontal 9-dilation of a row of mask bits: e / o = ballots of the even / odd columns
+static __device__ __forceinline__ void nmss_hdil9(unsigned long long e, unsigned long long o, unsigned long long &de, unsigned long long &dn)
+{
+    const unsigned long long a = e | o, x = a | (a << 1) | (a >> 1);                  // lanes l - 1 .. l + 1, both columns of each
+    const unsigned long long el = e << 2, er = e >> 2, ol = o << 2, orr = o >> 2;
+    de = x | el | er | ol;                                           // column 2 l: even l - 2 .. l + 2, odd l - 2 .. l + 1
+    dn = x | ol | orr | er;                                          // column 2 l + 1: odd l - 2 .. l + 2, even l - 1 .. l + 2
+}
+#define NMSS_MAX9(h, j) fmaxf(fmaxf(fmaxf(fmaxf(h[(j) % NMSS_HR], h[((j) + 11) % NMSS_HR]), h[((j) + 10) % NMSS_HR]),                        \
+                                    fmaxf(fmaxf(h[((j) + 9) % NMSS_HR], h[((j) + 8) % NMSS_HR]), h[((j) + 7) % NMSS_HR])),                   \
+                              fmaxf(fmaxf(h[((j) + 6) % NMSS_HR], h[((j) + 5) % NMSS_HR]), h[((j) + 4) % NMSS_HR]))
+
+// f(0) && f(1) && ... with the argument as a type: the row loop's 24 steps written out
+template <class F, int... J> static __device__ __forceinline__ bool nmss_unrolled(F &f, std::integer_sequence<int, J...>)
+{
+    return (f(std::integral_constant<int, J>{}) && ...);
+}
+
+// (240 registers: two wavefronts per SIMD; capped at 168 or 128 registers the rings spill)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 3))) sp_nms_stream_kernel(const float *__restrict__ scores, int H, int W, float thr, int border,
+                                                           float *__restrict__ nms_out /*may be NULL*/, unsigned long long *__restrict__ cand,
+                                                           int cand_cap, int *__restrict__ cand_count)
+{
+    __shared__ unsigned long long stage[NMSS_STAGE];
+    const int lane = threadIdx.x, b = blockIdx.z;
+    const int xa = blockIdx.x * NMSS_U - NMS_HALO + 2 * lane, xb = xa + 1;                   // the lane's two columns
+    const int ys = blockIdx.y * NMSS_G, ye = min(ys + NMSS_G, H);                             // output rows [ys, ye)
+    const float *img = scores + (size_t)b * H * W;
+    const bool ina = xa >= 0 && xa < W, inb = xb >= 0 && xb < W;
+    const bool useful = lane >= NMS_HALO / 2 && lane < (NMSS_COLS - NMS_HALO) / 2;
+    const bool outa = useful && ina, outb = useful && inb;
+    const bool bora = xa >= border && xa < W - border, borb = xb >= border && xb < W - border;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    float sa[NMSS_SR], sb[NMSS_SR], h1a[NMSS_HR], h1b[NMSS_HR], h2a[NMSS_HR], h2b[NMSS_HR], h3a[NMSS_HR], h3b[NMSS_HR];
+#pragma unroll
+    for (int i = 0; i < NMSS_SR; ++i) sa[i] = sb[i] = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NMSS_HR; ++i) h1a[i] = h1b[i] = h2a[i] = h2b[i] = h3a[i] = h3b[i] = -INFINITY;
+    unsigned m0a = 0u, m0b = 0u, d1a = 0u, d1b = 0u, m1a = 0u, m1b = 0u, d2a = 0u, d2b = 0u;      // bit histories, bit 0 = the newest row
+    int staged = 0;
+    // append the staged keys to the image's list: ONE atomic per flush (per-candidate atomics on the adjacent per-image counters serialise)
+    auto flush = [&]() {
+        int base = 0;
+        if (lane == 0) base = atomicAdd(&cand_count[b], staged);
+        base = __shfl(base, 0, 64);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        for (int i = lane; i < staged; i += 64)
+            if (base + i < cand_cap) cand[(size_t)b * cand_cap + base + i] = stage[i];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        staged = 0;
+    };
+    const int rend = ye + NMS_HALO;
+    int r0 = ys - NMS_HALO;
+    // unconditional reads at clamped coordinates (no branch around the load); -inf is selected outside the image when the row is used
+    const int xac = min(max(xa, 0), W - 1), xbc = min(max(xb, 0), W - 1);
+    auto load_row = [&](int r, float &va, float &vb) __attribute__((always_inline)) {
+        const float *row = img + (size_t)min(max(r, 0), H - 1) * W;
+        va = row[xac]; vb = row[xbc];
+    };
+#pragma unroll
+    for (int i = 0; i < NMSS_PF; ++i) load_row(r0 + i, sa[i], sb[i]);
+    // one row step; j = the row's slot in the score ring as a compile-time constant, so that every ring access is a named register
+    auto step = [&](auto jc) __attribute__((always_inline)) -> bool {
+            constexpr int j = decltype(jc)::value;
+            const int r = r0 + j;
+            if (r >= rend) return false;
+            // lag 0: row r, horizontal max
+            // rows / columns outside the image hold -inf and carry no mask bit: the tests are geometric (a lane constant and a wave-uniform flag)
+            const bool rin4 = (unsigned)(r - 4) < (unsigned)H, rin8 = (unsigned)(r - 8) < (unsigned)H,
+                       rin12 = (unsigned)(r - 12) < (unsigned)H, rin16 = (unsigned)(r - 16) < (unsigned)H, rin20 = (unsigned)(r - 20) < (unsigned)H;
+            // the row was read NMSS_PF steps ago (its latency hides under those steps); read row r + NMSS_PF into the slots that fell free
+            load_row(r + NMSS_PF, sa[(j + NMSS_PF) % NMSS_SR], sb[(j + NMSS_PF) % NMSS_SR]);
+            const bool rin = (unsigned)r < (unsigned)H;
+            const float s0a = (rin & ina) ? sa[j] : -INFINITY, s0b = (rin & inb) ? sb[j] : -INFINITY;
+            sa[j] = s0a; sb[j] = s0b;
+            nmss_hmax9(s0a, s0b, h1a[j % NMSS_HR], h1b[j % NMSS_HR]);
+            // lag 4: P1, M0
+            const float s4a = sa[(j + 20) % NMSS_SR], s4b = sb[(j + 20) % NMSS_SR];
+            const float p1a = NMSS_MAX9(h1a, j), p1b = NMSS_MAX9(h1b, j);
+            m0a = (m0a << 1) | (unsigned)((s4a == p1a) & ina & rin4);
+            m0b = (m0b << 1) | (unsigned)((s4b == p1b) & (inb & rin4));
+            // lag 8: D1 = 9 x 9 dilation of M0 (rows r - 12 .. r - 4 = bits 8 .. 0), SS1, its horizontal max
+            unsigned long long de, dn;
+            nmss_hdil9(__ballot((m0a & 0x1ffu) != 0u), __ballot((m0b & 0x1ffu) != 0u), de, dn);
+            d1a = (d1a << 1) | (unsigned)((de >> lane) & 1ull);
+            d1b = (d1b << 1) | (unsigned)((dn >> lane) & 1ull);
+            const float s8a = sa[(j + 16) % NMSS_SR], s8b = sb[(j + 16) % NMSS_SR];
+            nmss_hmax9((((d1a & 1u) != 0u) & ina & rin8) ? 0.f : s8a, (((d1b & 1u) != 0u) & (inb & rin8)) ? 0.f : s8b,
+                       h2a[j % NMSS_HR], h2b[j % NMSS_HR]);
+            // lag 12: P2, M1 (M0 of row r - 12 = bit 8 of m0, D1 of row r - 12 = bit 4 of d1)
+            const float s12a = sa[(j + 12) % NMSS_SR], s12b = sb[(j + 12) % NMSS_SR];
+            const float p2a = NMSS_MAX9(h2a, j), p2b = NMSS_MAX9(h2b, j);
+            m1a = (m1a << 1) | ((m0a >> 8) & 1u) | (unsigned)((((d1a >> 4) & 1u) == 0u) & (s12a == p2a) & ina & rin12);
+            m1b = (m1b << 1) | ((m0b >> 8) & 1u) | (unsigned)((((d1b >> 4) & 1u) == 0u) & (s12b == p2b) & (inb & rin12));
+            // lag 16: D2, SS2, its horizontal max
+            nmss_hdil9(__ballot((m1a & 0x1ffu) != 0u), __ballot((m1b & 0x1ffu) != 0u), de, dn);
+            d2a = (d2a << 1) | (unsigned)((de >> lane) & 1ull);
+            d2b = (d2b << 1) | (unsigned)((dn >> lane) & 1ull);
+            const float s16a = sa[(j + 8) % NMSS_SR], s16b = sb[(j + 8) % NMSS_SR];
+            nmss_hmax9((((d2a & 1u) != 0u) & ina & rin16) ? 0.f : s16a, (((d2b & 1u) != 0u) & (inb & rin16)) ? 0.f : s16b,
+                       h3a[j % NMSS_HR], h3b[j % NMSS_HR]);
+            // lag 20: P3, M2, output row r - 20
+            const int yo = r - NMS_HALO;
+            if (yo < ys) return true;                                // warm-up (yo < ye always: r < rend)
+            const float s20a = sa[(j + 4) % NMSS_SR], s20b = sb[(j + 4) % NMSS_SR];
+            const float p3a = NMSS_MAX9(h3a, j), p3b = NMSS_MAX9(h3b, j);
+            const bool m2a = (((m1a >> 8) & 1u) != 0u) | ((((d2a >> 4) & 1u) == 0u) & (s20a == p3a) & ina & rin20);
+            const bool m2b = (((m1b >> 8) & 1u) != 0u) | ((((d2b >> 4) & 1u) == 0u) & (s20b == p3b) & (inb & rin20));
+            const float va = m2a ? s20a : 0.f, vb = m2b ? s20b : 0.f;
+            if (nms_out) {
+                float *o = nms_out + (size_t)b * H * W + (size_t)yo * W;
+                if (outa) o[xa] = va;
+                if (outb) o[xb] = vb;
+            }
+            const bool rowin = yo >= border && yo < H - border;
+            const bool ca = outa & rowin & bora & (va > thr), cb = outb & rowin & borb & (vb > thr);
+            const unsigned long long ba = __ballot(ca), bb = __ballot(cb);
+            if (ba | bb) {
+                const int na = __popcll(ba);
+                if (ca) stage[staged + __popcll(ba & below)] = ((unsigned long long)__float_as_uint(va) << 32) | (unsigned long long)(~(unsigned)(yo * W + xa));
+                if (cb) stage[staged + na + __popcll(bb & below)] = ((unsigned long long)__float_as_uint(vb) << 32) | (unsigned long long)(~(unsigned)(yo * W + xb));
+                staged += na + __popcll(bb);
+                if (staged > NMSS_STAGE - NMSS_U) flush();
+            }
+            return true;
+    };
+    for (; r0 < rend; r0 += NMSS_SR)
+        if (!nmss_unrolled(step, std::make_integer_sequence<int, NMSS_SR>{})) break;
+    if (staged) flush();
+}
+
+// ------------------------------------------------------------------------------------------
 // one 1024-thread workgroup per image.  keys are unique (raster index in the low word).
 #define SEL_T 1024
 __global__ void __launch_bounds__(SEL_T) sp_select_kernel(const unsigned long long *__restrict__ cand, int cand_cap,
@@ -342,13 +513,13 @@ __global__ void __launch_bounds__(SEL_T) sp_select_kernel(const unsigned long lo
 // one wavefront per keypoint; dense [B,Hc,Wc,256] NHWC raw descriptors
 __global__ void __launch_bounds__(256) sp_sample_kernel(const float *__restrict__ dense, int Hc, int Wc,
                                                         const float *__restrict__ kpts, const int *__restrict__ n_kpts,
-                                                        int K, float *__restrict__ desc /*[B,K,256]*/)
+                                                        int K, float *__restrict__ desc /*[B,K,256], rows ldd floats apart*/, int ldd)
 {
     const int b = blockIdx.y;
     const int kp = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (kp >= K) return;
-    float4 *o = (float4 *)(desc + ((size_t)b * K + kp) * 256) + lane;
+    float4 *o = (float4 *)(desc + ((size_t)b * K + kp) * ldd) + lane;
     if (kp >= n_kpts[b]) { *o = make_float4(0.f, 0.f, 0.f, 0.f); return; }
     const float s = 8.f;
     float kx = kpts[((size_t)b * K + kp) * 2], ky = kpts[((size_t)b * K + kp) * 2 + 1];
@@ -389,13 +560,22 @@ int mfr_sp_scoremap(const float *logits, int B, int Hc, int Wc, float *scores, v
     return 0;
 }
 
-int mfr_sp_nms_candidates(const float *scores, int B, int H, int W, int nms_radius, float threshold, int border,
-                          float *nms_out, uint64_t *cand, int cand_cap, int32_t *cand_count, void *stream)
+int mfr_sp_nms_candidates_variant(const float *scores, int B, int H, int W, int nms_radius, float threshold, int border,
+                                  float *nms_out, uint64_t *cand, int cand_cap, int32_t *cand_count, int variant, void *stream)
 {
     if (!scores || !cand || !cand_count || B <= 0 || H <= 0 || W <= 0 || cand_cap <= 0) return MFR_E_ARG;
     if (nms_radius != NMS_R) return MFR_E_ARG;          // compiled for the reference's radius (matchers.py:65)
+    if (variant != 0 && variant != 1) return MFR_E_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (mfr_zero_async(cand_count, sizeof(int32_t) * (size_t)B, s) != hipSuccess) return MFR_E_LAUNCH;
+    if (variant == 0) {                                 // streaming: a wavefront per (strip, segment, image), no LDS tile
+        if ((long long)H * W > 0x7fffffffLL) return MFR_E_ARG;
+        dim3 grid((W + NMSS_U - 1) / NMSS_U, (H + NMSS_G - 1) / NMSS_G, B);
+        hipLaunchKernelGGL(sp_nms_stream_kernel, grid, dim3(64), 0, s, scores, H, W, threshold, border, nms_out,
+                           (unsigned long long *)cand, cand_cap, cand_count);
+        CHECK_LAUNCH();
+        return 0;
+    }
     dim3 grid((W + NMS_TW - 1) / NMS_TW, (H + NMS_TH - 1) / NMS_TH, B);
     // 62.5 KiB of LDS (two float tiles + three sets of bit rows): two workgroups per CU
     const size_t smem = 2 * NMS_N * sizeof(float) + 3 * 2 * NMS_LH * sizeof(unsigned long long);
@@ -403,6 +583,19 @@ int mfr_sp_nms_candidates(const float *scores, int B, int H, int W, int nms_radi
     hipLaunchKernelGGL(sp_nms_kernel, grid, dim3(NMS_THREADS), smem, s, scores, H, W, threshold, border,
                        nms_out, (unsigned long long *)cand, cand_cap, cand_count);
     CHECK_LAUNCH();
+    return 0;
+}
+
+int mfr_sp_nms_candidates(const float *scores, int B, int H, int W, int nms_radius, float threshold, int border,
+                          float *nms_out, uint64_t *cand, int cand_cap, int32_t *cand_count, void *stream)
+{
+    return mfr_sp_nms_candidates_variant(scores, B, H, W, nms_radius, threshold, border, nms_out, cand, cand_cap, cand_count, MFR_SP_NMS_DEFAULT_VARIANT, stream);
+}
+
+int mfr_sp_nms_stream_geometry(int *useful_cols, int *segment_rows)
+{
+    if (!useful_cols || !segment_rows) return MFR_E_ARG;
+    *useful_cols = NMSS_U; *segment_rows = NMSS_G;
     return 0;
 }
 
@@ -417,14 +610,22 @@ int mfr_sp_select_topk(const uint64_t *cand, int cand_cap, const int32_t *cand_c
     return 0;
 }
 
+// desc rows ldd >= 256 floats apart (a multiple of 4, desc 16-byte aligned): the descriptors can land in a wider buffer, e.g. the left half of
+// SuperGlue's [x | a] rows; what lies beyond a row's 256 floats is not touched
+int mfr_sp_sample_descriptors_ld(const float *dense_nhwc, int B, int Hc, int Wc, const float *kpts,
+                                 const int32_t *n_kpts, int K, float *desc, int ldd, void *stream)
+{
+    if (!dense_nhwc || !kpts || !n_kpts || !desc || B <= 0 || Hc <= 0 || Wc <= 0 || K <= 0 || ldd < 256 || (ldd & 3) || (((size_t)desc) & 15)) return MFR_E_ARG;
+    hipLaunchKernelGGL(sp_sample_kernel, dim3((K + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, dense_nhwc, Hc, Wc,
+                       kpts, n_kpts, K, desc, ldd);
+    CHECK_LAUNCH();
+    return 0;
+}
+
 int mfr_sp_sample_descriptors(const float *dense_nhwc, int B, int Hc, int Wc, const float *kpts,
                               const int32_t *n_kpts, int K, float *desc, void *stream)
 {
-    if (!dense_nhwc || !kpts || !n_kpts || !desc || B <= 0 || Hc <= 0 || Wc <= 0 || K <= 0) return MFR_E_ARG;
-    hipLaunchKernelGGL(sp_sample_kernel, dim3((K + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, dense_nhwc, Hc, Wc,
-                       kpts, n_kpts, K, desc);
-    CHECK_LAUNCH();
-    return 0;
+    return mfr_sp_sample_descriptors_ld(dense_nhwc, B, Hc, Wc, kpts, n_kpts, K, desc, 256, stream);
 }
 
 }  // extern "C"

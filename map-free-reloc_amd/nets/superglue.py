@@ -10,7 +10,6 @@ time to head-major (c' = 64 h + d) by permuting the q/k/v output rows and the me
 so every head is a contiguous 256-byte slice for the attention kernel.
 """
 import torch
-import torch.nn.functional as F
 
 from .. import _lib
 from .linear import SplitBatchedNT, SplitLinear
@@ -104,7 +103,8 @@ class SuperGlueHIP:
         self.score_gemm = SplitBatchedNT() if self.lin_final.split == "f16x2" else None      # (the bf16x3 arithmetic keeps the library's batched fp32 GEMM)
         self.bin_score = fw["bin_score"]
         self._ws = None
-        self._size = {}
+        self._xa = None
+        self.in_place = True      # False: the tests' A/B partner -- contiguous copies of the counts / keypoints into the match head
 
     def attention(self, qkv, n_tok, cross, out=None, ldo=256, variant=None):
         """qkv [B2,K,768] (q | k | v, each head-major) -> message [B2,K,256] (or into `out`, row stride ldo floats);
@@ -131,36 +131,54 @@ class SuperGlueHIP:
             self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
         m0 = torch.empty(B, ldS, dtype=torch.int32, device=dev)
         ms0 = torch.empty(B, ldS, dtype=torch.float32, device=dev)
-        pts0 = torch.zeros(B, maxN, 2, dtype=torch.float32, device=dev)
-        pts1 = torch.zeros(B, maxN, 2, dtype=torch.float32, device=dev)
+        pts0 = torch.empty(B, maxN, 2, dtype=torch.float32, device=dev)       # the match kernel writes every row (zeros from n_corr on)
+        pts1 = torch.empty(B, maxN, 2, dtype=torch.float32, device=dev)
         nc = torch.empty(B, dtype=torch.int32, device=dev)
-        _lib.check(lib.mfr_sg_sinkhorn_match_variant(
-            _lib.ptr(S.contiguous()), B, ldS, _lib.ptr(n0), _lib.ptr(n1), self.bin_score, self.iters, self.match_thr,
-            _lib.ptr(kpts0.contiguous()), _lib.ptr(kpts1.contiguous()), K, _lib.ptr(self._ws), self._ws.numel(),
+        # n0 / n1 and kpts0 / kpts1 are read in place through a pair stride (the [0::2] / [1::2] views of the interleaved tensors); anything else is copied
+        if not (n0.dim() == 1 and n1.dim() == 1 and n0.stride(0) == n1.stride(0) >= 1):
+            n0, n1 = n0.contiguous(), n1.contiguous()
+        if not (kpts0.stride() == kpts1.stride() and kpts0.stride(0) >= 2 * K and kpts0.stride()[1:] == (2, 1)):
+            kpts0, kpts1 = kpts0.contiguous(), kpts1.contiguous()
+        _lib.check(lib.mfr_sg_sinkhorn_match_strided(
+            _lib.ptr(S.contiguous()), B, ldS, n0.data_ptr(), n1.data_ptr(), n0.stride(0), self.bin_score, self.iters, self.match_thr,
+            kpts0.data_ptr(), kpts1.data_ptr(), K, kpts0.stride(0), _lib.ptr(self._ws), self._ws.numel(),
             _lib.ptr(m0), _lib.ptr(ms0), _lib.ptr(pts0), _lib.ptr(pts1), maxN, _lib.ptr(nc), int(variant), _lib.stream_ptr()),
             "mfr_sg_sinkhorn_match")
         return dict(matches0=m0, matching_scores0=ms0, pts0=pts0, pts1=pts1, n_corr=nc)
+
+    def xa_buffer(self, B2, K):
+        """-> the [B2, K, 256] left half of a fresh [x~ | a] buffer (rows of 512 floats) for SuperPointHIP.sample(out=...): final_descriptors, handed
+        this view as `desc`, adds the keypoint encoding to it in place instead of reading a separate descriptor tensor"""
+        self._xa = torch.empty(B2 * K, 512, dtype=torch.float32, device=self.device)
+        return self._xa.view(B2, K, 512)[:, :, :256]
 
     @torch.no_grad()
     def final_descriptors(self, kpts, scores, desc, n, image_hw):
         H, W = image_hw
         B2, K, _ = kpts.shape
-        key = (H, W, kpts.device)
-        if key not in self._size:      # cached: an H2D copy is not allowed while a HIP graph is capturing
-            self._size[key] = torch.tensor([float(W), float(H)], device=kpts.device)
-        size = self._size[key]
-        kn = (kpts - size / 2) / (float(max(W, H)) * 0.7)                             # normalize_keypoints
-        # keypoint encoder MLP(3 -> 32 -> 64 -> 128 -> 256).  First layer (K = 3): three broadcast multiply-adds in a fixed order; the others
-        # through csrc/gemm_split.hip -- no library GEMM, and every row's sums are independent of the batch size
+        xa, self._xa = self._xa, None
+        if not (xa is not None and xa.shape[0] == B2 * K and desc.data_ptr() == xa.data_ptr() and tuple(desc.shape) == (B2, K, 256)
+                and desc.stride() == (K * 512, 512, 1)):
+            xa = None                                                   # a separate desc: the copy route below
+        # normalize_keypoints + the keypoint encoder's first layer (K = 3: three broadcast multiply-adds in a fixed order) + ReLU in one launch
+        # (csrc/elementwise.hip); the other layers of MLP(3 -> 32 -> 64 -> 128 -> 256) through csrc/gemm_split.hip -- no library GEMM, and every row's
+        # sums are independent of the batch size
         w0, b0 = self.kenc[0]
-        h = (kn[..., 0:1] * w0[:, 0] + kn[..., 1:2] * w0[:, 1]) + (scores.unsqueeze(-1) * w0[:, 2] + b0)
-        h = F.relu_(h).reshape(B2 * K, -1)
-        for i, lin in enumerate(self.kenc_lin):
-            h = lin(h, relu=i < len(self.kenc_lin) - 1)
-        # xa = [x~ | a]: the running descriptors (minus the folded bias offset) and the attention output side by side
-        xa = torch.empty(B2 * K, 512, dtype=torch.float32, device=kpts.device)
-        xv, av = xa[:, :256], xa[:, 256:]
-        torch.add(desc.reshape(B2 * K, 256), h.reshape(B2 * K, 256), out=xv)
+        h = torch.empty(B2 * K, w0.shape[0], dtype=torch.float32, device=kpts.device)
+        _lib.check(_lib.load().mfr_sg_kenc_in(_lib.ptr(kpts.contiguous()), _lib.ptr(scores.contiguous()), _lib.ptr(w0), _lib.ptr(b0), B2 * K, H, W,
+                                              _lib.ptr(h), _lib.stream_ptr()), "mfr_sg_kenc_in")
+        for lin in self.kenc_lin[:-1]:
+            h = lin(h, relu=True)
+        # xa = [x~ | a]: the running descriptors (minus the folded bias offset) and the attention output side by side.  desc + kenc(kpts, scores):
+        # with the descriptors already in xa's left half the last encoder layer accumulates onto them in its epilogue (it rounds its own result first,
+        # so h + desc has the bits of desc + h); a separate desc costs a pass
+        if xa is not None:
+            xv, av = xa[:, :256], xa[:, 256:]
+            self.kenc_lin[-1](h, out=xv, accumulate=True)
+        else:
+            xa = torch.empty(B2 * K, 512, dtype=torch.float32, device=kpts.device)
+            xv, av = xa[:, :256], xa[:, 256:]
+            torch.add(desc.reshape(B2 * K, 256), self.kenc_lin[-1](h).reshape(B2 * K, 256), out=xv)
         qkv = torch.empty(B2 * K, 768, dtype=torch.float32, device=kpts.device)
         hid = torch.empty(B2 * K, 512, dtype=torch.float32, device=kpts.device)
         for L in self.layers:
@@ -181,5 +199,6 @@ class SuperGlueHIP:
             S = self.score_gemm(md[0::2], md[1::2], out_mul=1.0 / 16.0)
         else:
             S = torch.bmm(md[0::2], md[1::2].transpose(1, 2)) * (1.0 / 16.0)
-        return self.sinkhorn_match(S, n[0::2].contiguous(), n[1::2].contiguous(),
-                                   kpts[0::2].contiguous(), kpts[1::2].contiguous(), maxN)
+        if not self.in_place:
+            return self.sinkhorn_match(S, n[0::2].contiguous(), n[1::2].contiguous(), kpts[0::2].contiguous(), kpts[1::2].contiguous(), maxN)
+        return self.sinkhorn_match(S, n[0::2], n[1::2], kpts[0::2], kpts[1::2], maxN)

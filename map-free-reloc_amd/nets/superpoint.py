@@ -26,6 +26,7 @@ class SuperPointHIP:
         self.device = torch.device(device)
         self.nms_radius, self.thr = int(nms_radius), float(keypoint_threshold)
         self.K, self.border = int(max_keypoints), int(remove_borders)
+        self.nms_variant = None                                           # None = the library's default NMS kernel; 0 / 1 pin one (A/B, tests)
         self.fused_conv_relu = bool(options.get("FUSED_CONV_RELU"))
         self.fused_conv1 = bool(options.get("FUSED_CONV1"))
         self.use_wino = options.get("CONV") == "wino"                     # "miopen": library conv + epilogue kernels (options.py)
@@ -128,15 +129,23 @@ class SuperPointHIP:
         _lib.check(lib.mfr_sp_scoremap(_lib.ptr(logits), B, Hc, Wc, _lib.ptr(out), _lib.stream_ptr()), "mfr_sp_scoremap")
         return out
 
-    def nms_candidates(self, scores, want_dense=False):
+    def nms_candidates(self, scores, want_dense=False, variant=None):
+        """variant None = the library's default, 0 = the streaming kernel, 1 = the tile kernel (csrc/superpoint_post.hip)"""
         lib = _lib.load()
         B, H, W = scores.shape
         cand = torch.empty(B, CAND_CAP, dtype=torch.int64, device=scores.device)
         cnt = torch.empty(B, dtype=torch.int32, device=scores.device)
         dense = torch.empty_like(scores) if want_dense else None
-        _lib.check(lib.mfr_sp_nms_candidates(_lib.ptr(scores), B, H, W, self.nms_radius, self.thr, self.border,
-                                             _lib.ptr(dense), _lib.ptr(cand), CAND_CAP, _lib.ptr(cnt),
-                                             _lib.stream_ptr()), "mfr_sp_nms_candidates")
+        if variant is None:
+            variant = self.nms_variant
+        if variant is None:
+            _lib.check(lib.mfr_sp_nms_candidates(_lib.ptr(scores), B, H, W, self.nms_radius, self.thr, self.border,
+                                                 _lib.ptr(dense), _lib.ptr(cand), CAND_CAP, _lib.ptr(cnt),
+                                                 _lib.stream_ptr()), "mfr_sp_nms_candidates")
+        else:
+            _lib.check(lib.mfr_sp_nms_candidates_variant(_lib.ptr(scores), B, H, W, self.nms_radius, self.thr, self.border,
+                                                         _lib.ptr(dense), _lib.ptr(cand), CAND_CAP, _lib.ptr(cnt), int(variant),
+                                                         _lib.stream_ptr()), "mfr_sp_nms_candidates_variant")
         return cand, cnt, dense
 
     def select(self, cand, cnt, W):
@@ -149,15 +158,21 @@ class SuperPointHIP:
                                           _lib.ptr(sc), _lib.ptr(n), _lib.stream_ptr()), "mfr_sp_select_topk")
         return kpts, sc, n
 
-    def sample(self, dense_nhwc, kpts, n):
+    def sample(self, dense_nhwc, kpts, n, out=None):
+        """out: a [B,K,256] destination whose rows may lie more than 256 floats apart (images K rows apart), e.g. the left half of SuperGlue's
+        [x | a] buffer (SuperGlueHIP.xa_buffer); what lies between the rows is not touched.  None: a new contiguous tensor"""
         lib = _lib.load()
         B, Hc, Wc, C = dense_nhwc.shape
         assert C == 256
-        desc = torch.empty(B, self.K, 256, dtype=torch.float32, device=kpts.device)
-        _lib.check(lib.mfr_sp_sample_descriptors(_lib.ptr(dense_nhwc.contiguous()), B, Hc, Wc, _lib.ptr(kpts),
-                                                 _lib.ptr(n), self.K, _lib.ptr(desc), _lib.stream_ptr()),
-                   "mfr_sp_sample_descriptors")
-        return desc
+        if out is None:
+            out = torch.empty(B, self.K, 256, dtype=torch.float32, device=kpts.device)
+        ldd = out.stride(1)
+        if tuple(out.shape) != (B, self.K, 256) or out.dtype != torch.float32 or out.stride(2) != 1 or out.stride(0) != self.K * ldd or ldd < 256:
+            raise ValueError("sample: out must be [B, K, 256] float32 rows of one pitch, images K rows apart")
+        _lib.check(lib.mfr_sp_sample_descriptors_ld(_lib.ptr(dense_nhwc.contiguous()), B, Hc, Wc, _lib.ptr(kpts),
+                                                    _lib.ptr(n), self.K, out.data_ptr(), ldd, _lib.stream_ptr()),
+                   "mfr_sp_sample_descriptors_ld")
+        return out
 
     def logits(self, x):
         """encoder output [B,128,Hc,Wc] -> the detector head's 65 logits per cell [B,65,Hc,Wc] (convPa + ReLU, convPb)"""
@@ -180,12 +195,12 @@ class SuperPointHIP:
         return self.convDb(rows).view(B, Hc, Wc, 256)
 
     @torch.no_grad()
-    def __call__(self, image):
+    def __call__(self, image, desc_out=None):
         """image [B2,1,H,W] f32 in [0,1] on the GPU -> dict(kpts [B2,K,2] (x,y), scores [B2,K],
-        desc [B2,K,256] token-major, n [B2] i32).  Rows >= n are zero."""
+        desc [B2,K,256] token-major, n [B2] i32).  Rows >= n are zero.  desc_out: where the descriptors go (see sample)."""
         x = self.encode(image)
         scores = self.score_map(self.logits(x))
         cand, cnt, _ = self.nms_candidates(scores)
         kpts, sc, n = self.select(cand, cnt, scores.shape[2])
-        desc = self.sample(self.descriptor_rows(x), kpts, n)
+        desc = self.sample(self.descriptor_rows(x), kpts, n, out=desc_out)
         return dict(kpts=kpts, scores=sc, desc=desc, n=n)

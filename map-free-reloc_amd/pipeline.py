@@ -156,7 +156,8 @@ class SuperGluePnPPipeline:
     def match(self, images):
         """images [2B,1,H,W] -> dict(pts0, pts1 [B,K,2], n_corr [B], ...)  (SuperGlue_matcher.match)"""
         H, W = images.shape[-2:]
-        sp = self.sp(images)
+        # SuperPoint writes its descriptors straight into the left half of SuperGlue's [x | a] buffer (no desc + h pass); in_place = False: a separate tensor
+        sp = self.sp(images, desc_out=self.sg.xa_buffer(images.shape[0], self.K) if self.sg.in_place else None)
         m = self.sg(sp, (H, W), maxN=self.K)
         m["n_kpts"] = sp["n"]
         return m
