@@ -18,7 +18,8 @@ the module on seeded weights (tests/test_gpu_eloftr.py).
 What runs where:
   * backbone: every RepVGG block folded into ONE 3x3 convolution + bias + ReLU (`fold_weights`, float64 on the host); the 1 -> 64 stride-2 stem is
     mfr_eloftr_stem_s2, the rest the project's 3x3 kernels (nets/conv.py), under the f16x2 range guard like LoFTR's backbone.  In the 18 blocks with an
-    identity branch the unit part of that branch is added through the same launch's fp32 residual operand (`skip_form`);
+    identity branch the unit part of that branch is added through the same launch's fp32 residual operand (`skip_form`).  Under bf16x3 the three
+    stride-2 layers are the framework's convolution (the implicit-GEMM kernel is f16x2 only), restricted to the library's deterministic solvers;
   * transformer: tokens live in xm [2, B L, 512] (side-major; x in the left half, the up-sampled message in the right half: the MLP's concatenation
     exists in place, as in nets/loftr.py).  Aggregation + LayerNorm, rotary encoding, short-sequence attention, x4 up-sampling, leaky ReLU:
     csrc/eloftr.hip; projections and the MLP: csrc/gemm_split.hip (HIP.SPLIT arithmetic); LayerNorm + residual: mfr_layernorm;
@@ -29,6 +30,7 @@ What runs where:
   * two-stage fine matching: mfr_eloftr_fine_match, one wavefront per match; the drop of matches outside the unpadded frame and the ordered
     compaction: mfr_eloftr_compact.  No host synchronisation anywhere in the stage: slots behind a pair's match count are skipped on the device.
 """
+import contextlib
 import ctypes
 import typing
 
@@ -146,6 +148,18 @@ class ELoFTRFeatures(typing.NamedTuple):
     s3: torch.Tensor                # [n, 256, H/8, W/8]
 
 
+@contextlib.contextmanager
+def _deterministic_library():
+    """the framework's convolution restricted to the library's deterministic solvers for the calls inside (the flag alone: torch.backends.cudnn.flags
+    would also set a benchmark limit the library does not have, and warn)"""
+    before = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = True
+    try:
+        yield
+    finally:
+        torch.backends.cudnn.deterministic = before
+
+
 class _Conv:
     """one folded convolution layer (3x3 stride 1 / 2 or 1x1): the project's kernels where they exist for the arithmetic, as nets/loftr.LoFTRHIP._c"""
 
@@ -175,7 +189,11 @@ class _Conv:
             if self.b is not None:
                 y = y + self.b.view(1, -1, 1, 1)
         else:
-            y = F.conv2d(x, self.w, self.b, stride=self.stride, padding=self.k // 2)
+            # the library's convolution (bf16x3: the stride-2 3x3 layers; CONV = "miopen": all of them).  Its default choice for the 64 -> 128 stride-2
+            # layer returned different bits from run to run on the same input (tests/test_gpu_pool_poison.py found it, docs/HISTORY.md); restricted to
+            # its deterministic solvers it is reproducible like every kernel of the project
+            with _deterministic_library():
+                y = F.conv2d(x, self.w, self.b, stride=self.stride, padding=self.k // 2)
         if residual is not None:
             y = y + residual
         return F.relu_(y) if act == 1 else F.leaky_relu_(y, 0.01) if act == 2 else y

@@ -315,6 +315,18 @@ def _check_pairs(tag, out, o32, o64, safe, wc, frame=None):
             assert bool((pts[:, 0::2] < frame[1]).all() and (pts[:, 1::2] < frame[0]).all())
 
 
+def _digest(out):
+    """SHA-256 (first 16 hex digits) of the stage outputs that decide the end-to-end test, in pipeline order: two suite logs, one of a failing and one
+    of a passing run, then show at which stage the runs part, without running anything again.  Only what the header specifies is hashed: of the
+    coarse matcher's index rows the first n_coarse[p] entries of every pair, pts0 / pts1 whole (zero-filled behind n_corr)."""
+    import hashlib
+    h = lambda t: hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()[:16]
+    n = out["n_coarse"].cpu()
+    head = lambda t: torch.cat([t[p, :int(n[p])] for p in range(n.numel())])
+    return " ".join(f"{k}={v}" for k, v in (("n_coarse", h(out["n_coarse"])), ("i_ids", h(head(out["i_ids"]))), ("j_ids", h(head(out["j_ids"]))),
+                                            ("pts0", h(out["pts0"])), ("pts1", h(out["pts1"]))))
+
+
 @pytest.mark.parametrize("split", SPLITS)
 def test_end_to_end_vs_module(e2e_oracle, hip, split):
     """two pairs at 160 x 128: the match set, the coordinates, n_corr > 0 on both, ascending order, the maxN cap"""
@@ -323,6 +335,7 @@ def test_end_to_end_vs_module(e2e_oracle, hip, split):
         net = hip(split)
         out = net(o["im"].to(DEV))
         capped = net(o["im"].to(DEV), maxN=20)
+    print(f"[eloftr] digest [{split}] " + _digest(out))
     assert bool((out["n_corr"] > 0).all())
     _check_pairs(f"end to end [{split}]", out, o["o32"], o["o64"], o["safe"], 16)
     assert capped["pts0"].shape[1] == 20 and bool((capped["n_corr"] == torch.clamp(out["n_corr"], max=20)).all())
