@@ -1,4 +1,6 @@
-"""ctypes loader for csrc/libmfr_hip.so (C-ABI: include/mfr_hip.h).
+"""ctypes loader for csrc/libmfr_hip.so.  include/mfr_hip.h is the only statement of the C-ABI:
+the signatures are parsed from it at the first load(), and call() is the one checked way into
+an entry point that returns a status.
 
 torch is imported first so that its bundled HIP runtime (libamdhip64.so.7) is the one the
 library binds to -- device pointers and streams handed over from torch tensors then belong to
@@ -6,185 +8,66 @@ the same runtime.  Loading fails loudly; nothing in this package falls back to a
 """
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "csrc", "libmfr_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mfr_hip.h")
 
 _lib = None
+_calls = {}      # name -> (n_args, indices of the pointer parameters, has trailing stream, parameter names)
+SIGNATURES = {}  # name -> (restype, argtypes); filled from the header by load()
 
-_vp, _i, _d, _u64, _sz = C.c_void_p, C.c_int, C.c_double, C.c_uint64, C.c_size_t
-
-# name -> (restype, argtypes); mirrors include/mfr_hip.h declaration by declaration
-SIGNATURES = {
-    "mfr_abi_version": (_i, []),
-    "mfr_target_arch": (C.c_char_p, []),
-    "mfr_f16x2_guard_bind": (_i, [_vp]),
-    "mfr_test_f64_ops": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
-    "mfr_test_sample": (_i, [_u64, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_pnp_workspace_bytes": (_sz, [_i, _i, _i]),
-    "mfr_pnp_solve_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _d, _d, _u64, _vp,
-                                 _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mfr_depth_min": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "mfr_pnp_lift": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
-    "mfr_pnp_ransac": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _d, _d, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                            _vp, _vp, _vp, _vp]),
-    "mfr_rig_pnp_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "mfr_rig_pnp_ransac": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _d, _d, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                _vp, _vp, _vp, _vp]),
-    "mfr_rig_pnp_solve_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _d, _d, _u64, _vp,
-                                     _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mfr_emat_workspace_bytes": (_sz, [_i, _i, _i]),
-    "mfr_magsac_lut": (_i, [_vp, _i]),
-    "mfr_emat_solve_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _d, _d, _i, _u64, _vp, _i, _vp, _i, _d, _vp, _sz,
-                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mfr_procrustes_workspace_bytes": (_sz, [_i, _i, _i]),
-    "mfr_procrustes_solve_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _d, _d, _i, _u64, _vp, _vp, _sz,
-                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mfr_procrustes_icp_workspace_bytes": (_sz, [_i, _i, _i]),
-    "mfr_procrustes_icp_refine": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _d, _d, _d, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mfr_sp_scoremap": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "mfr_sp_nms_candidates": (_i, [_vp, _i, _i, _i, _i, C.c_float, _i, _vp, _vp, _i, _vp, _vp]),
-    "mfr_sp_nms_candidates_variant": (_i, [_vp, _i, _i, _i, _i, C.c_float, _i, _vp, _vp, _i, _vp, _i, _vp]),
-    "mfr_sp_nms_stream_geometry": (_i, [_vp, _vp]),
-    "mfr_sp_select_topk": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "mfr_sp_sample_descriptors": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
-    "mfr_sp_sample_descriptors_ld": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
-    "mfr_gemm_f16x2_pack_bytes": (_sz, [_i, _i]),
-    "mfr_gemm_f16x2_pack": (_i, [_vp, _i, _i, _vp, _vp]),
-    "mfr_gemm_f16x2": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "mfr_gemm_f16x2_pack_batched": (_i, [_vp, _i, _i, C.c_longlong, _i, _i, C.c_float, _vp, _vp]),
-    "mfr_gemm_f16x2_batched": (_i, [_vp, _i, C.c_longlong, _vp, _vp, _vp, _i, C.c_longlong, _i, _i, _i, _i, _i, _vp]),
-    "mfr_conv_igemm_k": (_i, [_i, _i, _i]),
-    "mfr_conv_igemm_f16x2": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "mfr_conv_igemm_f16x2_pad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "mfr_conv_igemm_f16x2_upadd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "mfr_gemm_f16x2_windows": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
-    "mfr_gemm_bf16x3_windows": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
-    "mfr_mlp_ln_f16x2": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _i, _i, _i, _vp]),
-    "mfr_mlp_ln_bf16x3": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _i, _i, _i, _vp]),
-    "mfr_gemm_f16x2_ln": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_float, _vp, _i, _i, _i, _i, _i, _vp]),
-    "mfr_gemm_bf16x3_ln": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_float, _vp, _i, _i, _i, _i, _i, _vp]),
-    "mfr_gemm_bf16x3_pack_bytes": (_sz, [_i, _i]),
-    "mfr_gemm_bf16x3_pack": (_i, [_vp, _i, _i, _vp, _vp]),
-    "mfr_gemm_bf16x3": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "mfr_sg_attention": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
-    "mfr_sg_attention_variant": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp]),
-    "mfr_sg_match_workspace_bytes": (_sz, [_i, _i]),
-    "mfr_sg_sinkhorn_match": (_i, [_vp, _i, _i, _vp, _vp, C.c_float, _i, C.c_float, _vp, _vp, _i, _vp, _sz,
-                                   _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "mfr_sg_sinkhorn_match_variant": (_i, [_vp, _i, _i, _vp, _vp, C.c_float, _i, C.c_float, _vp, _vp, _i, _vp, _sz,
-                                           _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
-    "mfr_sg_sinkhorn_match_strided": (_i, [_vp, _i, _i, _vp, _vp, C.c_longlong, C.c_float, _i, C.c_float, _vp, _vp, _i, C.c_longlong, _vp, _sz,
-                                           _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
-    "mfr_sg_kenc_in": (_i, [_vp, _vp, _vp, _vp, C.c_longlong, _i, _i, _vp, _vp]),
-    "mfr_gemm_f16x2_ln_gelu": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_float, _vp, _i, _i, _i, _i, _vp]),
-    "mfr_gemm_bf16x3_ln_gelu": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_float, _vp, _i, _i, _i, _i, _vp]),
-    "mfr_lg_rotary_table": (_i, [_vp, _vp, _i, _vp, _vp]),
-    "mfr_lg_rotary_apply": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
-    "mfr_lg_ln_gelu": (_i, [_vp, _i, _i, _vp, _vp, C.c_float, _vp]),
-    "mfr_lg_assign_workspace_bytes": (_sz, [_i, _i, _i]),
-    "mfr_lg_assign": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _i, _vp, _sz,
-                           _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "mfr_loftr_linear_attention_workspace_bytes": (_sz, [_i, _i, _i]),
-    "mfr_loftr_linear_attention": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i, _vp]),
-    "mfr_loftr_coarse_match_workspace_bytes": (_sz, [_i, _i, _i]),
-    "mfr_loftr_coarse_match": (_i, [_vp, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "mfr_loftr_ot_match_workspace_bytes": (_sz, [_i, _i, _i]),
-    "mfr_loftr_ot_match": (_i, [_vp, _i, _i, _i, _i, _i, C.c_float, _i, C.c_float, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
-    "mfr_loftr_coarse_match_variant": (_i, [_vp, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _vp, _sz, _vp, _vp, _vp, _vp, _i, _vp]),
-    "mfr_loftr_fine_attention": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
-    "mfr_loftr_gather_windows": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_loftr_fine_match": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_float, _vp, _vp, _vp, _vp, _vp]),
-    "mfr_conv3x3_c1_relu": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_bias_relu_nchw": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "mfr_conv1x1_nchw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_nchw_to_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, C.c_longlong, _i, _vp]),
-    "mfr_nchw_to_rows_gather": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, C.c_longlong, _i, _vp]),
-    "mfr_bias_pool2_relu_nchw": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_wino_bf16x3_filter_bytes": (_sz, [_i, _i]),
-    "mfr_wino_bf16x3_filter_transform": (_i, [_vp, _i, _i, _vp, _vp]),
-    "mfr_conv3x3_wino_bf16x3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_sp_conv1ab_f16x2": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "mfr_wino_f16x2_filter_bytes": (_sz, [_i, _i]),
-    "mfr_wino_f16x2_filter_transform": (_i, [_vp, _i, _i, _vp, _vp]),
-    "mfr_conv3x3_wino_f16x2": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_conv3x3_direct_f16x2_filter_bytes": (_sz, [_i, _i]),
-    "mfr_conv3x3_direct_f16x2_filter_pack": (_i, [_vp, _i, _i, _vp, _vp]),
-    "mfr_conv3x3_direct_f16x2": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_conv3x3s2_direct_f16x2": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_conv3x3_direct_f16x2_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
-    "mfr_conv3x3_direct_f16x2_tiled": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
-    "mfr_wino_filter_bytes": (_sz, [_i, _i]),
-    "mfr_wino_filter_transform": (_i, [_vp, _i, _i, _vp, _vp]),
-    "mfr_conv3x3_wino": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_conv3x3_wino_variant": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_layernorm": (_i, [_vp, _i, _vp, _vp, _vp, _i, C.c_longlong, _i, C.c_float, _vp, _i, _vp]),
-    "mfr_conv_gemm_bf16": (_i, [_vp, C.c_longlong, _vp, _vp, C.c_longlong, _vp, _i, _i, _i, _vp, _vp, C.c_longlong, _i,
-                                _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "mfr_conv_pack_nhwc_halo": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
-    "mfr_conv_unpack_nchw": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_conv_pack_cm_halo": (_i, [_vp, _i, C.c_longlong, _i, _i, _i, C.c_longlong, _i, _i, C.c_longlong, _vp, _vp]),
-    "mfr_upsample2x_add": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "mfr_upsample_bilinear": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    "mfr_corr_warp_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mfr_corr_warp_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mfr_kabsch_fwd": (_i, [_vp, _i, _vp, _vp]),
-    "mfr_kabsch_bwd": (_i, [_vp, _vp, _i, _vp, _vp]),
-    "mfr_rootsift": (_i, [_vp, _i, _vp, _vp, _vp]),
-    "mfr_desc_ratio_match": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _d, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "mfr_sift_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "mfr_sift_level_offset": (C.c_longlong, [_i, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_sift_blur_taps": (_i, [_i, _vp, _vp]),
-    "mfr_sift_detect": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mfr_jpeg_workspace_bytes": (_sz, [_i, _i, _i, C.c_longlong, _i]),
-    "mfr_jpeg_decode": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
-    "mfr_png_depth_workspace_bytes": (_sz, [_i, _i, _i]),
-    "mfr_png_depth_decode": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_longlong, _vp, _sz, _vp, _vp, _vp]),
-    "mfr_resize_gray_bilinear": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
-    "mfr_scale_workspace_bytes": (_sz, [_i, _i]),
-    "mfr_scale_from_depth_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp,
-                                        _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "mfr_abs_pose_workspace_bytes": (_sz, [_i]),
-    "mfr_test_abs_pose_subset": (_i, [_u64, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_abs_pose_fuse": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _d, _d, _i, _u64, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "mfr_dpt_prep": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
-    "mfr_dpt_groupnorm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_float, _i, _vp, _vp]),
-    "mfr_dpt_maxpool3s2": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_dpt_layernorm": (_i, [_vp, _i, _vp, _vp, _vp, _i, C.c_longlong, _i, C.c_float, _vp, _i, _vp]),
-    "mfr_dpt_bias_gelu": (_i, [_vp, _i, C.c_longlong, _i, _vp, _vp]),
-    "mfr_dpt_add_relu": (_i, [_vp, _vp, C.c_longlong, _vp, _vp, _vp]),
-    "mfr_dpt_tokens": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
-    "mfr_dpt_tokens_inverse": (_i, [_vp, _i, C.c_longlong, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_dpt_shuffle": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_dpt_head_tail": (_i, [_vp, _vp, C.c_float, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp, _vp]),
-    "mfr_dpt_prep_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
-    "mfr_dpt_head_tail_rows": (_i, [_vp, _vp, C.c_float, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
-    "mfr_da_patch_rows": (_i, [_vp, _i, _i, _i, _i, _i, _i] + [C.c_float] * 6 + [_vp, _i, _vp]),
-    "mfr_da_patch_rows_tab": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i] + [C.c_float] * 6 + [_vp, _i, _vp, _vp]),
-    "mfr_da_tokens": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
-    "mfr_da_head_tail": (_i, [_vp, _vp, C.c_float, _i, _i, _i, _i, _i, C.c_float, _i, _i, _vp, _vp, _vp]),
-    "mfr_da_head_tail_rows": (_i, [_vp, _vp, C.c_float, _i, _i, _i, _i, _i, C.c_float, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
-    "mfr_eloftr_stem_s2": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_eloftr_aggregate": (_i, [_vp, _i, C.c_longlong, _i, _i, _i, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp]),
-    "mfr_eloftr_rotary": (_i, [_vp, _vp, _i, _vp, C.c_longlong, _i, _vp]),
-    "mfr_eloftr_attention": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
-    "mfr_eloftr_upsample4_rows": (_i, [_vp, _i, _i, _i, _i, _vp, _i, C.c_longlong, _vp]),
-    "mfr_eloftr_upsample2x": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
-    "mfr_eloftr_leaky_relu": (_i, [_vp, _i, C.c_longlong, _i, C.c_float, _vp]),
-    "mfr_eloftr_rows_to_nchw": (_i, [_vp, _i, C.c_longlong, _i, _i, _i, C.c_float, _vp, _vp]),
-    "mfr_eloftr_gather_windows": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, C.c_longlong, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "mfr_eloftr_fine_match": (_i, [_vp, _vp, _vp, _vp, C.c_longlong, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "mfr_eloftr_compact": (_i, [_vp, _vp, _vp, C.c_longlong, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-}
+# the header's whole type vocabulary; a new C type is added here on purpose
+_SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+            "long long": C.c_longlong, "uint64_t": C.c_uint64}
+_POINTEES = {"void", "float", "double", "int", "int32_t", "int64_t", "long long", "uint8_t", "uint16_t", "uint64_t"}
+_DECL = re.compile(r"(?:^|[;{}])\s*([A-Za-z_][\w\s*]*?)\b(mfr_[a-z0-9_]+)\s*\(([^()]*)\)\s*(?=;)")
+_VALUE_INT = {"mfr_abi_version", "mfr_conv_igemm_k"}   # `int` is a value here, not a status: called as lib.mfr_x(...), like the size queries
+_CURRENT = object()
 
 
 class MfrLibraryError(RuntimeError):
     pass
 
 
+def _ctype(decl, what, ret=False):
+    m = re.fullmatch(r"(const )?([\w ]+?) ?(\*?)", decl)
+    const, base, star = m.groups() if m else (None, None, None)
+    if ret and (const, base, star) == ("const ", "char", "*"):
+        return C.c_char_p
+    if star and base in _POINTEES:
+        return C.c_void_p
+    if not star and not const and base in _SCALARS:
+        return _SCALARS[base]
+    raise MfrLibraryError(f"{what}: C type '{decl}' is not in _lib's type map")
+
+
+def parse_header(text):
+    """[(name, restype, argtypes, parameter names)] for every `ret mfr_x(args);` of the header text"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    decls = []
+    for ret, name, params in _DECL.findall(text):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        argtypes, argnames = [], []
+        for p in [] if params == ["void"] else params:
+            m = re.fullmatch(r"(.*?)(\w+)", p)
+            if m is None:
+                raise MfrLibraryError(f"{name}: cannot read parameter '{p}'")
+            argtypes.append(_ctype(m.group(1).strip(), f"{name}({m.group(2)})"))
+            argnames.append(m.group(2))
+        decls.append((name, _ctype(" ".join(ret.split()), f"{name} return", ret=True), argtypes, argnames))
+    named = set(re.findall(r"\b(mfr_[a-z0-9_]+)\s*\(", text))
+    if len(decls) != len(named) or {d[0] for d in decls} != named:
+        raise MfrLibraryError(f"mfr_hip.h names {len(named)} entry points but {len(decls)} declarations could be read: "
+                              f"{sorted(named.symmetric_difference(d[0] for d in decls))}")
+    return decls
+
+
 def load(require_gpu=False):
-    """Load libmfr_hip.so and bind every symbol of the C-ABI.  Raises MfrLibraryError if the
-    library (or, with require_gpu, a GPU) is missing -- never falls back."""
+    """Load libmfr_hip.so and bind every symbol the header declares.  Raises MfrLibraryError if the
+    library, the header (or, with require_gpu, a GPU) is missing -- never falls back."""
     global _lib
     if _lib is None:
         import torch  # noqa: F401  (binds the HIP runtime first)
@@ -192,14 +75,23 @@ def load(require_gpu=False):
             raise MfrLibraryError(
                 f"{SO_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 f"(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
+        if not os.path.exists(HEADER_PATH):
+            raise MfrLibraryError(f"{HEADER_PATH} not found: the C-ABI is bound from it")
+        with open(HEADER_PATH) as f:
+            decls = parse_header(f.read())
         lib = C.CDLL(SO_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, res, args, names in decls:
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:
                 raise MfrLibraryError(f"libmfr_hip.so does not export {name}") from e
             fn.restype = res
             fn.argtypes = args
+            SIGNATURES[name] = (res, args)
+            if res is C.c_int and name not in _VALUE_INT:
+                has_stream = bool(names) and names[-1] == "stream" and args[-1] is C.c_void_p
+                n = len(args) - has_stream
+                _calls[name] = (n, tuple(i for i in range(n) if args[i] is C.c_void_p), has_stream, names)
         _lib = lib
     if require_gpu:
         import torch
@@ -224,3 +116,33 @@ def ptr(t):
 def stream_ptr():
     import torch
     return torch.cuda.current_stream().cuda_stream
+
+
+def call(name, *args, stream=_CURRENT):
+    """Enter the status-returning entry point `name`.  The argument count is checked against the header;
+    a pointer parameter takes a contiguous tensor, None or an address (int); a trailing `void *stream` is
+    filled with the current stream unless stream= is given (None = the null stream); a non-zero status raises."""
+    if _lib is None:
+        load()
+    try:
+        n, pointers, has_stream, names = _calls[name]
+    except KeyError:
+        raise MfrLibraryError(f"{name} is not a status-returning entry point of include/mfr_hip.h") from None
+    if len(args) != n:
+        raise TypeError(f"{name} takes {n} arguments ({', '.join(names[:n])}), got {len(args)}")
+    args = list(args)
+    for i in pointers:
+        a = args[i]
+        if a is not None and not isinstance(a, int):
+            if not hasattr(a, "data_ptr"):
+                raise TypeError(f"{name}: parameter {names[i]} takes a tensor, None or an address, got {type(a).__name__}")
+            args[i] = ptr(a)
+    if has_stream:
+        args.append(stream_ptr() if stream is _CURRENT else stream)
+    elif stream is not _CURRENT:
+        raise TypeError(f"{name} has no stream parameter")
+    try:
+        rc = getattr(_lib, name)(*args)              # looked up on the library object, as lib.mfr_x(...) is: a test may wrap an entry there
+    except C.ArgumentError as e:                     # a scalar parameter given something else (ctypes' own argtypes check)
+        raise TypeError(f"{name}: {e}") from None
+    check(rc, name)

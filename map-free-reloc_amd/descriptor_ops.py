@@ -21,21 +21,21 @@ def _chk(t, dtype, name):
 
 def rootsift(desc):
     """[..., 128] f32 raw SIFT descriptors -> (rootSIFT descriptors, squared norms [...])"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     desc = _chk(desc, torch.float32, "desc")
     if desc.shape[-1] != 128:
         raise ValueError("SIFT descriptors are 128-d")
     out = torch.empty_like(desc)
     n2 = torch.empty(desc.shape[:-1], dtype=torch.float32, device=desc.device)
     rows = desc.numel() // 128
-    _lib.check(lib.mfr_rootsift(_lib.ptr(desc), rows, _lib.ptr(out), _lib.ptr(n2), _lib.stream_ptr()), "mfr_rootsift")
+    _lib.call("mfr_rootsift", desc, rows, out, n2)
     return out, n2
 
 
 def ratio_match(des0, des1, norm0, norm1, kp0, kp1, n0, n1, ratio=0.8, max_corr=None):
     """des0 [B,N0,128], des1 [B,N1,128] (rootSIFT), norms, kp0 [B,N0,2], kp1 [B,N1,2], n0/n1 [B] i32.
     Returns dict(pts0 [B,maxN,2], pts1, n_corr [B], nn_idx [B,N0], nn_d2 [B,N0,2])."""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     des0 = _chk(des0, torch.float32, "des0"); des1 = _chk(des1, torch.float32, "des1")
     norm0 = _chk(norm0, torch.float32, "norm0"); norm1 = _chk(norm1, torch.float32, "norm1")
     kp0 = _chk(kp0, torch.float32, "kp0"); kp1 = _chk(kp1, torch.float32, "kp1")
@@ -49,10 +49,7 @@ def ratio_match(des0, des1, norm0, norm1, kp0, kp1, n0, n1, ratio=0.8, max_corr=
     pts0 = torch.zeros(B, maxN, 2, dtype=torch.float32, device=dev)
     pts1 = torch.zeros(B, maxN, 2, dtype=torch.float32, device=dev)
     n_corr = torch.zeros(B, dtype=torch.int32, device=dev)
-    _lib.check(lib.mfr_desc_ratio_match(_lib.ptr(des0), _lib.ptr(des1), _lib.ptr(norm0), _lib.ptr(norm1), _lib.ptr(kp0),
-                                        _lib.ptr(kp1), B, N0, N1, _lib.ptr(n0), _lib.ptr(n1), float(ratio), _lib.ptr(nn_idx),
-                                        _lib.ptr(nn_d2), _lib.ptr(pts0), _lib.ptr(pts1), maxN, _lib.ptr(n_corr),
-                                        _lib.stream_ptr()), "mfr_desc_ratio_match")
+    _lib.call("mfr_desc_ratio_match", des0, des1, norm0, norm1, kp0, kp1, B, N0, N1, n0, n1, float(ratio), nn_idx, nn_d2, pts0, pts1, maxN, n_corr)
     return dict(pts0=pts0, pts1=pts1, n_corr=n_corr, nn_idx=nn_idx, nn_d2=nn_d2)
 
 

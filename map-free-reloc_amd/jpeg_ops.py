@@ -142,13 +142,12 @@ class JpegDecoder:
         """the device half on tensors already on the device (headers u8 [n, HEADER_BYTES], records u8, offsets i64 [n + 1]), launched on
         torch's current stream; the workspace and the round counters are marked as used by that stream (the caching allocator then does
         not hand them to other work before these launches are done, whichever stream allocated them)"""
-        lib = _lib.load(require_gpu=True)
+        _lib.load(require_gpu=True)
         ws = self.workspace(n, H, W, max_record)
         self.rounds = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
         cur = torch.cuda.current_stream(self.device)
-        _lib.check(lib.mfr_jpeg_decode(_lib.ptr(headers), _lib.ptr(records), _lib.ptr(offsets), n, H, W, int(max_record), _lib.ptr(out), _lib.ptr(rgb),
-                                       _lib.ptr(status), _lib.ptr(self.rounds), _lib.ptr(ws), ws.numel(), self.subseq_bits,
-                                       cur.cuda_stream), "mfr_jpeg_decode")
+        _lib.call("mfr_jpeg_decode", headers, records, offsets, n, H, W, int(max_record), out, rgb, status, self.rounds, ws, ws.numel(), self.subseq_bits,
+                  stream=cur.cuda_stream)
         ws.record_stream(cur)
         self.rounds.record_stream(cur)
 
@@ -203,7 +202,7 @@ class GrayResizer:
         return t
 
     def __call__(self, rgb, out, status=None):
-        lib = _lib.load(require_gpu=True)
+        _lib.load(require_gpu=True)
         n, H, W, c = rgb.shape
         h, w = out.shape[-2:]
         assert c == 3 and rgb.dtype == torch.uint8 and out.dtype == torch.float32 and out.shape == (n, 1, h, w)
@@ -211,9 +210,7 @@ class GrayResizer:
         y0, y1, fy = self.taps(h, H)
         x0, x1, fx = self.taps(w, W)
         cur = torch.cuda.current_stream(self.device)
-        _lib.check(lib.mfr_resize_gray_bilinear(_lib.ptr(rgb), n, H, W, _lib.ptr(status), _lib.ptr(y0), _lib.ptr(y1), _lib.ptr(fy),
-                                                _lib.ptr(x0), _lib.ptr(x1), _lib.ptr(fx), h, w, _lib.ptr(out), cur.cuda_stream),
-                   "mfr_resize_gray_bilinear")
+        _lib.call("mfr_resize_gray_bilinear", rgb, n, H, W, status, y0, y1, fy, x0, x1, fx, h, w, out, stream=cur.cuda_stream)
         for t in (y0, y1, fy, x0, x1, fx):
             t.record_stream(cur)
         return out

@@ -48,21 +48,18 @@ def fuse_abs_pose(train_q, train_c, pred_R, pred_t, offsets, mode, thr_deg=15.0,
     mask = torch.zeros(max(P, 1), dtype=torch.int32, device=device)
     status = torch.empty(Q, dtype=torch.int32, device=device)
     with torch.cuda.device(device):
-        _lib.check(lib.mfr_abs_pose_fuse(
-            _lib.ptr(train_q), _lib.ptr(train_c), _lib.ptr(pred_R), _lib.ptr(pred_t), P, _lib.ptr(offsets), Q, int(mode),
-            float(thr_deg), float(thr_mult), int(lo_iters), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(ws), ws_bytes,
-            _lib.ptr(abs_q), _lib.ptr(abs_c), _lib.ptr(mask), _lib.ptr(status), _lib.stream_ptr()), "mfr_abs_pose_fuse")
+        _lib.call("mfr_abs_pose_fuse", train_q, train_c, pred_R, pred_t, P, offsets, Q, int(mode), float(thr_deg), float(thr_mult), int(lo_iters),
+                  int(seed) & 0xFFFFFFFFFFFFFFFF, ws, ws_bytes, abs_q, abs_c, mask, status)
     return dict(abs_q=abs_q, abs_c=abs_c, inlier_mask=mask[:P], status=status)
 
 
 def test_lo_subsets(seed, base_masks, calls, iters, nsub, device=None):
     """test hook (mfr_test_abs_pose_subset): the random subsets of the local optimisation as bit masks [n, calls, iters] (int64 bit
     patterns), drawn from the set bits of base_masks [n] for (seed, query index, LO call, iteration)"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     base = _dev(np.asarray(base_masks, np.uint64).view(np.int64), torch.int64, device, (-1,))
     out = torch.zeros(base.numel(), int(calls), int(iters), dtype=torch.int64, device=device)
     with torch.cuda.device(device):
-        _lib.check(lib.mfr_test_abs_pose_subset(int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(base), base.numel(), int(calls), int(iters), int(nsub),
-                                                _lib.ptr(out), _lib.stream_ptr()), "mfr_test_abs_pose_subset")
+        _lib.call("mfr_test_abs_pose_subset", int(seed) & 0xFFFFFFFFFFFFFFFF, base, base.numel(), int(calls), int(iters), int(nsub), out)
     return out

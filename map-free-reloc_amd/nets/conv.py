@@ -50,13 +50,10 @@ class WinoConv3x3:
         nb = lib.mfr_wino_filter_bytes(self.ci, self.co)
         if nb:
             self.u_exact = torch.empty(nb // 4, dtype=torch.float32, device=dev)
-            _lib.check(lib.mfr_wino_filter_transform(_lib.ptr(self.w), self.ci, self.co, _lib.ptr(self.u_exact), _lib.stream_ptr()),
-                       "mfr_wino_filter_transform")
+            _lib.call("mfr_wino_filter_transform", self.w, self.ci, self.co, self.u_exact)
         nb = getattr(lib, f"mfr_wino_{self.split}_filter_bytes")(self.ci, self.co)
         self.u_split = torch.empty(nb, dtype=torch.uint8, device=dev)
-        _lib.check(getattr(lib, f"mfr_wino_{self.split}_filter_transform")(_lib.ptr(self.w), self.ci, self.co, _lib.ptr(self.u_split), _lib.stream_ptr()),
-                   f"mfr_wino_{self.split}_filter_transform")
-        self._conv_split = getattr(lib, f"mfr_conv3x3_wino_{self.split}")
+        _lib.call(f"mfr_wino_{self.split}_filter_transform", self.w, self.ci, self.co, self.u_split)
         self.direct = None                                       # built on first use (CONV_KERNEL 'auto' / 'direct', f16x2)
 
     def rows(self, x, act=0):
@@ -75,20 +72,17 @@ class WinoConv3x3:
 
     def __call__(self, x, act=0, pool=False, residual=None):
         """act: 0 none, 1 ReLU, 2 LeakyReLU(0.01); pool: fused 2x2 max-pool; residual [B,Cout,H,W] added before the activation"""
-        lib = _lib.load()
         mode = options.get("CONV_KERNEL")
         if mode == "direct" or (mode == "auto" and self.split == "f16x2"):
             return self._direct()(x, act=act, pool=pool, residual=residual)
         x = x.contiguous()
         B, C, H, W = x.shape
         y = torch.empty((B, self.co, H // 2, W // 2) if pool else (B, self.co, H, W), dtype=torch.float32, device=x.device)
-        res = _lib.ptr(residual.contiguous()) if residual is not None else None
+        res = residual.contiguous() if residual is not None else None
         if self.u_exact is None or prefer_split(H, W, self.split):
-            _lib.check(self._conv_split(_lib.ptr(x), _lib.ptr(self.u_split), _lib.ptr(self.b), res, B, C, self.co, H, W, int(act), int(pool),
-                                        _lib.ptr(y), _lib.stream_ptr()), f"mfr_conv3x3_wino_{self.split}")
+            _lib.call(f"mfr_conv3x3_wino_{self.split}", x, self.u_split, self.b, res, B, C, self.co, H, W, int(act), int(pool), y)
         else:
-            _lib.check(lib.mfr_conv3x3_wino(_lib.ptr(x), _lib.ptr(self.u_exact), _lib.ptr(self.b), res, B, C, self.co, H, W, int(act), int(pool),
-                                            _lib.ptr(y), _lib.stream_ptr()), "mfr_conv3x3_wino")
+            _lib.call("mfr_conv3x3_wino", x, self.u_exact, self.b, res, B, C, self.co, H, W, int(act), int(pool), y)
         return y
 
 
@@ -113,50 +107,41 @@ class DirectConv3x3:
         self.co, self.ci = int(weight.shape[0]), int(weight.shape[1])
         self.split = "f16x2"
         self.packed = torch.empty(lib.mfr_conv3x3_direct_f16x2_filter_bytes(self.ci, self.co), dtype=torch.uint8, device=weight.device)
-        _lib.check(lib.mfr_conv3x3_direct_f16x2_filter_pack(_lib.ptr(self.w), self.ci, self.co, _lib.ptr(self.packed), _lib.stream_ptr()),
-                   "mfr_conv3x3_direct_f16x2_filter_pack")
+        _lib.call("mfr_conv3x3_direct_f16x2_filter_pack", self.w, self.ci, self.co, self.packed)
 
     def rows(self, x, act=0):
         """token-major output [B, H, W, Cout] (mfr_conv3x3_direct_f16x2_rows): for the layer in front of a 1x1 / linear layer"""
-        lib = _lib.load()
         x = x.contiguous()
         B, C, H, W = x.shape
         assert C == self.ci and x.dtype == torch.float32 and self.co % 4 == 0
         y = torch.empty(B, H, W, self.co, dtype=torch.float32, device=x.device)
         mode = self._tile_mode(W, False)
         if mode:
-            _lib.check(lib.mfr_conv3x3_direct_f16x2_tiled(_lib.ptr(x), _lib.ptr(self.packed), _lib.ptr(self.b), None, B, C, self.co, H, W, int(act), 0, _lib.ptr(y),
-                                                          self.co, mode, 0, _lib.stream_ptr()), "mfr_conv3x3_direct_f16x2_tiled")
+            _lib.call("mfr_conv3x3_direct_f16x2_tiled", x, self.packed, self.b, None, B, C, self.co, H, W, int(act), 0, y, self.co, mode, 0)
             return y
-        _lib.check(lib.mfr_conv3x3_direct_f16x2_rows(_lib.ptr(x), _lib.ptr(self.packed), _lib.ptr(self.b), B, C, self.co, H, W, int(act), _lib.ptr(y), self.co,
-                                                     _lib.stream_ptr()), "mfr_conv3x3_direct_f16x2_rows")
+        _lib.call("mfr_conv3x3_direct_f16x2_rows", x, self.packed, self.b, B, C, self.co, H, W, int(act), y, self.co)
         return y
 
     def strided(self, x, act=0):
         """the same filter at stride 2 (pad 1): y [B, Cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1] (mfr_conv3x3s2_direct_f16x2)"""
-        lib = _lib.load()
         x = x.contiguous()
         B, C, H, W = x.shape
         assert C == self.ci and x.dtype == torch.float32
         y = torch.empty(B, self.co, (H - 1) // 2 + 1, (W - 1) // 2 + 1, dtype=torch.float32, device=x.device)
-        _lib.check(lib.mfr_conv3x3s2_direct_f16x2(_lib.ptr(x), _lib.ptr(self.packed), _lib.ptr(self.b), B, C, self.co, H, W, int(act), _lib.ptr(y), _lib.stream_ptr()),
-                   "mfr_conv3x3s2_direct_f16x2")
+        _lib.call("mfr_conv3x3s2_direct_f16x2", x, self.packed, self.b, B, C, self.co, H, W, int(act), y)
         return y
 
     def __call__(self, x, act=0, pool=False, residual=None):
-        lib = _lib.load()
         x = x.contiguous()
         B, C, H, W = x.shape
         assert C == self.ci and x.dtype == torch.float32
         y = torch.empty((B, self.co, H // 2, W // 2) if pool else (B, self.co, H, W), dtype=torch.float32, device=x.device)
-        res = _lib.ptr(residual.contiguous()) if residual is not None else None
+        res = residual.contiguous() if residual is not None else None
         mode = self._tile_mode(W, pool)
         if mode:
-            _lib.check(lib.mfr_conv3x3_direct_f16x2_tiled(_lib.ptr(x), _lib.ptr(self.packed), _lib.ptr(self.b), res, B, C, self.co, H, W, int(act), int(pool),
-                                                          _lib.ptr(y), 0, mode, 0, _lib.stream_ptr()), "mfr_conv3x3_direct_f16x2_tiled")
+            _lib.call("mfr_conv3x3_direct_f16x2_tiled", x, self.packed, self.b, res, B, C, self.co, H, W, int(act), int(pool), y, 0, mode, 0)
             return y
-        _lib.check(lib.mfr_conv3x3_direct_f16x2(_lib.ptr(x), _lib.ptr(self.packed), _lib.ptr(self.b), res, B, C, self.co, H, W, int(act), int(pool),
-                                                _lib.ptr(y), _lib.stream_ptr()), "mfr_conv3x3_direct_f16x2")
+        _lib.call("mfr_conv3x3_direct_f16x2", x, self.packed, self.b, res, B, C, self.co, H, W, int(act), int(pool), y)
         return y
 
 
@@ -182,7 +167,7 @@ class IgemmConv:
             m = m.reshape(co, K)
         nb = lib.mfr_gemm_f16x2_pack_bytes(co, K)
         self.packed = torch.empty(nb, dtype=torch.uint8, device=w.device)
-        _lib.check(lib.mfr_gemm_f16x2_pack(_lib.ptr(m.contiguous()), co, K, _lib.ptr(self.packed), _lib.stream_ptr()), "mfr_gemm_f16x2_pack")
+        _lib.call("mfr_gemm_f16x2_pack", m.contiguous(), co, K, self.packed)
         self.b = None if bias is None else bias.contiguous().float()
         # round 6: the strided 3x3 layers through the direct halo-staged kernel (CONV_KERNEL 'auto' / 'direct'); the implicit-GEMM form stays for the A/B
         self.direct_s2 = DirectConv3x3(w, self.b) if (kh, kw, self.stride, self.pad) == (3, 3, 2, 1) and ci > 1 else None
@@ -191,7 +176,6 @@ class IgemmConv:
         """up_add [B, Cout, Ho / 2, Wo / 2]: y = conv(x) + bias + its 2x bilinear up-sampling (align_corners=True) in the same launch (LoFTR's FPN merge)"""
         if self.direct_s2 is not None and up_add is None and options.get("CONV_KERNEL") in ("auto", "direct"):
             return self.direct_s2.strided(x, act=1 if relu else 0)
-        lib = _lib.load()
         x = x.contiguous()
         B, C, H, W = x.shape
         assert C == self.ci and x.dtype == torch.float32
@@ -200,9 +184,7 @@ class IgemmConv:
         if up_add is not None:
             lo = up_add.contiguous()
             assert not relu and lo.shape == (B, self.co, Ho // 2, Wo // 2) and Ho % 2 == 0 and Wo % 2 == 0 and lo.dtype == torch.float32
-            _lib.check(lib.mfr_conv_igemm_f16x2_upadd(_lib.ptr(x), _lib.ptr(self.packed), _lib.ptr(self.b), _lib.ptr(lo), Ho // 2, Wo // 2, _lib.ptr(y), B, C, H, W,
-                                                      self.co, self.kh, self.kw, self.stride, self.pad, _lib.stream_ptr()), "mfr_conv_igemm_f16x2_upadd")
+            _lib.call("mfr_conv_igemm_f16x2_upadd", x, self.packed, self.b, lo, Ho // 2, Wo // 2, y, B, C, H, W, self.co, self.kh, self.kw, self.stride, self.pad)
             return y
-        _lib.check(lib.mfr_conv_igemm_f16x2(_lib.ptr(x), _lib.ptr(self.packed), _lib.ptr(self.b), _lib.ptr(y), B, C, H, W, self.co, self.kh, self.kw,
-                                            self.stride, self.pad, 1 if relu else 0, _lib.stream_ptr()), "mfr_conv_igemm_f16x2")
+        _lib.call("mfr_conv_igemm_f16x2", x, self.packed, self.b, y, B, C, H, W, self.co, self.kh, self.kw, self.stride, self.pad, 1 if relu else 0)
         return y

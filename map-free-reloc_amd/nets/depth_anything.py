@@ -188,7 +188,7 @@ def _grid_of(net_h, net_w):
 def patch_rows(img, net_h, net_w, ldk=PATCH_LDK, mean=MEAN, std=STD):
     """img u8 [B, H, W, 3] or f32 [B, 3, H, W] in [0, 1] -> patch rows [B, gh, gw, ldk]: bilinear resize (align_corners=False) to (net_h, net_w), (x - mean) / std,
     the 14 x 14 unfold with column (c 14 + i) 14 + j, zero columns from 588 (mfr_da_patch_rows)"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     gh, gw = _grid_of(net_h, net_w)
     assert img.is_cuda and img.dim() == 4
     if img.dtype == torch.uint8:
@@ -199,55 +199,53 @@ def patch_rows(img, net_h, net_w, ldk=PATCH_LDK, mean=MEAN, std=STD):
         dtype, B, (H, W) = 1, img.shape[0], img.shape[2:]
     img = img.contiguous()
     out = torch.empty(B, gh, gw, int(ldk), dtype=torch.float32, device=img.device)
-    _lib.check(lib.mfr_da_patch_rows(img.data_ptr(), dtype, B, H, W, gh, gw, *[float(v) for v in mean], *[float(v) for v in std], out.data_ptr(), int(ldk),
-                                     _lib.stream_ptr()), "mfr_da_patch_rows")
+    _lib.call("mfr_da_patch_rows", img.data_ptr(), dtype, B, H, W, gh, gw, *[float(v) for v in mean], *[float(v) for v in std], out.data_ptr(), int(ldk))
     return out
 
 
 def patch_rows_tab(img, rows, net_h, net_w, status, ldk=PATCH_LDK, mean=MEAN, std=STD):
     """img u8 [N, H, W, 3], rows i32 [m] on the GPU -> [m, gh, gw, ldk] = patch_rows(img[rows]) without the gather (mfr_da_patch_rows_tab).  status: i32 [1] on the
     GPU, bit 0 is set when a row index is outside [0, N) (that image's rows are zeros); the caller clears it"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     gh, gw = _grid_of(net_h, net_w)
     assert img.is_cuda and img.dtype == torch.uint8 and img.dim() == 4 and img.shape[3] == 3 and img.is_contiguous()
     assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= 1
     N, H, W = img.shape[:3]
     m = dpt._i32_table(rows).numel()
     out = torch.empty(m, gh, gw, int(ldk), dtype=torch.float32, device=img.device)
-    _lib.check(lib.mfr_da_patch_rows_tab(img.data_ptr(), N, rows.data_ptr(), m, H, W, gh, gw, *[float(v) for v in mean], *[float(v) for v in std], out.data_ptr(),
-                                         int(ldk), status.data_ptr(), _lib.stream_ptr()), "mfr_da_patch_rows_tab")
+    _lib.call("mfr_da_patch_rows_tab", img.data_ptr(), N, rows.data_ptr(), m, H, W, gh, gw, *[float(v) for v in mean], *[float(v) for v in std], out.data_ptr(),
+              int(ldk), status.data_ptr())
     return out
 
 
 def tokens(x, cls, pos, B):
     """x [B HW, C] (the embedding product's rows; unit column stride, any row stride), cls [C], pos [1 + HW, C] -> token rows [B, 1 + HW, C]"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] % B == 0
     HW, C = x.shape[0] // B, x.shape[1]
     pos = dpt._f32(pos)
     assert pos.shape == (1 + HW, C) and cls.numel() == C
     out = torch.empty(B, 1 + HW, C, dtype=torch.float32, device=x.device)
-    _lib.check(lib.mfr_da_tokens(x.data_ptr(), x.stride(0), _lib.ptr(dpt._f32(cls).reshape(C)), pos.data_ptr(), B, C, HW, out.data_ptr(), C, _lib.stream_ptr()),
-               "mfr_da_tokens")
+    _lib.call("mfr_da_tokens", x.data_ptr(), x.stride(0), dpt._f32(cls).reshape(C), pos.data_ptr(), B, C, HW, out.data_ptr(), C)
     return out
 
 
 def head_tail(f, w, bias, out_h, out_w, metric=True, max_depth=20.0, millimetres=False):
     """f [B, C, Hh, Wh] (ReLU(conv2)'s output), w [C] and bias of conv3 -> metres [B, out_h, out_w] f32 (and u16 millimetres, or None): max_depth sigmoid (metric) or
     ReLU, then F.interpolate(bilinear, align_corners=False) to the output size"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     f = dpt._f32(f)
     B, C, Hh, Wh = f.shape
     metres = torch.empty(B, out_h, out_w, dtype=torch.float32, device=f.device)
     mm = torch.empty(B, out_h, out_w, dtype=torch.uint16, device=f.device) if millimetres else None
-    _lib.check(lib.mfr_da_head_tail(f.data_ptr(), _lib.ptr(dpt._f32(w).reshape(C)), float(bias), B, C, Hh, Wh, 1 if metric else 0, float(max_depth), int(out_h), int(out_w),
-                                    metres.data_ptr(), _lib.ptr(mm), _lib.stream_ptr()), "mfr_da_head_tail")
+    _lib.call("mfr_da_head_tail", f.data_ptr(), dpt._f32(w).reshape(C), float(bias), B, C, Hh, Wh, 1 if metric else 0, float(max_depth), int(out_h), int(out_w),
+              metres.data_ptr(), mm)
     return metres, mm
 
 
 def head_tail_rows(f, w, bias, src, dst, metres, status, mm=None, metric=True, max_depth=20.0, quantize=False):
     """plane dst[k] of metres [D, Ho, Wo] (and of mm, or None) <- head_tail(f[src[k]]): nets/dpt.head_tail_rows' tables, quantize and status (mfr_da_head_tail_rows)"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     f = dpt._f32(f)
     B, C, Hh, Wh = f.shape
     assert metres.is_cuda and metres.dtype == torch.float32 and metres.dim() == 3 and metres.is_contiguous()
@@ -256,9 +254,8 @@ def head_tail_rows(f, w, bias, src, dst, metres, status, mm=None, metric=True, m
     assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= 1
     d = dpt._i32_table(src).numel()
     dpt._i32_table(dst, d)
-    _lib.check(lib.mfr_da_head_tail_rows(f.data_ptr(), _lib.ptr(dpt._f32(w).reshape(C)), float(bias), B, C, Hh, Wh, 1 if metric else 0, float(max_depth), Ho, Wo,
-                                         src.data_ptr(), dst.data_ptr(), d, metres.data_ptr(), _lib.ptr(mm), D, 1 if quantize else 0, status.data_ptr(),
-                                         _lib.stream_ptr()), "mfr_da_head_tail_rows")
+    _lib.call("mfr_da_head_tail_rows", f.data_ptr(), dpt._f32(w).reshape(C), float(bias), B, C, Hh, Wh, 1 if metric else 0, float(max_depth), Ho, Wo,
+              src.data_ptr(), dst.data_ptr(), d, metres.data_ptr(), mm, D, 1 if quantize else 0, status.data_ptr())
     return metres
 
 

@@ -185,7 +185,7 @@ def _f32(t):
 
 def prep(img, net_h, net_w):
     """img u8 [B, H, W, 3] or f32 [B, 3, H, W] in [0, 1] -> [B, 3, net_h, net_w]: bilinear resize (align_corners=False) and (x - 0.5) / 0.5"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     assert img.is_cuda and img.dim() == 4
     if img.dtype == torch.uint8:
         assert img.shape[3] == 3
@@ -195,103 +195,99 @@ def prep(img, net_h, net_w):
         dtype, B, (H, W) = 1, img.shape[0], img.shape[2:]
     img = img.contiguous()
     out = torch.empty(B, 3, net_h, net_w, dtype=torch.float32, device=img.device)
-    _lib.check(lib.mfr_dpt_prep(img.data_ptr(), dtype, B, H, W, out.data_ptr(), int(net_h), int(net_w), _lib.stream_ptr()), "mfr_dpt_prep")
+    _lib.call("mfr_dpt_prep", img.data_ptr(), dtype, B, H, W, out.data_ptr(), int(net_h), int(net_w))
     return out
 
 
 def groupnorm(x, gamma, beta, groups, eps=GN_EPS, relu=False, residual=None):
     """GroupNorm over NCHW [+ residual] [ReLU]"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     x = _f32(x)
     B, C, H, W = x.shape
     res = None if residual is None else _f32(residual)
     assert res is None or res.shape == x.shape
     y = torch.empty_like(x)
-    _lib.check(lib.mfr_dpt_groupnorm(x.data_ptr(), _lib.ptr(_f32(gamma)), _lib.ptr(_f32(beta)), _lib.ptr(res), B, C, H * W, int(groups), float(eps),
-                                     1 if relu else 0, y.data_ptr(), _lib.stream_ptr()), "mfr_dpt_groupnorm")
+    _lib.call("mfr_dpt_groupnorm", x.data_ptr(), _f32(gamma), _f32(beta), res, B, C, H * W, int(groups), float(eps), 1 if relu else 0, y.data_ptr())
     return y
 
 
 def maxpool3s2(x, pad_h=None, pad_w=None):
     """3x3 / 2 max-pool behind a zero padding of (lo, hi) per axis; None: TF-"SAME" for that axis"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     x = _f32(x)
     B, C, H, W = x.shape
     (pt, pb), (pl, pr) = pad_h or same_padding(H, 3, 2), pad_w or same_padding(W, 3, 2)
     Ho, Wo = (H + pt + pb - 3) // 2 + 1, (W + pl + pr - 3) // 2 + 1
     y = torch.empty(B, C, max(Ho, 0), max(Wo, 0), dtype=torch.float32, device=x.device)
-    _lib.check(lib.mfr_dpt_maxpool3s2(x.data_ptr(), B * C, H, W, int(pt), int(pb), int(pl), int(pr), y.data_ptr(), _lib.stream_ptr()), "mfr_dpt_maxpool3s2")
+    _lib.call("mfr_dpt_maxpool3s2", x.data_ptr(), B * C, H, W, int(pt), int(pb), int(pl), int(pr), y.data_ptr())
     return y
 
 
 def layernorm(x, gamma, beta, eps=LN_EPS, residual=None, out=None):
     """rows of x [M, C] (unit column stride, any row stride), C a multiple of 64: out = [residual +] LayerNorm(x) gamma + beta"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
     M, C = x.shape
     if out is None:
         out = torch.empty(M, C, dtype=torch.float32, device=x.device)
     assert out.shape == (M, C) and out.stride(1) == 1 and (residual is None or (residual.shape == (M, C) and residual.stride(1) == 1))
-    _lib.check(lib.mfr_dpt_layernorm(x.data_ptr(), x.stride(0), _lib.ptr(_f32(gamma)), _lib.ptr(_f32(beta)), None if residual is None else residual.data_ptr(),
-                                     0 if residual is None else residual.stride(0), M, C, float(eps), out.data_ptr(), out.stride(0), _lib.stream_ptr()),
-               "mfr_dpt_layernorm")
+    _lib.call("mfr_dpt_layernorm", x.data_ptr(), x.stride(0), _f32(gamma), _f32(beta), None if residual is None else residual.data_ptr(),
+              0 if residual is None else residual.stride(0), M, C, float(eps), out.data_ptr(), out.stride(0))
     return out
 
 
 def bias_gelu(x, bias=None):
     """x [M, N] <- GELU_erf(x + bias), in place"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
-    _lib.check(lib.mfr_dpt_bias_gelu(x.data_ptr(), x.stride(0), x.shape[0], x.shape[1], None if bias is None else _lib.ptr(_f32(bias)), _lib.stream_ptr()),
-               "mfr_dpt_bias_gelu")
+    _lib.call("mfr_dpt_bias_gelu", x.data_ptr(), x.stride(0), x.shape[0], x.shape[1], None if bias is None else _f32(bias))
     return x
 
 
 def tokens(x, cls, pos):
     """x [B, C, gh, gw] (the patch projection's output), cls [C], pos [1 + gh gw, C] -> token rows [B, 1 + gh gw, C]"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     x = _f32(x)
     B, C, gh, gw = x.shape
     pos = _f32(pos)
     assert pos.shape == (1 + gh * gw, C) and cls.numel() == C
     out = torch.empty(B, 1 + gh * gw, C, dtype=torch.float32, device=x.device)
-    _lib.check(lib.mfr_dpt_tokens(x.data_ptr(), _lib.ptr(_f32(cls).reshape(C)), pos.data_ptr(), B, C, gh * gw, out.data_ptr(), C, _lib.stream_ptr()), "mfr_dpt_tokens")
+    _lib.call("mfr_dpt_tokens", x.data_ptr(), _f32(cls).reshape(C), pos.data_ptr(), B, C, gh * gw, out.data_ptr(), C)
     return out
 
 
 def tokens_inverse(rows, gh, gw, bias_img=None, gelu=False, skip=1):
     """rows [B, skip + gh gw, C] -> NCHW [B, C, gh, gw] = act(rows without the first `skip` + bias_img [B, C])"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     assert rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 3 and rows.stride(2) == 1
     B, T, C = rows.shape
     assert T == skip + gh * gw and (bias_img is None or bias_img.shape == (B, C))
     out = torch.empty(B, C, gh, gw, dtype=torch.float32, device=rows.device)
-    _lib.check(lib.mfr_dpt_tokens_inverse(rows.data_ptr(), rows.stride(1), rows.stride(0), int(skip), None if bias_img is None else _lib.ptr(_f32(bias_img)),
-                                          1 if gelu else 0, B, C, gh * gw, out.data_ptr(), _lib.stream_ptr()), "mfr_dpt_tokens_inverse")
+    _lib.call("mfr_dpt_tokens_inverse", rows.data_ptr(), rows.stride(1), rows.stride(0), int(skip), None if bias_img is None else _f32(bias_img),
+              1 if gelu else 0, B, C, gh * gw, out.data_ptr())
     return out
 
 
 def shuffle(g, bias, B, C, H, W, s, out=None):
     """g [B H W, C s^2] (the GEMM of fold_conv_transpose) -> ConvTranspose2d's output [B, C, H s, W s] (`out`: written there, contiguous)"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     assert g.is_cuda and g.dtype == torch.float32 and g.shape == (B * H * W, C * s * s) and g.stride(1) == 1
     if out is None:
         out = torch.empty(B, C, H * s, W * s, dtype=torch.float32, device=g.device)
     assert out.shape == (B, C, H * s, W * s) and out.dtype == torch.float32 and out.is_contiguous()
-    _lib.check(lib.mfr_dpt_shuffle(g.data_ptr(), g.stride(0), None if bias is None else _lib.ptr(_f32(bias)), B, C, H, W, int(s), out.data_ptr(), _lib.stream_ptr()),
-               "mfr_dpt_shuffle")
+    _lib.call("mfr_dpt_shuffle", g.data_ptr(), g.stride(0), None if bias is None else _f32(bias), B, C, H, W, int(s), out.data_ptr())
     return out
 
 
 def head_tail(f, w, bias, out_h, out_w, invert=False, scale=1.0, shift=0.0, millimetres=False):
     """f [B, C, Hh, Wh] (the head's ReLU(conv3x3) output), w [C] and bias of the 1x1 layer -> metres [B, out_h, out_w] f32 (and u16 millimetres, or None)"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     f = _f32(f)
     B, C, Hh, Wh = f.shape
     metres = torch.empty(B, out_h, out_w, dtype=torch.float32, device=f.device)
     mm = torch.empty(B, out_h, out_w, dtype=torch.uint16, device=f.device) if millimetres else None
-    _lib.check(lib.mfr_dpt_head_tail(f.data_ptr(), _lib.ptr(_f32(w).reshape(C)), float(bias), B, C, Hh, Wh, 1 if invert else 0, float(scale), float(shift),
-                                     int(out_h), int(out_w), metres.data_ptr(), _lib.ptr(mm), _lib.stream_ptr()), "mfr_dpt_head_tail")
+    _lib.call("mfr_dpt_head_tail", f.data_ptr(), _f32(w).reshape(C), float(bias), B, C, Hh, Wh, 1 if invert else 0, float(scale), float(shift),
+              int(out_h), int(out_w), metres.data_ptr(), mm)
     return metres, mm
 
 
@@ -303,14 +299,13 @@ def _i32_table(t, n=None):
 def prep_rows(img, rows, net_h, net_w, status):
     """img u8 [N, H, W, 3], rows i32 [m] on the GPU -> [m, 3, net_h, net_w] = prep(img[rows]) without the gather (mfr_dpt_prep_rows).  status: i32 [1] on the GPU,
     bit 0 is set when a row index is outside [0, N) (that image is zeros); the caller clears it"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     assert img.is_cuda and img.dtype == torch.uint8 and img.dim() == 4 and img.shape[3] == 3 and img.is_contiguous()
     assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= 1
     N, H, W = img.shape[:3]
     m = _i32_table(rows).numel()
     out = torch.empty(m, 3, net_h, net_w, dtype=torch.float32, device=img.device)
-    _lib.check(lib.mfr_dpt_prep_rows(img.data_ptr(), N, rows.data_ptr(), m, H, W, out.data_ptr(), int(net_h), int(net_w), status.data_ptr(), _lib.stream_ptr()),
-               "mfr_dpt_prep_rows")
+    _lib.call("mfr_dpt_prep_rows", img.data_ptr(), N, rows.data_ptr(), m, H, W, out.data_ptr(), int(net_h), int(net_w), status.data_ptr())
     return out
 
 
@@ -318,7 +313,7 @@ def head_tail_rows(f, w, bias, src, dst, metres, status, mm=None, invert=False, 
     """plane dst[k] of metres [D, Ho, Wo] f32 (and of mm, u16 [D, Ho, Wo] or None) <- head_tail(f[src[k]]), for every entry of the i32 tables src / dst [d] on the
     GPU (mfr_dpt_head_tail_rows): one feature image may feed several planes, planes not listed keep their contents.  quantize: the metres written are
     millimetres_to_metres(mm).  status as in prep_rows"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     f = _f32(f)
     B, C, Hh, Wh = f.shape
     assert metres.is_cuda and metres.dtype == torch.float32 and metres.dim() == 3 and metres.is_contiguous()
@@ -327,21 +322,20 @@ def head_tail_rows(f, w, bias, src, dst, metres, status, mm=None, invert=False, 
     assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= 1
     d = _i32_table(src).numel()
     _i32_table(dst, d)
-    _lib.check(lib.mfr_dpt_head_tail_rows(f.data_ptr(), _lib.ptr(_f32(w).reshape(C)), float(bias), B, C, Hh, Wh, 1 if invert else 0, float(scale), float(shift), Ho, Wo,
-                                          src.data_ptr(), dst.data_ptr(), d, metres.data_ptr(), _lib.ptr(mm), D, 1 if quantize else 0, status.data_ptr(),
-                                          _lib.stream_ptr()), "mfr_dpt_head_tail_rows")
+    _lib.call("mfr_dpt_head_tail_rows", f.data_ptr(), _f32(w).reshape(C), float(bias), B, C, Hh, Wh, 1 if invert else 0, float(scale), float(shift), Ho, Wo,
+              src.data_ptr(), dst.data_ptr(), d, metres.data_ptr(), mm, D, 1 if quantize else 0, status.data_ptr())
     return metres
 
 
 def add_relu(a, b=None, want_sum=True):
     """-> (a + b, relu(a + b)) in one pass (b None: (a, relu(a)))"""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     a = _f32(a)
     b = None if b is None else _f32(b)
     assert b is None or b.shape == a.shape
     s = torch.empty_like(a) if (want_sum and b is not None) else None
     r = torch.empty_like(a)
-    _lib.check(lib.mfr_dpt_add_relu(a.data_ptr(), _lib.ptr(b), a.numel(), _lib.ptr(s), r.data_ptr(), _lib.stream_ptr()), "mfr_dpt_add_relu")
+    _lib.call("mfr_dpt_add_relu", a.data_ptr(), b, a.numel(), s, r.data_ptr())
     return (a if b is None else s), r
 
 
@@ -353,15 +347,14 @@ class PadIgemmConv(IgemmConv):
         super().__init__(weight, bias, stride=stride, padding=0)
 
     def __call__(self, x, pad=(0, 0), relu=False):
-        lib = _lib.load()
         x = _f32(x)
         B, C, H, W = x.shape
         assert C == self.ci
         lo, hi = int(pad[0]), int(pad[1])
         Ho, Wo = (H + lo + hi - self.kh) // self.stride + 1, (W + lo + hi - self.kw) // self.stride + 1
         y = torch.empty(B, self.co, Ho, Wo, dtype=torch.float32, device=x.device)
-        _lib.check(lib.mfr_conv_igemm_f16x2_pad(x.data_ptr(), _lib.ptr(self.packed), _lib.ptr(self.b), y.data_ptr(), B, C, H, W, self.co, self.kh, self.kw, self.stride,
-                                                lo, hi, 1 if relu else 0, _lib.stream_ptr()), "mfr_conv_igemm_f16x2_pad")
+        _lib.call("mfr_conv_igemm_f16x2_pad", x.data_ptr(), self.packed, self.b, y.data_ptr(), B, C, H, W, self.co, self.kh, self.kw, self.stride,
+                  lo, hi, 1 if relu else 0)
         return y
 
 
@@ -371,7 +364,7 @@ def upsample(x, size):
     B, C, H, W = x.shape
     Ho, Wo = int(size[0]), int(size[1])
     y = torch.empty(B, C, Ho, Wo, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().mfr_upsample_bilinear(x.data_ptr(), y.data_ptr(), B * C, H, W, Ho, Wo, 0, _lib.stream_ptr()), "mfr_upsample_bilinear")
+    _lib.call("mfr_upsample_bilinear", x.data_ptr(), y.data_ptr(), B * C, H, W, Ho, Wo, 0)
     return y
 
 
@@ -396,8 +389,8 @@ class DepthNetBase:
             self._n_tok[(B, T)] = torch.full((B,), T, dtype=torch.int32, device=self.device)
         n_tok = self._n_tok[(B, T)]
         base = qkv.data_ptr()
-        _lib.check(_lib.load().mfr_sg_attention_variant(base, base + h * 4, base + 2 * h * 4, 3 * h, B, T, self.arch["VIT_HEADS"], n_tok.data_ptr(), 0, out.data_ptr(), h,
-                                                        self.att_variant, _lib.stream_ptr()), "mfr_sg_attention")
+        _lib.call("mfr_sg_attention_variant", base, base + h * 4, base + 2 * h * 4, 3 * h, B, T, self.arch["VIT_HEADS"], n_tok.data_ptr(), 0, out.data_ptr(), h,
+                  self.att_variant)
         return out
 
     def vit_layer(self, L, x, B, T):

@@ -260,8 +260,7 @@ class EfficientLoFTRHIP:
         B, _, H, W = x.shape
         w, b = self.stem
         y = torch.empty(B, w.shape[0], H // 2, W // 2, dtype=torch.float32, device=x.device)
-        _lib.check(_lib.load().mfr_eloftr_stem_s2(_lib.ptr(x.contiguous()), _lib.ptr(w), _lib.ptr(b), B, H, W, w.shape[0], _lib.ptr(y), _lib.stream_ptr()),
-                   "mfr_eloftr_stem_s2")
+        _lib.call("mfr_eloftr_stem_s2", x.contiguous(), w, b, B, H, W, w.shape[0], y)
         return y
 
     def backbone(self, x):
@@ -282,8 +281,7 @@ class EfficientLoFTRHIP:
         assert x.stride(1) == 1 and x.shape[0] == nimg * hc * wc
         q = torch.empty(nimg * La, HIDDEN, dtype=torch.float32, device=x.device) if want_q else None
         kv = torch.empty(nimg * La, HIDDEN, dtype=torch.float32, device=x.device) if want_kv else None
-        _lib.check(_lib.load().mfr_eloftr_aggregate(x.data_ptr(), x.stride(0), hc * wc * x.stride(0), nimg, hc, wc, _lib.ptr(blk["wagg"]), _lib.ptr(blk["ln"][0]),
-                                                    _lib.ptr(blk["ln"][1]), 1e-5, _lib.ptr(q), _lib.ptr(kv), _lib.stream_ptr()), "mfr_eloftr_aggregate")
+        _lib.call("mfr_eloftr_aggregate", x.data_ptr(), x.stride(0), hc * wc * x.stride(0), nimg, hc, wc, blk["wagg"], blk["ln"][0], blk["ln"][1], 1e-5, q, kv)
         return q, kv
 
     def rotary(self, qkv, hw_agg):
@@ -291,21 +289,18 @@ class EfficientLoFTRHIP:
         if hw_agg not in self._cs:
             self._cs[hw_agg] = rotary_table(hw_agg[0], hw_agg[1], qkv.device)
         La = hw_agg[0] * hw_agg[1]
-        _lib.check(_lib.load().mfr_eloftr_rotary(qkv.data_ptr(), qkv.data_ptr() + HIDDEN * 4, qkv.stride(0), _lib.ptr(self._cs[hw_agg]), qkv.shape[0], La,
-                                                 _lib.stream_ptr()), "mfr_eloftr_rotary")
+        _lib.call("mfr_eloftr_rotary", qkv.data_ptr(), qkv.data_ptr() + HIDDEN * 4, qkv.stride(0), self._cs[hw_agg], qkv.shape[0], La)
         return qkv
 
     def attention(self, qkv, nimg, La):
         """qkv [nimg * La, 768] -> softmax attention per image and head [nimg * La, 256]"""
         out = torch.empty(nimg * La, HIDDEN, dtype=torch.float32, device=qkv.device)
         base, ld = qkv.data_ptr(), qkv.stride(0)
-        _lib.check(_lib.load().mfr_eloftr_attention(base, ld, base + HIDDEN * 4, base + 2 * HIDDEN * 4, ld, nimg, La, La, HEADS, _lib.ptr(out), HIDDEN,
-                                                    _lib.stream_ptr()), "mfr_eloftr_attention")
+        _lib.call("mfr_eloftr_attention", base, ld, base + HIDDEN * 4, base + 2 * HIDDEN * 4, ld, nimg, La, La, HEADS, out, HIDDEN)
         return out
 
     def block(self, blk, xq, xkv, nimg, hw, rotary):
         """one EfficientLoFTRAggregatedAttention on the rows xq [nimg * L, 512] (x | message; x updated in place) attending to the x half of xkv"""
-        lib = _lib.load()
         hc, wc = hw
         L, hw_agg = hc * wc, (hc // AGG, wc // AGG)
         La = hw_agg[0] * hw_agg[1]
@@ -321,10 +316,9 @@ class EfficientLoFTRHIP:
             self.rotary(qkv, hw_agg)
         msg = blk["lo"](self.attention(qkv, nimg, La))
         right = xq[:, HIDDEN:]
-        _lib.check(lib.mfr_eloftr_upsample4_rows(_lib.ptr(msg), HIDDEN, nimg, hw_agg[0], hw_agg[1], right.data_ptr(), xq.stride(0), L * xq.stride(0),
-                                                 _lib.stream_ptr()), "mfr_eloftr_upsample4_rows")
+        _lib.call("mfr_eloftr_upsample4_rows", msg, HIDDEN, nimg, hw_agg[0], hw_agg[1], right.data_ptr(), xq.stride(0), L * xq.stride(0))
         hid = blk["l1"](xq)
-        _lib.check(lib.mfr_eloftr_leaky_relu(_lib.ptr(hid), hid.stride(0), hid.shape[0], hid.shape[1], 0.01, _lib.stream_ptr()), "mfr_eloftr_leaky_relu")
+        _lib.call("mfr_eloftr_leaky_relu", hid, hid.stride(0), hid.shape[0], hid.shape[1], 0.01)
         x = xq[:, :HIDDEN]
         self.layernorm(blk["l2"](hid), blk["mlp_ln"], x, residual=x)            # x += LayerNorm(fc2(leaky(fc1([x | up(msg)]))))
         return xq
@@ -347,8 +341,7 @@ class EfficientLoFTRHIP:
         xm = torch.empty(2, B * L, 2 * C, dtype=torch.float32, device=src0.s3.device)
         for s, (src, idx) in enumerate(((src0, idx0), (src1, idx1))):
             tab = (ctypes.c_int32 * B)(*idx)
-            _lib.check(_lib.load().mfr_nchw_to_rows_gather(_lib.ptr(src.s3), None, src.s3.shape[0], C, L, tab, B, _lib.ptr(xm[s]), L * 2 * C, 2 * C,
-                                                           _lib.stream_ptr()), "mfr_nchw_to_rows_gather")
+            _lib.call("mfr_nchw_to_rows_gather", src.s3, None, src.s3.shape[0], C, L, ctypes.addressof(tab), B, xm[s], L * 2 * C, 2 * C)
         return xm
 
     # ------------------------------------------------------------------ fine level
@@ -356,7 +349,7 @@ class EfficientLoFTRHIP:
         B, C, H, W = x.shape
         out = torch.empty(B, C, 2 * H, 2 * W, dtype=torch.float32, device=x.device)
         assert add is None or (add.shape == out.shape and add.is_contiguous())
-        _lib.check(_lib.load().mfr_eloftr_upsample2x(_lib.ptr(x.contiguous()), _lib.ptr(add), _lib.ptr(out), B * C, H, W, _lib.stream_ptr()), "mfr_eloftr_upsample2x")
+        _lib.call("mfr_eloftr_upsample2x", x.contiguous(), add, out, B * C, H, W)
         return out
 
     def coarse_map(self, xm, nimg, hw):
@@ -364,8 +357,7 @@ class EfficientLoFTRHIP:
         hc, wc = hw
         out = torch.empty(nimg, HIDDEN, hc, wc, dtype=torch.float32, device=xm.device)
         rows = xm.view(-1, 2 * HIDDEN)
-        _lib.check(_lib.load().mfr_eloftr_rows_to_nchw(rows.data_ptr(), rows.stride(0), hc * wc * rows.stride(0), nimg, HIDDEN, hc * wc, 1.0 / 16.0, _lib.ptr(out),
-                                                       _lib.stream_ptr()), "mfr_eloftr_rows_to_nchw")
+        _lib.call("mfr_eloftr_rows_to_nchw", rows.data_ptr(), rows.stride(0), hc * wc * rows.stride(0), nimg, HIDDEN, hc * wc, 1.0 / 16.0, out)
         return out
 
     def pyramid(self, coarse, s2, s1):
@@ -386,8 +378,7 @@ class EfficientLoFTRHIP:
         nimg, Hh, Wh, C = half.shape
         B = n.numel()
         out = torch.zeros(B * maxN, win * win, C, dtype=torch.float32, device=half.device)
-        _lib.check(_lib.load().mfr_eloftr_gather_windows(_lib.ptr(half), nimg, Hh, Wh, C, _lib.ptr(img_ids), _lib.ptr(cells), cells.stride(0), _lib.ptr(n), B, maxN,
-                                                         wc, 8, win, pad, _lib.ptr(out), _lib.stream_ptr()), "mfr_eloftr_gather_windows")
+        _lib.call("mfr_eloftr_gather_windows", half, nimg, Hh, Wh, C, img_ids, cells, cells.stride(0), n, B, maxN, wc, 8, win, pad, out)
         return out
 
     def fine_match(self, w0, w1, ci, cj, n, maxN, wc, return_arg=False):
@@ -395,8 +386,7 @@ class EfficientLoFTRHIP:
         B = n.numel()
         pts0 = torch.zeros(B, maxN, 2, dtype=torch.float32, device=w0.device); pts1 = torch.zeros_like(pts0)
         arg = torch.full((B, maxN), -1, dtype=torch.int32, device=w0.device) if return_arg else None
-        _lib.check(_lib.load().mfr_eloftr_fine_match(_lib.ptr(w0), _lib.ptr(w1), _lib.ptr(ci), _lib.ptr(cj), ci.stride(0), _lib.ptr(n), B, maxN, wc, 8, _lib.ptr(pts0),
-                                                     _lib.ptr(pts1), _lib.ptr(arg), _lib.stream_ptr()), "mfr_eloftr_fine_match")
+        _lib.call("mfr_eloftr_fine_match", w0, w1, ci, cj, ci.stride(0), n, B, maxN, wc, 8, pts0, pts1, arg)
         return (pts0, pts1, arg) if return_arg else (pts0, pts1)
 
     def compact(self, pts0, pts1, conf, n, frame_hw):
@@ -404,8 +394,7 @@ class EfficientLoFTRHIP:
         o0, o1 = torch.empty_like(pts0), torch.empty_like(pts1)
         oc = torch.empty(B, maxN, dtype=torch.float32, device=pts0.device)
         n_out = torch.empty(B, dtype=torch.int32, device=pts0.device)
-        _lib.check(_lib.load().mfr_eloftr_compact(_lib.ptr(pts0), _lib.ptr(pts1), _lib.ptr(conf), conf.stride(0), _lib.ptr(n), B, maxN, int(frame_hw[1]), int(frame_hw[0]),
-                                                  _lib.ptr(o0), _lib.ptr(o1), _lib.ptr(oc), _lib.ptr(n_out), _lib.stream_ptr()), "mfr_eloftr_compact")
+        _lib.call("mfr_eloftr_compact", pts0, pts1, conf, conf.stride(0), n, B, maxN, int(frame_hw[1]), int(frame_hw[0]), o0, o1, oc, n_out)
         return o0, o1, oc, n_out
 
     # ------------------------------------------------------------------ full forward

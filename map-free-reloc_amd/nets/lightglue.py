@@ -131,10 +131,8 @@ class Assignment:
             nc = torch.empty(B, dtype=torch.int32, device=dev)
             kpts0, kpts1 = kpts0.contiguous(), kpts1.contiguous()
             out.update(pts0=pts0, pts1=pts1, n_corr=nc)
-        _lib.check(lib.mfr_lg_assign(S.data_ptr(), B, N0, N1, S.stride(1), _lib.ptr(z0.contiguous()), _lib.ptr(z1.contiguous()), _lib.ptr(n0), _lib.ptr(n1),
-                                     self.thr, _lib.ptr(kpts0), _lib.ptr(kpts1), K, _lib.ptr(self._ws), self._ws.numel(),
-                                     _lib.ptr(m0), _lib.ptr(m1), _lib.ptr(ms0), _lib.ptr(ms1), _lib.ptr(pts0), _lib.ptr(pts1), maxN or 0, _lib.ptr(nc),
-                                     _lib.stream_ptr()), "mfr_lg_assign")
+        _lib.call("mfr_lg_assign", S.data_ptr(), B, N0, N1, S.stride(1), z0.contiguous(), z1.contiguous(), n0, n1, self.thr, kpts0, kpts1, K,
+                  self._ws, self._ws.numel(), m0, m1, ms0, ms1, pts0, pts1, maxN or 0, nc)
         return out
 
 
@@ -164,20 +162,19 @@ class LightGlueHIP:
         """normalised keypoints [B2, K, 2] -> cs [B2 * K, 64] = (cos | sin) of the 32 angles"""
         M = kn.shape[0] * kn.shape[1]
         cs = torch.empty(M, 64, dtype=torch.float32, device=kn.device)
-        _lib.check(_lib.load().mfr_lg_rotary_table(_lib.ptr(kn.contiguous()), _lib.ptr(self.wr), M, _lib.ptr(cs), _lib.stream_ptr()), "mfr_lg_rotary_table")
+        _lib.call("mfr_lg_rotary_table", kn.contiguous(), self.wr, M, cs)
         return cs
 
     def rotate(self, qkv, cs):
         """qkv [M, 768] (q | k | v): q and k rotated in place"""
         base = qkv.data_ptr()
-        _lib.check(_lib.load().mfr_lg_rotary_apply(base, base + 256 * 4, qkv.stride(0), qkv.shape[0], _lib.ptr(cs), _lib.stream_ptr()), "mfr_lg_rotary_apply")
+        _lib.call("mfr_lg_rotary_apply", base, base + 256 * 4, qkv.stride(0), qkv.shape[0], cs)
         return qkv
 
     def attention(self, qkv, n_tok, cross, out, ldo):
         B2, K, _ = qkv.shape
         base = qkv.data_ptr()
-        _lib.check(_lib.load().mfr_sg_attention_variant(base, base + 256 * 4, base + 512 * 4, 768, B2, K, 4, _lib.ptr(n_tok), 1 if cross else 0,
-                                                        out.data_ptr(), ldo, self.att_variant, _lib.stream_ptr()), "mfr_sg_attention")
+        _lib.call("mfr_sg_attention_variant", base, base + 256 * 4, base + 512 * 4, 768, B2, K, 4, n_tok, 1 if cross else 0, out.data_ptr(), ldo, self.att_variant)
         return out
 
     def block(self, L, xa, qkv, hid, cs, n, B2, K):
@@ -191,8 +188,7 @@ class LightGlueHIP:
             L["lin1"].ln_gelu(xa, L["ln"], hid)
         else:
             L["lin1"](xa, out=hid)
-            _lib.check(_lib.load().mfr_lg_ln_gelu(hid.data_ptr(), hid.stride(0), hid.shape[0], _lib.ptr(L["ln"][0]), _lib.ptr(L["ln"][1]), 1e-5, _lib.stream_ptr()),
-                       "mfr_lg_ln_gelu")
+            _lib.call("mfr_lg_ln_gelu", hid.data_ptr(), hid.stride(0), hid.shape[0], L["ln"][0], L["ln"][1], 1e-5)
         L["lin2"](hid, out=xv, accumulate=True)                           # x += W2 hid + b2, in place
         return xa
 

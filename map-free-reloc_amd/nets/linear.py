@@ -14,17 +14,14 @@ class SplitLinear:
         self.split = split or options.get("SPLIT")
         if self.split not in ("f16x2", "bf16x3"):
             raise ValueError(f"SplitLinear: unknown split {self.split!r}")
-        self._pack_bytes = getattr(lib, f"mfr_gemm_{self.split}_pack_bytes")
-        self._pack = getattr(lib, f"mfr_gemm_{self.split}_pack")
-        self._gemm = getattr(lib, f"mfr_gemm_{self.split}")
-        self._gemm_ln = getattr(lib, f"mfr_gemm_{self.split}_ln")
+        self._gemm = f"mfr_gemm_{self.split}"
         self.N, self.K = int(weight.shape[0]), int(weight.shape[1])
-        nb = self._pack_bytes(self.N, self.K)
+        nb = getattr(lib, self._gemm + "_pack_bytes")(self.N, self.K)
         if nb == 0:
             raise ValueError(f"SplitLinear: K = {self.K} must be a multiple of 32")
         w = weight.contiguous().float()
         self.packed = torch.empty(nb, dtype=torch.uint8, device=w.device)
-        _lib.check(self._pack(_lib.ptr(w), self.N, self.K, _lib.ptr(self.packed), _lib.stream_ptr()), f"mfr_gemm_{self.split}_pack")
+        _lib.call(self._gemm + "_pack", w, self.N, self.K, self.packed)
         self.bias = None if bias is None else bias.contiguous().float()
 
     def windows(self, feat_nhwc, img_ids, cell_ids, wc, stride, win, out, window_bias=None):
@@ -37,10 +34,8 @@ class SplitLinear:
         assert window_bias is None or (window_bias.shape == (nwin, self.N) and window_bias.is_contiguous())
         if getattr(self, "_zero_row", None) is None:
             self._zero_row = torch.zeros(self.K, dtype=torch.float32, device=feat_nhwc.device)
-        lib = _lib.load()
-        _lib.check(getattr(lib, f"mfr_gemm_{self.split}_windows")(_lib.ptr(feat_nhwc), Bimg, Hf, Wf, C, _lib.ptr(img_ids), _lib.ptr(cell_ids), nwin, wc, stride, win,
-                                                                   _lib.ptr(self._zero_row), _lib.ptr(self.packed), _lib.ptr(self.bias), _lib.ptr(window_bias),
-                                                                   out.data_ptr(), out.stride(0), self.N, _lib.stream_ptr()), f"mfr_gemm_{self.split}_windows")
+        _lib.call(self._gemm + "_windows", feat_nhwc, Bimg, Hf, Wf, C, img_ids, cell_ids, nwin, wc, stride, win, self._zero_row, self.packed, self.bias,
+                  window_bias, out.data_ptr(), out.stride(0), self.N)
         return out
 
     def ln_gelu(self, x, ln, out, eps=1e-5):
@@ -48,9 +43,8 @@ class SplitLinear:
         assert self.N == 512 and x.dim() == 2 and x.shape[1] == self.K and x.stride(1) == 1 and x.dtype == torch.float32
         M = x.shape[0]
         assert out.shape == (M, 512) and out.stride(1) == 1
-        fn = getattr(_lib.load(), f"mfr_gemm_{self.split}_ln_gelu")
-        _lib.check(fn(x.data_ptr(), x.stride(0), _lib.ptr(self.packed), _lib.ptr(self.bias), _lib.ptr(ln[0]), _lib.ptr(ln[1]), float(eps), out.data_ptr(), out.stride(0),
-                      M, self.N, self.K, _lib.stream_ptr()), f"mfr_gemm_{self.split}_ln_gelu")
+        _lib.call(self._gemm + "_ln_gelu", x.data_ptr(), x.stride(0), self.packed, self.bias, ln[0], ln[1], float(eps), out.data_ptr(), out.stride(0),
+                  M, self.N, self.K)
         return out
 
     def ln_fusable(self):
@@ -69,11 +63,11 @@ class SplitLinear:
         assert out.shape == (M, self.N) and out.stride(1) == 1
         if ln is not None:
             assert self.ln_fusable() and not relu and kernel_flag == 0
-            _lib.check(self._gemm_ln(x.data_ptr(), x.stride(0), _lib.ptr(self.packed), _lib.ptr(self.bias), _lib.ptr(ln[0]), _lib.ptr(ln[1]), float(eps),
-                                     out.data_ptr(), out.stride(0), M, self.N, self.K, 1 if accumulate else 0, _lib.stream_ptr()), f"mfr_gemm_{self.split}_ln")
+            _lib.call(self._gemm + "_ln", x.data_ptr(), x.stride(0), self.packed, self.bias, ln[0], ln[1], float(eps),
+                      out.data_ptr(), out.stride(0), M, self.N, self.K, 1 if accumulate else 0)
             return out
-        _lib.check(self._gemm(x.data_ptr(), x.stride(0), _lib.ptr(self.packed), _lib.ptr(self.bias), out.data_ptr(), out.stride(0),
-                              M, self.N, self.K, (1 if relu else 0) | (2 if accumulate else 0) | kernel_flag, _lib.stream_ptr()), f"mfr_gemm_{self.split}")
+        _lib.call(self._gemm, x.data_ptr(), x.stride(0), self.packed, self.bias, out.data_ptr(), out.stride(0),
+                  M, self.N, self.K, (1 if relu else 0) | (2 if accumulate else 0) | kernel_flag)
         return out
 
 
@@ -101,9 +95,9 @@ class SplitBatchedNT:
             out = torch.empty(nb, M, N, dtype=torch.float32, device=x.device)
         assert out.shape == (nb, M, N) and out.stride(2) == 1
         st = _lib.stream_ptr()
-        _lib.check(self.lib.mfr_gemm_f16x2_pack_batched(w.data_ptr(), w.stride(1), nb, w.stride(0), N, K, float(out_mul), _lib.ptr(pk), st), "mfr_gemm_f16x2_pack_batched")
-        _lib.check(self.lib.mfr_gemm_f16x2_batched(x.data_ptr(), x.stride(1), x.stride(0), _lib.ptr(pk), None, out.data_ptr(), out.stride(1), out.stride(0),
-                                                   nb, M, N, K, 0, st), "mfr_gemm_f16x2_batched")
+        _lib.call("mfr_gemm_f16x2_pack_batched", w.data_ptr(), w.stride(1), nb, w.stride(0), N, K, float(out_mul), pk, stream=st)
+        _lib.call("mfr_gemm_f16x2_batched", x.data_ptr(), x.stride(1), x.stride(0), pk, None, out.data_ptr(), out.stride(1), out.stride(0),
+                  nb, M, N, K, 0, stream=st)
         return out
 
 
@@ -114,13 +108,13 @@ class FusedMlpLn:
     def __init__(self, lin1, lin2):
         assert lin1.split == lin2.split and lin1.N == 256 and lin2.N == 128 and lin2.K == 256 and lin1.K % 64 == 0
         self.l1, self.l2 = lin1, lin2
-        self._fn = getattr(_lib.load(require_gpu=True), f"mfr_mlp_ln_{lin1.split}")
+        _lib.load(require_gpu=True)
+        self._fn = f"mfr_mlp_ln_{lin1.split}"
 
     def __call__(self, x, out, ln, accumulate=False, eps=1e-5):
         assert x.dim() == 2 and x.shape[1] == self.l1.K and x.stride(1) == 1 and x.dtype == torch.float32
         M = x.shape[0]
         assert out.shape == (M, 128) and out.stride(1) == 1
-        _lib.check(self._fn(x.data_ptr(), x.stride(0), self.l1.K, _lib.ptr(self.l1.packed), _lib.ptr(self.l1.bias), _lib.ptr(self.l2.packed), _lib.ptr(self.l2.bias),
-                            _lib.ptr(ln[0]), _lib.ptr(ln[1]), float(eps), out.data_ptr(), out.stride(0), M, 1 if accumulate else 0, _lib.stream_ptr()),
-                   f"mfr_mlp_ln_{self.l1.split}")
+        _lib.call(self._fn, x.data_ptr(), x.stride(0), self.l1.K, self.l1.packed, self.l1.bias, self.l2.packed, self.l2.bias,
+                  ln[0], ln[1], float(eps), out.data_ptr(), out.stride(0), M, 1 if accumulate else 0)
         return out

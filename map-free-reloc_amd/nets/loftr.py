@@ -211,21 +211,18 @@ class LoFTRHIP:
         base = kv.data_ptr()
         # q / kv may be column slices of one [B, L, 3 D] buffer (self layers): rows stay L * ld apart, only the row stride differs
         assert q.stride(2) == 1 and kv.stride(2) == 1 and q.stride(0) == L * q.stride(1) and kv.stride(0) == L * kv.stride(1)
-        _lib.check(lib.mfr_loftr_linear_attention(q.data_ptr(), q.stride(1), base, base + D * 4, kv.stride(1), B, L, heads, _lib.ptr(self._ws_la),
-                                                  self._ws_la.numel(), _lib.ptr(out), D, _lib.stream_ptr()),
-                   "mfr_loftr_linear_attention")
+        _lib.call("mfr_loftr_linear_attention", q.data_ptr(), q.stride(1), base, base + D * 4, kv.stride(1), B, L, heads, self._ws_la,
+                  self._ws_la.numel(), out, D)
         return out
 
     def fine_attention(self, q, kv):
         """q [Bw,25,128]; kv [Bw,25,256] (k | v) -> message [Bw,25,128]: LinearAttention of the fine transformer
         (8 heads x 16, 5x5 windows), one wavefront per window (csrc/loftr.hip)"""
-        lib = _lib.load()
         Bw, L, D = q.shape
         assert q.stride(2) == 1 and kv.stride(2) == 1 and q.stride(0) == L * q.stride(1) and kv.stride(0) == L * kv.stride(1)
         out = torch.empty(Bw, L, D, dtype=torch.float32, device=q.device)
         base = kv.data_ptr()
-        _lib.check(lib.mfr_loftr_fine_attention(q.data_ptr(), q.stride(1), base, base + D * 4, kv.stride(1), Bw, L, D, 8, _lib.ptr(out), D,
-                                                _lib.stream_ptr()), "mfr_loftr_fine_attention")
+        _lib.call("mfr_loftr_fine_attention", q.data_ptr(), q.stride(1), base, base + D * 4, kv.stride(1), Bw, L, D, 8, out, D)
         return out
 
     def coarse_match(self, S, hw0, hw1, variant=0):
@@ -239,10 +236,8 @@ class LoFTRHIP:
         i_ids = torch.zeros(B, L0, dtype=torch.int32, device=S.device); j_ids = torch.zeros_like(i_ids)
         mconf = torch.zeros(B, L0, dtype=torch.float32, device=S.device)
         n = torch.empty(B, dtype=torch.int32, device=S.device)
-        _lib.check(lib.mfr_loftr_coarse_match_variant(_lib.ptr(S.contiguous()), B, hw0[0], hw0[1], hw1[0], hw1[1], self.temp, self.thr,
-                                                      self.border, _lib.ptr(self._ws_cm), self._ws_cm.numel(), _lib.ptr(i_ids),
-                                                      _lib.ptr(j_ids), _lib.ptr(mconf), _lib.ptr(n), variant, _lib.stream_ptr()),
-                   "mfr_loftr_coarse_match")
+        _lib.call("mfr_loftr_coarse_match_variant", S.contiguous(), B, hw0[0], hw0[1], hw1[0], hw1[1], self.temp, self.thr,
+                  self.border, self._ws_cm, self._ws_cm.numel(), i_ids, j_ids, mconf, n, variant)
         return i_ids, j_ids, mconf, n
 
     def ot_match(self, S, hw0, hw1, variant=0, return_potentials=False):
@@ -260,30 +255,26 @@ class LoFTRHIP:
         n = torch.empty(B, dtype=torch.int32, device=S.device)
         u = torch.empty(B, L0 + 1, dtype=torch.float32, device=S.device) if return_potentials else None
         v = torch.empty(B, L1 + 1, dtype=torch.float32, device=S.device) if return_potentials else None
-        _lib.check(lib.mfr_loftr_ot_match(_lib.ptr(S.contiguous()), B, hw0[0], hw0[1], hw1[0], hw1[1], self.bin_score, self.skh_iters, self.thr,
-                                          self.border, _lib.ptr(self._ws_ot), self._ws_ot.numel(), _lib.ptr(i_ids), _lib.ptr(j_ids),
-                                          _lib.ptr(mconf), _lib.ptr(n), _lib.ptr(u) if u is not None else None,
-                                          _lib.ptr(v) if v is not None else None, variant, _lib.stream_ptr()), "mfr_loftr_ot_match")
+        _lib.call("mfr_loftr_ot_match", S.contiguous(), B, hw0[0], hw0[1], hw1[0], hw1[1], self.bin_score, self.skh_iters, self.thr,
+                  self.border, self._ws_ot, self._ws_ot.numel(), i_ids, j_ids, mconf, n, u, v, variant)
         return (i_ids, j_ids, mconf, n, u, v) if return_potentials else (i_ids, j_ids, mconf, n)
 
     def upsample2x_add(self, lo, y):
         """y += F.interpolate(lo, scale_factor=2, bilinear, align_corners=True), one pass (csrc/loftr_fused.hip)"""
-        lib = _lib.load()
         B, C, H, W = lo.shape
         assert y.shape == (B, C, 2 * H, 2 * W) and y.is_contiguous()
-        _lib.check(lib.mfr_upsample2x_add(_lib.ptr(lo.contiguous()), _lib.ptr(y), B * C, H, W, _lib.stream_ptr()), "mfr_upsample2x_add")
+        _lib.call("mfr_upsample2x_add", lo.contiguous(), y, B * C, H, W)
         return y
 
     @staticmethod
     def layernorm(x, norm, out, residual=None):
         """out = [residual +] LayerNorm(x) over the last dim (128 / 256); x, out, residual are 2-D row-strided views
         (csrc/loftr_fused.hip: strides let the result land inside the MLP's [x | message] operand / update x in place)"""
-        lib = _lib.load()
         rows, C = x.shape
         assert x.stride(1) == 1 and out.stride(1) == 1 and out.shape == x.shape
-        _lib.check(lib.mfr_layernorm(x.data_ptr(), x.stride(0), _lib.ptr(norm[0]), _lib.ptr(norm[1]),
-                                     residual.data_ptr() if residual is not None else None, residual.stride(0) if residual is not None else 0,
-                                     rows, C, 1e-5, out.data_ptr(), out.stride(0), _lib.stream_ptr()), "mfr_layernorm")
+        _lib.call("mfr_layernorm", x.data_ptr(), x.stride(0), norm[0], norm[1],
+                  residual.data_ptr() if residual is not None else None, residual.stride(0) if residual is not None else 0,
+                  rows, C, 1e-5, out.data_ptr(), out.stride(0))
         return out
 
     def coarse_match_features(self, f0, f1, hw):
@@ -305,21 +296,15 @@ class LoFTRHIP:
 
     def fine_match(self, xf, M, lin_idx, k1, pts1, out_scale, expec=None):
         """xf [2, M * W * W, 256] (fine features in the first 128 columns) -> pts1[lin_idx] = k1[lin_idx] + expectation * out_scale (in place)"""
-        lib = _lib.load()
-        _lib.check(lib.mfr_loftr_fine_match(_lib.ptr(xf[0]), _lib.ptr(xf[1]), xf.shape[-1], 128, M, self.W, out_scale,
-                                            _lib.ptr(lin_idx) if lin_idx is not None else None, _lib.ptr(k1) if k1 is not None else None,
-                                            _lib.ptr(pts1) if pts1 is not None else None, _lib.ptr(expec) if expec is not None else None,
-                                            _lib.stream_ptr()), "mfr_loftr_fine_match")
+        _lib.call("mfr_loftr_fine_match", xf[0], xf[1], xf.shape[-1], 128, M, self.W, out_scale, lin_idx, k1, pts1, expec)
 
     def gather_windows(self, feat_nhwc, img_ids, cell_ids, wc, stride, out=None):
-        lib = _lib.load()
         Bimg, Hf, Wf, C = feat_nhwc.shape
         M = img_ids.numel()
         if out is None:
             out = torch.empty(M, self.W * self.W, C, dtype=torch.float32, device=feat_nhwc.device)
         assert out.is_contiguous() and out.shape == (M, self.W * self.W, C)
-        _lib.check(lib.mfr_loftr_gather_windows(_lib.ptr(feat_nhwc), Bimg, Hf, Wf, C, _lib.ptr(img_ids), _lib.ptr(cell_ids), M,
-                                                wc, stride, self.W, _lib.ptr(out), _lib.stream_ptr()), "mfr_loftr_gather_windows")
+        _lib.call("mfr_loftr_gather_windows", feat_nhwc, Bimg, Hf, Wf, C, img_ids, cell_ids, M, wc, stride, self.W, out)
         return out
 
     # ------------------------------------------------------------------ transformer layers
@@ -411,8 +396,7 @@ class LoFTRHIP:
         for s, (src, idx) in enumerate(((src0, idx0), (src1, idx1))):
             # the index table is a kernel argument: no index tensor, no interleaved [2B,256,hc,wc] copy of the coarse maps
             tab = (ctypes.c_int32 * B)(*idx)
-            _lib.check(_lib.load().mfr_nchw_to_rows_gather(_lib.ptr(src.coarse), _lib.ptr(pe), src.coarse.shape[0], C, L0, tab, B, _lib.ptr(xm[s]), L0 * 2 * C,
-                                                           2 * C, _lib.stream_ptr()), "mfr_nchw_to_rows_gather")
+            _lib.call("mfr_nchw_to_rows_gather", src.coarse, pe, src.coarse.shape[0], C, L0, ctypes.addressof(tab), B, xm[s], L0 * 2 * C, 2 * C)
         self._transformer(self.coarse, xm, self.linear_attention, B, L0)
         c = self._coarse_matches(xm, (hc, wc), H)
         c["sides"] = ((src0.fine, idx0), (src1.fine, idx1))
@@ -434,8 +418,7 @@ class LoFTRHIP:
         pe = self._pos_encoding(C, hc, wc, fc.device)
         L0 = hc * wc
         xm = torch.empty(2, (B2 // 2) * L0, 2 * C, dtype=torch.float32, device=fc.device)
-        _lib.check(_lib.load().mfr_nchw_to_rows(_lib.ptr(fc.contiguous()), _lib.ptr(pe), B2, C, L0, 1, _lib.ptr(xm), L0 * 2 * C, 2 * C,
-                                                _lib.stream_ptr()), "mfr_nchw_to_rows")
+        _lib.call("mfr_nchw_to_rows", fc.contiguous(), pe, B2, C, L0, 1, xm, L0 * 2 * C, 2 * C)
         return xm
 
     def _pos_encoding(self, C, hc, wc, device):
@@ -468,8 +451,7 @@ class LoFTRHIP:
             return ff.permute(0, 2, 3, 1)
         n, Cf, Hf, Wf = ff.shape
         ff_nhwc = torch.empty(n, Hf, Wf, Cf, dtype=torch.float32, device=ff.device)        # LDS-tiled transpose (csrc/elementwise.hip)
-        _lib.check(_lib.load().mfr_nchw_to_rows(_lib.ptr(ff.contiguous()), None, n, Cf, Hf * Wf, 0, _lib.ptr(ff_nhwc), Hf * Wf * Cf, Cf, _lib.stream_ptr()),
-                   "mfr_nchw_to_rows")
+        _lib.call("mfr_nchw_to_rows", ff.contiguous(), None, n, Cf, Hf * Wf, 0, ff_nhwc, Hf * Wf * Cf, Cf)
         return ff_nhwc
 
     def fine_stage(self, c):

@@ -109,15 +109,13 @@ class SuperGlueHIP:
     def attention(self, qkv, n_tok, cross, out=None, ldo=256, variant=None):
         """qkv [B2,K,768] (q | k | v, each head-major) -> message [B2,K,256] (or into `out`, row stride ldo floats);
         variant None = the arithmetic resolved at construction (HIP.SPLIT: 0 = f16x2, 2 = bf16x3), 1 = exact-fp32 matrix-core kernel (A/B, tests)"""
-        lib = _lib.load()
         if variant is None:
             variant = self.att_variant
         B2, K, _ = qkv.shape
         if out is None:
             out = torch.empty(B2, K, 256, dtype=torch.float32, device=qkv.device)
         base = qkv.data_ptr()
-        _lib.check(lib.mfr_sg_attention_variant(base, base + 256 * 4, base + 512 * 4, 768, B2, K, 4, _lib.ptr(n_tok),
-                                                1 if cross else 0, out.data_ptr(), ldo, int(variant), _lib.stream_ptr()), "mfr_sg_attention")
+        _lib.call("mfr_sg_attention_variant", base, base + 256 * 4, base + 512 * 4, 768, B2, K, 4, n_tok, 1 if cross else 0, out.data_ptr(), ldo, int(variant))
         return out
 
     def sinkhorn_match(self, S, n0, n1, kpts0, kpts1, maxN=None, variant=0):
@@ -139,11 +137,8 @@ class SuperGlueHIP:
             n0, n1 = n0.contiguous(), n1.contiguous()
         if not (kpts0.stride() == kpts1.stride() and kpts0.stride(0) >= 2 * K and kpts0.stride()[1:] == (2, 1)):
             kpts0, kpts1 = kpts0.contiguous(), kpts1.contiguous()
-        _lib.check(lib.mfr_sg_sinkhorn_match_strided(
-            _lib.ptr(S.contiguous()), B, ldS, n0.data_ptr(), n1.data_ptr(), n0.stride(0), self.bin_score, self.iters, self.match_thr,
-            kpts0.data_ptr(), kpts1.data_ptr(), K, kpts0.stride(0), _lib.ptr(self._ws), self._ws.numel(),
-            _lib.ptr(m0), _lib.ptr(ms0), _lib.ptr(pts0), _lib.ptr(pts1), maxN, _lib.ptr(nc), int(variant), _lib.stream_ptr()),
-            "mfr_sg_sinkhorn_match")
+        _lib.call("mfr_sg_sinkhorn_match_strided", S.contiguous(), B, ldS, n0.data_ptr(), n1.data_ptr(), n0.stride(0), self.bin_score, self.iters,
+                  self.match_thr, kpts0.data_ptr(), kpts1.data_ptr(), K, kpts0.stride(0), self._ws, self._ws.numel(), m0, ms0, pts0, pts1, maxN, nc, int(variant))
         return dict(matches0=m0, matching_scores0=ms0, pts0=pts0, pts1=pts1, n_corr=nc)
 
     def xa_buffer(self, B2, K):
@@ -165,8 +160,7 @@ class SuperGlueHIP:
         # sums are independent of the batch size
         w0, b0 = self.kenc[0]
         h = torch.empty(B2 * K, w0.shape[0], dtype=torch.float32, device=kpts.device)
-        _lib.check(_lib.load().mfr_sg_kenc_in(_lib.ptr(kpts.contiguous()), _lib.ptr(scores.contiguous()), _lib.ptr(w0), _lib.ptr(b0), B2 * K, H, W,
-                                              _lib.ptr(h), _lib.stream_ptr()), "mfr_sg_kenc_in")
+        _lib.call("mfr_sg_kenc_in", kpts.contiguous(), scores.contiguous(), w0, b0, B2 * K, H, W, h)
         for lin in self.kenc_lin[:-1]:
             h = lin(h, relu=True)
         # xa = [x~ | a]: the running descriptors (minus the folded bias offset) and the attention output side by side.  desc + kenc(kpts, scores):

@@ -54,7 +54,6 @@ class SuperPointHIP:
         """3x3 layer = ONE launch of the fused Winograd/MFMA kernel (conv + bias + ReLU [+ 2x2 max-pool],
         csrc/winograd_conv.hip).  Option CONV = 'miopen' (or an unsupported shape): library conv without bias + one fused
         HIP epilogue pass (csrc/elementwise.hip)."""
-        lib = _lib.load()
         w, b = self.w[name + ".weight"], self.w[name + ".bias"]
         pad = w.shape[-1] // 2
         if self.use_wino and relu and name in self.upk:
@@ -66,7 +65,7 @@ class SuperPointHIP:
                 B, C, H, W = x.shape
                 x = x.contiguous()
                 y = torch.empty(B, w.shape[0], H, W, dtype=torch.float32, device=x.device)
-                _lib.check(lib.mfr_conv1x1_nchw(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), B, C, w.shape[0], H * W, _lib.ptr(y), _lib.stream_ptr()), "mfr_conv1x1_nchw")
+                _lib.call("mfr_conv1x1_nchw", x, w, b, B, C, w.shape[0], H * W, y)
                 return y
             if w.shape[-1] == 1:            # options CONV = "miopen": one batched library GEMM [Cout,Cin] x [Cin,HW] per image
                 B, C, H, W = x.shape
@@ -78,36 +77,31 @@ class SuperPointHIP:
         B, C, H, W = x.shape
         if pool:
             y = torch.empty(B, C, H // 2, W // 2, dtype=x.dtype, device=x.device)
-            _lib.check(lib.mfr_bias_pool2_relu_nchw(_lib.ptr(x), _lib.ptr(b), B, C, H, W, _lib.ptr(y), _lib.stream_ptr()),
-                       "mfr_bias_pool2_relu_nchw")
+            _lib.call("mfr_bias_pool2_relu_nchw", x, b, B, C, H, W, y)
             return y
-        _lib.check(lib.mfr_bias_relu_nchw(_lib.ptr(x), _lib.ptr(b), B, C, H * W, _lib.stream_ptr()), "mfr_bias_relu_nchw")
+        _lib.call("mfr_bias_relu_nchw", x, b, B, C, H * W)
         return x
 
     def _conv1a(self, image):
         """first layer (1 -> 64 channels) as one fused HIP pass (csrc/elementwise.hip)"""
-        lib = _lib.load()
         B, C, H, W = image.shape
         w, b = self.w["conv1a.weight"], self.w["conv1a.bias"]
         if C != 1 or w.shape[0] != 64 or (W & 3):
             return self._conv(image, "conv1a")
         y = torch.empty(B, 64, H, W, dtype=torch.float32, device=image.device)
-        _lib.check(lib.mfr_conv3x3_c1_relu(_lib.ptr(image.contiguous()), _lib.ptr(w), _lib.ptr(b), B, H, W, 64, _lib.ptr(y),
-                                           _lib.stream_ptr()), "mfr_conv3x3_c1_relu")
+        _lib.call("mfr_conv3x3_c1_relu", image.contiguous(), w, b, B, H, W, 64, y)
         return y
 
     def _conv1ab(self, image):
         """conv1a + ReLU + conv1b + ReLU + 2x2 max-pool in ONE kernel (csrc/winograd_split.hip mfr_sp_conv1ab_f16x2, option FUSED_CONV1): the
         64-channel full-resolution intermediate never reaches memory; bit-identical to the two launches it replaces"""
-        lib = _lib.load()
         B, C, H, W = image.shape
         cv = self.upk.get("conv1b")
         if (not self.fused_conv1 or cv is None or cv.split != "f16x2" or C != 1 or H < 2 or W < 2
                 or tuple(self.w["conv1a.weight"].shape) != (64, 1, 3, 3) or (cv.ci, cv.co) != (64, 64)):
             return None
         y = torch.empty(B, 64, H // 2, W // 2, dtype=torch.float32, device=image.device)
-        _lib.check(lib.mfr_sp_conv1ab_f16x2(_lib.ptr(image.contiguous()), _lib.ptr(self.w["conv1a.weight"]), _lib.ptr(self.w["conv1a.bias"]),
-                                            _lib.ptr(cv.u_split), _lib.ptr(cv.b), B, H, W, _lib.ptr(y), _lib.stream_ptr()), "mfr_sp_conv1ab_f16x2")
+        _lib.call("mfr_sp_conv1ab_f16x2", image.contiguous(), self.w["conv1a.weight"], self.w["conv1a.bias"], cv.u_split, cv.b, B, H, W, y)
         return y
 
     def encode(self, image):
@@ -121,17 +115,15 @@ class SuperPointHIP:
 
     # -- stage wrappers (each is one C-ABI call; exposed for stage-level parity tests) --
     def score_map(self, logits):
-        lib = _lib.load()
         B, C, Hc, Wc = logits.shape
         assert C == 65
         logits = logits.contiguous()
         out = torch.empty(B, Hc * 8, Wc * 8, dtype=torch.float32, device=logits.device)
-        _lib.check(lib.mfr_sp_scoremap(_lib.ptr(logits), B, Hc, Wc, _lib.ptr(out), _lib.stream_ptr()), "mfr_sp_scoremap")
+        _lib.call("mfr_sp_scoremap", logits, B, Hc, Wc, out)
         return out
 
     def nms_candidates(self, scores, want_dense=False, variant=None):
         """variant None = the library's default, 0 = the streaming kernel, 1 = the tile kernel (csrc/superpoint_post.hip)"""
-        lib = _lib.load()
         B, H, W = scores.shape
         cand = torch.empty(B, CAND_CAP, dtype=torch.int64, device=scores.device)
         cnt = torch.empty(B, dtype=torch.int32, device=scores.device)
@@ -139,29 +131,22 @@ class SuperPointHIP:
         if variant is None:
             variant = self.nms_variant
         if variant is None:
-            _lib.check(lib.mfr_sp_nms_candidates(_lib.ptr(scores), B, H, W, self.nms_radius, self.thr, self.border,
-                                                 _lib.ptr(dense), _lib.ptr(cand), CAND_CAP, _lib.ptr(cnt),
-                                                 _lib.stream_ptr()), "mfr_sp_nms_candidates")
+            _lib.call("mfr_sp_nms_candidates", scores, B, H, W, self.nms_radius, self.thr, self.border, dense, cand, CAND_CAP, cnt)
         else:
-            _lib.check(lib.mfr_sp_nms_candidates_variant(_lib.ptr(scores), B, H, W, self.nms_radius, self.thr, self.border,
-                                                         _lib.ptr(dense), _lib.ptr(cand), CAND_CAP, _lib.ptr(cnt), int(variant),
-                                                         _lib.stream_ptr()), "mfr_sp_nms_candidates_variant")
+            _lib.call("mfr_sp_nms_candidates_variant", scores, B, H, W, self.nms_radius, self.thr, self.border, dense, cand, CAND_CAP, cnt, int(variant))
         return cand, cnt, dense
 
     def select(self, cand, cnt, W):
-        lib = _lib.load()
         B = cand.shape[0]
         kpts = torch.empty(B, self.K, 2, dtype=torch.float32, device=cand.device)
         sc = torch.empty(B, self.K, dtype=torch.float32, device=cand.device)
         n = torch.empty(B, dtype=torch.int32, device=cand.device)
-        _lib.check(lib.mfr_sp_select_topk(_lib.ptr(cand), CAND_CAP, _lib.ptr(cnt), B, W, self.K, _lib.ptr(kpts),
-                                          _lib.ptr(sc), _lib.ptr(n), _lib.stream_ptr()), "mfr_sp_select_topk")
+        _lib.call("mfr_sp_select_topk", cand, CAND_CAP, cnt, B, W, self.K, kpts, sc, n)
         return kpts, sc, n
 
     def sample(self, dense_nhwc, kpts, n, out=None):
         """out: a [B,K,256] destination whose rows may lie more than 256 floats apart (images K rows apart), e.g. the left half of SuperGlue's
         [x | a] buffer (SuperGlueHIP.xa_buffer); what lies between the rows is not touched.  None: a new contiguous tensor"""
-        lib = _lib.load()
         B, Hc, Wc, C = dense_nhwc.shape
         assert C == 256
         if out is None:
@@ -169,9 +154,7 @@ class SuperPointHIP:
         ldd = out.stride(1)
         if tuple(out.shape) != (B, self.K, 256) or out.dtype != torch.float32 or out.stride(2) != 1 or out.stride(0) != self.K * ldd or ldd < 256:
             raise ValueError("sample: out must be [B, K, 256] float32 rows of one pitch, images K rows apart")
-        _lib.check(lib.mfr_sp_sample_descriptors_ld(_lib.ptr(dense_nhwc.contiguous()), B, Hc, Wc, _lib.ptr(kpts),
-                                                    _lib.ptr(n), self.K, out.data_ptr(), ldd, _lib.stream_ptr()),
-                   "mfr_sp_sample_descriptors_ld")
+        _lib.call("mfr_sp_sample_descriptors_ld", dense_nhwc.contiguous(), B, Hc, Wc, kpts, n, self.K, out.data_ptr(), ldd)
         return out
 
     def logits(self, x):
@@ -190,8 +173,7 @@ class SuperPointHIP:
             cDa = self._conv(x, "convDa")
             B, C, Hc, Wc = cDa.shape
             rows = torch.empty(B * Hc * Wc, C, dtype=torch.float32, device=cDa.device)
-            _lib.check(_lib.load().mfr_nchw_to_rows(_lib.ptr(cDa.contiguous()), None, B, C, Hc * Wc, 0, _lib.ptr(rows), Hc * Wc * C, C, _lib.stream_ptr()),
-                       "mfr_nchw_to_rows")
+            _lib.call("mfr_nchw_to_rows", cDa.contiguous(), None, B, C, Hc * Wc, 0, rows, Hc * Wc * C, C)
         return self.convDb(rows).view(B, Hc, Wc, 256)
 
     @torch.no_grad()

@@ -42,7 +42,7 @@ class RangeGuard:
     def __enter__(self):
         if self.active:
             self.flag.zero_()
-            _lib.check(_lib.load().mfr_f16x2_guard_bind(self.flag.data_ptr()), "mfr_f16x2_guard_bind")
+            _lib.call("mfr_f16x2_guard_bind", self.flag.data_ptr())
         return self
 
     def __exit__(self, *exc):
@@ -57,7 +57,7 @@ class RangeGuard:
         class _Keep:
             def __enter__(self):
                 if g.active:
-                    _lib.check(_lib.load().mfr_f16x2_guard_bind(g.flag.data_ptr()), "mfr_f16x2_guard_bind")
+                    _lib.call("mfr_f16x2_guard_bind", g.flag.data_ptr())
 
             def __exit__(self, *exc):
                 return g.__exit__()

@@ -118,11 +118,10 @@ class DepthPngDecoder:
     def decode_device(self, headers, records, offsets, n, H, W, max_record, out, status):
         """the device half on tensors already on the device (headers u8 [n, HEADER_BYTES], records u8, offsets i64 [n + 1]), launched on
         torch's current stream; the scratch is marked as used by that stream"""
-        lib = _lib.load(require_gpu=True)
+        _lib.load(require_gpu=True)
         sc = self.scratch(n, H, W)
         cur = torch.cuda.current_stream(self.device)
-        _lib.check(lib.mfr_png_depth_decode(_lib.ptr(headers), _lib.ptr(records), _lib.ptr(offsets), n, H, W, int(max_record), _lib.ptr(sc),
-                                            sc.numel(), _lib.ptr(out), _lib.ptr(status), cur.cuda_stream), "mfr_png_depth_decode")
+        _lib.call("mfr_png_depth_decode", headers, records, offsets, n, H, W, int(max_record), sc, sc.numel(), out, status, stream=cur.cuda_stream)
         sc.record_stream(cur)
 
     def decode(self, files, out=None):

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .._lib import check, load, ptr, stream_ptr
+from .._lib import call, load
 from .encoder import PreActBlock
 
 
@@ -21,7 +21,7 @@ class _CorrWarp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, v, grid):
-        lib = load(require_gpu=True)
+        load(require_gpu=True)
         if not (q.is_cuda and k.is_cuda and v.is_cuda):
             raise RuntimeError("correlation-volume warping runs on the HIP device only (no CPU fallback)")
         q, k, v = (t.detach().float().contiguous() for t in (q, k, v))
@@ -32,8 +32,7 @@ class _CorrWarp(torch.autograd.Function):
         warped = torch.empty_like(v)
         pos = torch.empty(B, 2 if g is not None else 0, N, device=v.device, dtype=torch.float32)
         stats = torch.empty(3, B, N, device=v.device, dtype=torch.float32)      # max_score, row_max, row_sum
-        check(lib.mfr_corr_warp_fwd(ptr(q), ptr(k), ptr(v), ptr(g), B, Dq, N, ptr(warped), ptr(pos) if g is not None else None,
-                                    ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), stream_ptr()), "mfr_corr_warp_fwd")
+        call("mfr_corr_warp_fwd", q, k, v, g, B, Dq, N, warped, pos if g is not None else None, stats[0], stats[1], stats[2])
         ctx.save_for_backward(q, k, v, g, warped, pos, stats)
         return warped, pos, stats[0]
 
@@ -41,7 +40,7 @@ class _CorrWarp(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_warped, d_pos, d_max):
         q, k, v, g, warped, pos, stats = ctx.saved_tensors
-        lib = load(require_gpu=True)
+        load(require_gpu=True)
         B, Dq, N = q.shape
         d_warped = torch.zeros_like(warped) if d_warped is None else d_warped.float().contiguous()
         delta = (d_warped * warped).sum(1)
@@ -55,8 +54,7 @@ class _CorrWarp(torch.autograd.Function):
             delta = delta + d_max * stats[0]
         delta = delta.contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        check(lib.mfr_corr_warp_bwd(ptr(q), ptr(k), ptr(v), ptr(g), B, Dq, N, ptr(d_warped), ptr(d_pos), ptr(d_max), ptr(delta),
-                                    ptr(stats[1]), ptr(stats[2]), ptr(dq), ptr(dk), ptr(dv), stream_ptr()), "mfr_corr_warp_bwd")
+        call("mfr_corr_warp_bwd", q, k, v, g, B, Dq, N, d_warped, d_pos, d_max, delta, stats[1], stats[2], dq, dk, dv)
         return dq, dk, dv, None
 
 

@@ -57,12 +57,10 @@ def _table(key, dev, make):
 def seg_gemm(A, a_off, sA, segA, Bm, b_off, sB, segB, Lk, nkc_total, nkc_z, bias, C, ldc, M, N, nz=1, zA=None, zB=None, zC=None, zk=None):
     """C[i, j] (+ slices) = sum_k A[i, k] B[j, k]; see include/mfr_hip.h (mfr_conv_gemm_bf16).  A, Bm: flat bf16 tensors, a_off / b_off:
     element offsets of their logical origins; C: flat bf16 or f32 tensor.  Device tensors only -- there is no CPU path."""
-    from .._lib import check, load, ptr, stream_ptr
-    lib = load(require_gpu=True)
-    p = lambda t: ptr(t) if t is not None else None
-    check(lib.mfr_conv_gemm_bf16(A.data_ptr() + 2 * a_off, sA, ptr(segA), Bm.data_ptr() + 2 * b_off, sB, ptr(segB), Lk, nkc_total, nkc_z,
-                                 p(bias), ptr(C), ldc, 1 if C.dtype == torch.bfloat16 else 0, M, N, nz, p(zA), p(zB), p(zC), p(zk),
-                                 stream_ptr()), "mfr_conv_gemm_bf16")
+    from .._lib import call, load
+    load(require_gpu=True)
+    call("mfr_conv_gemm_bf16", A.data_ptr() + 2 * a_off, sA, segA, Bm.data_ptr() + 2 * b_off, sB, segB, Lk, nkc_total, nkc_z,
+         bias, C, ldc, 1 if C.dtype == torch.bfloat16 else 0, M, N, nz, zA, zB, zC, zk)
 
 
 def _src(x):
@@ -73,25 +71,24 @@ def _src(x):
 def pack_nhwc_halo(x, guard_rows, Wp):
     """x [B, C, H, W] -> flat bf16  guard_rows * C zeros | haloed NHWC image [B, H+2, Wp, C] | guard_rows * C zeros  (one kernel,
     transposing through LDS; csrc/conv_gemm_bf16.hip).  Wp = W + 1: one zero column in front of every row, shared with the row before"""
-    from .._lib import check, load, ptr, stream_ptr
-    lib = load(require_gpu=True)
+    from .._lib import call, load
+    load(require_gpu=True)
     x = _src(x)
     B, C, H, W = x.shape
     out = torch.empty((2 * guard_rows + B * (H + 2) * Wp) * C, dtype=torch.bfloat16, device=x.device)
-    check(lib.mfr_conv_pack_nhwc_halo(ptr(x), 0 if x.dtype == torch.float32 else 1, B, C, H, W, Wp, ptr(out), guard_rows, stream_ptr()), "mfr_conv_pack_nhwc_halo")
+    call("mfr_conv_pack_nhwc_halo", x, 0 if x.dtype == torch.float32 else 1, B, C, H, W, Wp, out, guard_rows)
     return out
 
 
 def pack_cm_halo(x, Wq, L, ncopies, first_shift, slack):
     """x [B, C, H, W] -> [ncopies, slack + B C L + slack] bf16: channel-major haloed images (rows of Wq positions), copy k shifted by
     first_shift + k positions along its rows"""
-    from .._lib import check, load, ptr, stream_ptr
-    lib = load(require_gpu=True)
+    from .._lib import call, load
+    load(require_gpu=True)
     x = _src(x)
     B, C, H, W = x.shape
     out = torch.empty(ncopies, 2 * slack + B * C * L, dtype=torch.bfloat16, device=x.device)
-    check(lib.mfr_conv_pack_cm_halo(ptr(x), 0 if x.dtype == torch.float32 else 1, B * C, H, W, Wq, L, ncopies, first_shift, slack, ptr(out), stream_ptr()),
-          "mfr_conv_pack_cm_halo")
+    call("mfr_conv_pack_cm_halo", x, 0 if x.dtype == torch.float32 else 1, B * C, H, W, Wq, L, ncopies, first_shift, slack, out)
     return out
 
 
@@ -115,10 +112,10 @@ def tap_tables(C, Wp, dev, order=None):
 
 def unpack_nchw(haloed, B, N, H, W, Wp):
     """haloed NHWC result [B, H+2, Wp, N] bf16 -> contiguous [B, N, H, W] bf16 (one transposing kernel)"""
-    from .._lib import check, load, ptr, stream_ptr
-    lib = load(require_gpu=True)
+    from .._lib import call, load
+    load(require_gpu=True)
     y = torch.empty(B, N, H, W, dtype=torch.bfloat16, device=haloed.device)
-    check(lib.mfr_conv_unpack_nchw(ptr(haloed), B, N, H, W, Wp, ptr(y), stream_ptr()), "mfr_conv_unpack_nchw")
+    call("mfr_conv_unpack_nchw", haloed, B, N, H, W, Wp, y)
     return y
 
 

@@ -152,13 +152,12 @@ class _UpsampleAC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, Ho, Wo):
-        from .._lib import check, load, ptr, stream_ptr
-        lib = load(require_gpu=True)
+        from .._lib import call, load
+        load(require_gpu=True)
         x = x.contiguous()
         B, C, H, W = x.shape
         out = torch.empty(B, C, Ho, Wo, dtype=x.dtype, device=x.device)
-        check(lib.mfr_upsample_bilinear(ptr(x), ptr(out), B * C, H, W, Ho, Wo, 0 if x.dtype == torch.float32 else 1, stream_ptr()),
-              "mfr_upsample_bilinear")
+        call("mfr_upsample_bilinear", x, out, B * C, H, W, Ho, Wo, 0 if x.dtype == torch.float32 else 1)
         ctx.in_shape = tuple(x.shape)
         return out
 

@@ -14,22 +14,23 @@ class _KabschRotation(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, H):
-        from .._lib import check, load, ptr, stream_ptr
-        lib = load(require_gpu=True)
+        from .._lib import call, load
+        load(require_gpu=True)
         H = H.detach().float().contiguous()
         R = torch.empty_like(H)
-        check(lib.mfr_kabsch_fwd(ptr(H), H.shape[0], ptr(R), stream_ptr()), "mfr_kabsch_fwd")
+        call("mfr_kabsch_fwd", H, H.shape[0], R)
         ctx.save_for_backward(H)
         return R
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gR):
-        from .._lib import check, load, ptr, stream_ptr
+        from .._lib import call, load
+        load(require_gpu=True)
         (H,) = ctx.saved_tensors
         gR = gR.float().contiguous()
         gH = torch.empty_like(H)
-        check(load(require_gpu=True).mfr_kabsch_bwd(ptr(H), ptr(gR), H.shape[0], ptr(gH), stream_ptr()), "mfr_kabsch_bwd")
+        call("mfr_kabsch_bwd", H, gR, H.shape[0], gH)
         return gH
 
 

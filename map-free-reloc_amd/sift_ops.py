@@ -81,7 +81,7 @@ class SiftDetector:
         return ws[off:off + 4 * B * ho.value * wo.value].view(torch.float32).view(B, ho.value, wo.value)
 
     def __call__(self, gray):
-        lib = _lib.load(require_gpu=True)
+        _lib.load(require_gpu=True)
         if not (isinstance(gray, torch.Tensor) and gray.is_cuda):
             gray = torch.as_tensor(np.asarray(gray))
             gray = gray.to(self.device)
@@ -104,9 +104,7 @@ class SiftDetector:
         octave = torch.zeros(B, N, dtype=torch.int32, device=dev)
         n = torch.zeros(B, dtype=torch.int32, device=dev)
         status = torch.zeros(B, dtype=torch.int32, device=dev)
-        _lib.check(lib.mfr_sift_detect(_lib.ptr(gray), B, H, W, self.nfeatures, N, self.cand_cap, _lib.ptr(ws), ws.numel(),
-                                       _lib.ptr(kpts), _lib.ptr(desc), _lib.ptr(size), _lib.ptr(angle), _lib.ptr(response),
-                                       _lib.ptr(octave), _lib.ptr(n), _lib.ptr(status), _lib.stream_ptr()), "mfr_sift_detect")
+        _lib.call("mfr_sift_detect", gray, B, H, W, self.nfeatures, N, self.cand_cap, ws, ws.numel(), kpts, desc, size, angle, response, octave, n, status)
         return dict(kpts=kpts, desc=desc, n=n, size=size, angle=angle, response=response, octave=octave, status=status)
 
     def per_image(self, gray_u8):

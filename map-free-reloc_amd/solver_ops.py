@@ -68,17 +68,17 @@ class _Workspace:
 
 def depth_min_partials(depth):
     """[B,H,W] f32 -> [B,16] partial minima (pose_solver.py:196 depth_0.min())."""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     depth = _chk(depth, torch.float32, "depth")
     B, H, W = depth.shape
     out = torch.empty(B, NSEG, dtype=torch.float32, device=depth.device)
-    _lib.check(lib.mfr_depth_min(_lib.ptr(depth), B, H, W, _lib.ptr(out), _lib.stream_ptr()), "mfr_depth_min")
+    _lib.call("mfr_depth_min", depth, B, H, W, out)
     return out
 
 
 def pnp_lift(pts0, pts1, n_corr, depth0, K0):
     """pose_solver.py:186-206: returns xyz [B,maxN,3] f64, obs [B,maxN,2] f64, src_idx, n_valid."""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     pts0, pts1, n_corr, B, maxN, dev = _chk_corr(pts0, pts1, n_corr)
     depth0 = _chk(depth0, torch.float32, "depth0")
     K0, _, kdt = _chk_K(K0)
@@ -88,16 +88,14 @@ def pnp_lift(pts0, pts1, n_corr, depth0, K0):
     obs = torch.zeros(B, maxN, 2, dtype=torch.float64, device=dev)
     src = torch.zeros(B, maxN, dtype=torch.int32, device=dev)
     nv = torch.zeros(B, dtype=torch.int32, device=dev)
-    _lib.check(lib.mfr_pnp_lift(_lib.ptr(pts0), _lib.ptr(pts1), _lib.ptr(n_corr), B, maxN, _lib.ptr(depth0),
-                                _lib.ptr(part), H, W, _lib.ptr(K0), kdt, _lib.ptr(xyz), _lib.ptr(obs), _lib.ptr(src),
-                                _lib.ptr(nv), _lib.stream_ptr()), "mfr_pnp_lift")
+    _lib.call("mfr_pnp_lift", pts0, pts1, n_corr, B, maxN, depth0, part, H, W, K0, kdt, xyz, obs, src, nv)
     return xyz, obs, src, nv
 
 
 def pnp_ransac(xyz, obs, n_valid, K1, pair_ids, max_iters=1000, thr=3.0, conf=0.9999, seed=0):
     """cv.solvePnPRansac(P3P) + refit + ITERATIVE refinement restatement (pose_solver.py:209-235)
     on already lifted points.  Returns dict(R, t, n_inliers, status, mask, best_iter, iters_run, counts)."""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     xyz = _chk(xyz, torch.float64, "xyz"); obs = _chk(obs, torch.float64, "obs")
     n_valid = _chk(n_valid, torch.int32, "n_valid"); K1, _, kdt = _chk_K(K1)
     pair_ids = _chk(pair_ids, torch.int64, "pair_ids")
@@ -108,10 +106,8 @@ def pnp_ransac(xyz, obs, n_valid, K1, pair_ids, max_iters=1000, thr=3.0, conf=0.
     R, t, ni, st = _pose_out(B, dev)
     mask = torch.empty(B, maxN, dtype=torch.uint8, device=dev)
     bi, ir = _i32(dev, B), _i32(dev, B)
-    _lib.check(lib.mfr_pnp_ransac(_lib.ptr(xyz), _lib.ptr(obs), _lib.ptr(n_valid), B, maxN, _lib.ptr(K1), kdt, max_iters,
-                                  float(thr), float(conf), int(seed), _lib.ptr(pair_ids), _lib.ptr(counts),
-                                  _lib.ptr(inl), _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(st), _lib.ptr(mask),
-                                  _lib.ptr(bi), _lib.ptr(ir), _lib.stream_ptr()), "mfr_pnp_ransac")
+    _lib.call("mfr_pnp_ransac", xyz, obs, n_valid, B, maxN, K1, kdt, max_iters, float(thr), float(conf), int(seed), pair_ids,
+              counts, inl, R, t, ni, st, mask, bi, ir)
     return dict(R=R, t=t, n_inliers=ni, status=st, mask=mask, best_iter=bi, iters_run=ir, counts=counts)
 
 
@@ -134,11 +130,8 @@ class PnPBatchSolver(_Workspace):
         ws = self._ws(lib.mfr_pnp_workspace_bytes(B, maxN, self.max_iters), dev)
         R, t, ni, st = _pose_out(B, dev)
         mask = torch.empty(B, maxN, dtype=torch.uint8, device=dev) if want_mask else None
-        _lib.check(lib.mfr_pnp_solve_batch(
-            _lib.ptr(pts0), _lib.ptr(pts1), _lib.ptr(n_corr), B, maxN, _lib.ptr(depth0), H, W, _lib.ptr(K0),
-            _lib.ptr(K1), kdt, self.max_iters, self.reproj_thr, self.confidence, self.seed, _lib.ptr(pair_ids),
-            _lib.ptr(ws), ws.numel(), _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(st),
-            _lib.ptr(mask), _lib.stream_ptr()), "mfr_pnp_solve_batch")
+        _lib.call("mfr_pnp_solve_batch", pts0, pts1, n_corr, B, maxN, depth0, H, W, K0, K1, kdt, self.max_iters, self.reproj_thr,
+                  self.confidence, self.seed, pair_ids, ws, ws.numel(), R, t, ni, st, mask)
         out = dict(R=R, t=t, n_inliers=ni, status=st)
         if want_mask:
             out["mask"] = mask
@@ -159,7 +152,7 @@ def rig_rows(rig_T):
 def rig_pnp_ransac(xyz, obs, n_valid, K1, rig, pair_ids, max_iters=1000, thr=3.0, conf=0.9999, seed=0):
     """The rig solver on already lifted rows (csrc/pnp_rig.hip): xyz [B,T,maxN,3], obs [B,T,maxN,2], n_valid [B,T], K1 [B,T,3,3],
     rig [B,T,12] f64 (rig_rows).  Returns dict(R, t, n_inliers, status, mask [B,T,maxN], best_iter, iters_run, counts)."""
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     xyz = _chk(xyz, torch.float64, "xyz"); obs = _chk(obs, torch.float64, "obs")
     n_valid = _chk(n_valid, torch.int32, "n_valid"); K1, _, kdt = _chk_K(K1)
     rig = _chk(rig, torch.float64, "rig"); pair_ids = _chk(pair_ids, torch.int64, "pair_ids")
@@ -172,10 +165,8 @@ def rig_pnp_ransac(xyz, obs, n_valid, K1, rig, pair_ids, max_iters=1000, thr=3.0
     R, t, ni, st = _pose_out(B, dev)
     mask = torch.empty(B, T, maxN, dtype=torch.uint8, device=dev)
     bi, ir = _i32(dev, B), _i32(dev, B)
-    _lib.check(lib.mfr_rig_pnp_ransac(_lib.ptr(xyz), _lib.ptr(obs), _lib.ptr(n_valid), B, T, maxN, _lib.ptr(K1), kdt, _lib.ptr(rig),
-                                      max_iters, float(thr), float(conf), int(seed), _lib.ptr(pair_ids), _lib.ptr(counts),
-                                      _lib.ptr(inl), _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(st), _lib.ptr(mask),
-                                      _lib.ptr(bi), _lib.ptr(ir), _lib.stream_ptr()), "mfr_rig_pnp_ransac")
+    _lib.call("mfr_rig_pnp_ransac", xyz, obs, n_valid, B, T, maxN, K1, kdt, rig, max_iters, float(thr), float(conf), int(seed), pair_ids,
+              counts, inl, R, t, ni, st, mask, bi, ir)
     return dict(R=R, t=t, n_inliers=ni, status=st, mask=mask, best_iter=bi, iters_run=ir, counts=counts)
 
 
@@ -212,11 +203,8 @@ class RigPnPBatchSolver(_Workspace):
         ws = self._ws(lib.mfr_rig_pnp_workspace_bytes(B, T, maxN, self.max_iters), dev)
         R, t, ni, st = _pose_out(B, dev)
         mask = torch.empty(B, T, maxN, dtype=torch.uint8, device=dev) if want_mask else None
-        _lib.check(lib.mfr_rig_pnp_solve_batch(
-            _lib.ptr(pts0), _lib.ptr(pts1), _lib.ptr(n_corr), B, T, maxN, _lib.ptr(depth0), H, W, _lib.ptr(K0),
-            _lib.ptr(K1), kdt, _lib.ptr(rig), self.max_iters, self.reproj_thr, self.confidence, self.seed, _lib.ptr(pair_ids),
-            _lib.ptr(ws), ws.numel(), _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(st),
-            _lib.ptr(mask), _lib.stream_ptr()), "mfr_rig_pnp_solve_batch")
+        _lib.call("mfr_rig_pnp_solve_batch", pts0, pts1, n_corr, B, T, maxN, depth0, H, W, K0, K1, kdt, rig, self.max_iters, self.reproj_thr,
+                  self.confidence, self.seed, pair_ids, ws, ws.numel(), R, t, ni, st, mask)
         out = dict(R=R, t=t, n_inliers=ni, status=st)
         if want_mask:
             out["mask"] = mask
@@ -231,7 +219,7 @@ def magsac_lut_host(M=MAGSAC_LUT_M):
     """[M + 1, 2] float64 (normalised MAGSAC++ loss, IRLS weight) over r^2 / cut in [0, 1]: mfr_magsac_lut (host code of the library)"""
     import numpy as np
     t = np.zeros((M + 1, 2), dtype=np.float64)
-    _lib.check(_lib.load().mfr_magsac_lut(t.ctypes.data, M), "mfr_magsac_lut")
+    _lib.call("mfr_magsac_lut", t.ctypes.data, M)
     return t
 
 
@@ -268,12 +256,8 @@ class EssentialBatchSolver(_Workspace):
         if diagnostics:
             bi, ir, lo, cnt = _i32(dev, B), _i32(dev, B), _i32(dev, B), _i32(dev, B, self.max_iters)
             los = torch.zeros(B, self.max_iters, dtype=torch.float64, device=dev)
-        _lib.check(lib.mfr_emat_solve_batch(
-            _lib.ptr(pts0), _lib.ptr(pts1), _lib.ptr(n_corr), B, maxN, _lib.ptr(K0), _lib.ptr(K1), kdt, self.pix_thr,
-            self.confidence, self.max_iters, self.seed, _lib.ptr(pair_ids), self.score, _lib.ptr(lut), MAGSAC_LUT_M,
-            self.max_thr_ratio, _lib.ptr(ws), ws.numel(),
-            _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(st), _lib.ptr(mask), _lib.ptr(bi), _lib.ptr(ir),
-            _lib.ptr(cnt), _lib.ptr(los), _lib.ptr(lo), _lib.stream_ptr()), "mfr_emat_solve_batch")
+        _lib.call("mfr_emat_solve_batch", pts0, pts1, n_corr, B, maxN, K0, K1, kdt, self.pix_thr, self.confidence, self.max_iters, self.seed,
+                  pair_ids, self.score, lut, MAGSAC_LUT_M, self.max_thr_ratio, ws, ws.numel(), R, t, ni, st, mask, bi, ir, cnt, los, lo)
         out = dict(R=R, t=t, n_inliers=ni, status=st, mask=mask)
         if diagnostics:
             out.update(best_iter=bi, iters_run=ir, counts=cnt, losses=los, lo_runs=lo)
@@ -299,11 +283,8 @@ class ProcrustesBatchSolver(_Workspace):
         bi = ir = cnt = None
         if diagnostics:
             bi, ir, cnt = _i32(dev, B), _i32(dev, B), _i32(dev, B, self.max_iters)
-        _lib.check(lib.mfr_procrustes_solve_batch(
-            _lib.ptr(pts0), _lib.ptr(pts1), _lib.ptr(n_corr), B, maxN, _lib.ptr(depth0), _lib.ptr(depth1), H, W, _lib.ptr(K0),
-            _lib.ptr(K1), kdt, self.max_corr_dist, self.confidence, self.max_iters, self.seed, _lib.ptr(pair_ids),
-            _lib.ptr(ws), ws.numel(), _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(st), _lib.ptr(bi),
-            _lib.ptr(ir), _lib.ptr(cnt), _lib.stream_ptr()), "mfr_procrustes_solve_batch")
+        _lib.call("mfr_procrustes_solve_batch", pts0, pts1, n_corr, B, maxN, depth0, depth1, H, W, K0, K1, kdt, self.max_corr_dist,
+                  self.confidence, self.max_iters, self.seed, pair_ids, ws, ws.numel(), R, t, ni, st, bi, ir, cnt)
         out = dict(R=R, t=t, n_inliers=ni, status=st)
         if diagnostics:
             out.update(best_iter=bi, iters_run=ir, counts=cnt)
@@ -330,10 +311,8 @@ class ProcrustesIcpRefine(_Workspace):
         ws = self._ws(lib.mfr_procrustes_icp_workspace_bytes(B, H, W), dev)
         ni, it = _i32(dev, B), _i32(dev, B)
         fit = torch.empty(B, dtype=torch.float64, device=dev); rm = torch.empty(B, dtype=torch.float64, device=dev)
-        _lib.check(lib.mfr_procrustes_icp_refine(_lib.ptr(depth0), _lib.ptr(depth1), B, H, W, _lib.ptr(K0), _lib.ptr(K1), kdt, self.max_corr_dist,
-                                                 self.rel_fitness, self.rel_rmse, self.max_iter, _lib.ptr(status), _lib.ptr(ws),
-                                                 ws.numel(), _lib.ptr(R), _lib.ptr(t), _lib.ptr(ni), _lib.ptr(fit), _lib.ptr(rm),
-                                                 _lib.ptr(it), _lib.stream_ptr()), "mfr_procrustes_icp_refine")
+        _lib.call("mfr_procrustes_icp_refine", depth0, depth1, B, H, W, K0, K1, kdt, self.max_corr_dist, self.rel_fitness, self.rel_rmse,
+                  self.max_iter, status, ws, ws.numel(), R, t, ni, fit, rm, it)
         return dict(R=R, t=t, n_inliers=ni, fitness=fit, rmse=rm, iters=it)
 
 
@@ -358,43 +337,37 @@ class ScaleFromDepthBatch(_Workspace):
         tm = torch.empty(B, 3, dtype=torch.float64, device=dev)
         bs = torch.empty(B, dtype=torch.float64, device=dev)
         ni, st = _i32(dev, B), _i32(dev, B)
-        _lib.check(lib.mfr_scale_from_depth_batch(
-            _lib.ptr(pts0), _lib.ptr(pts1), _lib.ptr(emat_mask), _lib.ptr(n_corr), B, maxN, _lib.ptr(depth0),
-            _lib.ptr(depth1), H, W, _lib.ptr(K0), _lib.ptr(K1), kdt, _lib.ptr(R), _lib.ptr(t), _lib.ptr(in_status),
-            self.scale_thr, _lib.ptr(ws), ws.numel(), _lib.ptr(tm), _lib.ptr(bs), _lib.ptr(ni),
-            _lib.ptr(st), _lib.stream_ptr()), "mfr_scale_from_depth_batch")
+        _lib.call("mfr_scale_from_depth_batch", pts0, pts1, emat_mask, n_corr, B, maxN, depth0, depth1, H, W, K0, K1, kdt, R, t, in_status,
+                  self.scale_thr, ws, ws.numel(), tm, bs, ni, st)
         return dict(t_metric=tm, best_scale=bs, n_inliers=ni, status=st)
 
 
 def test_f64_ops(a, b, c):
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     a = _chk(a, torch.float64, "a"); b = _chk(b, torch.float64, "b"); c = _chk(c, torch.float64, "c")
     out = torch.empty(a.numel(), 3, dtype=torch.float64, device=a.device)
-    _lib.check(lib.mfr_test_f64_ops(_lib.ptr(a), _lib.ptr(b), _lib.ptr(c), a.numel(), _lib.ptr(out),
-                                    _lib.stream_ptr()), "mfr_test_f64_ops")
+    _lib.call("mfr_test_f64_ops", a, b, c, a.numel(), out)
     return out
 
 
 def test_sample(seed, pair_ids, iters, n, k):
-    lib = _lib.load(require_gpu=True)
+    _lib.load(require_gpu=True)
     pair_ids = _chk(pair_ids, torch.int64, "pair_ids")
     B = pair_ids.numel()
     out = torch.empty(B, iters, k, dtype=torch.int32, device=pair_ids.device)
-    _lib.check(lib.mfr_test_sample(int(seed), _lib.ptr(pair_ids), B, iters, n, k, _lib.ptr(out), _lib.stream_ptr()),
-               "mfr_test_sample")
+    _lib.call("mfr_test_sample", int(seed), pair_ids, B, iters, n, k, out)
     return out
 
 
 def test_replay_counts(counts, n, conf, model_points):
     """ransac_replay_counts (csrc/solver_dev.h) alone: counts [B,max_iters] i32 -> [B,3] i32 (best, bit, run).  A test hook the public
-    header does not declare, so it is bound here."""
+    header does not declare, so _lib binds no signature for it: every argument is converted here (int status returned, ctypes' default)."""
     import ctypes as C
     lib = _lib.load(require_gpu=True)
-    fn = lib.mfr_test_replay_counts
-    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
     counts = _chk(counts, torch.int32, "counts")
     B, max_iters = counts.shape
     out = _i32(counts.device, B, 3)
-    _lib.check(fn(_lib.ptr(counts), B, max_iters, int(n), float(conf), int(model_points), _lib.ptr(out), _lib.stream_ptr()),
-               "mfr_test_replay_counts")
+    vp = C.c_void_p
+    _lib.check(lib.mfr_test_replay_counts(vp(_lib.ptr(counts)), C.c_int(B), C.c_int(max_iters), C.c_int(int(n)), C.c_double(conf),
+                                          C.c_int(int(model_points)), vp(_lib.ptr(out)), vp(_lib.stream_ptr())), "mfr_test_replay_counts")
     return out
