@@ -248,6 +248,45 @@ int mfr_emat_solve_batch(const float *pts0, const float *pts1, const int32_t *n_
                          void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Rig essential-matrix path (additive; csrc/emat_rig.hip): ONE METRIC pose for a window of T query frames without any depth map,
+ * POSE_SOLVER 'RigEssentialMatrix' of the multi-frame model.  The rig's known metric baselines make the scale observable (Clipp et
+ * al. 2008).  Upstream has no such solver.  Model, rig rows and row layout as the rig PnP path: (R, t) reference -> LAST window frame;
+ * rig [B,T,12] f64; frame j of sample b is row b*T + j of pts0 / pts1 / n_corr / K1 ([B*T,3,3]) and of stage 1's outputs; K0 [B,3,3]
+ * belongs to the one reference view of a sample.  1 <= T <= 16.
+ *   Stage 1 = mfr_emat_solve_batch over the B*T rows (K0 repeated per row, RANSAC key pair_id*T + j): R1 [B*T,9], t1 [B*T,3] unit,
+ *   n_inliers1, status1 [B*T], mask1 [B*T,maxN], device memory.
+ *   Stage 2 = mfr_rig_emat_solve, deterministic.  T = 1: stage 1's row passes through bit for bit (unit translation).  Usable frames:
+ *   status1 OK; T > 1 and fewer than two -> MFR_ST_NO_MODEL (or the frames' common failure status when none is usable), NaN pose, 0
+ *   inliers.  Hypothesis h = 2*pair + {0, 1} over the unordered pairs (j < k) of usable frames in combinations order (rotation of j,
+ *   then of k): R_h = R_Am^T R1_m, t_h = least-squares intersection of the two frames' translation directions, u_f x (R_Af t + t_Af) = 0
+ *   (3x3 normal equations M t = -c by cofactors).  Skipped (count -1): det M <= 1e-6 (tr M / 3)^3 (directions within ~1e-3 rad of
+ *   parallel, e.g. zero baseline), or (R_Af t + t_Af) . u_f <= 0 for either frame.  Score: over ALL frames' correspondences, per frame
+ *   E_k = [t_k/|t_k|]x R_k of the composed model (|t_k| < 1e-12: the frame contributes nothing), a point counts when its squared Sampson
+ *   distance < thr2_k (the single-frame path's threshold and K-normalisation, per frame, in K's dtype) and cheirality holds; the largest
+ *   pooled count wins, the first on a tie; none scored -> MFR_ST_NO_MODEL.  Refine: with >= 6 pooled inliers Levenberg-Marquardt over the
+ *   six pose parameters on the signed Sampson residuals (each through its frame's rig row; translation not renormalised; the schedule of
+ *   the single-frame COUNT-score polish), then re-score: n_inliers and inlier_mask [B*T,maxN] are that pooled set.  Non-finite pose or
+ *   |t| > 1000 -> MFR_ST_DEGENERATE.
+ * mfr_rig_emat_solve_batch runs both stages from raw correspondences, no host synchronisation between them (arguments of
+ * mfr_emat_solve_batch).  hyp_counts [B, T*(T-1)] (T > 1) and best_hyp [B] (-1: none / T = 1) are optional diagnostics (NULL ok), as
+ * is inlier_mask.  Bad arguments (T < 1, T > 16, NULL pointers, workspace too small) return MFR_E_* and launch nothing.
+ * ------------------------------------------------------------------------------------------ */
+size_t mfr_rig_emat_workspace_bytes(int B, int T, int maxN);
+int mfr_rig_emat_solve(const float *pts0, const float *pts1, const int32_t *n_corr, int B, int T, int maxN,
+                       const void *K0, const void *K1, int k_dtype, const double *rig, double pix_thr,
+                       const double *R1, const double *t1, const int32_t *n_inliers1, const int32_t *status1, const uint8_t *mask1,
+                       void *workspace, size_t workspace_bytes,
+                       double *R, double *t, int32_t *n_inliers, int32_t *status, uint8_t *inlier_mask /*may be NULL*/,
+                       int32_t *hyp_counts, int32_t *best_hyp, void *stream);
+size_t mfr_rig_emat_batch_workspace_bytes(int B, int T, int maxN, int max_iters);
+int mfr_rig_emat_solve_batch(const float *pts0, const float *pts1, const int32_t *n_corr, int B, int T, int maxN,
+                             const void *K0, const void *K1, int k_dtype, const double *rig, double pix_thr, double confidence,
+                             int max_iters, uint64_t seed, const int64_t *pair_ids, int score_method, const double *magsac_lut, int lut_m,
+                             double max_thr_ratio, void *workspace, size_t workspace_bytes,
+                             double *R, double *t, int32_t *n_inliers, int32_t *status, uint8_t *inlier_mask /*may be NULL*/,
+                             int32_t *hyp_counts, int32_t *best_hyp, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Procrustes path: ProcrustesSolver.estimate_pose, lib/models/matching/pose_solver.py:238-320 with
  * PROCRUSTES.REFINE False (config/matching/mapfree/sg_procrustes_dptkitti.yaml; the optional ICP
  * refinement is mfr_procrustes_icp_refine below).  int-truncate both views (:248-249) -> depth gather (:256-258) -> valid vs each map's
@@ -262,6 +301,36 @@ int mfr_procrustes_solve_batch(const float *pts0, const float *pts1, const int32
                                double max_corr_dist, double confidence, int max_iters, uint64_t seed, const int64_t *pair_ids,
                                void *workspace, size_t workspace_bytes, double *R, double *t, int32_t *n_inliers,
                                int32_t *status, int32_t *best_iter, int32_t *iters_run, int32_t *counts_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Rig Procrustes path (additive; the rig entry point of csrc/procrustes.hip): ONE pose for a window of T query frames from 3-D/3-D
+ * correspondences, POSE_SOLVER 'RigProcrustes' of the multi-frame model.  Where the rig PnP path reads the reference view's depth map
+ * alone, this one reads all T + 1 maps.  Upstream has no such solver.
+ *   Model: (R, t) reference -> LAST window frame, as the rig PnP path; rig [B,T,12] f64 = R_Aj row-major then t_Aj
+ *   (A_j: last frame's camera -> frame j's camera; the last row is the identity).
+ *   Rows: frame j of sample b is row b*T + j of pts0 / pts1 / n_corr / K1 ([B*T,3,3]) / depth1 ([B*T,H,W]) / n_valid; depth0 [B,H,W]
+ *   and K0 [B,3,3] belong to the one reference view of a sample.  1 <= T <= 16.
+ *   Lift: as the Procrustes path per frame -- the reference pixel through depth0 / K0, the frame-j pixel through depth1[j] / K1[j], each
+ *   map compared against its own minimum (depth0's taken once per sample) -- then Q' = R_Aj^T (Q - t_Aj) carries the query point into
+ *   the last frame's camera.  Valid rows are compacted into ONE pooled list in (frame, index) order, N = sum of n_valid[j].
+ *   Solve: the Procrustes path's RANSAC on the pooled (P, Q'), the same kernels: hypothesis `it` is the Kabsch fit of
+ *   sample_distinct<3>(seed, pair_id, it, N) (the key is pair_id itself: pooled sampling has no frame draw), best = count then squared
+ *   error sum, confidence exit, final re-fit.  n_inliers = the pooled count after the re-fit.
+ *   Status: all correspondences of a sample count together: fewer than 3 -> MFR_ST_TOO_FEW, fewer than 3 valid -> MFR_ST_BAD_DEPTH
+ *   (NaN pose); no model -> the identity pose with 0 inliers and status OK, as the Procrustes path.
+ *   With T = 1 and the identity rig every output equals mfr_procrustes_solve_batch bit for bit.
+ * inlier_mask [B*T,maxN] u8 over ORIGINAL correspondence indices (the points n_inliers counts), n_valid [B*T], best_iter / iters_run
+ * [B], counts_out [B,max_iters] are optional (NULL ok).  Bad arguments (T < 1, T > 16, NULL pointers, workspace too small) return
+ * MFR_E_* and launch nothing.
+ * ------------------------------------------------------------------------------------------ */
+size_t mfr_rig_procrustes_workspace_bytes(int B, int T, int maxN, int max_iters);
+int mfr_rig_procrustes_solve_batch(const float *pts0, const float *pts1, const int32_t *n_corr, int B, int T, int maxN,
+                                   const float *depth0, const float *depth1, int H, int W,
+                                   const void *K0, const void *K1, int k_dtype, const double *rig,
+                                   double max_corr_dist, double confidence, int max_iters, uint64_t seed, const int64_t *pair_ids,
+                                   void *workspace, size_t workspace_bytes,
+                                   double *R, double *t, int32_t *n_inliers, int32_t *status, uint8_t *inlier_mask /*may be NULL*/,
+                                   int32_t *n_valid, int32_t *best_iter, int32_t *iters_run, int32_t *counts_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * SuperPoint post-processing.  Reference call site: SuperGlue_matcher.match,

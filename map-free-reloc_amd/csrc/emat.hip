@@ -36,33 +36,17 @@ __global__ void __launch_bounds__(256) emat_prep_kernel(
     const void *__restrict__ K0, const void *__restrict__ K1, int k_dtype, double pix_thr,
     double *__restrict__ x0, double *__restrict__ x1, double *__restrict__ thr2)
 {
-    // pose_solver.py:39-43 in the dtype K arrives in: numpy float32 arithmetic for a float32 K, float64 (keypoints widened) for
-    // the Map-free loader's float64 K; the threshold mean likewise
+    // emat_dev.h: emat_thr2 / emat_normalize, pose_solver.py:39-43 in the dtype K arrives in
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     int n = n_corr[b];
     if (n > maxN) n = maxN;
     const size_t o = ((size_t)b * maxN + i) * 2;
-    if (k_dtype == MFR_K_F32) {
-        const float *k0 = (const float *)K0 + 9 * b, *k1 = (const float *)K1 + 9 * b;
-        if (i == 0) {
-            const float m = (((k0[0] + k1[4]) + k0[4]) + k1[0]) / 4.0f;       // np.mean([fx0, fy1, fy0, fx1]) in f32
-            const double thr = pix_thr / (double)m;
-            thr2[b] = thr * thr;
-        }
-        if (i >= n) return;
-        x0[o] = (double)((pts0[o] - k0[2]) / k0[0]); x0[o + 1] = (double)((pts0[o + 1] - k0[5]) / k0[4]);
-        x1[o] = (double)((pts1[o] - k1[2]) / k1[0]); x1[o + 1] = (double)((pts1[o + 1] - k1[5]) / k1[4]);
-    } else {
-        const double *k0 = (const double *)K0 + 9 * b, *k1 = (const double *)K1 + 9 * b;
-        if (i == 0) {
-            const double m = (((k0[0] + k1[4]) + k0[4]) + k1[0]) / 4.0;
-            const double thr = pix_thr / m;
-            thr2[b] = thr * thr;
-        }
-        if (i >= n) return;
-        x0[o] = ((double)pts0[o] - k0[2]) / k0[0]; x0[o + 1] = ((double)pts0[o + 1] - k0[5]) / k0[4];
-        x1[o] = ((double)pts1[o] - k1[2]) / k1[0]; x1[o + 1] = ((double)pts1[o + 1] - k1[5]) / k1[4];
-    }
+    if (i == 0) thr2[b] = emat_thr2(K0, b, K1, b, k_dtype, pix_thr);
+    if (i >= n) return;
+    double x[4];
+    emat_normalize(pts0 + o, pts1 + o, K0, b, K1, b, k_dtype, x);
+    x0[o] = x[0]; x0[o + 1] = x[1];
+    x1[o] = x[2]; x1[o + 1] = x[3];
 }
 
 // grid (ceil(iters/64), B), one lane per hypothesis

@@ -8,6 +8,37 @@
 
 namespace mfr {
 
+// pose_solver.py:39-43 in the dtype K arrives in: numpy float32 arithmetic for a float32 K, float64 (keypoints widened) for the Map-free
+// loader's float64 K; the threshold mean likewise.  K0 row b0 / K1 row b1 (the rig solver has one K0 per sample, one K1 per frame).
+// thr^2 with thr = PIX_THRESHOLD / mean(fx0, fy1, fy0, fx1) (:43, Q8)
+MFR_DEV double emat_thr2(const void *K0, int b0, const void *K1, int b1, int k_dtype, double pix_thr)
+{
+    double thr;
+    if (k_dtype == MFR_K_F32) {
+        const float *k0 = (const float *)K0 + 9 * (size_t)b0, *k1 = (const float *)K1 + 9 * (size_t)b1;
+        const float m = (((k0[0] + k1[4]) + k0[4]) + k1[0]) / 4.0f;       // np.mean([fx0, fy1, fy0, fx1]) in f32
+        thr = pix_thr / (double)m;
+    } else {
+        const double *k0 = (const double *)K0 + 9 * (size_t)b0, *k1 = (const double *)K1 + 9 * (size_t)b1;
+        const double m = (((k0[0] + k1[4]) + k0[4]) + k1[0]) / 4.0;
+        thr = pix_thr / m;
+    }
+    return thr * thr;
+}
+// one correspondence p0 <-> p1 (pixels) K-normalised (:39-40): x = {x0, y0, x1, y1}
+MFR_DEV void emat_normalize(const float *p0, const float *p1, const void *K0, int b0, const void *K1, int b1, int k_dtype, double x[4])
+{
+    if (k_dtype == MFR_K_F32) {
+        const float *k0 = (const float *)K0 + 9 * (size_t)b0, *k1 = (const float *)K1 + 9 * (size_t)b1;
+        x[0] = (double)((p0[0] - k0[2]) / k0[0]); x[1] = (double)((p0[1] - k0[5]) / k0[4]);
+        x[2] = (double)((p1[0] - k1[2]) / k1[0]); x[3] = (double)((p1[1] - k1[5]) / k1[4]);
+    } else {
+        const double *k0 = (const double *)K0 + 9 * (size_t)b0, *k1 = (const double *)K1 + 9 * (size_t)b1;
+        x[0] = ((double)p0[0] - k0[2]) / k0[0]; x[1] = ((double)p0[1] - k0[5]) / k0[4];
+        x[2] = ((double)p1[0] - k1[2]) / k1[0]; x[3] = ((double)p1[1] - k1[5]) / k1[4];
+    }
+}
+
 MFR_DEV double sampson2(const double *E, double a, double b, double c, double d)
 {
     const double Ex0 = (E[0] * a + E[1] * b) + E[2], Ex1 = (E[3] * a + E[4] * b) + E[5], Ex2 = (E[6] * a + E[7] * b) + E[8];

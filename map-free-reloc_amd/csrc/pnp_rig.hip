@@ -32,6 +32,7 @@
 #include "zero_fill.h"
 #include "solver_dev.h"
 #include "pnp_dev.h"
+#include "rig_dev.h"
 
 using namespace mfr;
 
@@ -41,26 +42,7 @@ using namespace mfr;
 #define RIG_FRAME_CTR 0x80000000u
 
 // ------------------------------------------------------------------------------------------
-// (R, t) reference -> last frame, seen from frame j: Rc = R_A R, tc = R_A t + t_A.  A = {R_A row-major, t_A}.
-MFR_DEV void rig_compose(const double *A, const double *R, const double *t, double *Rc, double *tc)
-{
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) Rc[3 * i + c] = (A[3 * i] * R[c] + A[3 * i + 1] * R[3 + c]) + A[3 * i + 2] * R[6 + c];
-    rot_apply(A, A + 9, t, tc);
-}
-// (R', t') reference -> frame j carried to the last frame: R = R_A^T R', t = R_A^T (t' - t_A)
-MFR_DEV void rig_to_last(const double *A, const double *Rp, const double *tp, double *R, double *t)
-{
-    const double d[3] = { tp[0] - A[9], tp[1] - A[10], tp[2] - A[11] };
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) R[3 * i + c] = (A[i] * Rp[c] + A[3 + i] * Rp[3 + c]) + A[6 + i] * Rp[6 + c];
-        t[i] = (A[i] * d[0] + A[3 + i] * d[1]) + A[6 + i] * d[2];
-    }
-}
+// rig_compose / rig_to_last: rig_dev.h
 
 // what both kernels know about sample b
 struct RigSample {
@@ -351,8 +333,6 @@ __global__ void rig_mask_scatter_kernel(const uint8_t *mask_valid, const int32_t
 // C-ABI
 extern "C" {
 
-#define MFR_RIG_MAX_T 16
-
 static size_t rig_hyp_smem_bytes(void)
 {
     return (size_t)(24 * HYP_BLOCK + 5 * PT_TILE) * sizeof(double) + 2 * HYP_BLOCK * sizeof(int);
@@ -373,12 +353,6 @@ static int rig_launch_ransac(const double *xyz, const double *obs, const int32_t
                        iters_run);
     CHECK_LAUNCH();
     return 0;
-}
-
-// B T maxN must index as int (the pooled index j maxN + i and the rows do)
-static bool rig_dims_ok(int B, int T, int maxN)
-{
-    return B > 0 && T >= 1 && T <= MFR_RIG_MAX_T && maxN > 0 && (long long)B * T * maxN <= 0x7fffffffLL / 3;
 }
 
 int mfr_rig_pnp_ransac(const double *xyz, const double *obs, const int32_t *n_valid, int B, int T, int maxN,

@@ -8,8 +8,10 @@ entries, so a new correspondence source or solver is one `register_*` call.  Bat
 
 FeatureMatchingMultiFrameModel (MODEL: 'FeatureMatchingMultiFrame') is the matching family's consumer of multi-frame samples
 (DATASET.QUERY_FRAME_COUNT > 1, datasets.MapFreeSceneMultiFrame): the reference view is matched against all T window frames and ONE
-pose is solved for the rig the device-tracking poses make of them (csrc/pnp_rig.hip).  The reference has no counterpart: its only
-multi-frame consumer, RegressionMultiFrameModel, regresses against the last frame.
+pose is solved for the rig the device-tracking poses make of them: POSE_SOLVER 'PNP' (alias 'RigPNP', csrc/pnp_rig.hip: depth on the
+reference side), 'RigProcrustes' (the rig entry point of csrc/procrustes.hip: depth on both sides, all T + 1 maps) or 'RigEssentialMatrix'
+(csrc/emat_rig.hip: no depth, the rig's baselines fix the scale).  The reference has no counterpart: its only multi-frame consumer,
+RegressionMultiFrameModel, regresses against the last frame.
 """
 import numpy as np
 import torch
@@ -82,15 +84,23 @@ class FeatureMatchingMultiFrameModel(torch.nn.Module):
     The T pairs (reference, frame j) go through the batched matcher stage of pipeline.FusedPosePipeline as one batch: interleaved [2T,1,H,W]
     gray planes with T equal `ref_keys`, so SuperPoint / LoFTR's backbone runs once on the reference view (HIP.REF_FEATURE_CACHE, forced on
     here).  'Precomputed' reads the ordinary single-frame correspondences_*.npz: the row of a window frame is its position among the seq1
-    frames of poses.txt, as wire.py writes it.  Then solver_ops.RigPnPBatchSolver.  A sample without `rig_T` (no poses_device.txt in the
+    frames of poses.txt, as wire.py writes it.  Then solver_ops.RigPnPBatchSolver ('PNP' / 'RigPNP': reads depth0) or
+    solver_ops.RigProcrustesBatchSolver ('RigProcrustes': reads depth0 and depth1 [1,T,H,W]; PROCRUSTES.REFINE, the whole-cloud ICP, is
+    refused on a rig) or solver_ops.RigEssentialBatchSolver ('RigEssentialMatrix': reads no depth, builds no depth stage, opens no depth
+    file).  The plain single-frame names other than 'PNP' stay refused: a rig solver has a name of its own.  A sample without `rig_T` (no poses_device.txt in the
     scene) is an error: there is no silent fall-back to the last frame alone.  With DPT.SOURCE 'online' the reference view's depth map is computed by the
-    fused route's depth stage (nets/dpt.FusedDepthStage), once per distinct reference view."""
+    fused route's depth stage (nets/dpt.FusedDepthStage), once per distinct reference view; 'RigProcrustes' asks the same call for the T window maps too."""
     MATCHERS = ('SuperGlue', 'LightGlue', 'LoFTR', 'SIFT', 'Precomputed')
+    RIG_SOLVERS = {'PNP': 'PNP', 'RigPNP': 'PNP', 'RigProcrustes': 'Procrustes', 'RigEssentialMatrix': 'EssentialMatrix'}      # name -> the single-frame solver whose stages (depth views) the pipeline builds
 
     def __init__(self, cfg):
         super().__init__()
-        if cfg.POSE_SOLVER != 'PNP':
-            raise NotImplementedError(f"FeatureMatchingMultiFrame solves the rig with POSE_SOLVER 'PNP' only, got {cfg.POSE_SOLVER!r}")
+        if cfg.POSE_SOLVER not in self.RIG_SOLVERS:
+            raise NotImplementedError(f"FeatureMatchingMultiFrame solves the rig with POSE_SOLVER 'PNP' (alias 'RigPNP'), 'RigProcrustes' or 'RigEssentialMatrix', "
+                                      f"got {cfg.POSE_SOLVER!r}")
+        self.kind = self.RIG_SOLVERS[cfg.POSE_SOLVER]
+        if self.kind == 'Procrustes' and cfg.PROCRUSTES.REFINE:
+            raise NotImplementedError("FeatureMatchingMultiFrame: PROCRUSTES.REFINE (whole-cloud ICP) is not defined for a rig; set PROCRUSTES.REFINE: False")
         fm = cfg.FEATURE_MATCHING
         if fm not in self.MATCHERS or (fm == 'SIFT' and cfg.SIFT.get('DETECTOR', 'opencv') != 'hip'):
             raise NotImplementedError(f"FeatureMatchingMultiFrame: FEATURE_MATCHING={fm!r} has no batched stage "
@@ -99,11 +109,19 @@ class FeatureMatchingMultiFrameModel(torch.nn.Module):
         self.cfg = cfg.clone()
         self.cfg.HIP.REF_FEATURE_CACHE = True
         self.cfg.HIP.GRAPH_FUSED = False                        # the captured stage takes no ref_keys
-        pipe = FusedPosePipeline(self.cfg)
+        pcfg = self.cfg.clone()
+        pcfg.POSE_SOLVER = self.kind                            # the pipeline knows the single-frame names: its matcher and depth stages are what is used of it
+        pipe = FusedPosePipeline(pcfg)
         self.match, self.guard, self.device = pipe.match, pipe.guard, pipe.device
-        self.depth = pipe.depth                                 # DPT.SOURCE 'online': the reference map comes from the fused route's stage (PNP reads depth0 only)
+        self.depth = pipe.depth                                 # DPT.SOURCE 'online': the maps come from the fused route's stage (PNP reads depth0 only, Procrustes all T + 1)
         seed = int(cfg.RANSAC.SEED) if 'RANSAC' in cfg else 0
-        self.solver = ops.RigPnPBatchSolver(cfg.PNP.RANSAC_ITER, cfg.PNP.REPROJECTION_INLIER_THRESHOLD, cfg.PNP.CONFIDENCE, seed)
+        if self.kind == 'PNP':
+            self.solver = ops.RigPnPBatchSolver(cfg.PNP.RANSAC_ITER, cfg.PNP.REPROJECTION_INLIER_THRESHOLD, cfg.PNP.CONFIDENCE, seed)
+        elif self.kind == 'Procrustes':
+            self.solver = ops.RigProcrustesBatchSolver(cfg.PROCRUSTES.MAX_CORR_DIST, 0.999, seed)
+        else:
+            self.solver = ops.RigEssentialBatchSolver(cfg.EMAT_RANSAC.PIX_THRESHOLD, cfg.EMAT_RANSAC.CONFIDENCE, seed, score=cfg.HIP.EMAT_SCORE,
+                                                      max_thr_ratio=cfg.HIP.MAGSAC_MAX_THR_RATIO)
         self.precomputed = fm == 'Precomputed'
         self._seq1, self._twin = {}, None
 
@@ -143,9 +161,14 @@ class FeatureMatchingMultiFrameModel(torch.nn.Module):
         with self.guard:
             m = self.match(batch)
             if self.depth is not None:                          # the colour bytes of the reference view (image0 is byte / 255), once per distinct reference view
-                ref = (data['image0'][0].to(dev, torch.float32) * 255.0).round().clamp_(0, 255).to(torch.uint8).permute(1, 2, 0)[None].contiguous()
-                data['depth0'] = self.depth.maps(ref, [0], [(batch['scene_root'], data['pair_names'][0][0])])
-        out = self.solver(m['pts0'][None], m['pts1'][None], m['n_corr'][None].to(torch.int32), data['depth0'].to(dev, torch.float32),
+                views = data['image0'] if self.kind == 'PNP' else torch.cat([data['image0'], data['image1'][0]])    # Procrustes: then the T window frames (E-matrix: no stage)
+                rgb = (views.to(dev, torch.float32) * 255.0).round().clamp_(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+                planes = self.depth.maps(rgb, [0], [(batch['scene_root'], data['pair_names'][0][0])], query_rows=range(1, rgb.shape[0]))
+                data['depth0'] = planes[0:1]
+                if self.kind != 'PNP':
+                    data['depth1'] = planes[1:][None]
+        depths = [data[k].to(dev, torch.float32) for k in {'PNP': ('depth0',), 'Procrustes': ('depth0', 'depth1'), 'EssentialMatrix': ()}[self.kind]]
+        out = self.solver(m['pts0'][None], m['pts1'][None], m['n_corr'][None].to(torch.int32), *depths,
                           data['K_color0'].to(dev), data['K_color1_multi'].to(dev), data['rig_T'].to(dev, torch.float64),
                           data['pair_id'].to(dev, torch.int64).reshape(1))
         st = self.guard.fold(out['status'])

@@ -291,6 +291,137 @@ class ProcrustesBatchSolver(_Workspace):
         return out
 
 
+class RigProcrustesBatchSolver(_Workspace):
+    """One pose (reference -> LAST window frame) for a rig of T query frames per sample from 3-D/3-D correspondences over all T + 1 depth
+    maps, one C-ABI call (the rig entry point of csrc/procrustes.hip).  pts0 / pts1 [B,T,maxN,2] f32, n_corr [B,T] i32, depth0 [B,H,W],
+    depth1 [B,T,H,W], K0 [B,3,3], K1_multi [B,T,3,3], rig_T [B,T,4,4] f64 (A_j: last frame's camera -> frame j's camera), pair_ids [B].
+    The mask is [B,T,maxN] over ORIGINAL correspondence indices; diagnostics adds n_valid [B,T], best_iter, iters_run, counts."""
+
+    def __init__(self, max_corr_dist=0.05, confidence=0.999, seed=0, max_iters=4096):
+        self.max_corr_dist, self.confidence = float(max_corr_dist), float(confidence)
+        self.seed, self.max_iters = int(seed), max(int(max_iters), 1)
+
+    def __call__(self, pts0, pts1, n_corr, depth0, depth1, K0, K1_multi, rig_T, pair_ids, want_mask=False, diagnostics=False):
+        lib = _lib.load(require_gpu=True)
+        pts0 = _chk(pts0, torch.float32, "pts0"); pts1 = _chk(pts1, torch.float32, "pts1")
+        n_corr = _chk(n_corr, torch.int32, "n_corr")
+        if pts0.dim() != 4 or pts0.shape != pts1.shape or pts0.shape[-1] != 2:
+            raise ValueError(f"pts0 / pts1: expected [B,T,maxN,2], got {tuple(pts0.shape)} / {tuple(pts1.shape)}")
+        B, T, maxN, _ = pts0.shape
+        if not 1 <= T <= RIG_MAX_T:
+            raise ValueError(f"a rig holds 1..{RIG_MAX_T} frames, got T = {T}")
+        dev = pts0.device
+        depth0 = _chk(depth0, torch.float32, "depth0"); depth1 = _chk(depth1, torch.float32, "depth1")
+        K0, K1, kdt = _chk_K(K0, K1_multi)
+        rig = rig_rows(rig_T)
+        pair_ids = _chk(pair_ids, torch.int64, "pair_ids")
+        if (tuple(n_corr.shape) != (B, T) or tuple(K1.shape) != (B, T, 3, 3) or tuple(rig.shape) != (B, T, 12)
+                or depth0.dim() != 3 or depth0.shape[0] != B or tuple(depth1.shape) != (B, T) + tuple(depth0.shape[1:])
+                or tuple(K0.shape) != (B, 3, 3) or tuple(pair_ids.shape) != (B,)):
+            raise ValueError("RigProcrustesBatchSolver: n_corr [B,T], K1_multi [B,T,3,3], rig_T [B,T,4,4], depth0 [B,H,W], depth1 [B,T,H,W], "
+                             "K0 [B,3,3], pair_ids [B] must match pts0 [B,T,maxN,2]")
+        _, H, W = depth0.shape
+        ws = self._ws(lib.mfr_rig_procrustes_workspace_bytes(B, T, maxN, self.max_iters), dev)
+        R, t, ni, st = _pose_out(B, dev)
+        mask = torch.empty(B, T, maxN, dtype=torch.uint8, device=dev) if want_mask else None
+        nv = bi = ir = cnt = None
+        if diagnostics:
+            nv, bi, ir, cnt = _i32(dev, B, T), _i32(dev, B), _i32(dev, B), _i32(dev, B, self.max_iters)
+        _lib.call("mfr_rig_procrustes_solve_batch", pts0, pts1, n_corr, B, T, maxN, depth0, depth1, H, W, K0, K1, kdt, rig,
+                  self.max_corr_dist, self.confidence, self.max_iters, self.seed, pair_ids, ws, ws.numel(), R, t, ni, st, mask, nv, bi, ir, cnt)
+        out = dict(R=R, t=t, n_inliers=ni, status=st)
+        if want_mask:
+            out["mask"] = mask
+        if diagnostics:
+            out.update(n_valid=nv, best_iter=bi, iters_run=ir, counts=cnt)
+        return out
+
+
+def _chk_rig(pts0, pts1, n_corr, K0, K1_multi, rig_T, who):
+    """the rig solvers' common arguments -> (pts0, pts1, n_corr, K0, K1, k tag, rig rows, B, T, maxN, device)"""
+    pts0 = _chk(pts0, torch.float32, "pts0"); pts1 = _chk(pts1, torch.float32, "pts1")
+    n_corr = _chk(n_corr, torch.int32, "n_corr")
+    if pts0.dim() != 4 or pts0.shape != pts1.shape or pts0.shape[-1] != 2:
+        raise ValueError(f"pts0 / pts1: expected [B,T,maxN,2], got {tuple(pts0.shape)} / {tuple(pts1.shape)}")
+    B, T, maxN, _ = pts0.shape
+    if not 1 <= T <= RIG_MAX_T:
+        raise ValueError(f"a rig holds 1..{RIG_MAX_T} frames, got T = {T}")
+    K0, K1, kdt = _chk_K(K0, K1_multi)
+    rig = rig_rows(rig_T)
+    if tuple(n_corr.shape) != (B, T) or tuple(K1.shape) != (B, T, 3, 3) or tuple(rig.shape) != (B, T, 12) or tuple(K0.shape) != (B, 3, 3):
+        raise ValueError(f"{who}: n_corr [B,T], K1_multi [B,T,3,3], rig_T [B,T,4,4], K0 [B,3,3] must match pts0 [B,T,maxN,2]")
+    return pts0, pts1, n_corr, K0, K1, kdt, rig, B, T, maxN, pts0.device
+
+
+def rig_emat_stage1(solver, pts0, pts1, n_corr, K0, K1_multi, pair_ids):
+    """Stage 1 of the essential-matrix rig solver: `solver` (an EssentialBatchSolver) over the B*T rows, K0 repeated per row, RANSAC key
+    pair_id*T + j.  pts0 / pts1 [B,T,maxN,2] -> dict(R [B,T,3,3], t [B,T,3] unit, n_inliers, status [B,T], mask [B,T,maxN])"""
+    B, T, maxN, _ = pts0.shape
+    rows = lambda x: x.reshape((B * T,) + tuple(x.shape[2:])).contiguous()
+    pid = (pair_ids.reshape(B, 1) * T + torch.arange(T, dtype=torch.int64, device=pair_ids.device)).reshape(-1)
+    o = solver(rows(pts0), rows(pts1), rows(n_corr), K0.repeat_interleave(T, dim=0).contiguous(), rows(K1_multi), pid)
+    return {k: o[k].reshape((B, T) + tuple(o[k].shape[1:])) for k in ("R", "t", "n_inliers", "status", "mask")}
+
+
+def rig_emat_stage2(pts0, pts1, n_corr, K0, K1_multi, rig_T, stage1, pix_thr=2.0, want_mask=False, diagnostics=False):
+    """Stage 2 of the essential-matrix rig solver (csrc/emat_rig.hip) on stage 1's device outputs: the rig-level hypotheses, pooled score,
+    refinement.  -> dict(R, t, n_inliers, status [, mask [B,T,maxN]] [, hyp_counts [B,T(T-1)], best_hyp [B]])"""
+    lib = _lib.load(require_gpu=True)
+    pts0, pts1, n_corr, K0, K1, kdt, rig, B, T, maxN, dev = _chk_rig(pts0, pts1, n_corr, K0, K1_multi, rig_T, "rig_emat_stage2")
+    R1 = _chk(stage1["R"], torch.float64, "stage1 R"); t1 = _chk(stage1["t"], torch.float64, "stage1 t")
+    n1 = _chk(stage1["n_inliers"], torch.int32, "stage1 n_inliers"); s1 = _chk(stage1["status"], torch.int32, "stage1 status")
+    m1 = _chk(stage1["mask"], torch.uint8, "stage1 mask")
+    if R1.numel() != B * T * 9 or t1.numel() != B * T * 3 or n1.numel() != B * T or s1.numel() != B * T or m1.numel() != B * T * maxN:
+        raise ValueError("rig_emat_stage2: stage 1's outputs must hold one row per frame of pts0 [B,T,maxN,2]")
+    ws = torch.empty(max(int(lib.mfr_rig_emat_workspace_bytes(B, T, maxN)), 256), dtype=torch.uint8, device=dev)
+    R, t, ni, st = _pose_out(B, dev)
+    mask = torch.empty(B, T, maxN, dtype=torch.uint8, device=dev) if want_mask else None
+    hc = bh = None
+    if diagnostics:
+        hc, bh = torch.full((B, max(T * (T - 1), 1)), -1, dtype=torch.int32, device=dev), _i32(dev, B)
+    _lib.call("mfr_rig_emat_solve", pts0, pts1, n_corr, B, T, maxN, K0, K1, kdt, rig, float(pix_thr), R1, t1, n1, s1, m1, ws, ws.numel(),
+              R, t, ni, st, mask, hc, bh)
+    out = dict(R=R, t=t, n_inliers=ni, status=st)
+    if want_mask:
+        out["mask"] = mask
+    if diagnostics:
+        out.update(hyp_counts=hc, best_hyp=bh)
+    return out
+
+
+class RigEssentialBatchSolver(_Workspace):
+    """One METRIC pose (reference -> LAST window frame) for a rig of T query frames per sample without any depth map: the single-frame
+    essential-matrix solver per frame, then the rig's baselines fix rotation, scale and inlier set (csrc/emat_rig.hip), one C-ABI call, no
+    host synchronisation between the stages.  pts0 / pts1 [B,T,maxN,2] f32, n_corr [B,T] i32, K0 [B,3,3], K1_multi [B,T,3,3], rig_T
+    [B,T,4,4] f64, pair_ids [B].  With T = 1 the result is EssentialBatchSolver's (unit translation).  Options as EssentialBatchSolver."""
+
+    def __init__(self, pix_thr=2.0, confidence=0.9999, seed=0, max_iters=1000, score="magsac", max_thr_ratio=1.0):
+        self.stage1 = EssentialBatchSolver(pix_thr, confidence, seed, max_iters, score, max_thr_ratio)
+
+    def __call__(self, pts0, pts1, n_corr, K0, K1_multi, rig_T, pair_ids, want_mask=False, diagnostics=False):
+        lib = _lib.load(require_gpu=True)
+        s1 = self.stage1
+        pts0, pts1, n_corr, K0, K1, kdt, rig, B, T, maxN, dev = _chk_rig(pts0, pts1, n_corr, K0, K1_multi, rig_T, "RigEssentialBatchSolver")
+        pair_ids = _chk(pair_ids, torch.int64, "pair_ids")
+        if tuple(pair_ids.shape) != (B,):
+            raise ValueError("RigEssentialBatchSolver: pair_ids [B] must match pts0 [B,T,maxN,2]")
+        ws = self._ws(lib.mfr_rig_emat_batch_workspace_bytes(B, T, maxN, s1.max_iters), dev)
+        lut = s1._table(dev) if s1.score == 0 else None
+        R, t, ni, st = _pose_out(B, dev)
+        mask = torch.empty(B, T, maxN, dtype=torch.uint8, device=dev) if want_mask else None
+        hc = bh = None
+        if diagnostics:
+            hc, bh = torch.full((B, max(T * (T - 1), 1)), -1, dtype=torch.int32, device=dev), _i32(dev, B)
+        _lib.call("mfr_rig_emat_solve_batch", pts0, pts1, n_corr, B, T, maxN, K0, K1, kdt, rig, s1.pix_thr, s1.confidence, s1.max_iters, s1.seed,
+                  pair_ids, s1.score, lut, MAGSAC_LUT_M, s1.max_thr_ratio, ws, ws.numel(), R, t, ni, st, mask, hc, bh)
+        out = dict(R=R, t=t, n_inliers=ni, status=st)
+        if want_mask:
+            out["mask"] = mask
+        if diagnostics:
+            out.update(hyp_counts=hc, best_hyp=bh)
+        return out
+
+
 class ProcrustesIcpRefine(_Workspace):
     """PROCRUSTES.REFINE (pose_solver.py:290-319): whole-cloud point-to-point ICP from the RANSAC transform, for a batch of
     pairs (csrc/procrustes_icp.hip).  R [B,3,3], t [B,3] f64 are refined IN PLACE; returns n_inliers / fitness / rmse / iters."""

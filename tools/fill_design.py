@@ -76,6 +76,16 @@ sub.update({"DAS_ST_SUM": " / ".join(f3(d["stages_sum_ms_per_frame"]) for d in S
             "DAS_L_TFLOPS": f"{S3[2]['tflops_whole_pass']:.0f}", "DAS_HEAD_MB": " / ".join(f"{d['head_map_bytes_per_frame']['bytes'] / 1e6:.0f}" for d in S3),
             "DAS_BATCH": str(da["workload"]["batch"]), "DAS_TOKENS": str(S3[0]["tokens"]), "DAS_H_TOKENS": str(hyb["tokens"]), "DAS_REPEATS": str(da["workload"]["repeats"]),
             "DAS_ITERS": str(da["workload"]["iters"]), "DAS_WINDOW": f"{da['workload']['min_window_ms']:.0f}"})
+rs = json.load(open(P("profiles", "rig_solvers.json")))         # the rig solvers side by side (tools/bench_rig_solvers.py)
+ra, rt = rs["accuracy_cpu_mirrors"], rs.get("solve_batch")
+f4 = lambda v: f"{v:.4f}"
+for tag, key in (("PNP", "rig_pnp_T9"), ("PR", "rig_procrustes_T9"), ("EM", "rig_essential_matrix_T9"), ("L", "procrustes_last_frame")):
+    sub.update({f"RIGS_{tag}_R": f4(ra[key]["median_rot_rad"]), f"RIGS_{tag}_T": f4(ra[key]["median_trans_m"])})
+sub["RIGS_BASE"] = f2(ra["largest_baseline_m_median"])
+if rt:
+    sub.update({"RIGS_PR_MS": f2(rt["rig_procrustes"]["median_ms"]), "RIGS_PRROWS_MS": f2(rt["procrustes_rows"]["median_ms"]),
+                "RIGS_PNP_MS": f2(rt["rig_pnp"]["median_ms"]), "RIGS_EM_MS": f2(rt["rig_emat_both_stages"]["median_ms"]), "RIGS_EM2_MS": f2(rt["rig_emat_stage2"]["median_ms"]),
+                "RIGS_EM1_MS": f2(rt["rig_emat_stage1_emat_rows"]["median_ms"])})
 census = subprocess.check_output([sys.executable, P("tools", "census_table.py")], text=True).rstrip("\n")
 out = open(P("docs", "DESIGN.template.md")).read()
 parts = {"CENSUS_TABLE_PLACEHOLDER": census, "KERNEL_TABLE_PLACEHOLDER": rd("_design_kernel_table.md"), "SECTION44_PLACEHOLDER": rd("_design_44.md"),
@@ -87,5 +97,5 @@ for k, v in parts.items():
 for k in sorted(sub, key=len, reverse=True):
     out = out.replace(k, sub[k])
 open(P("DESIGN.md"), "w").write(out)
-left = [w for w in ("PLACEHOLDER", "SG_", "LOFTR_", "C1_", "RPR_", "CPU_", "HOSTFED", "DPTF_", "DAS_") if w in out]
+left = [w for w in ("PLACEHOLDER", "SG_", "LOFTR_", "C1_", "RPR_", "CPU_", "HOSTFED", "DPTF_", "DAS_", "RIGS_") if w in out]
 print("DESIGN.md written,", len(out), "bytes; unresolved markers:", left, "; longest line", max(len(l) for l in out.splitlines()))
