@@ -384,6 +384,12 @@ int mfr_sp_sample_descriptors_ld(const float *dense_nhwc, int B, int Hc, int Wc,
  *                          kpts0/kpts1 [B,K,2]; also matches0 [B,ldS] (-1 = none), mscores0 [B,ldS].
  *                          mfr_sg_sinkhorn_match_variant: 0 = one sweep over S per iteration (round 4, default when ldS % 4 == 0 and
  *                          ldS <= 1024), 1 = a row pass and a column pass per iteration (rounds 1-3); the same bits either way.
+ *                          Any ldS > 0 with n0, n1 <= ldS <= K.  S needs 4-byte alignment only: an S that is not 16-byte aligned is read
+ *                          with 4-byte loads by the two-pass kernels, and every output has the bits an aligned copy gives.
+ *                          The scores of the valid n0 x n1 block must be finite.  If a pair's block holds a NaN or +inf, the first
+ *                          iteration (iters >= 1) turns its potentials into NaN and no row has an arg-max: that pair returns no matches
+ *                          (n_corr 0, matches0 all -1, mscores0 and pts0 / pts1 all zero) and nothing is read out of bounds; the other
+ *                          pairs of the launch are unaffected.  (-inf is not a masking value: its result is not defined.)
  * ------------------------------------------------------------------------------------------ */
 /*   mfr_gemm_f16x2 / mfr_gemm_bf16x3   the transformers' linear layers, y [M, ldy] (+)= act(x [M, ldx] W [N, K]^T + bias), fp32 in / fp32 out, on
  *                          the 16-bit matrix cores at fp32 accuracy by operand splitting (csrc/gemm_split.hip; rounds 1-2 called the library's fp32

@@ -40,13 +40,15 @@ static __device__ __forceinline__ void lse_add(Lse &a, float x)
     a.s = __builtin_fmaf(a.s, __expf(a.m - nm), __expf(x - nm));
     a.m = nm;
 }
-// merge of a partial (m, s); an empty partial (m = -inf) leaves a unchanged (select, not a branch: the discarded side may hold a NaN)
+// merge of a partial (m, s); an empty partial (m = -inf) leaves a unchanged (select, not a branch: the discarded side may hold a NaN).
+// A partial whose only term was a NaN is (-inf, NaN) -- fmaxf skips a NaN, so its maximum never moved -- and is NOT empty: it goes through the
+// merge and poisons the sum, so that one NaN score reaches u and v wherever it stands (an empty partial's s is exactly 0).
 static __device__ __forceinline__ void lse_merge(Lse &a, float m, float s)
 {
     const float nm = fmaxf(a.m, m);
     const float t = s * __expf(m - nm);
     const float ns = __builtin_fmaf(a.s, __expf(a.m - nm), t);
-    const bool keep = m == -INFINITY;
+    const bool keep = m == -INFINITY && s == s;
     a.s = keep ? a.s : ns;
     a.m = keep ? a.m : nm;
 }
@@ -96,7 +98,9 @@ static __device__ __forceinline__ int sg_row_of(int g, int r, int nq, int t) { r
 // rows 0..m (row m = dustbin row).  S: [B, ldS, ldS] raw scores (already / sqrt(256)).  One wavefront per row; a lane takes
 // float4 pieces (16-byte loads of the row and of v, all issued before the first use), reduces them with max-then-sum (no
 // data-dependent branch per element) and the 64 partial (max, sum) pairs merge in a butterfly.
-__global__ void __launch_bounds__(256) sg_row_kernel(const float *__restrict__ S, int ldS, const int *__restrict__ n0,
+// al16: S is 16-byte aligned.  If not, the fast path fetches the same four columns of a piece with four 4-byte loads: the same terms in the same
+// order, so the same bits as from an aligned copy of S (the general path below sums in another order and would not give them).
+__global__ void __launch_bounds__(256) sg_row_kernel(const float *__restrict__ S, int ldS, int al16, const int *__restrict__ n0,
                                                      const int *__restrict__ n1, int nstr, float alpha,
                                                      const float *__restrict__ v /*[B, SG_LDV]*/,
                                                      float *__restrict__ u /*[B, SG_LDV]*/)
@@ -109,13 +113,18 @@ __global__ void __launch_bounds__(256) sg_row_kernel(const float *__restrict__ S
     const float norm = -__logf((float)(m + n));
     Lse a = { -INFINITY, 0.f };
     if (i < m && !(ldS & 3) && ldS <= 1024) {
-        const float4 *row4 = (const float4 *)(S + ((size_t)b * ldS + i) * ldS), *v4 = (const float4 *)vb;
+        const float *row = S + ((size_t)b * ldS + i) * ldS;
+        const float4 *row4 = (const float4 *)row, *v4 = (const float4 *)vb;
         float x[16];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int j4 = lane + 64 * k;                         // float4 index: columns 4 j4 .. 4 j4 + 3
             float4 r = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY), w = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (4 * j4 < n) { r = row4[j4]; w = v4[j4]; }
+            if (4 * j4 < n) {
+                if (al16) r = row4[j4];
+                else r = make_float4(row[4 * j4], row[4 * j4 + 1], row[4 * j4 + 2], row[4 * j4 + 3]);   // (4 j4 + 3 < ldS: ldS % 4 == 0)
+                w = v4[j4];
+            }
             x[4 * k] = (4 * j4 < n) ? r.x + w.x : -INFINITY;
             x[4 * k + 1] = (4 * j4 + 1 < n) ? r.y + w.y : -INFINITY;
             x[4 * k + 2] = (4 * j4 + 2 < n) ? r.z + w.z : -INFINITY;
@@ -468,7 +477,7 @@ __global__ void __launch_bounds__(256) sg_match_kernel(
         float sc = 0.f;
         if (i < m && n > 0) {
             j = idx0[(size_t)b * ldS + i];
-            const bool mutual = idx1[(size_t)b * ldS + j] == i;
+            const bool mutual = j >= 0 && j < n && idx1[(size_t)b * ldS + j] == i;      // (a row of NaNs has no arg-max: its index is out of range)
             // Z_ij = S_ij + u_i + v_j - norm ; val0 = S_ij + v_j
             const float z = val0[(size_t)b * ldS + i] + u[(size_t)b * SG_LDV(ldS) + i] - norm;
             sc = mutual ? __expf(z) : 0.f;
@@ -541,14 +550,16 @@ int mfr_sg_sinkhorn_match_strided(const float *S, int B, int ldS, const int32_t 
     int *idx0 = (int *)(ws + w.idx0), *idx1 = (int *)(ws + w.idx1);
     // u = v = 0 (upstream log_sinkhorn_iterations)
     if (mfr_zero_async(ws + w.u, w.idx0 - w.u, s) != hipSuccess) return MFR_E_LAUNCH;
-    const bool sweep = variant == 0 && !(ldS & 3) && ldS <= 1024 && !((uintptr_t)S & 15);
+    // 16-byte loads of S need an aligned S: otherwise the two-pass kernels, whose row pass then reads S with 4-byte loads (the same bits)
+    const int al16 = !((uintptr_t)S & 15);
+    const bool sweep = variant == 0 && !(ldS & 3) && ldS <= 1024 && al16;
     const dim3 rgrid((ldS + 1 + 3) / 4, B), cgrid((ldS + 1 + 63) / 64, B);
     for (int it = 0; it < iters; ++it) {
         if (sweep) {
             hipLaunchKernelGGL(sg_sweep_kernel, dim3(16, B), dim3(512), 0, s, S, ldS, n0, n1, nstr, bin_score, v, u, part_m, part_s);
             hipLaunchKernelGGL(sg_colmerge_kernel, cgrid, dim3(64), 0, s, ldS, n0, n1, nstr, part_m, part_s, v);
         } else {
-            hipLaunchKernelGGL(sg_row_kernel, rgrid, dim3(256), 0, s, S, ldS, n0, n1, nstr, bin_score, v, u);
+            hipLaunchKernelGGL(sg_row_kernel, rgrid, dim3(256), 0, s, S, ldS, al16, n0, n1, nstr, bin_score, v, u);
             hipLaunchKernelGGL(sg_col_kernel, cgrid, dim3(1024), 0, s, S, ldS, n0, n1, nstr, bin_score, u, v);
         }
     }
